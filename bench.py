@@ -10,9 +10,15 @@ ranks -- dealt in interleaved 32-row stripes (voge_amd.distributed.Stripes), so 
 the whole image; --row-bands: one contiguous band per rank with measured rebalancing, rounds 1-2's scheme --: each
 rank traces / composites its own rows, the image is assembled by ONE all-gather (RCCL) and the per-Gaussian
 gradients by ONE all-reduce -> total work is fixed, "scaling": "strong".  --views runs the weak-scaling batch of
-N views instead (one whole view per rank); both alternatives and config 4 are also reported under `variants`.
+N views instead (one whole view per rank); with --full both alternatives and config 4 are also reported under `variants`.
 `python bench.py --gpus N` from a bare shell starts its own N ranks (torch.distributed.run as a child
 process, before this process touches a GPU); under torchrun it is one of the ranks.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the launch it timed).
+--full adds everything else the line can carry: four repeat regions, the stand-alone stage timings and rooflines, the
+variant frames, the CPU baselines, and with N > 1 the check that the assembled frame equals one GPU's render.
+--dump-outputs DIR writes what the last timed step computed -- the image and the gradients to verts, sigmas and colours --
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -35,8 +41,13 @@ TRACE_KERNELS = "voge_trace_topk_fwd(_iso) = binA + binB + sweep_iso_kernel<fals
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 30; --loop: the reference's whole loop, 2000 iterations)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: repeat regions, stage timings and rooflines, variants, CPU baselines, the "
+                         "multi-GPU exactness check and alternatives (a plain run sets up, warms up, times --steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--config", default="cfg3_50k_512")
     ap.add_argument("--anisotropic", action="store_true", help="full [N,3,3] Sigma^-1 (L L^T) instead of scalar sigmas")
     ap.add_argument("--default-bins", action="store_true", help="max_point_per_bin=None (the demos' default) instead of -1")
@@ -64,7 +75,29 @@ def parse():
     ap.add_argument("--loop", action="store_true",
                     help="BASELINE config 5 as a loop: a step = ONE ShapeFitting iteration (5 views batched, interpolate_attr + "
                          "get_silhouette MSE losses, backward, SGD step); implies --config cfg5_shapefit_128")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.only_stage and args.only_stage != "frame":
+        ap.error("--dump-outputs needs the frame: --only-stage runs none")
+    # (--only-stage is a profiling aid over the --full sections: it keeps them)
+    args.full = args.full or bool(args.only_stage)
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write {name: array} as out_dir/<name>.npy in float32 (float64 stays float64), at most DUMP_BYTES in all: over that, every
+    array is cut to a fixed, seeded sample of its flattened entries (the same entries from run to run), in ascending order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.size * DUMP_BYTES // total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -145,8 +178,8 @@ def loop_bench(args):
     The cost of an iteration is NOT constant along the optimisation: the sphere contracts onto the target, its Gaussians
     (fixed sigmas) overlap more and more, every pixel's list fills to K and the tiles' candidate lists grow -- a late
     iteration costs ~5x an early one.  `value` is therefore taken over the reference's WHOLE loop (Niter = 2000, rgb loss from
-    iteration 400, ShapeFitting.py:237,276; `--steps` other than the default 30 overrides the length), replayed as a HIP
-    graph; the first 300 iterations and the eager / one-view-at-a-time forms are reported beside it."""
+    iteration 400, ShapeFitting.py:237,276; `--steps` overrides the length), replayed as a HIP graph; with --full the first
+    300 iterations, the eager / one-view-at-a-time forms and the CPU baseline are reported beside it."""
     import importlib.util
     import numpy as np
     import torch
@@ -156,15 +189,18 @@ def loop_bench(args):
     demo = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(demo)
     B, V, K, size = 5, 20, 25, 128
-    niter = 2000 if args.steps == 30 else max(args.steps, 1)
+    niter = 2000 if args.steps is None else max(args.steps, 1)
     rgb_on = min(400, niter // 5)
     out, first, final = {}, {}, None
     for name, kw in (("graph", dict(graph=True)), ("eager", dict()), ("per_view_eager", dict(per_view=True))):
         if name == "graph" and args.no_graph:
             continue
+        if final is not None and not args.full:      # (a plain run: the headline's form alone)
+            break
         demo.fit(iters=200, quiet=True, rgb_on=0, **kw)                           # settle: pools, code objects, clocks
-        h = demo.fit(iters=min(300, niter), quiet=True, rgb_on=rgb_on, **kw)
-        first[name] = h["sec_per_iter"] * 1e3
+        if args.full:
+            h = demo.fit(iters=min(300, niter), quiet=True, rgb_on=rgb_on, **kw)
+            first[name] = h["sec_per_iter"] * 1e3
         h = demo.fit(iters=niter, quiet=True, rgb_on=rgb_on, **kw)
         out[name] = h["sec_per_iter"] * 1e3
         sil = np.asarray(h["silhouette"])
@@ -185,13 +221,19 @@ def loop_bench(args):
                    "launch": {"graph": "hip graph replay of the whole iteration (views gathered on the device)",
                               "eager": "eager"}[best], "parallelism": "1 gpu"},
         "ms_per_iteration": {k: round(v, 4) for k, v in out.items()},
-        "ms_per_iteration_first_300": {k: round(v, 4) for k, v in first.items()},
         "ms_per_iteration_note": "graph / eager: the batched iteration (demo/ShapeFitting.py BatchedIteration); per_view_eager: one "
                                  "renderer call per view as the reference's loop is written (ShapeFitting.py:258-259).  Whole loop vs "
                                  "its first 300 iterations: the iteration gets costlier as the shape contracts (see docstring)",
         "final_losses": {"silhouette": float(np.mean(final["silhouette"][-20:])), "rgb": float(np.mean(final["rgb"][-20:]))},
     }
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        # the headline loop's result: the fitted Gaussians after its last iteration, and the loss of every iteration
+        dump_outputs(args.dump_outputs, {"final_verts": final["final_verts"], "final_colors": final["final_colors"],
+                                         "loss_silhouette": np.asarray(final["silhouette"], np.float64),
+                                         "loss_rgb": np.asarray(final["rgb"], np.float64)})
+    if args.full:
+        result["ms_per_iteration_first_300"] = {k: round(v, 4) for k, v in first.items()}
+    if args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_loop(demo, B, K, size, final)
     print(json.dumps(result))
 
@@ -253,6 +295,8 @@ def main():
     args = parse()
     if args.loop:
         return loop_bench(args)
+    if args.steps is None:
+        args.steps = 30
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args))
 
@@ -360,6 +404,17 @@ def main():
             torch.cuda.synchronize()
 
         graph_checked = []      # (one entry per captured frame whose replayed gradients were compared with the eager step's)
+        # --dump-outputs: the step keeps a reference to its image (what the caller of the frame receives, with the gradients);
+        # a plain run drops it as soon as the loss is formed, as before
+        keep = primary and args.dump_outputs is not None
+        last = {}
+
+        def outputs_of(run):
+            """The arrays the last step of `run` handed to its caller: the image and the three gradients (a graph replay: the
+            static tensors its capture produced; the eager forms set them anew every step)."""
+            if getattr(run, "static", None) is not None:
+                return run.static
+            return dict(image=last["image"], **{"grad_" + k: p.grad for k, p in zip(("verts", "sigmas", "colors"), params)})
 
         def graphed_step(fwd, params):
             """One frame as a HIP graph replay (every replay runs exactly the kernels of an eager step on the same static
@@ -369,7 +424,12 @@ def main():
             def step():
                 for p in params:
                     p.grad = None
-                fwd().sum().backward(one)
+                if keep:
+                    img = fwd()
+                    last["image"] = img.detach()      # (the values alone: a reference to the autograd graph would keep this
+                    img.sum().backward(one)           #  step's AccumulateGrad nodes alive into the next one)
+                else:
+                    fwd().sum().backward(one)
             if args.no_graph:
                 for _ in range(60):      # allocator pools, lazily loaded code objects, clocks: what graph capture warms on the way
                     step()
@@ -397,6 +457,8 @@ def main():
                 with torch.cuda.graph(graph):
                     for _ in range(U):
                         step()
+                static = (dict(image=last["image"], **{"grad_" + k: p.grad for k, p in zip(("verts", "sigmas", "colors"), params)})
+                          if keep else None)
                 for _ in range(3):                                     # back-to-back replays, no host synchronisation between them
                     graph.replay()
                 torch.cuda.synchronize()
@@ -417,6 +479,7 @@ def main():
                         pending[0] = 0
                         graph.replay()
                 replay.U = U
+                replay.static = static
                 return replay, ("hip graph replay" if U == 1 else f"hip graph replay, {U} consecutive steps per graph launch")
             except Exception as e:  # pragma: no cover - depends on the runtime
                 print(f"[bench] HIP graph capture unavailable ({type(e).__name__}: {e}); running eagerly", file=sys.stderr)
@@ -526,6 +589,10 @@ def main():
                                   gather_rows_async(band_static.detach(), H_all, bounds=gb))
                         g_bwd.replay()                                          # ... and overlaps the band's backward
                         flat.allreduce()                                        # one eager all_reduce, in place
+                        if keep:
+                            img = finish()
+                            last["image"] = img.detach()
+                            return img.sum()
                         return finish().sum()                                   # the full-image loss every rank holds
                     run_split()
                     torch.cuda.synchronize()
@@ -546,6 +613,8 @@ def main():
                         r0, r1 = (rank * H, (rank + 1) * H) if by_views else (rows if rows is not None else (0, H))
                         img[:, r0:r1].sum().backward()      # each rank owns the loss of its band / view; grads are summed below
                     flat.allreduce()
+                    if keep:
+                        last["image"] = img.detach()
                     return img
 
         # settle (untimed, before the contract's W warmup steps): a fresh box ramps its clocks and pools over the first
@@ -579,7 +648,7 @@ def main():
         # are independent in every stage; stripes / bands / views only choose who computes which rows).  Every rank takes part
         # in the gather; rank 0 renders the whole frame (views mode: every view) alone and compares with torch.equal.
         split_exact = None
-        if multi and primary and not (args.only_stage and args.only_stage != "frame"):
+        if multi and primary and args.full and not (args.only_stage and args.only_stage != "frame"):
             with torch.no_grad():
                 band = fwd()
                 whole = gather_stripes(band, H, stripe_h) if striped else gather_rows(band, H_all, bounds=gb)
@@ -595,11 +664,14 @@ def main():
                                          f"max |diff| {float((whole - alone).abs().max()):.3e}")
             torch.cuda.synchronize()
         dt = timed(run, args.steps, args.warmup)
+        assert timed.last_steps == args.steps, (timed.last_steps, args.steps)      # (U divides --steps: the region ran exactly K steps)
         ms = dt / args.steps * 1e3
+        # --dump-outputs: what the last timed step handed its caller, copied to the host once the region is over
+        outputs = ({k: v.detach().cpu().numpy() for k, v in outputs_of(run).items()} if keep and rank == 0 else None)
         # (not part of the contract's number: four more regions of the same K steps, so that the line shows the spread of its
         #  headline -- at cfg3 a region is 20 x 0.26 ms)
         repeats = None
-        if primary and not multi:
+        if primary and not multi and args.full:
             repeats = [round(timed(run, args.steps, 0) / args.steps * 1e3, 5) for _ in range(4)]
         fps = (world if by_views else 1) * args.steps / dt      # (views mode: every step renders `world` frames, one per rank)
         # what the line says about the job it ran on: the process group's own view of the world, and every rank's local clock
@@ -622,6 +694,8 @@ def main():
      colors, host_scene, balance_log, launch, dt, ms, fps, rows_kw, graph_checked) = (
         M.by_views, M.striped, M.stripe_h, M.bands, M.rows, M.my_stripes, M.cams, M.R, M.T, M.make_frame, M.graphed_step, M.timed, M.barrier,
         M.renderer_of, M.fwd, M.params, M.gm, M.colors, M.host_scene, M.balance_log, M.launch, M.dt, M.ms, M.fps, M.rows_kw, M.graph_checked)
+    if M.outputs is not None:
+        dump_outputs(args.dump_outputs, M.outputs)
 
     sig_kind = "(N,3) per-axis sigmas" if args.diagonal else ("[N,3,3] L L^T sigmas" if args.anisotropic else "scalar sigmas")
     bins_kind = "None (default)" if args.default_bins else "-1"
@@ -674,7 +748,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / iters, nset
 
-    if rank == 0 and not multi:
+    if rank == 0 and not multi and args.full:
         # ---- per-stage kernel timings on the same inputs (HIP events, current stream) --------
         with torch.no_grad():
             from voge_amd.cameras import pixel_rays
@@ -901,7 +975,7 @@ def main():
             result["cpu_baseline"] = cpu_baseline(verts, sig, cols, H, W, K, focal, pp, (dd, el, az), args.cpu_seconds)
             # ... and the reference's own CPU-capable tensor program beside the C port
             result["cpu_baseline_torch"] = cpu_baseline_torch(verts, sig, cols, H, W, K, focal, pp, (dd, el, az), args.cpu_seconds)
-    if multi and not args.no_variants:
+    if multi and args.full and not args.no_variants:
         # the other ways to use the same N GPUs, same scene (every rank takes part): the contiguous bands of rounds 1-2, the
         # weak-scaling batch of views, and north_star's config 4 (200k Gaussians, 1024^2) in the default mode
         variants = {}
@@ -918,7 +992,7 @@ def main():
                 variants[vname] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
         result["variants"] = variants
-    if rank == 0 and multi:
+    if rank == 0 and multi and args.full:
         # the dominant kernel on rank 0's rows (same entry point, shorter image), timed live
         with torch.no_grad():
             from voge_amd.cameras import pixel_rays

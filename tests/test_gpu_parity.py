@@ -1217,7 +1217,7 @@ def test_bench_two_ranks_on_one_gpu(hip_lib, mode):
     env = dict(os.environ, VOGE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--balance-rounds", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--balance-rounds", "1", "--full"]
     if mode != "stripes":
         cmd += ["--no-variants", "--row-bands" if mode == "row_bands" else "--views"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
@@ -1259,7 +1259,7 @@ def test_bench_one_rank_through_rccl(hip_lib):
     env = dict(os.environ, VOGE_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1")
     env.pop("VOGE_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-variants",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-variants",
            "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -1269,6 +1269,48 @@ def test_bench_one_rank_through_rccl(hip_lib):
     assert c["gathered_frame_equals_single_gpu_render"] is True
     assert "hip graphs (band forward, band backward)" in c["launch"], c["launch"]      # (not the eager fallback)
     assert line["n_gpus"] == 1 and line["steps"] == 6 and line["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(hip_lib, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and carries nothing of --full; --dump-outputs
+    writes the last timed step's image and gradients, which equal the same seeded frame rendered here."""
+    import json
+    import subprocess
+    import sys
+    from voge_amd import scenes
+    from voge_amd.Meshes import GaussianMeshes
+    from voge_amd.Renderer import GaussianRenderer, GaussianRenderSettings, to_white_background
+    from voge_amd.cameras import PerspectiveCameras, look_at_view_transform
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VOGE_BENCH_FORCE_DIST", "VOGE_BENCH_BACKEND"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 10 and line["warmup"] == 2 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert not {"repeat_ms_per_step", "stages", "roofline", "variants", "cpu_baseline", "cpu_baseline_torch"} & set(line)
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("image", "grad_verts", "grad_sigmas", "grad_colors")}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20 and all(a.dtype == np.float32 for a in got.values())
+
+    N, (H, W), K, focal, pp, (dd, el, az) = scenes.CONFIGS["cfg3_50k_512"]
+    verts, sig, cols = scenes.random_gaussians(N, seed=0)
+    R, T = look_at_view_transform(dist=dd, elev=el, azim=az, device=DEV)
+    cams = PerspectiveCameras(focal_length=focal, principal_point=(pp,), image_size=((H, W),), R=R, T=T, device=DEV)
+    st = GaussianRenderSettings(image_size=(H, W), max_assign=K, thr_activation=0.01, absorptivity=1, max_point_per_bin=-1)
+    gm = GaussianMeshes(torch.from_numpy(verts), torch.from_numpy(sig)).to(DEV)
+    colors = torch.from_numpy(cols).to(DEV).requires_grad_(True)
+    img = to_white_background(GaussianRenderer(cams, st).to(DEV)(gm, R=R, T=T), colors)
+    img.sum().backward()
+    torch.cuda.synchronize()
+    want = {"image": n(img), "grad_verts": n(gm.verts.grad), "grad_sigmas": n(gm.sigmas.grad), "grad_colors": n(colors.grad)}
+    for k, w in want.items():
+        assert got[k].shape == w.shape and np.isfinite(got[k]).all(), k
+        # (two runs of the same step differ only in the order of the backward's float atomics)
+        assert np.abs(got[k] - w).max() <= 1e-4 * max(float(np.abs(w).max()), 1e-30), k
 
 
 @pytest.mark.parametrize("form", ["iso", "iso_view_shared", "general", "fragments_iso_lean"])

@@ -134,3 +134,21 @@ def test_host_logic_against_the_running_reference():
         assert np.abs(w[same] - g[c + "_weight"][same]).max() < 2e-4
         hit = (idx >= 0) & same[..., None]
         assert np.abs(ln[hit] - g[c + "_hit_length"][hit]).max() < 1e-4 * 4
+
+
+def test_bench_dump_outputs_caps_its_size_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 (float64 kept), and over the size cap the same seeded sample of every array."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    rng = np.random.default_rng(3)
+    small = {"a": rng.standard_normal((10, 20)), "b": rng.standard_normal(30).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "small"), {"a": small["a"].astype(np.float32), "b": small["b"]})
+    assert np.array_equal(np.load(str(tmp_path / "small" / "a.npy")), small["a"].astype(np.float32))
+    big = {"img": rng.standard_normal((40, 50)), "g": rng.standard_normal((1000, 3)).astype(np.float16)}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    x = {k: np.load(str(tmp_path / "x" / (k + ".npy"))) for k in big}
+    y = {k: np.load(str(tmp_path / "y" / (k + ".npy"))) for k in big}
+    assert x["img"].dtype == np.float64 and x["g"].dtype == np.float32
+    assert sum(a.nbytes for a in x.values()) <= 4000 and all(np.array_equal(x[k], y[k]) for k in big)
+    assert np.isin(x["img"], big["img"]).all()

@@ -11,7 +11,7 @@ for CFG in cfg3_50k_512 cfg4_200k_1024; do
   echo "==== $CFG"
   for r in 1 2 3; do
     for v in "" "$V"; do
-      VOGE_HIP_LIB=$v python bench.py --no-cpu-baseline --no-variants --config $CFG --steps 50 2>/dev/null | python -c "
+      VOGE_HIP_LIB=$v python bench.py --full --no-cpu-baseline --no-variants --config $CFG --steps 50 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stages']
 print('lib=%-10s frame %.1f fps  entry %.1f us  lean %.1f us' % (sys.argv[1] and 'xcdchain' or 'in-tree', d['value'], d['roofline']['avg_launch_ms']*1e3, s['trace_lean_fwd']['ms']*1e3))" "$v"
