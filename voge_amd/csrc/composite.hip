@@ -47,8 +47,8 @@ __host__ __device__ inline size_t comp_lds_bytes(const int K, const bool bwd) {
 
 // (the wave form keeps no per-workgroup state: no CompLds block in front of the arrays)
 __host__ __device__ inline size_t compn_lds_bytes(const int K, const int NS, const bool bwd, const int threads, const bool wave) {
-  // (+ one cell per pixel of a wave: the window radius, composite_core.h)
-  return (wave ? 0 : sizeof(CompLds)) + sizeof(float) * (size_t)compn_rows(K, NS, threads, wave) * (bwd ? 5 : 3) + (wave ? 64 * sizeof(unsigned) : 0);      // (backward: + u, + the row sums of compn_bwd_wave<NS, true>)
+  // (wave form: + 64 words nobody reads -- they held the pixels' window radii; kept, so the LDS size and occupancy stay as measured)
+  return (wave ? 0 : sizeof(CompLds)) + sizeof(float) * (size_t)compn_rows(K, NS, threads, wave) * (bwd ? 5 : 3) + (wave ? 64 * sizeof(unsigned) : 0);      // (backward: + u, + the row sums of compn_bwd_wave)
 }
 
 
@@ -329,17 +329,10 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
 // A lane owns the aligned group of slots [NS q, NS q + NS) of its pixel, so every pair of list
 // entries it reads from LDS serves 2 NS (row, column) evaluations, the lane's own group is the
 // diagonal block (registers only), global loads / stores are 4 NS bytes wide and the per-pixel
-// scans run over K / NS lanes.  The one-slot kernel above remains the reference form: it handles
-// the backward without given weights and is what VOGE_COMP_ONE_SLOT=1 builds select.
+// scans run over K / NS lanes.  The one-slot kernel above handles the backward without given weights.
 // ------------------------------------------------------------------------------------------
 #ifndef VOGE_COMP_WPE
 #define VOGE_COMP_WPE 1
-#endif
-#ifndef VOGE_CS_LDS
-#define VOGE_CS_LDS 1      // the shade sums' cross-lane reduction through LDS columns instead of a shuffle tree (see the shade block)
-#endif
-#ifndef VOGE_COMP_LDS_RMAX
-#define VOGE_COMP_LDS_RMAX 1
 #endif
 // WAVE: every pixel's lanes sit inside ONE wave (64 / LP pixels per wave, the remaining lanes idle), so the
 // per-pixel scans, flags and reductions are wave shuffles / ballots and the kernel has no workgroup barrier at
@@ -596,8 +589,8 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
     float um[NS], ga[NS], gl[NS], gd[NS];
 #pragma unroll
     for (int a = 0; a < NS; ++a) um[a] = gw[a] * wg[a];
-    compn_bwd_wave<NS, true>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo,
-                             occ, ga, gl, gd, nullptr, LR);
+    compn_bwd_wave<NS>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, occ, ga,
+                       gl, gd, LR);
     if (active) {
       if (vec && NS == 4) {
         at_bytes_w<float4>(out0, fb) = make_float4(ga[0], ga[1], ga[NS - 2], ga[NS - 1]);
@@ -615,11 +608,9 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
     return;
   }
   if (!BWD && WAVE) {
-    // forward, wave form: the row pass shared with the sweep's fused epilogue (composite_core.h)
+    // forward, wave form: the row pass shared with round 3's fused sweep epilogue (composite_core.h)
     float w[NS];
-    unsigned *const Lcells = reinterpret_cast<unsigned *>(LE + rows);      // (forward: three row arrays, then the cells)
-    compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo, occ, w,
-                       (VOGE_COMP_LDS_RMAX && blockDim.x == 64) ? Lcells + (in_wg ? p : 0) : nullptr);      // (one-wave workgroups)
+    compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo, occ, w);
     if (active) {
       if (vec && NS == 4) at_bytes_w<float4>(out0, fb) = make_float4(w[0], w[1], w[NS - 2], w[NS - 1]);
       else if (vec) at_bytes_w<v2f>(out0, fb) = (v2f){w[0], w[1]};
@@ -660,13 +651,12 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
         }
         part[SC] += w[a];
       }
-#if VOGE_CS_LDS
       if (SC == 3 && LP >= 3 && blockDim.x == 64) {      // (uniform; one-wave workgroups: the scratch below is the wave's OWN rows -- in a
                                                           //  workgroup of several waves another wave may still be walking them)
         // Three colour sums and sum w over the pixel's lanes.  Round 6: through LDS -- every lane leaves its four partial sums in the
         // (now idle) row arrays, the pixel's lanes 0 .. 2 each add up ONE colour's column and the weights' column in lane order:
-        // two dependent LDS round trips instead of the four of a shuffle tree (which were 5 us of this kernel, -DVOGE_CS_ABL; a
-        // tree with fewer shuffles but five dependent steps gained nothing).  A fixed association per pixel, as before.
+        // two dependent LDS round trips instead of the four of a shuffle tree (which were 5 us of this kernel; a tree with fewer
+        // shuffles but five dependent steps gained nothing).  A fixed association per pixel, as before.
         float *const A0 = const_cast<float *>(Llen), *const A1 = const_cast<float *>(Lsp), *const A2 = const_cast<float *>(LE);
         wave_lds_sync();      // (the walks' reads of these rows are over)
         constexpr int T_ = 64;      // (rows >= 128 for every K with LP >= 3: compn_rows)
@@ -696,16 +686,11 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
         }
         return;
       }
-#endif
       // the pixel's lanes are consecutive in the wave: sum towards its first lane (a fixed association per pixel)
 #pragma unroll
       for (int c = 0; c <= SC; ++c) {
         float x = part[c];
-#ifdef VOGE_CS_ABL      // (timing experiment: no cross-lane reduction of the shade sums)
-        for (int o = 64; o < LP; o <<= 1) {
-#else
         for (int o = 1; o < LP; o <<= 1) {
-#endif
           const float y = __shfl_down(x, o, 64);
           if (q + o < LP && in_wg) x += y;
         }
@@ -1037,7 +1022,6 @@ static int launch_composite(int mode, const int32_t *idx, const float *act, cons
   // workgroup size: the smallest multiple of 64 that is >= VOGE_COMP_T and holds one pixel
   const int threads = (K <= VOGE_COMP_T) ? VOGE_COMP_T : kCompThreads;
   hipStream_t st = (hipStream_t)stream;
-#ifndef VOGE_COMP_ONE_SLOT
 #ifndef VOGE_COMP_NS
 #define VOGE_COMP_NS 4
 #endif
@@ -1047,10 +1031,9 @@ static int launch_composite(int mode, const int32_t *idx, const float *act, cons
 #endif
     const int NS = ((mode == 0 ? VOGE_COMP_NS : VOGE_COMP_NS_BWD) == 4 && (K & 3) == 0) ? 4 : 2;
     const int LPn = compn_lanes(K, NS);
-#ifndef VOGE_COMP_WAVE          // bit 0: forward, bit 1: backward take the barrier-free one-wave-per-pixel form
-#define VOGE_COMP_WAVE 3        // measured (cfg3, one-wave workgroups): backward 101 -> 87 us, forward 52 -> 50 us (the
-#endif                          // forward lost 7 us in this form while it still ran as 256-thread workgroups)
-    const bool wavem = ((VOGE_COMP_WAVE >> (mode == 0 ? 0 : 1)) & 1) && LPn <= 64;   // needs a pixel's lanes inside one wave
+    // the barrier-free one-wave-per-pixel form wherever a pixel's lanes fit one wave -- measured (cfg3, one-wave workgroups):
+    // backward 101 -> 87 us, forward 52 -> 50 us (the forward lost 7 us in this form while it still ran as 256-thread workgroups)
+    const bool wavem = LPn <= 64;
 #ifndef VOGE_COMP_WAVE_T
 #define VOGE_COMP_WAVE_T 64     // waves of the barrier-free form never talk to each other: one-wave workgroups schedule finest
                                 // (cfg3 backward: 256 / 128 / 64 threads -> 92.2 / 89.1 / 86.7 us)
@@ -1079,19 +1062,12 @@ static int launch_composite(int mode, const int32_t *idx, const float *act, cons
 #undef VOGE_LAUNCH_COMPN
     return launch_status();
   }
-#endif
+  // mode 1: the one-slot kernel
   const int ppw = threads / K;
   const dim3 grid((unsigned)((npix + ppw - 1) / ppw)), block(threads);
-  const size_t lds = comp_lds_bytes(K, mode != 0);
-  if (mode == 2)
-    hipLaunchKernelGGL(composite_kernel<2>, grid, block, lds, st, idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, ppw, o0,
-                       o1, o2, valid_num);
-  else if (mode == 1)
-    hipLaunchKernelGGL(composite_kernel<1>, grid, block, lds, st, idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, ppw, o0,
-                       o1, o2, valid_num);
-  else
-    hipLaunchKernelGGL(composite_kernel<0>, grid, block, lds, st, idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, ppw, o0,
-                       o1, o2, valid_num);
+  const size_t lds = comp_lds_bytes(K, true);
+  hipLaunchKernelGGL(composite_kernel<1>, grid, block, lds, st, idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, ppw, o0,
+                     o1, o2, valid_num);
   return launch_status();
 }
 

@@ -1,7 +1,8 @@
 // Shared pieces of the depth-ordered compositing (VoGE/Aggregation.py:30-107): constants, the erfc / Gaussian
 // evaluators, the LDS row layout, and the forward row pass of the lane-owns-NS-slots form.  Used by composite.hip
-// (voge_composite_fwd / _bwd) and by the sweep's fused epilogue in trace_fwd.hip: ONE implementation, so fragments
-// composited inside the sweep are bit-identical to the stand-alone kernel's.
+// (voge_composite_fwd / _bwd) and by the fused epilogue of round 3's sweep in trace_fwd.hip (-DVOGE_AB builds; measured
+// and not used: HISTORY.md §5): ONE implementation, so fragments composited inside the sweep are bit-identical to the
+// stand-alone kernel's.
 #pragma once
 #include "voge_common.h"
 
@@ -9,22 +10,11 @@ namespace voge {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-#ifdef VOGE_COMP_PRECISE
-#define FAST_EXP(x) expf(x)
-#define FAST_SQRT(x) sqrtf(x)
-#else
 // hardware exp2 / sqrt: ~1-2 ulp, far inside the 1e-4 parity tolerance; the libm versions cost
 // ~35 VALU instructions per lane in a VALU-bound kernel
 #define FAST_EXP(x) __builtin_amdgcn_exp2f((x) * 1.4426950408889634f)
 #define FAST_SQRT(x) __builtin_amdgcn_sqrtf(x)
-#endif
 
-#ifndef VOGE_CF_ABL
-#define VOGE_CF_ABL 0      // timing experiments on the forward composite (bit 0: no window walks, bit 1: no own block)
-#endif
-#ifndef VOGE_CF_COLWALK
-#define VOGE_CF_COLWALK 1  // forward composite, sorted pixels: walks over the rows around a lane's own COLUMNS (each column's own window) instead of
-#endif                     // over the columns around its rows (the pixel's widest window); see compn_fwd_rows
 #ifndef VOGE_COMP_MAXT
 #define VOGE_COMP_MAXT 256
 #endif
@@ -41,20 +31,11 @@ constexpr float kBig = 3.0e38f;
 
 // log2(erfc(x)/2) as a polynomial in x' = x sqrt(log2 e) on [0, 5 sqrt(log2 e)], weighted minimax
 // on the absolute error of 2^Q (tools/fit_erfc.py).  Degree 6: |err| <= 1.5e-7 (the accuracy of
-// Abramowitz-Stegun 7.1.26); VOGE_ERFC_DEG=8 gives 5.2e-8 and h(0) = 1/2 exactly for two more
-// packed FMAs per pair of entries.
-#ifndef VOGE_ERFC_DEG
-#define VOGE_ERFC_DEG 6
-#endif
-#if VOGE_ERFC_DEG == 8
-constexpr float kQ0 = -1.000000000e+00f, kQ1 = -1.355323434e+00f, kQ2 = -6.365932822e-01f,
-                kQ3 = -8.570024371e-02f, kQ4 = 1.359716244e-02f, kQ5 = -3.297536168e-04f,
-                kQ6 = -4.863584472e-04f, kQ7 = 1.211055496e-04f, kQ8 = -1.022832203e-05f;
-#else
+// Abramowitz-Stegun 7.1.26); degree 8 gives 5.2e-8 and h(0) = 1/2 exactly for two more packed FMAs
+// per pair of entries (tools/fit_erfc.py fits degrees 6 to 8).
 constexpr float kQ0 = -9.999997020e-01f, kQ1 = -1.355341077e+00f, kQ2 = -6.364040971e-01f,
                 kQ3 = -8.642258495e-02f, kQ4 = 1.487037074e-02f, kQ5 = -1.475012978e-03f,
                 kQ6 = 4.851150516e-05f;
-#endif
 
 __device__ __forceinline__ v2f pk_fma(const v2f a, const v2f b, const v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat(const float x) { return (v2f){x, x}; }
@@ -63,13 +44,7 @@ __device__ __forceinline__ v2f splat(const float x) { return (v2f){x, x}; }
 __device__ __forceinline__ v2f h_pair(v2f xp) {
   xp.x = fminf(xp.x, kXcap);
   xp.y = fminf(xp.y, kXcap);
-#if VOGE_ERFC_DEG == 8
-  v2f q = pk_fma(splat(kQ8), xp, splat(kQ7));
-  q = pk_fma(q, xp, splat(kQ6));
-  q = pk_fma(q, xp, splat(kQ5));
-#else
   v2f q = pk_fma(splat(kQ6), xp, splat(kQ5));
-#endif
   q = pk_fma(q, xp, splat(kQ4));
   q = pk_fma(q, xp, splat(kQ3));
   q = pk_fma(q, xp, splat(kQ2));
@@ -120,7 +95,8 @@ __host__ __device__ inline int compn_rows(const int K, const int NS, const int t
 // index) and visible to the wave.  lm / sm / em: the lane's own len, s = sqrt(dsd + 1e-10), E = exp(-act) (E = 0 for
 // an empty slot).  `sorted`: the pixel's list is depth ordered (the windowed walk); otherwise every column is visited.
 // LP, q, seg_lo, d0, k0, K are PER-LANE values (pixels of different lane counts may share a wave: the packed kernels);
-// LPmax is a wave-uniform upper bound of LP (the trip count of the scans).
+// LPmax is a wave-uniform upper bound of LP (the trip count of the scans).  LP and seg_lo are no longer read here (the
+// column walks need no pixel-wide window radius); the callers, round 3's sweep among them, still pass them.
 // Returns the weights of the lane's slots.  The association of the scans is a function of the lane's index in the
 // pixel only, so a pixel's result does not depend on where it sits (row bands == whole frame, fused == stand-alone).
 template <int NS>
@@ -128,20 +104,16 @@ __device__ __forceinline__ void compn_fwd_rows(const float (&lm)[NS], const floa
                                                const float *Llen, const float *Lsp, const float *LE, const int d0,
                                                const int k0, const int K, const int q, const int LP, const int LPmax,
                                                const bool in_wg, const bool active, const bool sorted, const int seg_lo,
-                                               const float occ, float (&w)[NS], unsigned *Lcell = nullptr) {
+                                               const float occ, float (&w)[NS]) {
   float sp[NS];
 #pragma unroll
   for (int a = 0; a < NS; ++a) sp[a] = sm[a] * kCs;
-  float mx = 0.0f, esum = 0.0f;
+  float esum = 0.0f;
 #pragma unroll
-  for (int a = 0; a < NS; ++a) {
-    mx = fmaxf(mx, (em[a] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[a]) : 0.0f);
-    esum += em[a];
-  }
-  // Exclusive prefix (over the lanes of the pixel) of the per-lane sums of E, Hillis-Steele on wave shuffles with the
-  // window radius riding along
-#if VOGE_CF_COLWALK
-  float ex;      // (no pixel-wide window radius: a column walk goes as far as its own columns reach)
+  for (int a = 0; a < NS; ++a) esum += em[a];
+  // Exclusive prefix (over the lanes of the pixel) of the per-lane sums of E, Hillis-Steele on wave shuffles (no pixel-wide
+  // window radius rides along: a column walk goes as far as its own columns reach)
+  float ex;
   {
     const float y = __shfl_up(esum, 1, 64);
     float x = (q > 0 && in_wg) ? y : 0.0f;
@@ -151,40 +123,6 @@ __device__ __forceinline__ void compn_fwd_rows(const float (&lm)[NS], const floa
     }
     ex = x;
   }
-#else
-  float ex, wave_rmax;
-  if (Lcell != nullptr) {
-    // the window radius through the pixel's LDS cell (compn_bwd_wave), the prefix sum alone through the shuffles
-    if (in_wg && q == 0) *Lcell = 0u;
-    wave_lds_sync();
-    if (in_wg && mx > 0.0f) atomicMax(Lcell, __float_as_uint(mx));
-    const float y = __shfl_up(esum, 1, 64);
-    float x = (q > 0 && in_wg) ? y : 0.0f;
-    for (int o = 1; o < LPmax; o <<= 1) {
-      const float z = __shfl_up(x, o, 64);
-      if (q >= o && in_wg) x += z;
-    }
-    ex = x;
-    wave_lds_sync();
-    wave_rmax = in_wg ? __uint_as_float(*lds_volatile(Lcell)) : 0.0f;
-  } else {
-    v2f x = {esum, mx};
-    const v2f y = (v2f){__shfl_up(x.x, 1, 64), __shfl_up(x.y, 1, 64)};
-    x = (q > 0 && in_wg) ? (v2f){y.x, fmaxf(mx, y.y)} : (v2f){0.0f, mx};
-    for (int o = 1; o < LPmax; o <<= 1) {
-      const v2f z = (v2f){__shfl_up(x.x, o, 64), __shfl_up(x.y, o, 64)};
-      if (q >= o && in_wg) {
-        x.x += z.x;
-        x.y = fmaxf(x.y, z.y);
-      }
-    }
-    ex = x.x;
-    wave_rmax = __shfl(x.y, min(63, seg_lo + LP - 1), 64);      // the pixel's last lane holds the maximum
-  }
-#endif
-#if !VOGE_CF_COLWALK
-  const float rwin = sorted ? (in_wg ? wave_rmax : 0.0f) : 0.0f;
-#endif
   bool any_e = false;
 #pragma unroll
   for (int a = 0; a < NS; ++a) any_e = any_e || (em[a] != 0.0f);
@@ -201,7 +139,7 @@ __device__ __forceinline__ void compn_fwd_rows(const float (&lm)[NS], const floa
     for (int a = 0; a < NS; ++a) {
       accF[a].x = em[a] * h0;         // self
 #pragma unroll
-      for (int b2 = a + 1; b2 < ((VOGE_CF_ABL & 2) ? 0 : NS); ++b2) {
+      for (int b2 = a + 1; b2 < NS; ++b2) {
         const float gap = lm[b2] - lm[a];
         const v2f xp = (v2f){gap * sp[b2], gap * sp[a]};                 // (row a, col b), (row b, col a)
         const v2f h = h_pair(xp);
@@ -209,12 +147,11 @@ __device__ __forceinline__ void compn_fwd_rows(const float (&lm)[NS], const floa
         accF[b2].y = fmaf(em[a], h.y, accF[b2].y);
       }
     }
-#if VOGE_CF_COLWALK
     // Column walks (round 6): the lane walks the ROWS around its own columns, each as far as that column's own window
     // kSat / s_j reaches, and adds -E_j h (row behind: the column is in front of it) / +E_j h (row in front) to the row's cell
     // of LR -- the pixel's s' row, which a sorted pixel's walks no longer read: a lane's own s' and E are in its registers.
-    // The row walks below went as far as the pixel's WIDEST window for every column.  Read - add - write as in
-    // compn_bwd_wave<NS, true>: in one iteration the lanes of a wave address different row pairs.
+    // Row walks went as far as the pixel's WIDEST window for every column (HISTORY.md R6).  Read - add - write as in
+    // compn_bwd_wave: in one iteration the lanes of a wave address different row pairs.
     float *const LR = const_cast<float *>(Lsp);
     float reachB = -kBig, reachF = kBig, lmS[NS], spS[NS];
 #pragma unroll
@@ -259,41 +196,6 @@ __device__ __forceinline__ void compn_fwd_rows(const float (&lm)[NS], const floa
       pre += em[a];                                                     // inclusive prefix sum of E
       S[a] = ((pre - (accF[a].x + accF[a].y)) + (accB[a].x + accB[a].y)) + *lds_volatile(LR + d0 + a);
     }
-#else
-    float lmB = lm[0];                 // the last live row decides how far back to walk
-#pragma unroll
-    for (int a = 1; a < NS; ++a) lmB = (em[a] != 0.0f) ? lm[a] : lmB;
-#if VOGE_CF_ABL & 1      // (timing experiment: no window walks)
-    if (lmB == -7.0f)
-#endif
-    for (int e = d0 - 2;; e -= 2) {      // column pairs in front of every own row; row 0 is the nearest
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(lm[0] - l2.y < rwin)) break;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (splat(lm[a]) - l2) * s2;
-        accF[a] = pk_fma(E2, h_pair(xa), accF[a]);
-      }
-    }
-#if VOGE_CF_ABL & 1
-    if (lmB == -7.0f)
-#endif
-    for (int e = d0 + NS;; e += 2) {     // column pairs behind every own row
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(l2.x - lmB < rwin)) break;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (l2 - splat(lm[a])) * s2;
-        accB[a] = pk_fma(E2, h_pair(xa), accB[a]);
-      }
-    }
-    float pre = ex;
-#pragma unroll
-    for (int a = 0; a < NS; ++a) {
-      pre += em[a];                                                     // inclusive prefix sum of E
-      S[a] = (pre - (accF[a].x + accF[a].y)) + (accB[a].x + accB[a].y);
-    }
-#endif
   } else if (any_e && active) {          // unsorted list: every column, signs from the data
     const int r0 = d0 - k0;
     for (int j = 0; j < K; ++j) {
@@ -325,7 +227,7 @@ __device__ unsigned long long g_cw_stats[1 << 16][4];
 // Backward, wave form, with the forward's weights given (u_m = g_m w_m comes from the caller): the closed-form
 // gradients of the lane's own slots (header of composite.hip).  The pixel's padded rows len / s' / E s' are in LDS
 // (the sentinel pads' u entries are zero); this routine stores u into Lu itself.  Same conventions as compn_fwd_rows.
-// RCOL (round 5): the row sums r_m = sum_j E_j s_j phi(x_mj) are not walked for at all.  phi(x_mj), x_mj = (len_m - len_j) s_j,
+// Round 5: the row sums r_m = sum_j E_j s_j phi(x_mj) are not walked for at all.  phi(x_mj), x_mj = (len_m - len_j) s_j,
 // is a value the COLUMN walk of j's owner evaluates anyway (for u_m phi(x_mj)); that lane adds E_j s_j phi to row m's cell of
 // LR (an LDS row array laid out like Lu, zeroed by the caller) and the row's owner reads the sum afterwards.  The add is a plain
 // read - add - write: in one iteration of a walk the lanes of a wave address DIFFERENT row pairs (a pixel's lanes start NS rows
@@ -334,44 +236,18 @@ __device__ unsigned long long g_cw_stats[1 << 16][4];
 // (ds_add_f32 instead costs ~60 cycles per wave instruction: the kernel 129 -> 251 us.)  The column walk reaches every row inside column j's OWN window 3.5 / s_j -- where phi >= 4.8e-6 --
 // while the row walk went as far as the pixel's widest window: the terms dropped are below that, like the column sums' own.
 // One of the kernel's two window walks and its divergence are gone for one packed multiply and two LDS adds per column pair.
-// (RCOL = true needs LR: a row array of the caller's LDS laid out like Lu, zeroed together with it.)
-template <int NS, bool RCOL = false>
+// (LR: a row array of the caller's LDS laid out like Lu, zeroed together with it.)
+template <int NS>
 __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const float (&sm)[NS], const float (&em)[NS],
                                                const float (&um)[NS], const float *Llen, const float *Lsp, const float *LE,
                                                float *Lu, const int d0, const int k0, const int K, const int q, const int LP,
                                                const int LPmax, const bool in_wg, const bool active, const bool sorted,
-                                               const int seg_lo, const float occ, float (&ga)[NS], float (&gl)[NS],
-                                               float (&gd)[NS], unsigned *Lcell = nullptr, float *LR = nullptr) {
+                                               const float occ, float (&ga)[NS], float (&gl)[NS], float (&gd)[NS],
+                                               float *LR) {
   constexpr int NP = NS / 2;
-  const int lane = threadIdx.x & 63;
   float sp[NS], Es[NS];
 #pragma unroll
   for (int a = 0; a < NS; ++a) { sp[a] = sm[a] * kCs; Es[a] = em[a] * sp[a]; }
-  float mx = 0.0f;
-#pragma unroll
-  for (int a = 0; a < NS; ++a) mx = fmaxf(mx, (em[a] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[a]) : 0.0f);
-  float wave_rmax = 0.0f;
-  if (RCOL) {
-    // (the column walks go as far as each column's OWN window: nobody reads the pixel-wide radius -- until round 6 this form still
-    //  paid for it: an LDS store, an LDS atomic max and a read-back, three dependent round trips per round)
-  } else if (Lcell != nullptr) {
-    // the pixel's window radius through ONE LDS cell (the pixel's own; radii are >= 0, so their bit patterns order
-    // like unsigned integers): zero, max, read -- three LDS operations in the wave's in-order LDS queue instead of a
-    // chain of seven dependent cross-lane shuffles
-    if (in_wg && q == 0) *Lcell = 0u;
-    wave_lds_sync();
-    if (in_wg && mx > 0.0f) atomicMax(Lcell, __float_as_uint(mx));
-    wave_lds_sync();
-    wave_rmax = in_wg ? __uint_as_float(*lds_volatile(Lcell)) : 0.0f;
-  } else {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float y = __shfl_down(mx, o, 64);
-      if (lane + o < 64 && q + o < LP) mx = fmaxf(mx, y);
-    }
-    wave_rmax = __shfl(mx, seg_lo, 64);                // the pixel's first lane holds the maximum
-  }
-  const float rwin = sorted ? (in_wg ? wave_rmax : 0.0f) : 0.0f;
   bool any_e = false;
 #pragma unroll
   for (int a = 0; a < NS; ++a) any_e = any_e || (em[a] != 0.0f);
@@ -396,34 +272,9 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
         accR[b2].y = fmaf(Es[a], g.y, accR[b2].y);
       }
     }
-    if (!RCOL) {
-    float lmB = lm[0];                 // the last live row decides how far back to walk
+    // (the own block only; the other lanes' columns arrive through LR during their column walks below)
 #pragma unroll
-    for (int a = 1; a < NS; ++a) lmB = (em[a] != 0.0f) ? lm[a] : lmB;
-    for (int e = d0 - 2;; e -= 2) {      // column pairs in front of every own row; row 0 is the nearest
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(lm[0] - l2.y < rwin)) break;
-      CW_COUNT(0);
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (splat(lm[a]) - l2) * s2;
-        accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
-      }
-    }
-    for (int e = d0 + NS;; e += 2) {     // column pairs behind every own row
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(l2.x - lmB < rwin)) break;
-      CW_COUNT(0);
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (l2 - splat(lm[a])) * s2;
-        accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
-      }
-    }
-    }
-    // (RCOL: the own block only; the other lanes' columns arrive through LR during their column walks below)
-#pragma unroll
-    for (int a = 0; a < NS; ++a) rterm[a] = (accR[a].x + accR[a].y) * (RCOL ? 1.0f : kRsqrtPi / kCs);
+    for (int a = 0; a < NS; ++a) rterm[a] = accR[a].x + accR[a].y;
   } else if (any_e && active) {          // unsorted list: every column
     const int r0 = d0 - k0;
     for (int j = 0; j < K; ++j) {
@@ -486,7 +337,7 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
       }
       for (int e = d0 + NS;; e += 2) {     // row pairs behind every own column
         const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
-        v2f racc = RCOL ? ld2(LR, e) : splat(0.0f);
+        v2f racc = ld2(LR, e);
         bool need = false;
 #pragma unroll
         for (int b2 = 0; b2 < NS; ++b2) need = need || (l2.x - lm[b2] < rj[b2]);
@@ -499,13 +350,14 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
           const v2f g = gauss_pair(xp);
           const v2f y = u2 * g;
           aH[b2] = pk_fma(u2, h_pair(xp), aH[b2]); aP[b2] = aP[b2] + y; aL[b2] = pk_fma(y, d, aL[b2]);
-          if (RCOL) racc = pk_fma(splat(Es[b2]), g, racc);
+          racc = pk_fma(splat(Es[b2]), g, racc);
         }
-        if (RCOL) { *reinterpret_cast<v2f *>(LR + e) = racc; wave_lds_sync(); }
+        *reinterpret_cast<v2f *>(LR + e) = racc;
+        wave_lds_sync();
       }
       for (int e = d0 - 2;; e -= 2) {      // row pairs in front of every own column
         const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
-        v2f racc = RCOL ? ld2(LR, e) : splat(0.0f);
+        v2f racc = ld2(LR, e);
         bool need = false;
 #pragma unroll
         for (int b2 = 0; b2 < NS; ++b2) need = need || (lm[b2] - l2.y < rj[b2]);
@@ -518,15 +370,15 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
           const v2f g = gauss_pair(xp);
           const v2f y = u2 * g;
           bH[b2] = pk_fma(u2, h_pair(xp), bH[b2]); bP[b2] = bP[b2] + y; bL[b2] = pk_fma(y, d, bL[b2]);
-          if (RCOL) racc = pk_fma(splat(Es[b2]), g, racc);
+          racc = pk_fma(splat(Es[b2]), g, racc);
         }
-        if (RCOL) { *reinterpret_cast<v2f *>(LR + e) = racc; wave_lds_sync(); }
-      }
-      if (RCOL) {      // every column walk of the pixel has passed (its lanes share this wave): the row sums are complete
+        *reinterpret_cast<v2f *>(LR + e) = racc;
         wave_lds_sync();
-#pragma unroll
-        for (int a = 0; a < NS; ++a) rterm[a] = (rterm[a] + *lds_volatile(LR + d0 + a)) * (kRsqrtPi / kCs);
       }
+      // every column walk of the pixel has passed (its lanes share this wave): the row sums are complete
+      wave_lds_sync();
+#pragma unroll
+      for (int a = 0; a < NS; ++a) rterm[a] = (rterm[a] + *lds_volatile(LR + d0 + a)) * (kRsqrtPi / kCs);
       float suf = sx;
 #pragma unroll
       for (int b2 = NS - 1; b2 >= 0; --b2) {

@@ -53,9 +53,6 @@ __device__ unsigned long long g_fb_wall[kFbTimesWaves][2];       // its first an
 #define FB_TOUT() do {} while (0)
 #endif
 
-#ifndef VOGE_BWD_RCOL
-#define VOGE_BWD_RCOL 1
-#endif
 template <int NV4, int NS>
 struct FragBwdLds {
   // key = Gaussian index; values: (g_mu, g_a), (w g_rgb, -) for A = a I [NV4 = 2];
@@ -64,23 +61,12 @@ struct FragBwdLds {
   static constexpr int kRows = NS * 64 + 4 * kFbG;      // a round's padded rows: 64 lanes' slots + two sentinel pairs per pixel
   WaveTable<kFbNE, NV4> tab;
   float len[kRows], sp[kRows], E[kRows], u[kRows];
-#if VOGE_BWD_RCOL
-  float r[kRows];                 // row sums of the composite backward, accumulated by the column walks (compn_bwd_wave<NS, true>)
-#endif
-  unsigned rmax[kFbG];            // per pixel of the round: its window radius (compn_bwd_wave)
+  float r[kRows];                 // row sums of the composite backward, accumulated by the column walks (compn_bwd_wave)
+  unsigned spare[kFbG];           // (not read: it held the round's window radii; kept, so the LDS size and occupancy stay as measured)
 };
 
 #ifndef VOGE_FB_ABL
 #define VOGE_FB_ABL 0
-#endif
-#ifndef VOGE_FB_LDS_RMAX
-#define VOGE_FB_LDS_RMAX 1
-#endif
-#ifndef VOGE_FB_PAIR_TABLE
-#define VOGE_FB_PAIR_TABLE 1      // a lane's two table accumulations share one election loop (wt_add2)
-#endif
-#ifndef VOGE_FB_TABLE_BY_PIXEL
-#define VOGE_FB_TABLE_BY_PIXEL 1  // the table is taken pixel by pixel (no election: wt_add2_by_group) instead of by wt_add2's elections
 #endif
 #ifndef VOGE_FB_WPE
 #define VOGE_FB_WPE 4      // capping the registers for 5 / 6 waves per SIMD spills and is slower
@@ -123,10 +109,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
   // into three arrays there; the kernel's tail is bound by those requests.  acc stays; the forward zeroes it on its way.)
   auto sum_add = [&](const int key, const int c, const float v) { unsafeAtomicAdd(acc + NACC * (size_t)key + c, v); };
   __shared__ __attribute__((aligned(16))) FragBwdLds<NV4, NS> L;
-  float *const Llen = L.len, *const Lsp = L.sp, *const LE = L.E, *const Lu = L.u;
-#if VOGE_BWD_RCOL
-  float *const LR = L.r;
-#endif
+  float *const Llen = L.len, *const Lsp = L.sp, *const LE = L.E, *const Lu = L.u, *const LR = L.r;
   const int lane = threadIdx.x;
   FB_T0();
   const int blocks_x = (W + kFbGW - 1) / kFbGW;
@@ -342,18 +325,14 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
         *reinterpret_cast<v2f *>(Lsp + d0 + a) = (v2f){sm[a] * kCs, sm[a + 1] * kCs};
         *reinterpret_cast<v2f *>(LE + d0 + a) = (v2f){em[a] * (sm[a] * kCs), em[a + 1] * (sm[a + 1] * kCs)};
         *reinterpret_cast<v2f *>(Lu + d0 + a) = splat(0.0f);
-#if VOGE_BWD_RCOL
         *reinterpret_cast<v2f *>(LR + d0 + a) = splat(0.0f);
-#endif
       }
       if (q < 2) {      // the sentinel pair in front of the pixel's row and the one behind it
         for (int t2 = q; t2 < 2; t2 += LP) {
           Llen[r0 + t2] = -kBig; Lsp[r0 + t2] = 1.0f; LE[r0 + t2] = 0.0f; Lu[r0 + t2] = 0.0f;
           const int eb = r0 + RS - 2 + t2;
           Llen[eb] = kBig; Lsp[eb] = 1.0f; LE[eb] = 0.0f; Lu[eb] = 0.0f;
-#if VOGE_BWD_RCOL
           LR[r0 + t2] = 0.0f; LR[eb] = 0.0f;
-#endif
         }
       }
     }
@@ -362,13 +341,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
 #if VOGE_FB_ABL & 2       // (timing experiment: no composite)
     for (int a = 0; a < NS; ++a) { ga[a] = um[a]; gl[a] = um[a] * sm[a]; gd[a] = um[a] * em[a]; }
 #else
-#if VOGE_BWD_RCOL
-    compn_bwd_wave<NS, true>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, NS * LP, q, LP, npm, on, on, true, pk.s0, occ, ga, gl, gd,
-                             VOGE_FB_LDS_RMAX ? &L.rmax[on ? pk.ord : 0] : nullptr, LR);
-#else
-    compn_bwd_wave<NS>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, NS * LP, q, LP, npm, on, on, true, pk.s0, occ, ga, gl, gd,
-                       VOGE_FB_LDS_RMAX ? &L.rmax[on ? pk.ord : 0] : nullptr);
-#endif
+    compn_bwd_wave<NS>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, NS * LP, q, LP, npm, on, on, true, occ, ga, gl, gd, LR);
 #endif
     wave_lds_sync();      // the rows are rewritten by the next round
     FB_TICK(2);
@@ -391,8 +364,8 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
     }
     const float dn2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
     const float idn = __builtin_amdgcn_rcpf(dn2);
-    // (two slots per lane: both slots' terms first, then ONE election loop for both -- wt_add2)
-    constexpr bool PAIR = NS == 2 && VOGE_FB_PAIR_TABLE;
+    // (two slots per lane: both slots' terms first, then ONE table pass for both -- wt_find2, wt_add2_by_group)
+    constexpr bool PAIR = NS == 2;
     float4 valp[PAIR ? 2 : 1][NV4];
     bool gop[2] = {false, false};
 #pragma unroll
@@ -524,11 +497,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
       FB_TICK(3);
       int slot0, slot1;
       wt_find2(L.tab, id[0], gop[0], id[NS - 1], gop[1], slot0, slot1);
-#if VOGE_FB_TABLE_BY_PIXEL
       wt_add2_by_group(L.tab, slot0, valp[0], gop[0] && slot0 >= 0, slot1, valp[PAIR ? 1 : 0], gop[1] && slot1 >= 0, pk.ord);
-#else
-      wt_add2(L.tab, slot0, valp[0], gop[0] && slot0 >= 0, slot1, valp[PAIR ? 1 : 0], gop[1] && slot1 >= 0, lane);
-#endif
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         const int sl = a == 0 ? slot0 : slot1;

@@ -18,10 +18,6 @@
 
 namespace voge {
 
-#ifndef VOGE_SWEEP_V2
-#define VOGE_SWEEP_V2 1
-#endif
-
 constexpr int kS2TP = 65;      // floats per row of the len array (odd: the epilogue's transposed reads stay conflict-light)
 constexpr int kS2TQ = 66;      // u16 per row of the position array (= 33 u32 in the wide form)
 constexpr int kS2Pad = 4;      // never-hit records behind the staged chunk: a trip of four needs no bounds
@@ -42,31 +38,11 @@ __host__ __device__ inline size_t sweep2_pos_bytes(const int K) { return (sizeof
 struct Sweep2Gen {
   float e[11][64 + kS2Pad];
 };
-#ifndef VOGE_S2_QUADS
-#define VOGE_S2_QUADS 0      // 1: the scalar kernel, a tile's own list: one candidate stream per 4x4-pixel QUADRANT of the tile (see Sweep2Quad).
-                             // Built and measured in round 6 (profiles/r6_quads_ab.txt): bit-identical results, 30 % fewer candidates
-                             // evaluated per tile (93.7 -> 65.5), and SLOWER: a trip of four costs 669 instead of 490 ns (four
-                             // distinct record addresses per ds_read_b128 instead of one broadcast, 12 v_mov to pair the AoS
-                             // records for the packed evaluation), staging + 1.0, prologue + 0.6, epilogue + 1.3 us per tile
-                             // (ids through the stream): lean trace 63.1 -> 65.7 us, entry 71.2 -> 75.0 us.  Off.
-#endif
-// QUADS (round 6; tools/quadrant_sim.py, HISTORY R4: a candidate of an 8x8 tile's list hits 28-37 % of its rays, one stream per
-// 4x4 quadrant cuts a tile's trips from 94 to 58.5).  The staged chunk is kept as AoS (x, y, z, a) records in the bytes of
-// Sweep2Stage::x..a, every candidate is tested against the four quadrants' bounding cones when it is staged, and the survivors'
-// chunk positions are compacted into four byte lists (in the bytes of Sweep2Stage::pos: a handle is the stream position now,
-// which needs no look-up).  A trip then evaluates, in every lane, the next four candidates of ITS quadrant's list; the wave
-// runs as long as its longest quadrant.  The cones live here.
-struct Sweep2Quad {
-  float4 c[4];                  // (axis, cos) of quadrant q = (column >> 2) + 2 * (row >> 2)
-  float sn[4], ok[4];
-};
-constexpr int kS2QL = 64 + kS2Pad;      // bytes per quadrant list (padded with 64 = the never-hit record's position)
-static_assert(4 * kS2QL == sizeof(int) * (64 + kS2Pad), "the four byte lists take Sweep2Stage::pos's bytes");
 // gen: 0 scalar sigmas, 1 general forms (eleven coefficient arrays), 2 a launch of per-axis forms only (five: s11, s22, b)
 constexpr int kS2DiagRows = 5;
 __host__ __device__ inline size_t sweep2_lds_bytes(const int K, const int gen = 0) {
   return sweep2_len_bytes(K) + sweep2_pos_bytes(K) + sizeof(Sweep2Stage) +
-         (gen == 1 ? sizeof(Sweep2Gen) : (gen == 2 ? sizeof(float) * kS2DiagRows * (64 + kS2Pad) : (VOGE_S2_QUADS ? sizeof(Sweep2Quad) : 0)));
+         (gen == 1 ? sizeof(Sweep2Gen) : (gen == 2 ? sizeof(float) * kS2DiagRows * (64 + kS2Pad) : 0));
 }
 
 #ifndef VOGE_S2_EPI_B
@@ -75,28 +51,10 @@ __host__ __device__ inline size_t sweep2_lds_bytes(const int K, const int gen = 
 #ifndef VOGE_S2_EPI_R
 #define VOGE_S2_EPI_R 3      // ... and how many of them have their (mu, a) gathers in flight together (act / dsd wanted)
 #endif
-#ifndef VOGE_S2_READLANE
-#define VOGE_S2_READLANE 0      // the tile's own list: records out of the lanes' registers (v_readlane) instead of LDS staging
-#endif
-#ifndef VOGE_S2_PACKED
-#define VOGE_S2_PACKED 1        // two candidates per packed-fp32 instruction in the evaluation
-#endif
 #ifndef VOGE_S2_EXIT_GROUP
 #define VOGE_S2_EXIT_GROUP 16   // candidates between two exit tests (a power of two, >= 4)
 #endif
 constexpr int kExitGroup = VOGE_S2_EXIT_GROUP;
-#ifndef VOGE_S2_PREFETCH
-#define VOGE_S2_PREFETCH 1      // the next trip's staged records are requested before this trip's commits
-#endif
-#ifndef VOGE_S2_PUT_AT_CNT
-#define VOGE_S2_PUT_AT_CNT 1    // the 16-bit form's commit stores every candidate at row cnt (no row select); see commit()
-#endif
-#ifndef VOGE_S2_GEN_LEAN
-#define VOGE_S2_GEN_LEAN 0      // (experiment) the general kernel takes the scalar kernel's lean_insert / slow_insert instead of deep_insert
-#endif
-#ifndef VOGE_S2_PRIO_LEN
-#define VOGE_S2_PRIO_LEN 0   // (experiment) tiles with at least this many candidates run at raised wave priority; 0: off
-#endif
 
 // GEN = 2 (round 6): a launch whose general forms are ALL diagonal (the frame path's per-axis sigmas, gen_kind 1): five of the eleven
 // coefficient arrays exist (8 instead of 7 workgroups per CU at K = 40), the trips are the diagonal ones, and the insertion is the
@@ -123,9 +81,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
   // (GEN = 2: rows s11, s22, bx, by, bz of the eleven -- the others do not exist in that launch's LDS)
   auto grow = [&](const int r) -> float * { return &G.e[GEN == 2 ? (r < 2 ? r : r - 3) : r][0]; };
   auto ghas = [](const int r) { return GEN != 2 || r < 2 || (r >= 5 && r < 8); };
-  Sweep2Quad &QC = *reinterpret_cast<Sweep2Quad *>(smem_raw + sweep2_len_bytes(K) + sweep2_pos_bytes(K) + sizeof(Sweep2Stage));   // (!GEN, QUADS)
-  float4 *const QR = reinterpret_cast<float4 *>(&S.x[0]);                      // (QUADS) the staged records, AoS
-  [[maybe_unused]] unsigned char *const Q8 = reinterpret_cast<unsigned char *>(&S.pos[0]);      // (QUADS) the four position lists
 
   const int lane = threadIdx.x;
   const int tiles_x = (W + 7) >> 3;
@@ -155,8 +110,8 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       for (int it = lane; it < th * ipr; it += 64) {
         const int rr = it / ipr, j4 = it - rr * ipr;
         const size_t o = (((size_t)b * H + fty * 8 + rr) * W + (size_t)ftx * 8) * K + (size_t)j4 * 4;
-        st16i<(VOGE_NT_STORES & 1) != 0>(out_idx + o, -1, -1, -1, -1);
-        st16f<(VOGE_NT_STORES & 1) != 0>(out_len + o, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN);
+        st16i<true>(out_idx + o, -1, -1, -1, -1);
+        st16f<true>(out_len + o, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN);
       }
     } else {
       for (int it = lane; it < th * row_items; it += 64) {
@@ -195,9 +150,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
   const int32_t *src_id = (tc >= 0) ? (pooled ? pool_id : tl_id) + list_at : (binned ? bin_id + (size_t)bin * kQCap : nullptr);
   const float *src_lb = (tc >= 0) ? (pooled ? pool_lb : tl_lb) + list_at : (binned ? bin_lb + (size_t)bin * kQCap : nullptr);
   const bool pref = tc >= 0;      // the tile's own list is already filtered with this tile's cone
-#if VOGE_S2_PRIO_LEN > 0
-  if (src_n >= VOGE_S2_PRIO_LEN) __builtin_amdgcn_s_setprio(3);
-#endif
   const float4 *cullb = cull + (size_t)b * N;
   const float4 *msb = ms + (size_t)b * N;
   const float4 rec_none = make_float4(0.f, 0.f, 0.f, INFINITY);      // act = inf * 0 = NaN: never below the threshold
@@ -205,13 +157,10 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
   // What a list entry carries in its 16 (32) bits: the Gaussian's id itself where every id of the batch element fits 16
   // bits -- no look-up anywhere --, else the entry's POSITION in the tile's stream, resolved through the stream's id list
   // on an exact len tie and in the epilogue.
-  const bool quads = (VOGE_S2_QUADS != 0) && !GEN && pref && src_n <= 65536;      // (uniform) the per-quadrant form: handles are stream positions
-  const bool h_is_id = !quads && ((N <= 65536) || !binned);
+  const bool h_is_id = (N <= 65536) || !binned;
   auto id_of = [&](const unsigned h) -> int { return h_is_id ? (int)h : src_id[h]; };
   const float not_full = __uint_as_float(__float_as_uint(VOGE_SENT_LEN) - 1u);      // len <= this  <=>  len < the sentinel
-  if (quads) {
-    if (lane < kS2Pad) QR[64 + lane] = rec_none;
-  } else if (lane < kS2Pad) { S.x[64 + lane] = 0.f; S.y[64 + lane] = 0.f; S.z[64 + lane] = 0.f; S.a[64 + lane] = INFINITY; }
+  if (lane < kS2Pad) { S.x[64 + lane] = 0.f; S.y[64 + lane] = 0.f; S.z[64 + lane] = 0.f; S.a[64 + lane] = INFINITY; }
   if (GEN && lane < kS2Pad) G.e[0][64 + lane] = __uint_as_float(0x7fc00000u);      // (padding counts as isotropic)
   const float4 *evrb = GEN ? evr + (size_t)b * N * 3 : nullptr;
   bool tile_gen = false;      // (GEN) a general candidate was staged at some point: the epilogue needs the full records
@@ -251,34 +200,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       float smax = 0.f, cmin = 1.f;
       cone_partial(u, ax, ay, az, smax, cmin);
       wcone = cone_finish(ax, ay, az, n, wave_max(smax), wave_min(cmin), dirs_ok);
-    }
-    if (quads) {      // (uniform) the four quadrants' cones: reductions over lane bits 0, 1 (columns) and 3, 4 (rows)
-      // (bit 4 = the other 16-lane row of the pair: v_permlane16_swap hands every lane both rows' values -- no LDS round trip)
-      auto rows = [&](const float v, float &lo, float &hi) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-        lo = __uint_as_float(r[0]); hi = __uint_as_float(r[1]);
-      };
-      auto qsum = [&](float v) { v += VOGE_DPP(v, 0xB1); v += VOGE_DPP(v, 0x4E); v += VOGE_DPP(v, 0x128); float a, b2; rows(v, a, b2); return a + b2; };
-      auto qmax = [&](float v) { v = fmaxf(v, VOGE_DPP(v, 0xB1)); v = fmaxf(v, VOGE_DPP(v, 0x4E)); v = fmaxf(v, VOGE_DPP(v, 0x128)); float a, b2; rows(v, a, b2); return fmaxf(a, b2); };
-      const float sx = qsum(u.ok ? u.ux : 0.f), sy = qsum(u.ok ? u.uy : 0.f), sz = qsum(u.ok ? u.uz : 0.f);
-      const float n2 = fmaf(sz, sz, fmaf(sy, sy, sx * sx));
-      const float rn = __builtin_amdgcn_rsqf(n2);      // (the axis need not be exactly unit: the bounds below are taken against THIS axis, renormalised)
-      float ax = sx * rn, ay = sy * rn, az = sz * rn;
-      const float fix = __builtin_amdgcn_rsqf(fmaf(az, az, fmaf(ay, ay, ax * ax)));
-      ax *= fix; ay *= fix; az *= fix;
-      float smax = 0.f, cmin = 1.f;
-      {
-        const float cl = fmaf(u.uz, az, fmaf(u.uy, ay, u.ux * ax));
-        const float rx = fmaf(-cl, ax, u.ux), ry = fmaf(-cl, ay, u.uy), rz = fmaf(-cl, az, u.uz);
-        const float sl = __builtin_amdgcn_sqrtf(fmaf(rz, rz, fmaf(ry, ry, rx * rx)));
-        smax = u.ok ? sl : 2.0f; cmin = u.ok ? cl : -1.0f;
-      }
-      smax = qmax(smax) * (1.0f + 1e-6f) + 1e-6f; cmin = -qmax(-cmin) - 1e-6f;      // (hardware sqrt / rsq, ~1 ulp: margins as cam_rect_cone's)
-      const int myq = ((lane >> 2) & 1) | ((lane >> 4) & 2);
-      const unsigned long long qm = (0x0F0F0F0Full << (4 * (myq & 1))) << (32 * (myq >> 1));
-      const bool qok = (__ballot(u.ok) & qm) == qm;
-      const Cone c = cone_finish(ax, ay, az, n2 * rn * 0.25f, smax, cmin, qok);
-      if ((lane & 0x1B) == 0) { QC.c[myq] = make_float4(c.ax, c.ay, c.az, c.cs); QC.sn[myq] = c.sn; QC.ok[myq] = c.ok ? 1.f : 0.f; }
     }
   };
 
@@ -347,7 +268,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
     float worstf = valid ? not_full : __uint_as_float(0x7fc00000u);      // (NaN: a ray outside the image takes nothing)
     float tailf = -INFINITY;
     bool wdone = false;
-    [[maybe_unused]] unsigned qdone = 0u;      // (QUADS) bit q: quadrant q's stream is over (its exit test fired)
 
     // a candidate that passed `act < thr && len <= worst` but is not a plain append: exact (len, id) insertion
     auto slow_insert = [&](const float len, const unsigned p) {
@@ -472,11 +392,7 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       // 31), so "row cnt" of such a lane is row 0 of another ray's live list; there the non-appends go to the spare row K, the
       // only row two lanes of a column may both write.  (Round 5 tried put(cnt) for both forms, saw cfg4 -- the wide form --
       // fail, and reverted without finding this; tests/test_gpu_configs.py::test_streams_longer_than_16_bit_handles and ::test_rebuilt_sweep_equals_round_3_sweep_bit_for_bit (its last case) run the wide form.)
-#if VOGE_S2_PUT_AT_CNT
       put(WIDE ? (app ? cnt : Kv) : cnt, len, p);
-#else
-      put(app ? cnt : Kv, len, p);
-#endif
       cnt += app ? 1 : 0;
       tailf = app ? len : tailf;
       worstf = (app & (cnt == K)) ? len : worstf;      // the append that fills the list: its len is the admission bound now
@@ -490,7 +406,7 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
 #ifdef VOGE_SWEEP_SLOW
         dbg_moved = 0;
 #endif
-        if (GEN == 1 && !(VOGE_S2_GEN_LEAN)) {
+        if (GEN == 1) {
           deep_insert(len, p, slow);
         } else {
           const bool hard = lean_insert(len, p, slow, Kv);
@@ -530,173 +446,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       lb1 = load_lb(base + 128 + lane);
 #ifdef VOGE_SWEEP_TIMES
       const unsigned long long tsa = wall_clock64();
-#endif
-#if VOGE_S2_READLANE
-      if (pref) {
-        // ---- the tile's own list: nothing is staged.  Lane i holds entry base + i's record in registers; the wave reads
-        // candidate s out of lane s with v_readlane (the values land in SGPRs and feed the evaluation as scalar operands).
-        // The old form broadcast every record to all 64 lanes through LDS: a ds_read_b128 per candidate, 1 KB through the
-        // LDS crossbar each -- with nine waves per CU the LDS pipe was as busy as the VALUs (tools/valu_bench.hip prices a
-        // broadcast ds_read_b64 at ~6 LDS clocks). ----
-        const int nb = min(64, src_n - base);
-        const int hnd = h_is_id ? id : base + lane;
-        int n = nb;
-#ifdef VOGE_SWEEP_TIMES
-        const unsigned long long tsb = wall_clock64();
-        ts_fill += tsb - tsa;
-#endif
-        for (int s0 = 0; s0 < n; s0 += 4) {
-          if ((s0 & (kExitGroup - 1)) == 0 && binned && unit_rays && __all(!valid || cnt == K)) {
-            const float wmax = wave_max(valid ? worstf : -INFINITY);
-            const unsigned long long ex = __ballot(lane < nb && lbv > wmax);
-            if (ex) {
-              n = __builtin_ctzll(ex);
-              wdone = true;
-              if (n <= s0) break;
-            }
-          }
-          float len[4], act[4];
-          int pv[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {      // (lanes behind the list hold the never-hit record)
-            const int l = s0 + q;
-            const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrec.x), l));
-            const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrec.y), l));
-            const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrec.z), l));
-            const float sa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrec.w), l));
-            pv[q] = __builtin_amdgcn_readlane(hnd, l);
-            const float md = fmaf(sz, dz, fmaf(sy, dy, sx * dx));      // pair_eval_iso's operations, bit for bit
-            const float t = md * rdn2;
-            const float vx = fmaf(-t, dx, sx), vy = fmaf(-t, dy, sy), vz = fmaf(-t, dz, sz);
-            len[q] = t;
-            act[q] = sa * fmaf(vz, vz, fmaf(vy, vy, vx * vx));
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(len[q]), "+v"(act[q]));
-#pragma unroll
-          for (int q = 0; q < 4; ++q) commit(len[q], act[q], (unsigned)pv[q]);
-        }
-#ifdef VOGE_SWEEP_TIMES
-        ts_cons += wall_clock64() - tsb;
-        st_eval += min(n, nb);
-#endif
-        continue;
-      }
-#endif
-#if VOGE_S2_QUADS
-      if constexpr (!GEN && !WIDE) {
-        if (quads) {      // (uniform) ---- the tile's own list, one stream per quadrant (Sweep2Quad) ----
-          const int nb = min(64, src_n - base);
-          __syncthreads();      // (the previous chunk's readers are done)
-          QR[lane] = mrec;      // (behind the list: never-hit records)
-          S.lb[lane] = lbv;
-          reinterpret_cast<unsigned *>(Q8)[lane] = 0x40404040u;
-          if (lane < kS2Pad) reinterpret_cast<unsigned *>(Q8)[64 + lane] = 0x40404040u;
-          // (straight-line: the four cones are requested first, the candidate's reach is iso_cull_record's with selects for its
-          //  branches, cone_keep's early return is a mask -- as `if`s every quadrant's test sat in exec-mask regions of its own,
-          //  each behind its own LDS round trip: 1 us per chunk)
-          const float4 c0q = QC.c[0], c1q = QC.c[1], c2q = QC.c[2], c3q = QC.c[3];
-          const float4 snq = *reinterpret_cast<const float4 *>(&QC.sn[0]), okq = *reinterpret_cast<const float4 *>(&QC.ok[0]);
-          const float nm2 = fmaf(mrec.z, mrec.z, fmaf(mrec.y, mrec.y, mrec.x * mrec.x));
-          const float nm = __builtin_amdgcn_sqrtf(nm2);
-          float reach = __builtin_amdgcn_sqrtf(fmaxf(thr_act, 0.0f) * __builtin_amdgcn_rcpf(mrec.w * (1.0f - 4e-6f))) * (1.0f + 2e-5f) + 2e-5f * nm + 1e-30f;
-          reach = (mrec.w > 0.0f && mrec.w < 3e38f && reach >= 0.0f) ? reach : INFINITY;      // (iso_cull_record, trace_bin.h: conservative)
-          int cq[4];
-          unsigned kbits = 0u;      // bit q: this lane's staged entry is in quadrant q's list (the exit test re-counts with it)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float4 c4 = q == 0 ? c0q : (q == 1 ? c1q : (q == 2 ? c2q : c3q));
-            const float snv = q == 0 ? snq.x : (q == 1 ? snq.y : (q == 2 ? snq.z : snq.w));
-            const float okv = q == 0 ? okq.x : (q == 1 ? okq.y : (q == 2 ? okq.z : okq.w));
-            const float pp_ = fmaf(mrec.z, c4.z, fmaf(mrec.y, c4.y, mrec.x * c4.x));
-            const float rx = fmaf(-pp_, c4.x, mrec.x), ry = fmaf(-pp_, c4.y, mrec.y), rz = fmaf(-pp_, c4.z, mrec.z);
-            const float qq = __builtin_amdgcn_sqrtf(fmaf(rz, rz, fmaf(ry, ry, rx * rx))) * (1.0f - 1e-6f);      // (cone_keep with the hardware root, rounded down)
-            const float gap = fmaf(qq, c4.w, -fabsf(pp_) * snv);
-            const bool keep = (lane < nb) & !((qdone >> q) & 1u) & ((okv == 0.f) | !(gap > reach));
-            const unsigned long long m = __ballot(keep);
-            cq[q] = __popcll(m);
-            kbits |= keep ? (1u << q) : 0u;
-            Q8[q * kS2QL + (keep ? __popcll(m & ((1ull << lane) - 1ull)) : kS2QL - 1)] = (unsigned char)(keep ? lane : 64);
-          }
-          __syncthreads();
-#ifdef VOGE_SWEEP_TIMES
-          const unsigned long long tsb = wall_clock64();
-          ts_fill += tsb - tsa;
-          int st_trips = 0;
-#endif
-          const float lbl = S.lb[lane];
-          const int myq = ((lane >> 2) & 1) | ((lane >> 4) & 2);
-          const unsigned char *const myQ = Q8 + myq * kS2QL;
-          int trips = (max(max(cq[0], cq[1]), max(cq[2], cq[3])) + 3) >> 2;
-          unsigned Icur = *reinterpret_cast<const unsigned *>(myQ), Inx = *reinterpret_cast<const unsigned *>(myQ + 4);
-          float4 Rn[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) Rn[k] = QR[(Icur >> (8 * k)) & 0xffu];
-          for (int t = 0; t < trips; ++t) {
-            if ((t & 3) == 0 && binned && unit_rays) {
-              // the exit test, per quadrant: all of its rays hold K hits and the bound of a staged entry lies above every K-th len
-              const unsigned long long fullm = __ballot(!valid || cnt == K);
-              unsigned ready = 0u;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const unsigned long long qm = (0x0F0F0F0Full << (4 * (q & 1))) << (32 * (q >> 1));
-                if (!((qdone >> q) & 1u) && (fullm & qm) == qm) ready |= 1u << q;
-              }
-              if (ready != 0u) {      // (uniform)
-                float v = valid ? worstf : -INFINITY;
-                v = fmaxf(v, VOGE_DPP(v, 0xB1)); v = fmaxf(v, VOGE_DPP(v, 0x4E)); v = fmaxf(v, VOGE_DPP(v, 0x128));
-                const float wq[4] = {fmaxf(VOGE_LANE(v, 0), VOGE_LANE(v, 16)), fmaxf(VOGE_LANE(v, 4), VOGE_LANE(v, 20)),
-                                     fmaxf(VOGE_LANE(v, 32), VOGE_LANE(v, 48)), fmaxf(VOGE_LANE(v, 36), VOGE_LANE(v, 52))};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                  if ((ready >> q) & 1u) {
-                    const unsigned long long ex = __ballot(lane < nb && lbl > wq[q]);
-                    if (ex) {
-                      cq[q] = __popcll(__ballot((kbits >> q) & 1u) & ((1ull << __builtin_ctzll(ex)) - 1ull));
-                      qdone |= 1u << q;
-                    }
-                  }
-                }
-                trips = (max(max(cq[0], cq[1]), max(cq[2], cq[3])) + 3) >> 2;
-                wdone = qdone == 15u;
-                if (t >= trips) break;
-              }
-            }
-            const unsigned I = Icur;
-            float len[4], act[4];
-            {
-              // pair_eval_iso's operations, bit for bit, two candidates per packed instruction (as the 64-ray form below)
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const float4 r0 = Rn[2 * h], r1 = Rn[2 * h + 1];
-                const v2f x2 = (v2f){r0.x, r1.x}, y2 = (v2f){r0.y, r1.y}, z2 = (v2f){r0.z, r1.z}, a2 = (v2f){r0.w, r1.w};
-                const v2f md = pk_fma(z2, splat(dz), pk_fma(y2, splat(dy), x2 * splat(dx)));
-                const v2f tt = md * splat(rdn2);
-                const v2f vx = pk_fma(-tt, splat(dx), x2), vy = pk_fma(-tt, splat(dy), y2), vz = pk_fma(-tt, splat(dz), z2);
-                const v2f a = a2 * pk_fma(vz, vz, pk_fma(vy, vy, vx * vx));
-                len[2 * h] = tt.x; len[2 * h + 1] = tt.y;
-                act[2 * h] = a.x; act[2 * h + 1] = a.y;
-              }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(len[q]), "+v"(act[q]));
-            Icur = Inx;
-            Inx = *reinterpret_cast<const unsigned *>(myQ + min(4 * (t + 2), 64));
-#pragma unroll
-            for (int k = 0; k < 4; ++k) Rn[k] = QR[(Icur >> (8 * k)) & 0xffu];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) commit(len[k], act[k], (unsigned)base + ((I >> (8 * k)) & 0xffu));
-#ifdef VOGE_SWEEP_TIMES
-            ++st_trips;
-#endif
-          }
-#ifdef VOGE_SWEEP_TIMES
-          ts_cons += wall_clock64() - tsb;
-          st_eval += 4 * st_trips;
-#endif
-          continue;
-        }
-      }
 #endif
       // ---- stage ----
       int nbuf;
@@ -765,7 +514,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       // the same compare) or never-hit padding. ----
       const float lbl = S.lb[lane];      // (the bound of staged entry `lane`)
       int n = nbuf;
-#if VOGE_S2_PREFETCH
       // The records of trip s0 + 4 are requested BEFORE trip s0's commits (round 5): the loop used to issue its five
       // ds_read_b128 and wait for them at once -- behind the previous trip's eight ds_write still in the wave's LDS queue --
       // so every trip of four candidates began with an exposed LDS round trip (SQ_WAIT_ANY: 42 % of the kernel's wave
@@ -774,7 +522,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
       float4 Xn = *reinterpret_cast<const float4 *>(&S.x[0]), Yn = *reinterpret_cast<const float4 *>(&S.y[0]),
              Zn = *reinterpret_cast<const float4 *>(&S.z[0]), An = *reinterpret_cast<const float4 *>(&S.a[0]);
       int4 Pn = *reinterpret_cast<const int4 *>(&S.pos[0]);
-#endif
       // (GEN: the eleven further arrays one trip ahead as well -- read at their use they stalled every trip for an LDS round
       //  trip at two waves per SIMD: SQ_WAIT_ANY + 28 % against round 3's general sweep, profiles/r5_pmc_sq_counters_gen.txt)
       float4 Evn[GEN ? 11 : 1];
@@ -797,14 +544,8 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
             if (n <= s0) break;
           }
         }
-#if VOGE_S2_PREFETCH
         const float4 X = Xn, Y = Yn, Z = Zn, A = An;
-        const int4 P = Pn;
-#else
-        const float4 X = *reinterpret_cast<const float4 *>(&S.x[s0]), Y = *reinterpret_cast<const float4 *>(&S.y[s0]),
-                     Z = *reinterpret_cast<const float4 *>(&S.z[s0]), A = *reinterpret_cast<const float4 *>(&S.a[s0]);
-        const int4 P = *reinterpret_cast<const int4 *>(&S.pos[s0]);      // the entries' handles (id or stream position)
-#endif
+        const int4 P = Pn;      // the entries' handles (id or stream position)
         const int pv[4] = {P.x, P.y, P.z, P.w};
         float len[4], act[4];
         const unsigned gbits = GEN ? (unsigned)(gmask >> s0) & 15u : 0u;      // (uniform) which of the trip's four are general
@@ -876,7 +617,6 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
             }
           }
         } else {
-#if VOGE_S2_PACKED
         // pair_eval_iso's operations, bit for bit, two candidates per instruction (v_pk_mul / v_pk_fma_f32: the halves of a
         // ds_read_b128 are aligned register pairs already).  A packed FMA costs 1.7x a plain one on a SIMD that is shared
         // by several waves and the same as one when the wave runs alone (tools/valu_bench.hip) -- the heavy tiles at the
@@ -892,25 +632,12 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
           len[2 * h] = t.x; len[2 * h + 1] = t.y;
           act[2 * h] = a.x; act[2 * h + 1] = a.y;
         }
-#else
-        const float mx[4] = {X.x, X.y, X.z, X.w}, my[4] = {Y.x, Y.y, Y.z, Y.w}, mz[4] = {Z.x, Z.y, Z.z, Z.w}, av[4] = {A.x, A.y, A.z, A.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {      // pair_eval_iso's operations, bit for bit
-          const float md = fmaf(mz[q], dz, fmaf(my[q], dy, mx[q] * dx));
-          const float t = md * rdn2;      // (no +0: a len of -0 orders, ties and re-evaluates exactly like +0 under float compares)
-          const float vx = fmaf(-t, dx, mx[q]), vy = fmaf(-t, dy, my[q]), vz = fmaf(-t, dz, mz[q]);
-          len[q] = t;
-          act[q] = av[q] * fmaf(vz, vz, fmaf(vy, vy, vx * vx));
-        }
-#endif
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(len[q]), "+v"(act[q]));      // four interleaved chains, then the commits
-#if VOGE_S2_PREFETCH
         Xn = *reinterpret_cast<const float4 *>(&S.x[s0 + 4]); Yn = *reinterpret_cast<const float4 *>(&S.y[s0 + 4]);
         Zn = *reinterpret_cast<const float4 *>(&S.z[s0 + 4]); An = *reinterpret_cast<const float4 *>(&S.a[s0 + 4]);
         Pn = *reinterpret_cast<const int4 *>(&S.pos[s0 + 4]);
-#endif
         if (GEN && chunk_diag) {         // (uniform) s11, s22 and b: all a diagonal trip reads
 #pragma unroll
           for (int r = 0; r < 11; ++r)
@@ -1047,10 +774,10 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
               od[q] = (q < nv[u]) ? o.dsd : 0.0f;
             }
             if (nv[u] < 0) continue;
-            st16i<(VOGE_NT_STORES & 2) != 0>(t_idx + rel[u], oi[u][0], oi[u][1], oi[u][2], oi[u][3]);
-            st16f<(VOGE_NT_STORES & 2) != 0>(t_len + rel[u], ol[u][0], ol[u][1], ol[u][2], ol[u][3]);
-            st16f<(VOGE_NT_STORES & 2) != 0>(t_act + rel[u], oa[0], oa[1], oa[2], oa[3]);
-            st16f<(VOGE_NT_STORES & 2) != 0>(t_dsd + rel[u], od[0], od[1], od[2], od[3]);
+            st16i<true>(t_idx + rel[u], oi[u][0], oi[u][1], oi[u][2], oi[u][3]);
+            st16f<true>(t_len + rel[u], ol[u][0], ol[u][1], ol[u][2], ol[u][3]);
+            st16f<true>(t_act + rel[u], oa[0], oa[1], oa[2], oa[3]);
+            st16f<true>(t_dsd + rel[u], od[0], od[1], od[2], od[3]);
           }
         } else {
           float *const t_act = out_act + tile_pix * K, *const t_dsd = out_dsd + tile_pix * K;
@@ -1081,10 +808,10 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
                 od[q] = (q < nv[u]) ? o.dsd : 0.0f;
               }
               if (nv[u] < 0) continue;
-              st16i<(VOGE_NT_STORES & 2) != 0>(t_idx + rel[u], oi[u][0], oi[u][1], oi[u][2], oi[u][3]);
-              st16f<(VOGE_NT_STORES & 2) != 0>(t_len + rel[u], ol[u][0], ol[u][1], ol[u][2], ol[u][3]);
-              st16f<(VOGE_NT_STORES & 2) != 0>(t_act + rel[u], oa[0], oa[1], oa[2], oa[3]);
-              st16f<(VOGE_NT_STORES & 2) != 0>(t_dsd + rel[u], od[0], od[1], od[2], od[3]);
+              st16i<true>(t_idx + rel[u], oi[u][0], oi[u][1], oi[u][2], oi[u][3]);
+              st16f<true>(t_len + rel[u], ol[u][0], ol[u][1], ol[u][2], ol[u][3]);
+              st16f<true>(t_act + rel[u], oa[0], oa[1], oa[2], oa[3]);
+              st16f<true>(t_dsd + rel[u], od[0], od[1], od[2], od[3]);
             }
           }
         }

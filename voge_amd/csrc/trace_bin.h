@@ -19,12 +19,6 @@
 // Both tests are conservative (cone_keep / cone_keep_ell, voge_common.h), so the sweep's result equals the
 // brute-force "-1" candidate list of VoGE/RayTracing.py:22-26.
 #pragma once
-#ifndef VOGE_BINA_REGION_RECT
-#define VOGE_BINA_REGION_RECT 1
-#endif
-#ifndef VOGE_XCD_CHAIN
-#define VOGE_XCD_CHAIN 0     // 1: a region's 16 binA slices AND its 64 binB quads on XCD (region % 8): binB finds the segments in the L2 binA wrote them through
-#endif
 #include <type_traits>
 
 #include "voge_common.h"
@@ -201,15 +195,8 @@ binA_kernel(const ConeRec *__restrict__ cones /* [B][nst] */, const int nstx, co
             const CamView cam /* R != NULL: cones, centre and view axis from the camera; `cones` is not read */) {
   __shared__ BinALds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int region = blockIdx.x / kParts, part = blockIdx.x - region * kParts;
+  const int region = blockIdx.x / kParts, part = blockIdx.x - region * kParts;
   const int b = blockIdx.y;
-#if VOGE_XCD_CHAIN
-  if (((gridDim.x / kParts) & 7) == 0) {      // workgroup id % 8 = the XCD (round-robin dispatch): all of a region's slices on XCD region % 8
-    const int j = blockIdx.x >> 3;
-    region = (blockIdx.x & 7) + 8 * (j / kParts);
-    part = j % kParts;
-  }
-#endif
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *pool_top = 0ull;
   const int rx = region % nst0x, ry = region / nst0x;
   const int nst = nstx * nsty;
@@ -261,10 +248,10 @@ binA_kernel(const ConeRec *__restrict__ cones /* [B][nst] */, const int nstx, co
     const int cc = lane & (kCh * kCh - 1);
     const int cx = rx * kCh + (cc & (kCh - 1)), cy = ry * kCh + cc / kCh;
     ConeRec r = {0.f, 0.f, 1.f, 1.f, 0.f, -1.f, 0.f, 0.f};      // ok = -1: no such super-tile
-    // (VOGE_BINA_REGION_RECT, round 6: with the camera at hand and a contiguous band the region's OWN cone comes from its own four
+    // (round 6: with the camera at hand and a contiguous band the region's OWN cone comes from its own four
     //  corner rays -- lane 16 makes it in the same call that makes the sixteen children -- instead of the conservative union of the
     //  children below: tighter, and the union's chain of wave reductions leaves the head of every workgroup)
-    const bool region_rect = (VOGE_BINA_REGION_RECT != 0) && cam.R != nullptr && cam.h <= cam.stripe_h;      // (uniform)
+    const bool region_rect = cam.R != nullptr && cam.h <= cam.stripe_h;      // (uniform)
     if (cam.R != nullptr) {      // (uniform branch)
       const bool reg = region_rect && lane == kCh * kCh;
       const int j0 = reg ? rx * kCh * kST : cx * kST, i0 = reg ? ry * kCh * kST : cy * kST, ext = reg ? kCh * kST : kST;
@@ -442,7 +429,6 @@ binA_kernel(const ConeRec *__restrict__ cones /* [B][nst] */, const int nstx, co
               }
               fill += __popcll(m);
             }
-  #ifndef VOGE_NO_SEG_EXT      // (A/B builds: no extensions -- a segment beyond kSegCap counts as overflowed)
             if (__builtin_expect(fill > kSegCap, 0)) {      // (uniform, rare) this trip's entries beyond the inline part
               const int need = (fill - kSegCap + kExtChunk - 1) / kExtChunk;
               while (ext_have >= 0 && ext_have < need) {      // (uniform) one more chunk from the workgroup's arena
@@ -468,7 +454,6 @@ binA_kernel(const ConeRec *__restrict__ cones /* [B][nst] */, const int nstx, co
                 }
               }
             }
-  #endif
           }
           if (lane == 0) { L.base[cc] = fill; L.extn[cc] = ext_have; }
         }
@@ -533,13 +518,6 @@ struct BinLds {
   int toff[kTilesPerQuad];         // long path: where each tile's list starts in the pool (-1: the pool is exhausted)
 };
 
-#ifndef VOGE_ELL_KEY
-#define VOGE_ELL_KEY 0
-#endif
-
-#ifndef VOGE_BINB_XCD
-#define VOGE_BINB_XCD 0      // 1: the four quads of a super-tile on one XCD (measured: entry 69.8 -> 70.9 us, lean equal -- off)
-#endif
 #ifndef VOGE_BINB_GU
 #define VOGE_BINB_GU 8
 #endif
@@ -572,13 +550,9 @@ __device__ __forceinline__ void bin_test_batch(const BinStream &S, const int (&g
         const float4 e0 = S.ellb[2 * (size_t)gid[j]], e1 = S.ellb[2 * (size_t)gid[j] + 1];
         kp[j] = cone_keep_ell(c[j], e0, e1, S.qcone);
         el[j] = kp[j];
-        // order key: VOGE_ELL_KEY 0 = the centre's depth along the axis, 1 = the entry's own lower bound of len
+        // order key: the centre's depth along the axis
         const float pa = fmaf(c[j].z, S.qcone.az, fmaf(c[j].y, S.qcone.ay, c[j].x * S.qcone.ax));
-#if VOGE_ELL_KEY == 1
-        gkey[j] = pa - ell_support(e0, e1, S.qcone.ax, S.qcone.ay, S.qcone.az) + 0.0f;
-#else
         gkey[j] = pa + 0.0f;
-#endif
       }
     }
   }
@@ -916,20 +890,10 @@ binB_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ell, con
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   BIN_TS(1, 7);      // (kernel entry)
   const int b = blockIdx.y;
-  // super-tile of this batch element, quad inside it.  (VOGE_BINB_XCD=1 puts the four quads of a super-tile, which read the same
-  // 16 segments, 8 workgroup ids apart = on one XCD's L2: fewer HBM reads, but the entry is 1 us SLOWER with it and the
-  // renderer's form unchanged -- HISTORY R5 -- so it is off.)
-  int binl = blockIdx.x >> 2, qq = blockIdx.x & 3;
-#if VOGE_BINB_XCD
-  if ((int)blockIdx.x < ((nstx * nsty) >> 3) << 5) { binl = ((blockIdx.x >> 5) << 3) + (blockIdx.x & 7); qq = (blockIdx.x >> 3) & 3; }
-#endif
-#if VOGE_XCD_CHAIN
-  if ((nstx & 3) == 0 && (nsty & 3) == 0 && (((nstx >> 2) * (nsty >> 2)) & 7) == 0) {      // (the same rule as binA's: whole regions, a multiple of 8 of them)
-    const int j = blockIdx.x >> 3, region = (blockIdx.x & 7) + 8 * (j >> 6), w = j & 63, nst0x = nstx >> 2;
-    qq = w & 3;
-    binl = ((region / nst0x) * 4 + (w >> 4)) * nstx + (region % nst0x) * 4 + ((w >> 2) & 3);
-  }
-#endif
+  // super-tile of this batch element, quad inside it.  (Putting the four quads of a super-tile, which read the same 16
+  // segments, on one XCD's L2 means fewer HBM reads, but the entry is 1 us SLOWER with it and the renderer's form unchanged
+  // -- HISTORY R5.)
+  const int binl = blockIdx.x >> 2, qq = blockIdx.x & 3;
   const int stx = binl % nstx, sty = binl / nstx;
   const int bin = b * nstx * nsty + binl;
   const int quad = bin * 4 + qq;
@@ -1073,17 +1037,6 @@ binB_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ell, con
   BinKeys Kk;
   Kk.lo = lo; Kk.scale = scale; Kk.span = span; Kk.slack = 1.13f * rm * (1.0f + 1e-5f); Kk.flagged = flagged;
   auto bucket_of = [&](const uint64_t k) { return bin_bucket_of(Kk, ord2f((uint32_t)(k >> 32))); };
-#ifdef VOGE_NO_LONG      // (A/B builds: the pre-pool behaviour -- such quads stream every Gaussian in the sweep)
-  if (total > kQCap) {
-    if (tid == 0) q_count[quad] = -1;
-    if (lane == 0) {
-      if (tile_ok) tl_count[tile] = -1;
-      my_order[wave] = make_int2(tile_ok ? tile : -1, -1);
-    }
-    return;
-  }
-  {
-#else
   if (__builtin_expect(total > kQCap, 0)) {
     BinLong A;
     A.S = S; A.Kk = Kk; A.tcone = tcone; A.tile_ok = tile_ok; A.tile = tile; A.quad = quad; A.total = total;
@@ -1091,7 +1044,6 @@ binB_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ell, con
     A.pool_id = pool_id; A.pool_lb = pool_lb; A.my_order = my_order; A.seg_ext = seg_ext; A.bin = bin;
     binB_long_path<ELL>(A, L);
   } else {
-#endif
   for (int i = tid; i < total; i += kQT) {
     const uint64_t kk = L.keys[i];
     const int q = bucket_of(kk);
@@ -1253,15 +1205,15 @@ binB_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ell, con
       for (int it = tid; it < th * ipr; it += kQT) {
         const int rr = it / ipr, j4 = it - rr * ipr;
         const size_t o = (((size_t)b * H + fty * 8 + rr) * W + (size_t)ftx * 8) * K + (size_t)j4 * 4;
-        st16i<(VOGE_NT_STORES & 1) != 0>(out_idx + o, -1, -1, -1, -1);
-        st16f<(VOGE_NT_STORES & 1) != 0>(out_len + o, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN);
+        st16i<true>(out_idx + o, -1, -1, -1, -1);
+        st16f<true>(out_len + o, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN, VOGE_SENT_LEN);
         if (out_weight != nullptr) {
           // fused trace + composite: the fragments are (weight, idx, len); act / dsd only serve the backward, which
           // never reads a pixel without hits -- a quarter of the empty tiles' bytes stays unwritten
           *reinterpret_cast<float4 *>(out_weight + o) = make_float4(0.f, 0.f, 0.f, 0.f);
         } else if (out_act != nullptr) {      // (NULL: the scalar-sigma fragment entry points keep no act / dsd)
-          st16f<(VOGE_NT_STORES & 1) != 0>(out_act + o, VOGE_SENT_ACT, VOGE_SENT_ACT, VOGE_SENT_ACT, VOGE_SENT_ACT);
-          st16f<(VOGE_NT_STORES & 1) != 0>(out_dsd + o, 0.f, 0.f, 0.f, 0.f);
+          st16f<true>(out_act + o, VOGE_SENT_ACT, VOGE_SENT_ACT, VOGE_SENT_ACT, VOGE_SENT_ACT);
+          st16f<true>(out_dsd + o, 0.f, 0.f, 0.f, 0.f);
         }
       }
     } else {

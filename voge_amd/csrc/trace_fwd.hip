@@ -481,10 +481,7 @@ trace_fwd_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ evr
             }
           }
 #endif
-#ifndef VOGE_ISO_ROWS4
-#define VOGE_ISO_ROWS4 0
-#endif
-          topk_commit<(!ISO) || (VOGE_ISO_ROWS4 != 0)>(mykeys, TP, K, cnt, worst, tail, key, take);
+          topk_commit<!ISO>(mykeys, TP, K, cnt, worst, tail, key, take);
         };
 #ifdef VOGE_SWEEP_STATS
         st_eval += __popcll(m); ++st_batches;
@@ -767,10 +764,10 @@ trace_fwd_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ evr
       wave_lds_sync();      // the rows are rewritten by the next round
       if (cur.on) {
         const size_t ob = cur.pix * K + k0;
-        st16i<(VOGE_NT_STORES & 2) != 0>(out_idx + ob, oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_len + ob, ol[0], ol[1], ol[2], ol[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_act + ob, oa[0], oa[1], oa[2], oa[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_dsd + ob, od[0], od[1], od[2], od[3]);
+        st16i<true>(out_idx + ob, oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
+        st16f<true>(out_len + ob, ol[0], ol[1], ol[2], ol[3]);
+        st16f<true>(out_act + ob, oa[0], oa[1], oa[2], oa[3]);
+        st16f<true>(out_dsd + ob, od[0], od[1], od[2], od[3]);
         *reinterpret_cast<float4 *>(out_weight + ob) = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
         if (q == 0 && out_valid != nullptr) out_valid[cur.pix] = (int64_t)cur.cntp;
       }
@@ -849,10 +846,10 @@ trace_fwd_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ evr
             od[q] = o.dsd;
           }
         }
-        st16i<(VOGE_NT_STORES & 2) != 0>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
+        st16i<true>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
+        st16f<true>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
+        st16f<true>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
+        st16f<true>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
       }
     }
     // Fragment mode without act / dsd (out_act == NULL; voge_fragments_fwd_iso*): index and len are the key itself --
@@ -957,10 +954,10 @@ trace_fwd_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ evr
             od[q] = o.dsd;
           }
         }
-        st16i<(VOGE_NT_STORES & 2) != 0>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
-        st16f<(VOGE_NT_STORES & 2) != 0>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
+        st16i<true>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
+        st16f<true>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
+        st16f<true>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
+        st16f<true>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
       }
     }
   }
@@ -1143,7 +1140,7 @@ static size_t trace_ws_layout(int B, int N, int H, int W, void *base, TraceWs *w
        *sc = take(nbin * kParts * 4), *si = take(nbin * kParts * (size_t)kSegCap * 4), *bc = take(nbin * 4 * 4),
        *bi = take(nbin * 4 * kQCap * 4), *bl = take(nbin * 4 * kQCap * 4), *tc = take(ntile * 4),
        *ti = take(ntile * kTileCap * 4), *tl = take(ntile * kTileCap * 4), *sr = take(nbin * kParts * (size_t)kSegCap * 16),
-       *cq = take(nbin * kTilesPerBin * 8 * 2);      // (second half: the exactly sorted copy of VOGE_EXACT_ORDER builds)
+       *cq = take(nbin * kTilesPerBin * 8 * 2);      // (second half: unused since the exact order sort went -- HISTORY.md, "Removed switches")
   const size_t npool = trace_pool_entries(P);
   char *pi = take(npool * 4), *pl = take(npool * 4), *to = take(ntile * 4);
   const int nst0x = (W + kST0 - 1) / kST0, nst0y = (H + kST0 - 1) / kST0;
@@ -1173,47 +1170,6 @@ static size_t trace_ws_layout(int B, int N, int H, int W, void *base, TraceWs *w
   return off;
 }
 
-#ifndef VOGE_EXACT_ORDER
-#define VOGE_EXACT_ORDER 0        // (experiment) re-sort the launch order exactly by list length with one extra launch
-#endif
-// One workgroup: counting sort of the n launch slots by descending list length (overflowed lists first, empty tiles
-// and slots outside the image last).
-__global__ void __launch_bounds__(1024) order_sort_kernel(const int2 *__restrict__ in, int2 *__restrict__ out, const int n) {
-  constexpr int NB = 3072;      // >= kTileCap + 3 buckets, 3 per thread
-  __shared__ int hist[NB];
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < NB; i += 1024) hist[i] = 0;
-  __syncthreads();
-  auto bucket = [](const int2 v) { return (v.x < 0 || v.y == 0) ? kTileCap + 2 : (v.y < 0 ? 0 : 1 + (kTileCap - min(v.y, kTileCap))); };
-  for (int i = tid; i < n; i += 1024) atomicAdd(&hist[bucket(in[i])], 1);
-  __syncthreads();
-  const int a = hist[3 * tid], b = hist[3 * tid + 1], c = hist[3 * tid + 2];
-  int x = a + b + c;
-  const int own = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  int off = x - own;
-  for (int w = 0; w < wave; ++w) off += wsum[w];
-  hist[3 * tid] = off; hist[3 * tid + 1] = off + a; hist[3 * tid + 2] = off + a + b;
-  __syncthreads();
-  for (int i = tid; i < n; i += 1024) {
-    const int2 v = in[i];
-    out[atomicAdd(&hist[bucket(v)], 1)] = v;
-  }
-}
-
-#ifndef VOGE_FUSED_EPILOGUE
-#define VOGE_FUSED_EPILOGUE 0      // (experiment, see trace_chunk_fwd) composite inside the sweep's epilogue
-#endif
-#ifndef VOGE_SWEEP_LDS_PAD
-#define VOGE_SWEEP_LDS_PAD 0      // (occupancy experiments: extra dynamic LDS per workgroup)
-#endif
 // -DVOGE_AB builds only (libvoge_hip_ab.so, never the product library): a process-wide switch between sweep_iso_kernel (0)
 // and round 3's scalar-sigma sweep, trace_fwd_kernel<1, true> (1) -- for A/B timing and the bit-for-bit comparison in
 // tests/test_gpu_configs.py (voge_debug_sweep_variant).  The product library has neither the switch nor the old kernel.
@@ -1224,26 +1180,19 @@ static std::atomic<int> g_sweep_variant{0};
 template <bool ISO>
 static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *rays, int B, int N, int H, int W, int K,
                         float thr_act, int32_t *idx, float *len, float *act, float *dsd, int32_t *cnt, float occ,
-                        float *weight, int64_t *valid_num, hipStream_t st, const CamView &cam, const bool diag = false) {
+                        hipStream_t st, const CamView &cam, const bool diag = false) {
   constexpr int T = 64;
   // (diag: every general form of the launch is a per-axis one -- the frame path's gen_kind 1 -- sweep_iso_kernel<2>)
   const int gen = ISO ? 0 : (diag ? 2 : 1);
   const auto sweep = ISO ? sweep_iso_kernel<0> : (diag ? sweep_iso_kernel<2> : sweep_iso_kernel<1>);
-  // (fused composite epilogue: three padded per-pixel rows (len, s', E) for one round of 64 / (K/4) pixels)
-  const size_t comp = (weight != nullptr) ? sizeof(float) * 3 * (size_t)compn_rows(K, 4, 64, true) : 0;
-  const size_t lds = ((sizeof(uint64_t) * (size_t)(K + 1) * (T + 1) + 15) & ~(size_t)15) + ((sizeof(TraceLds<T, ISO>) + 15) & ~(size_t)15) +
-                     comp + VOGE_SWEEP_LDS_PAD;
-  // no composite inside the epilogue: sweep_iso_kernel (sweep_iso.h: float-compare commits, 6-byte list entries) -- <false> for
-  // scalar sigmas (round 4), <true> for the general forms (round 5)
+  // sweep_iso_kernel (sweep_iso.h: float-compare commits, 6-byte list entries) -- <0> for scalar sigmas (round 4), <1> / <2>
+  // for the general forms (round 5)
 #ifdef VOGE_AB
-  const bool v2 = VOGE_SWEEP_V2 && weight == nullptr && g_sweep_variant.load(std::memory_order_relaxed) != 1;
-  constexpr bool kOld = true;
+  const bool v2 = g_sweep_variant.load(std::memory_order_relaxed) != 1;
 #else
-  const bool v2 = VOGE_SWEEP_V2 && weight == nullptr;
-  constexpr bool kOld = !VOGE_SWEEP_V2 || VOGE_FUSED_EPILOGUE;      // (the product keeps round 3's sweeps out of the library)
-  if (!v2 && !kOld) return VOGE_ERR_BAD_ARG;
+  constexpr bool v2 = true;
 #endif
-  const size_t lds2 = sweep2_lds_bytes(K, gen) + VOGE_SWEEP_LDS_PAD;
+  const size_t lds2 = sweep2_lds_bytes(K, gen);
   {
     static DynLdsCache cache2[2];      // (one per kernel of this instantiation)
     if (v2) {
@@ -1251,25 +1200,24 @@ static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *ra
       if (rc) return rc;
     }
   }
-  if constexpr (kOld) if (!v2) {
+#ifdef VOGE_AB
+  const size_t lds = ((sizeof(uint64_t) * (size_t)(K + 1) * (T + 1) + 15) & ~(size_t)15) + ((sizeof(TraceLds<T, ISO>) + 15) & ~(size_t)15);
+  if (!v2) {
     static DynLdsCache cache;
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trace_fwd_kernel<1, ISO && kOld>), lds, cache);
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trace_fwd_kernel<1, ISO>), lds, cache);
     if (rc) return rc;
   }
+#endif
   hipLaunchKernelGGL(binB_kernel<!ISO>, dim3(ws.nstx * ws.nsty * 4, B), dim3(kQT), 0, st, ws.cull, ws.ell, ws.seg_count, ws.seg_id, ws.seg_rec,
                      cones, N, H, W, ws.nstx, ws.nsty, ws.nbin, ws.q_count, ws.q_id, ws.q_lb, ws.tl_count, ws.tl_id, ws.tl_lb,
                      ws.order, ws.pool_top, ws.pool_cap, ws.pool_id, ws.pool_lb, ws.tl_off, ws.seg_ext, ws.ext_id, K,
                      (v2 && act == nullptr) ? nullptr : idx /* (sweep_iso_kernel writes the empty tiles itself) */, len, act, dsd, cnt,
-                     weight, valid_num, cam);
+                     nullptr, nullptr, cam);
   {
     int rc = launch_status();
     if (rc) return rc;
   }
   const int2 *order = ws.order;
-#if VOGE_EXACT_ORDER
-  hipLaunchKernelGGL(order_sort_kernel, dim3(1), dim3(1024), 0, st, ws.order, ws.order + (size_t)ws.nbin * kTilesPerBin, ws.nbin * kTilesPerBin);
-  order = ws.order + (size_t)ws.nbin * kTilesPerBin;
-#endif
   dim3 grid(ws.nbin * kTilesPerBin);     // one workgroup per tile slot of every super-tile (slots outside the image exit)
   if (v2) {
     hipLaunchKernelGGL(sweep, grid, dim3(T), lds2, st, ws.cull, ws.ms, ws.evr, rays, ws.q_count, ws.q_id, ws.q_lb, ws.tl_id,
@@ -1277,12 +1225,12 @@ static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *ra
                        thr_act, idx, len, act, dsd, cnt, cam);
     return launch_status();
   }
+#ifdef VOGE_AB
   if (cam.R != nullptr) return VOGE_ERR_BAD_ARG;      // (round 3's sweeps read the bundle)
-  if constexpr (kOld) {
-    hipLaunchKernelGGL((trace_fwd_kernel<1, ISO && kOld>), grid, dim3(T), lds, st, ws.cull, ws.evr, ws.ms, rays, ws.q_count, ws.q_id, ws.q_lb,
-                       ws.tl_count, ws.tl_id, ws.tl_lb, ws.pool_id, ws.pool_lb, ws.tl_off, order, ((W + 7) / 8) * ((H + 7) / 8), ws.nstx,
-                       ws.nstx * ws.nsty, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, weight, valid_num);
-  }
+  hipLaunchKernelGGL((trace_fwd_kernel<1, ISO>), grid, dim3(T), lds, st, ws.cull, ws.evr, ws.ms, rays, ws.q_count, ws.q_id, ws.q_lb,
+                     ws.tl_count, ws.tl_id, ws.tl_lb, ws.pool_id, ws.pool_lb, ws.tl_off, order, ((W + 7) / 8) * ((H + 7) / 8), ws.nstx,
+                     ws.nstx * ws.nsty, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, nullptr, nullptr);
+#endif
   return launch_status();
 }
 
@@ -1518,19 +1466,14 @@ static int trace_chunk_fwd(const int iso_in, const IsoView view, const float *mu
   // One wave (an 8x8 pixel tile) per sweep workgroup.  Residency is set by the LDS top-K lists (~7 waves per CU at
   // K = 40), and independent single-wave workgroups measured 4-10 % faster than 16x8 / 16x16 tiles in round 1.
   // Fragments wanted as well (weight != NULL): the stand-alone composite kernel runs behind the sweep.  Compositing
-  // inside the sweep's epilogue (VOGE_FUSED_EPILOGUE=1 builds, K % 4 == 0; same bits, tests/test_gpu_parity.py) was
-  // built and measured: the sweep holds ~1.5 waves per SIMD (its top-K lists fill the LDS), so the composite's row
-  // walks run latency-bound there -- sweep 64 -> 142 us at cfg3 against 52 us for the kernel it would replace, which
-  // does the same instructions at eight waves per SIMD and reads its 126 MB mostly from the Infinity Cache.
-  const bool fused = VOGE_FUSED_EPILOGUE && weight != nullptr && (K & 3) == 0 && K <= 256 && cnt != nullptr;
+  // inside the sweep's epilogue was built and measured (same bits; HISTORY.md §5, trace_fwd_kernel): the sweep holds ~1.5 waves per
+  // SIMD (its top-K lists fill the LDS), so the composite's row walks run latency-bound there -- sweep 64 -> 142 us at
+  // cfg3 against 52 us for the kernel it would replace, which does the same instructions at eight waves per SIMD and
+  // reads its 126 MB mostly from the Infinity Cache.
   int rc;
-#ifndef VOGE_NO_ISO_SWEEP
-  if (iso_in) rc = launch_trace<true>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, fused ? weight : nullptr, fused ? valid_num : nullptr, st, cam);
-  else
-#endif
-  rc = launch_trace<false>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, fused ? weight : nullptr, fused ? valid_num : nullptr, st, cam,
-                           view.gen_kind == 1);
-  if (rc || weight == nullptr || fused) return rc;
+  if (iso_in) rc = launch_trace<true>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, st, cam);
+  else rc = launch_trace<false>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, st, cam, view.gen_kind == 1);
+  if (rc || weight == nullptr) return rc;
   if (act == nullptr)
     return voge_composite_fwd_iso(idx, cnt, len, reinterpret_cast<const float *>(ws.ms), cam.R != nullptr ? cam.rays_out : rays, occ,
                                   (long)B * H * W, K, weight, valid_num, stream);

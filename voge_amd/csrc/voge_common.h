@@ -259,11 +259,7 @@ __device__ __forceinline__ void topk_commit(uint64_t *keys, const int stride, co
   cnt += app ? 1 : 0;
   tail = app ? key : tail;
   worst = (app && cnt == K) ? key : worst;
-#ifdef VOGE_NO_SLOW
-  const bool slow = false;
-#else
   const bool slow = take && !app;
-#endif
   // (a divergent `if` is already "skip unless some lane needs it": s_and_saveexec + s_cbranch_execz)
   if (!ROWS4) {
     // row by row: the better form where nearly every out-of-order arrival sits one or two rows deep (scalar-sigma scenes,
@@ -347,9 +343,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 // both, sentinels alone 81.8 (tools/ab_bench.sh, interleaved).  The renderer's form keeps plain stores in its epilogue:
 // its (idx, len) are read by the composite that follows from the Infinity Cache (NT there: trace - 2.4 us, frame - 1 %);
 // the unfused pipeline (voge_fragments_fwd: trace with act / dsd, then the composite) is unchanged either way (118 us).
-#ifndef VOGE_NT_STORES
-#define VOGE_NT_STORES 3      // bit 0: sentinel tiles, bit 1: the epilogue with act / dsd (A/B builds: 0)
-#endif
 typedef float voge_v4f __attribute__((ext_vector_type(4)));
 typedef int voge_v4i __attribute__((ext_vector_type(4)));
 template <bool NT>
@@ -830,11 +823,7 @@ __device__ __forceinline__ void cam_two_cones(const CamK &k, const CamView &c, c
 }
 
 // Does the cull record carry an ellipsoid record (trace_fwd.hip, prep_one)?
-#ifdef VOGE_NO_ELL   // build without the ellipsoid tests (bounding spheres only): for A/B timing
-__device__ __forceinline__ bool cull_has_ell(const float4) { return false; }
-#else
 __device__ __forceinline__ bool cull_has_ell(const float4 c) { return (__float_as_uint(c.w) & 1u) != 0u && c.w > 0.0f && c.w < 3e38f; }
-#endif
 
 // Support function of the hit ellipsoid along n (|n| <= ~1), rounded up.  e0 = (M00, M11, M22, M01),
 // e1 = (M02, M12, slack of n^T M n, additive slack).
@@ -984,35 +973,7 @@ __device__ __forceinline__ void wt_add(WaveTable<NE, NV4> &t, const int slot, co
   }
 }
 
-// Two accumulations per lane in ONE election loop: a lane contends for its first slot until it wins it, then for its
-// second -- lanes that are through with one key move on while others still queue for theirs.  (Two wt_add calls in a row
-// cost the sum of their election rounds: 3.4 + 3.4 at cfg3; tools/fb_sections.py.)  Must be called by the whole wave.
-template <int NE, int NV4>
-__device__ __forceinline__ void wt_add2(WaveTable<NE, NV4> &t, const int slot0, const float4 (&v0)[NV4], const bool on0,
-                                        const int slot1, const float4 (&v1)[NV4], const bool on1, const int lane) {
-  lds_vint *owner = lds_volatile(t.owner);
-  bool p0 = on0, p1 = on1;
-#pragma unroll 1
-  while (__any(p0 | p1)) {
-    const bool use0 = p0, pend = p0 | p1;
-    const int s = use0 ? slot0 : slot1;
-    if (pend) owner[s] = lane;
-    if (pend && owner[s] == lane) {
-      float4 *dst = t.vals + s * NV4;
-#pragma unroll
-      for (int q = 0; q < NV4; ++q) {
-        float4 x = dst[q];
-        x.x += use0 ? v0[q].x : v1[q].x; x.y += use0 ? v0[q].y : v1[q].y;
-        x.z += use0 ? v0[q].z : v1[q].z; x.w += use0 ? v0[q].w : v1[q].w;
-        dst[q] = x;
-      }
-      p1 = use0 ? p1 : false;
-      p0 = false;
-    }
-  }
-}
-
-// The same two accumulations per lane WITHOUT an election, for callers whose lanes come in groups that cannot collide: the
+// Two accumulations per lane WITHOUT an election (wt_add's owner word), for callers whose lanes come in groups that cannot collide: the
 // lanes of one PIXEL hold distinct Gaussians (a Gaussian sits in a pixel's list once), so the pixels of a round take the table
 // one after the other -- `ord` = the lane's pixel ordinal in the round, 0 .. n - 1 -- and inside a step every lane reads,
 // adds and writes its two entries with no owner word written, read back and compared.  The fused backward's rounds hold 3-4
