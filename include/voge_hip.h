@@ -522,6 +522,39 @@ int voge_blend_bwd(const float *rgb, const float *weight, const float *bg, float
                    float *g_weight_add, voge_stream_t stream);
 
 /*
+ * Blend with a background that broadcasts to the image.  Replaces: VoGE/Renderer.py:165-171 (to_colored_background's
+ * `torch.min(rgb + ones * (1 - masks) * background_color, ones)` under torch broadcasting) when background_color is an
+ * image, a colour per view, a grey level or a tensor that requires grad; masks = get_silhouette (:157-159) is the input s.
+ *   rgb, img [B,H,W,C] (any C >= 1), s [B,H,W]: m = min(s, 1) -- a weight sum or a silhouette; thr > 0: m = [m > thr];
+ *   bg read at bg[b*sb + h*sh + w*sw + c*sc]: the element strides of bg.expand(B, H, W, C), 0 on broadcast dimensions;
+ *   img = min(rgb + (1 - m) * bg, 1).
+ */
+int voge_blend_bg_fwd(const float *rgb, const float *s, const float *bg, long sb, long sh, long sw, long sc, float thr,
+                      int B, int H, int W, int C, float *img, voge_stream_t stream);
+
+/*
+ * Its backward (autograd through Renderer.py:171).  g_img read at g_img[pix*gs_pix + c*gs_c] (0, 0: a broadcast scalar,
+ * read in place).  With g = g_img * pass(x), x = rgb + (1 - m) bg, pass = 1 / 0.5 / 0 for x below / at / above 1 (torch.min):
+ *   g_rgb [B,H,W,C] = g (NULL: not wanted);
+ *   g_m [B,H,W] = -sum_c g * bg = d img / d m (NULL: not wanted; must be NULL when thr > 0); the caller's min(sum w, 1)
+ *     applies its own pass(sum w) -- get_silhouette's backward;
+ *   g_bg = g * (1 - m) summed over the broadcast dimensions (NULL: not wanted), written at g_bg[b*gb + h*gh + w*gw + c*gc]
+ *     with 0 on the dimensions where the background broadcasts; gc == 0 sums the channels in the lane:
+ *     - no two pixels on one cell (gb, gh, gw non-zero or their dimension 1): plain stores;
+ *     - one cell per view or one overall (gh, gw zero): per-workgroup partials in `workspace`
+ *       (voge_blend_bg_bwd_workspace_bytes(B, H, W, C) bytes, owned by the caller), added up by a second pass in a fixed
+ *       order: bitwise the same on every run;
+ *     - anything else: VOGE_ERR_BAD_ARG -- hand in a dense [B,H,W,C] (or [B,H,W,1]) gradient and sum it down.
+ * No atomics; nothing to zero beforehand.
+ */
+int voge_blend_bg_bwd(const float *rgb, const float *s, const float *bg, long sb, long sh, long sw, long sc, float thr,
+                      const float *g_img, long gs_pix, long gs_c, int B, int H, int W, int C, float *g_rgb, float *g_m,
+                      float *g_bg, long gb, long gh, long gw, long gc, void *workspace, size_t workspace_bytes,
+                      voge_stream_t stream);
+/* Bytes of voge_blend_bg_bwd's workspace: views x workgroups per view x C floats (0 for invalid sizes). */
+size_t voge_blend_bg_bwd_workspace_bytes(int B, int H, int W, int C);
+
+/*
  * Fused merge + silhouette + blend ("shade").  Replaces, in one pass: interpolate_attr ->
  * merge_final (Aggregation.py:111-141), get_silhouette (Renderer.py:157-159) and
  * to_colored_background (Renderer.py:162-171):

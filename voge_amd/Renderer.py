@@ -326,12 +326,31 @@ def _background_tensor(color, device):
     return t
 
 
+def _plain_color(bg, C, device):
+    """A background that keeps the constant-colour routes -- a tuple, list or tensor with 1 or C elements, every leading
+    dimension 1, no grad -- as a device tensor of the C values (a grey level expanded); None for anything else."""
+    if not torch.is_tensor(bg):
+        if len(bg) not in (1, C):
+            return None
+        return _background_tensor(tuple(bg) * C if len(bg) == 1 else bg, device)
+    if bg.requires_grad or bg.numel() not in (1, C) or any(d != 1 for d in bg.shape[:-1]):
+        return None
+    if bg.numel() == C:
+        return bg if bg.device == device else bg.to(device)
+    if not bg.is_cuda:
+        return _background_tensor((float(bg.reshape(())),) * C, device)
+    return bg.to(device).reshape(1).expand(C)      # (the shade kernels' _dev copies it: no host sync)
+
+
 def to_colored_background(fragments: Fragments, colors: torch.Tensor,
                           background_color: Union[torch.Tensor, tuple, list] = (1, 1, 1), thr: float = -1):
-    if not torch.is_tensor(background_color):
-        background_color = _background_tensor(background_color, colors.device)
-    elif background_color.device != colors.device:
-        background_color = background_color.to(colors.device)
+    plain = _plain_color(background_color, colors.shape[-1], colors.device)
+    if plain is None:
+        # an image, a colour per view, a background that requires grad (Renderer.py:162-171 under torch broadcasting):
+        # interpolate_attr + get_silhouette -- one fused node each way on the frame path -- then the broadcast blend
+        rgb = interpolate_attr(fragments, colors)
+        return ops.blend_background(rgb, get_silhouette(fragments), background_color, thr)
+    background_color = plain
     lz = getattr(fragments, "_lazy", None)
     if lz is not None:
         # fragments whose composite is still pending: weights AND image in one pass (ops._CompositeShade)

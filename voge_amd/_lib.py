@@ -102,6 +102,10 @@ SIGNATURES = {
     "voge_silhouette_fwd": (_c_int, [_c_void_p, _c_long, _c_int] + [_c_void_p] * 3),
     "voge_silhouette_bwd": (_c_int, [_c_void_p] * 2 + [_c_long] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),
+    "voge_blend_bg_fwd": (_c_int, [_c_void_p] * 3 + [_c_long] * 4 + [_c_float] + [_c_int] * 4 + [_c_void_p] * 2),
+    "voge_blend_bg_bwd": (_c_int, [_c_void_p] * 3 + [_c_long] * 4 + [_c_float, _c_void_p, _c_long, _c_long] + [_c_int] * 4
+                          + [_c_void_p] * 3 + [_c_long] * 4 + [_c_void_p, _c_size_t, _c_void_p]),
+    "voge_blend_bg_bwd_workspace_bytes": (_c_size_t, [_c_int] * 4),
 }
 
 _lib = None

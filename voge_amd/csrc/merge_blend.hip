@@ -569,6 +569,118 @@ silhouette_bwd_kernel(const float *__restrict__ wsum, const float *__restrict__ 
   if (p < npix) g_pix[p] = g_sil[p] * clamp1_pass(wsum[p]);
 }
 
+// ------------------------------------------------------------------------------------------
+// Blend with a background that BROADCASTS to the image (to_colored_background with an image, a colour per view, a grey
+// level or a learnable colour: Renderer.py:162-171 as torch broadcasting evaluates it):
+//   img = min(rgb + (1 - m) bg, 1),  m = min(s, 1)  ([m > thr] when thr > 0).
+// One lane per pixel, its C channels in a loop.  bg is read through the element strides of bg.expand(B, H, W, C) -- 0 on
+// the broadcast dimensions, anything on the others (a permuted CHW photograph is read in place).  A workgroup covers
+// kBgPix consecutive pixels of ONE view: view b owns workgroups b * nwg .. b * nwg + nwg - 1, so a workgroup's partial sum
+// belongs to one view.
+// ------------------------------------------------------------------------------------------
+constexpr int kBgPix = 256;
+
+// Sum over the workgroup, in a fixed order (xor butterfly inside each wave, then the waves in order): the value of
+// thread 0 does not depend on timing.  Every thread of the workgroup must call it.
+__device__ __forceinline__ float bg_block_sum(float v, float *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.0f;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < kBgPix / 64; ++i) t += red[i];
+  }
+  __syncthreads();      // (red is reused by the next call)
+  return t;
+}
+
+__global__ void __launch_bounds__(kBgPix)
+blend_bg_fwd_kernel(const float *__restrict__ rgb, const float *__restrict__ s, const float *__restrict__ bg, const long sb,
+                    const long sh, const long sw, const long sc, const float thr, const int H, const int W, const int C,
+                    const int nwg, float *__restrict__ img) {
+  const int b = blockIdx.x / nwg;
+  const int q = (blockIdx.x - b * nwg) * kBgPix + threadIdx.x;      // pixel within view b
+  if (q >= H * W) return;
+  const int h = q / W, w = q - h * W;
+  const long pix = (long)b * H * W + q;
+  float m = fminf(s[pix], 1.0f);
+  if (thr > 0.0f) m = m > thr ? 1.0f : 0.0f;
+  const float um = 1.0f - m;
+  const float *bp = bg + b * sb + h * sh + w * sw;
+  for (int c = 0; c < C; ++c) img[pix * C + c] = fminf(fmaf(um, bp[c * sc], rgb[pix * C + c]), 1.0f);
+}
+
+// Its backward.  g = g_img * pass(x), x = rgb + (1 - m) bg:  g_rgb = g ;  g_m = -sum_c g bg (= d img / d m) ;
+// g_bg = g (1 - m), laid out at g_bg[b gb + h gh + w gw + c gc] (0 on the background's broadcast dimensions):
+//   slab == NULL: no two pixels share a cell -- plain stores (the channels summed in the lane first when gc == 0);
+//   slab != NULL: one cell per view (or overall) -- the workgroup's sum per channel (of all channels when gc == 0) goes to
+//                 slab[blockIdx.x * Cg + c]; blend_bg_slab_kernel adds the partials up in a fixed order.
+__global__ void __launch_bounds__(kBgPix)
+blend_bg_bwd_kernel(const float *__restrict__ rgb, const float *__restrict__ s, const float *__restrict__ bg, const long sb,
+                    const long sh, const long sw, const long sc, const float thr, const float *__restrict__ g_img,
+                    const long gs_pix, const long gs_c, const int H, const int W, const int C, const int nwg,
+                    float *__restrict__ g_rgb, float *__restrict__ g_m, float *__restrict__ g_bg, const long gb, const long gh,
+                    const long gw, const long gc, float *__restrict__ slab) {
+  __shared__ float red[kBgPix / 64];
+  const int b = blockIdx.x / nwg;
+  const int q = (blockIdx.x - b * nwg) * kBgPix + threadIdx.x;
+  const bool ok = q < H * W;      // (no early exit: the slab form sums over the whole workgroup)
+  const int h = ok ? q / W : 0, w = ok ? q - h * W : 0;
+  const long pix = (long)b * H * W + q;
+  float m = ok ? fminf(s[pix], 1.0f) : 1.0f;
+  if (thr > 0.0f) m = m > thr ? 1.0f : 0.0f;
+  const float um = 1.0f - m;
+  const float *bp = bg + b * sb + h * sh + w * sw;
+  float gm = 0.0f, gsum = 0.0f;      // d img / d m ; g_bg summed over the channels (gc == 0)
+  for (int c = 0; c < C; ++c) {
+    float gbc = 0.0f;
+    if (ok) {
+      const float bv = bp[c * sc];
+      const float x = fmaf(um, bv, rgb[pix * C + c]);
+      const float g = g_img[pix * gs_pix + c * gs_c] * clamp1_pass(x);
+      if (g_rgb != nullptr) g_rgb[pix * C + c] = g;
+      gm = fmaf(-g, bv, gm);
+      gbc = g * um;
+    }
+    if (g_bg == nullptr) continue;
+    if (gc == 0) {
+      gsum += gbc;
+    } else if (slab != nullptr) {
+      const float t = bg_block_sum(gbc, red);
+      if (threadIdx.x == 0) slab[(long)blockIdx.x * C + c] = t;
+    } else if (ok) {
+      g_bg[b * gb + h * gh + w * gw + c * gc] = gbc;
+    }
+  }
+  if (g_m != nullptr && ok) g_m[pix] = gm;
+  if (g_bg != nullptr && gc == 0) {
+    if (slab != nullptr) {
+      const float t = bg_block_sum(gsum, red);
+      if (threadIdx.x == 0) slab[blockIdx.x] = t;
+    } else if (ok) {
+      g_bg[b * gb + h * gh + w * gw] = gsum;
+    }
+  }
+}
+
+// Second pass of the slab form: cell (v, c) of the [Bv, Cg] gradient (Bv = B for a colour per view, 1 for one colour
+// overall) = the sum of the partials of the views it covers, each summed over its nwg workgroups -- one workgroup per cell,
+// a fixed assignment of partials to lanes and bg_block_sum: the same bits on every run.
+__global__ void __launch_bounds__(kBgPix)
+blend_bg_slab_kernel(const float *__restrict__ slab, const int B, const int nwg, const int Cg, const int per_view,
+                     float *__restrict__ g_bg, const long gb, const long gc) {
+  __shared__ float red[kBgPix / 64];
+  const int v = blockIdx.x / Cg, c = blockIdx.x - v * Cg;
+  const long n = (long)(per_view ? 1 : B) * nwg;
+  const long base = per_view ? (long)v * nwg : 0;
+  float acc = 0.0f;
+  for (long i = threadIdx.x; i < n; i += kBgPix) acc += slab[(base + i) * Cg + c];
+  const float t = bg_block_sum(acc, red);
+  if (threadIdx.x == 0) g_bg[v * gb + c * gc] = t;
+}
+
 static inline unsigned shade_grid(long npix) {   // blend_bwd_kernel: kShadePixPerWave pixels per wave
   const long waves = (npix + kShadePixPerWave - 1) / kShadePixPerWave;
   long b = (waves + 3) / 4;
@@ -710,6 +822,57 @@ extern "C" int voge_silhouette_bwd(const float *wsum, const float *g_sil, long n
   if (!wsum || !g_sil || !g_pix) return VOGE_ERR_BAD_ARG;
   hipLaunchKernelGGL(silhouette_bwd_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wsum,
                      g_sil, npix, g_pix);
+  return launch_status();
+}
+
+// (every pixel of a view is one lane of a kBgPix-lane workgroup: B * nwg workgroups in all, grid x * kBgPix < 2^32)
+static inline bool blend_bg_sizes_ok(int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return false;
+  const long hw = (long)H * W;
+  return hw <= (long)INT32_MAX - kBgPix && (long)B * ((hw + kBgPix - 1) / kBgPix) < (1L << 24);
+}
+
+extern "C" size_t voge_blend_bg_bwd_workspace_bytes(int B, int H, int W, int C) {
+  if (!blend_bg_sizes_ok(B, H, W, C)) return 0;
+  const long nwg = ((long)H * W + kBgPix - 1) / kBgPix;
+  return sizeof(float) * (size_t)B * (size_t)nwg * (size_t)C;
+}
+
+extern "C" int voge_blend_bg_fwd(const float *rgb, const float *s, const float *bg, long sb, long sh, long sw, long sc,
+                                 float thr, int B, int H, int W, int C, float *img, voge_stream_t stream) {
+  if (!rgb || !s || !bg || !img || !blend_bg_sizes_ok(B, H, W, C)) return VOGE_ERR_BAD_ARG;
+  if (sb < 0 || sh < 0 || sw < 0 || sc < 0) return VOGE_ERR_BAD_ARG;
+  const int nwg = (int)(((long)H * W + kBgPix - 1) / kBgPix);
+  hipLaunchKernelGGL(blend_bg_fwd_kernel, dim3((unsigned)(B * nwg)), dim3(kBgPix), 0, (hipStream_t)stream, rgb, s, bg, sb, sh, sw,
+                     sc, thr, H, W, C, nwg, img);
+  return launch_status();
+}
+
+extern "C" int voge_blend_bg_bwd(const float *rgb, const float *s, const float *bg, long sb, long sh, long sw, long sc,
+                                 float thr, const float *g_img, long gs_pix, long gs_c, int B, int H, int W, int C, float *g_rgb,
+                                 float *g_m, float *g_bg, long gb, long gh, long gw, long gc, void *workspace,
+                                 size_t workspace_bytes, voge_stream_t stream) {
+  if (!rgb || !s || !bg || !g_img || !blend_bg_sizes_ok(B, H, W, C)) return VOGE_ERR_BAD_ARG;
+  if (sb < 0 || sh < 0 || sw < 0 || sc < 0 || gs_pix < 0 || gs_c < 0 || gb < 0 || gh < 0 || gw < 0 || gc < 0) return VOGE_ERR_BAD_ARG;
+  if (g_m != nullptr && thr > 0.0f) return VOGE_ERR_BAD_ARG;      // ([m > thr] has no gradient)
+  const int nwg = (int)(((long)H * W + kBgPix - 1) / kBgPix);
+  const bool distinct = (gb != 0 || B == 1) && (gh != 0 || H == 1) && (gw != 0 || W == 1);
+  const bool uniform = (gh == 0 || H == 1) && (gw == 0 || W == 1);
+  float *slab = nullptr;
+  if (g_bg != nullptr && !distinct) {
+    if (!uniform) return VOGE_ERR_BAD_ARG;      // (the caller takes a dense [B,H,W,C] gradient and sums it down)
+    if (!workspace || workspace_bytes < voge_blend_bg_bwd_workspace_bytes(B, H, W, C)) return VOGE_ERR_BAD_ARG;
+    slab = static_cast<float *>(workspace);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(blend_bg_bwd_kernel, dim3((unsigned)(B * nwg)), dim3(kBgPix), 0, st, rgb, s, bg, sb, sh, sw, sc, thr, g_img,
+                     gs_pix, gs_c, H, W, C, nwg, g_rgb, g_m, g_bg, gb, gh, gw, gc, slab);
+  if (slab == nullptr) return launch_status();
+  const int e = launch_status();
+  if (e != 0) return e;
+  const int per_view = gb != 0 && B > 1, Cg = gc != 0 ? C : 1;
+  hipLaunchKernelGGL(blend_bg_slab_kernel, dim3((unsigned)((per_view ? B : 1) * Cg)), dim3(kBgPix), 0, st, slab, B, nwg, Cg, per_view,
+                     g_bg, gb, gc);
   return launch_status();
 }
 

@@ -1667,6 +1667,102 @@ class _Shade(torch.autograd.Function):
         return g_attr, g_w, None, None, None, None
 
 
+def _bg_view(bg, shape):
+    """bg as the [B,H,W,C] view of bg.expand(shape): strides, never a copy (0 on the broadcast dimensions)."""
+    e = bg.expand(shape)
+    return e.unsqueeze(0) if e.dim() == 3 else e.reshape((-1,) + tuple(shape[-3:]))
+
+
+class _BlendBackground(torch.autograd.Function):
+    """to_colored_background with a background that broadcasts to the image (VoGE/Renderer.py:162-171 under torch
+    broadcasting): forward(rgb [..,H,W,C], s [..,H,W], bg, thr) -> min(rgb + (1 - m) bg, 1), m = min(s, 1) ([m > thr] when
+    thr > 0), one launch each way (voge_blend_bg_fwd / _bwd).  bg is read through its broadcast strides; its gradient is
+    summed back to bg's own shape without atomics: plain stores when no two pixels share a cell, per-workgroup partials and a
+    fixed-order second pass when a view shares one colour, a dense gradient and sum_to_size for anything else."""
+
+    @staticmethod
+    def forward(ctx, rgb, s, bg, thr):
+        lib = _lib.load()
+        rgb_c = _dev(rgb, torch.float32, "rgb")
+        s_c = _dev(s, torch.float32, "silhouette")
+        img = torch.empty_like(rgb_c)
+        ctx.save_for_backward(rgb_c, s_c, bg)
+        ctx.thr = float(thr)
+        if img.numel() == 0:
+            return img
+        H, W, C = rgb_c.shape[-3:]
+        e = _bg_view(bg, rgb_c.shape)
+        with _on(rgb_c.device):
+            rc = lib.voge_blend_bg_fwd(_p(rgb_c), _p(s_c), _p(e), *e.stride(), ctx.thr, e.shape[0], H, W, C, _p(img), _stream())
+        _lib.check(rc, "voge_blend_bg_fwd")
+        return img
+
+    @staticmethod
+    def backward(ctx, g_img):
+        lib = _lib.load()
+        rgb, s, bg = ctx.saved_tensors
+        shape = rgb.shape
+        need = ctx.needs_input_grad
+        g_rgb = torch.empty_like(rgb) if need[0] else None
+        g_s = torch.empty_like(s) if need[1] and ctx.thr <= 0 else None      # ([m > thr] passes nothing to the silhouette)
+        g_bg = None
+        if rgb.numel() == 0:
+            return g_rgb, g_s, torch.zeros_like(bg) if need[2] else None, None
+        H, W, C = shape[-3:]
+        e = _bg_view(bg, shape)
+        B = e.shape[0]
+        if g_img.dtype == torch.float32 and g_img.is_cuda and all(st == 0 for st in g_img.stride()):
+            go, gs_pix, gs_c = g_img, 0, 0      # autograd's broadcast scalar (sum / mean losses), read in place
+        else:
+            go, gs_pix, gs_c = _dev(g_img, torch.float32, "grad_image"), C, 1
+        out, gst, dense, ws, nbytes = None, (0, 0, 0, 0), None, None, 0
+        if need[2]:
+            bs = (1,) * (len(shape) - bg.dim()) + tuple(bg.shape)      # bg's shape aligned with the image's
+            lead, Cg = bs[:-3], bs[-1]
+            global_ = all(d == 1 for d in lead)
+            if global_ or tuple(lead) == tuple(shape[:-3]):      # (one colour set for every view, or one per view)
+                out = torch.empty(bs, dtype=torch.float32, device=rgb.device)
+                gst = out.view(1 if global_ else B, bs[-3], bs[-2], Cg).expand(B, H, W, C).stride()
+            gb, gh, gw = gst[:3]
+            distinct = out is not None and (gb or B == 1) and (gh or H == 1) and (gw or W == 1)
+            uniform = out is not None and (gh == 0 or H == 1) and (gw == 0 or W == 1)
+            if not (distinct or uniform):
+                # (e.g. a [W,C] background, or one [H,W,C] image behind several views): a dense gradient, summed down by torch
+                out = dense = torch.empty((B, H, W, Cg), dtype=torch.float32, device=rgb.device)
+                gst = dense.expand(B, H, W, C).stride()
+            elif not distinct:
+                nbytes = lib.voge_blend_bg_bwd_workspace_bytes(B, H, W, C)
+                ws = _workspace(rgb.device, nbytes)
+        with _on(rgb.device):
+            rc = lib.voge_blend_bg_bwd(_p(rgb), _p(s), _p(e), *e.stride(), ctx.thr, _p(go), gs_pix, gs_c, B, H, W, C, _p(g_rgb),
+                                       _p(g_s), _p(out), *gst, _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_blend_bg_bwd")
+        if dense is not None:
+            g_bg = dense.view(tuple(shape[:-1]) + (dense.shape[-1],)).sum_to_size(bs).view(bg.shape)
+        elif out is not None:
+            g_bg = out.view(bg.shape)
+        return g_rgb, g_s, g_bg, None
+
+
+def blend_background(rgb, s, bg, thr=-1.0):
+    """min(rgb + (1 - m) bg, 1) with m = min(s, 1) ([m > thr] when thr > 0): rgb [.., H, W, C] (interpolate_attr), s [.., H, W]
+    (get_silhouette), bg a tensor, tuple or list that broadcasts to rgb's shape WITHOUT enlarging it (a background that would
+    make the image bigger raises ValueError; the reference returns the bigger image).  Arithmetic in fp32: a CPU or fp64
+    background is moved and cast, autograd runs through the cast."""
+    if not torch.is_tensor(bg):
+        bg = torch.tensor([float(c) for c in bg], dtype=torch.float32)
+    if rgb.dim() < 3 or tuple(s.shape) != tuple(rgb.shape[:-1]):
+        raise ValueError(f"blend_background: rgb {tuple(rgb.shape)} must be [..., H, W, C] and s {tuple(s.shape)} its [..., H, W]")
+    try:
+        grown = tuple(torch.broadcast_shapes(bg.shape, rgb.shape)) != tuple(rgb.shape)
+    except RuntimeError:
+        grown = True
+    if grown:
+        raise ValueError(f"background_color of shape {tuple(bg.shape)} does not broadcast to the image's shape {tuple(rgb.shape)} "
+                         "without enlarging it")
+    return _BlendBackground.apply(rgb, s, bg.to(device=rgb.device, dtype=torch.float32), float(thr))
+
+
 class _Silhouette(torch.autograd.Function):
     """get_silhouette (VoGE/Renderer.py:157-159): min(sum_k w_k, 1).  The backward is one value per pixel
     (g_sil * [sum w < 1]), returned as a [.., K] view with stride 0 along the slots: nothing of size [.., K] is
