@@ -202,7 +202,7 @@ class GaussianRenderer(nn.Module):
         behind = st['max_point_per_bin'] != -1      # the coarse stage's "skip z < 0" candidate rule (rasterize_coarse.cu:35)
         if sigmas.dim() == 1 and shared_verts and FUSED_PREAMBLE and not (behind and RayTracing.REFERENCE_CANDIDATES):
             # Round 6, the frame path: one (verts [N,3], sigmas [N]) set, fixed cameras -- the trace takes the CAMERA itself
-            # (ops._FrameTrace: no ray-generation launch, no ray node; rays, cones, camera centre and view axis are made inside
+            # (ops.frame_trace: no ray-generation launch, no ray node; rays, cones, camera centre and view axis are made inside
             # binA / binB / the sweep with the ray kernel's own operations) and stops behind the sweep like trace_lean
             cam = self._frame_camera(cams, image_size, kwargs.get('rows'))
             if cam is not None and ops.frame_eligible(verts2d, sigmas, *cam[:4], K, cam[4][1] * cam[5]):
@@ -233,29 +233,31 @@ class GaussianRenderer(nn.Module):
                 max_points_per_bin=st['max_point_per_bin'])
             weight, index, valid_num, hit_len = aggregation(sel_idx, sel_act, sel_len, sel_dsd, occ)
             return Fragments(vert_weight=weight, vert_index=index, valid_num=valid_num, vert_hit_length=hit_len)
+
+        def traced(mode, p0, p1, org, cam_fwd, smode=0):
+            # stop behind the sweep when the composite can wait: it runs when the weights are first read -- or inside
+            # to_colored_background's own pass (Fragments._lazy).  (Full 3x3 forms defer it too: the sweep keeps the packed
+            # (mu, A) records instead of act / dsd.)  merge_final later rewrites -1 -> 0 inside the fragments' index tensor;
+            # the reference clones it (Renderer.py:145) because its backward finds empty slots by idx == -1, this trace
+            # backward uses the per-pixel hit count instead, so no copy is needed.
+            if ops.lazy_eligible(mode, p0, p1, org, rays, K):
+                index, hit_len, lz = ops.trace_lean(mode, p0, p1, org, rays, cam_fwd, thr_act, K, smode, occ)
+                return Fragments(None, index, None, hit_len, _lazy=lz)
+            weight, index, valid_num, hit_len = ops.fragments(mode, p0, p1, org, rays, cam_fwd, thr_act, K, smode, occ)
+            return Fragments(vert_weight=weight, vert_index=index, valid_num=valid_num, vert_hit_length=hit_len)
+
         if sigmas.dim() == 1 and shared_verts and not origin.requires_grad and FUSED_PREAMBLE:
             # One (verts [N,3], sigmas [N]) set seen by every view, fixed cameras: the centring of
             # Renderer.py:130 and the 2*sigma / 2/sigma of :133-137 happen inside the trace's per-Gaussian
             # pass (and their chain rule inside its backward's) -- same values, no elementwise launches.
             cam_fwd = _view_axis(cams, origin[:, None]) if behind else None
-            smode = 2 if st['inverse_sigma'] else 1
-            if ops.lazy_eligible(2, verts2d, sigmas, origin, rays, K):
-                # stop behind the sweep: the composite runs when the weights are first read -- or inside
-                # to_colored_background's own pass (Fragments._lazy)
-                index, hit_len, lz = ops.trace_lean(2, verts2d, sigmas, origin, rays, cam_fwd, thr_act, K, smode, occ)
-                return Fragments(None, index, None, hit_len, _lazy=lz)
-            weight, index, valid_num, hit_len = ops.fragments(2, verts2d, sigmas, origin, rays, cam_fwd, thr_act, K, smode, occ)
-            return Fragments(vert_weight=weight, vert_index=index, valid_num=valid_num, vert_hit_length=hit_len)
+            return traced(2, verts2d, sigmas, origin, cam_fwd, 2 if st['inverse_sigma'] else 1)
         if (sigmas.dim() >= 2 and not st['inverse_sigma'] and not origin.requires_grad and FUSED_PREAMBLE
                 and verts.is_cuda and sigmas.shape[-1] == 3):
             # (N,3) / (N,3,3) sigmas: the centring and 2 * expend_sigma of Renderer.py:130-137 as ONE launch each way
             cam_fwd = _view_axis(cams, origin[:, None]) if behind else None
             mus0, isg0 = ops.general_preamble(verts2d if shared_verts else verts, sigmas, origin)
-            if ops.lazy_eligible(0, mus0, isg0, None, rays, K):
-                index, hit_len, lz = ops.trace_lean(0, mus0, isg0, None, rays, cam_fwd, thr_act, K, 0, occ)
-                return Fragments(None, index, None, hit_len, _lazy=lz)
-            weight, index, valid_num, hit_len = ops.fragments(0, mus0, isg0, None, rays, cam_fwd, thr_act, K, 0, occ)
-            return Fragments(vert_weight=weight, vert_index=index, valid_num=valid_num, vert_hit_length=hit_len)
+            return traced(0, mus0, isg0, None, cam_fwd)
         centred = verts - origin[:, None]                                         # Renderer.py:130
         cam_fwd = _view_axis(cams, centred) if behind else None
         B = centred.shape[0]
@@ -265,26 +267,12 @@ class GaussianRenderer(nn.Module):
             # isotropic form whose backward produces d/d(scalar) directly.
             a = 2.0 / sigmas if st['inverse_sigma'] else 2.0 * sigmas
             a = a.unsqueeze(0).expand(B, -1)
-            mus1, a1 = centred.reshape(-1, 3), a.reshape(-1)
-            if ops.lazy_eligible(1, mus1, a1, None, rays, K):
-                index, hit_len, lz = ops.trace_lean(1, mus1, a1, None, rays, cam_fwd, thr_act, K, 0, occ)
-                return Fragments(None, index, None, hit_len, _lazy=lz)
-            weight, index, valid_num, hit_len = ops.fragments(1, mus1, a1, None, rays, cam_fwd, thr_act, K, 0, occ)
-        else:
-            sigmas = expend_sigma(sigmas)
-            if sigmas.dim() == 3:
-                sigmas = sigmas.unsqueeze(0).expand(B, -1, -1, -1)
-            isigma = 2 * torch.inverse(sigmas) if st['inverse_sigma'] else 2 * sigmas
-            mus0, isg0 = centred.reshape(-1, 3), isigma.reshape(-1, 3, 3)
-            if ops.lazy_eligible(0, mus0, isg0, None, rays, K):
-                # (full 3x3 forms defer their composite too: the sweep keeps the packed (mu, A) records instead of act / dsd)
-                index, hit_len, lz = ops.trace_lean(0, mus0, isg0, None, rays, cam_fwd, thr_act, K, 0, occ)
-                return Fragments(None, index, None, hit_len, _lazy=lz)
-            weight, index, valid_num, hit_len = ops.fragments(0, mus0, isg0, None, rays, cam_fwd, thr_act, K, 0, occ)
-        # merge_final later rewrites -1 -> 0 inside the fragments' index tensor.  The reference clones
-        # it here (Renderer.py:145) because its backward finds empty slots by idx == -1; this trace
-        # backward uses the per-pixel hit count instead, so no copy is needed.
-        return Fragments(vert_weight=weight, vert_index=index, valid_num=valid_num, vert_hit_length=hit_len)
+            return traced(1, centred.reshape(-1, 3), a.reshape(-1), None, cam_fwd)
+        sigmas = expend_sigma(sigmas)
+        if sigmas.dim() == 3:
+            sigmas = sigmas.unsqueeze(0).expand(B, -1, -1, -1)
+        isigma = 2 * torch.inverse(sigmas) if st['inverse_sigma'] else 2 * sigmas
+        return traced(0, centred.reshape(-1, 3), isigma.reshape(-1, 3, 3), None, cam_fwd)
 
 
 def interpolate_attr(fragments: Fragments, vert_attr: torch.Tensor):

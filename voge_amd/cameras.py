@@ -123,7 +123,7 @@ def pixel_rays(cameras, image_size, rows=None):
 
 
 def camera_tensors(cameras, image_size, rows=None):
-    """What the camera-input trace (ops._FrameTrace) takes: (R [B,3,3], T [B,3], focal [B,2], pp [B,2], band, W) with
+    """What the camera-input trace (ops.frame_trace) takes: (R [B,3,3], T [B,3], focal [B,2], pp [B,2], band, W) with
     band = (row0, h, stripe_h, pitch) -- pixel_rays' arguments without the ray kernel -- or None when the camera does not
     fit that path (a pose or an intrinsic that wants a gradient, tensors on another device)."""
     R, T = cameras.R, cameras.T

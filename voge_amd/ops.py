@@ -233,30 +233,91 @@ def check_index_range(idx, n_attr):
         assert n_attr > int(idx.max()), "vert_attr.shape[0] must exceed vert_assign.max() (Aggregation.py:120)"
 
 
-class _RayTraceVoGE(torch.autograd.Function):
-    """Mirror of VoGE/RayTracing.py:154-206 (`_RayTraceVoGE`).
+def _trace_inputs(mode, p0, p1, origin, rays, cam_fwd, packed=False):
+    """Validate the Gaussians of a ray-bundle trace in one of its three forms against rays [B,H,W,3]:
+      mode 0: p0 = mus [P,3], p1 = isigmas [P,3,3]           (general 3x3 forms)
+      mode 1: p0 = mus [P,3], p1 = a [P]                     (A = a I)
+      mode 2: p0 = verts [N,3] | [B,N,3], p1 = sigmas [N] | [B,N], origin [B,3]   (the renderer's preamble folded in)
+    P = B*N rows unless `packed` (explicit candidate lists address any P).
+    -> p0, p1, origin (mode 2, else None), rays, cam_fwd (or None) as contiguous fp32; B, N, H, W, shared."""
+    p0_c, p1_c = _dev(p0, torch.float32, "means"), _dev(p1, torch.float32, "sigmas")
+    rays_c = _dev(rays, torch.float32, "rays")
+    assert rays_c.dim() == 4 and rays_c.shape[3] == 3 and mode in (0, 1, 2)
+    B, H, W, _ = rays_c.shape
+    o_c, shared = None, False
+    if mode == 2:
+        o_c = _dev(origin, torch.float32, "origin")
+        shared = p0_c.dim() == 2
+        assert p0_c.shape[-1] == 3 and (shared or p0_c.shape[0] == B) and p1_c.shape == p0_c.shape[:-1]
+        assert o_c.shape == (B, 3)
+        N = p0_c.shape[-2]
+    else:
+        P = p0_c.shape[0]
+        assert p0_c.dim() == 2 and p0_c.shape[1] == 3 and p1_c.shape == ((P,) if mode == 1 else (P, 3, 3))
+        assert packed or (B > 0 and P % B == 0), "mus must hold B*N rows"
+        N = P // max(B, 1)
+    fwd = None if cam_fwd is None else _dev(cam_fwd, torch.float32, "cam_fwd")
+    return p0_c, p1_c, o_c, rays_c, fwd, B, N, H, W, shared
 
-    forward(mus [P,3], isigmas [P,3,3], rays [B,H,W,3], bin_points, thr_act, bin_size, n_assign)
+
+def _trace_bwd(mode, p0, p1, origin, shared, sigma_mode, rays, idx, cnt, g_len, g_act, g_dsd, need_rays):
+    """The trace's backward alone (voge_trace_bwd / _iso / _iso_view) for the gradients of len, act and dsd of the slots idx
+    [B,H,W,K] -> (g0, g1, g_rays | None): the gradients of the trace's p0 / p1 (forms as in _trace_inputs) and of the rays."""
+    lib = _lib.load()
+    B, H, W, K = idx.shape
+    dev = rays.device
+    g0, g1 = torch.empty_like(p0), torch.empty_like(p1)
+    g_ray = torch.empty_like(rays) if need_rays else None
+    grads = (_p(idx), _p(cnt), _p(g_len), _p(g_act), _p(g_dsd))
+    with _on(dev):
+        if mode == 2:
+            N = p0.shape[-2]
+            nbytes = lib.voge_trace_bwd_iso_workspace_bytes(B * N)
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_trace_bwd_iso_view(_p(p0), _p(p1), _p(origin), int(shared), int(sigma_mode), _p(rays), *grads, B, N, B * H, W,
+                                             K, _p(ws), nbytes, _p(g_ray), _p(g0), _p(g1), _stream())
+        elif mode == 1:
+            nbytes = lib.voge_trace_bwd_iso_workspace_bytes(p0.shape[0])
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_trace_bwd_iso(_p(p0), _p(p1), _p(rays), *grads, p0.shape[0], B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g0),
+                                        _p(g1), _stream())
+        else:
+            nbytes = lib.voge_trace_bwd_workspace_bytes(p0.shape[0])
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_trace_bwd(_p(p0), _p(p1), _p(rays), *grads, p0.shape[0], B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g0),
+                                    _p(g1), _stream())
+    _lib.check(rc, "voge_trace_bwd")
+    return g0, g1, g_ray
+
+
+def _composite_bwd(act, ln, dsd, weight, cnt, g_weight, occ):
+    """voge_composite_bwd: the gradient of the weights -> (g_act, g_len, g_dsd)."""
+    K = act.shape[-1]
+    gw = _dev(g_weight, torch.float32, "grad_weight")
+    g_act, g_len, g_dsd = torch.empty_like(act), torch.empty_like(act), torch.empty_like(act)
+    with _on(act.device):
+        rc = _lib.load().voge_composite_bwd(_p(act), _p(ln), _p(dsd), _p(weight), _p(cnt), _p(gw), occ, act.numel() // max(K, 1), K,
+                                            _p(g_act), _p(g_len), _p(g_dsd), _stream())
+    _lib.check(rc, "voge_composite_bwd")
+    return g_act, g_len, g_dsd
+
+
+class _RayTrace(torch.autograd.Function):
+    """Mirror of VoGE/RayTracing.py:154-206 (`_RayTraceVoGE`) for the three forms of _trace_inputs:
+    forward(mode, p0, p1, origin, rays [B,H,W,3], cam_fwd, thr_act, n_assign, sigma_mode, bins, bin_size)
     -> sel_idx int32, sel_len, sel_act, sel_dsd, each [B,H,W,K].
-    bin_points: None -> every Gaussian of the batch element is a candidate (the
-    max_points_per_bin == -1 list of RayTracing.py:22-26, never materialised); a tensor
-    [B,BH,BW,M] -> explicit candidate lists as in the reference; a tensor [B,3] of dtype
-    float -> "all candidates in front of the camera" (view axis per batch element).
-    """
+    cam_fwd: None -> every Gaussian of the batch element is a candidate (the max_points_per_bin == -1 list of
+    RayTracing.py:22-26, never materialised); [B,3] -> "all candidates in front of the camera" (view axis per batch element).
+    bins (mode 0 only): explicit candidate lists [B,BH,BW,M] as in the reference (voge_trace_topk_list_fwd).
+    Mode 2 sees Gaussian n in view b as (verts - origin[b], a = 2 sigma (sigma_mode 1) | 2 / sigma (2) | sigma (0)) and has no
+    gradient for origin: callers that optimise the camera use the unfused form.  The scalar forms' backward returns the
+    gradient of the scalar directly (four sums per Gaussian instead of twelve)."""
 
     @staticmethod
-    def forward(ctx, mus, isigmas, rays, bin_points, thr_act, bin_size, n_assign):
+    def forward(ctx, mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode, bins, bin_size):
         lib = _lib.load()
-        mus_c = _dev(mus, torch.float32, "mus")
-        isg_c = _dev(isigmas, torch.float32, "isigmas")
-        rays_c = _dev(rays, torch.float32, "rays")
-        assert mus_c.dim() == 2 and mus_c.shape[1] == 3
-        assert isg_c.dim() == 3 and isg_c.shape[1:] == (3, 3) and isg_c.shape[0] == mus_c.shape[0]
-        assert rays_c.dim() == 4 and rays_c.shape[3] == 3
-        B, H, W, _ = rays_c.shape
-        P = mus_c.shape[0]
-        K = int(n_assign)
-        dev = rays_c.device
+        p0_c, p1_c, o_c, rays_c, fwd, B, N, H, W, shared = _trace_inputs(mode, p0, p1, origin, rays, cam_fwd, bins is not None)
+        K, dev = int(n_assign), rays_c.device
         sel_idx = torch.empty((B, H, W, K), dtype=torch.int32, device=dev)
         sel_len = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
         sel_act = torch.empty_like(sel_len)
@@ -265,179 +326,40 @@ class _RayTraceVoGE(torch.autograd.Function):
         # may later be rewritten in place by merge_final (-1 -> 0, Aggregation.py:131) without a defensive copy
         cnt = torch.empty((B, H, W), dtype=torch.int32, device=dev)
         with _on(dev):
-            if bin_points is not None and bin_points.dtype in (torch.int32, torch.int64):
-                bins = _dev(bin_points, torch.int32, "bin_points")
+            out = (_p(sel_idx), _p(sel_len), _p(sel_act), _p(sel_dsd), _p(cnt), _stream())
+            if bins is not None:
+                bins = _dev(bins, torch.int32, "bin_points")
                 assert bins.dim() == 4 and bins.shape[0] == B
-                rc = lib.voge_trace_topk_list_fwd(
-                    _p(mus_c), _p(isg_c), _p(rays_c), _p(bins), B, P, H, W, K, bins.shape[1], bins.shape[2],
-                    bins.shape[3], int(bin_size), float(thr_act), _p(sel_idx), _p(sel_len), _p(sel_act),
-                    _p(sel_dsd), _p(cnt), _stream())
-                _lib.check(rc, "voge_trace_topk_list_fwd")
+                rc = lib.voge_trace_topk_list_fwd(_p(p0_c), _p(p1_c), _p(rays_c), _p(bins), B, p0_c.shape[0], H, W, K, *bins.shape[1:],
+                                                  int(bin_size), float(thr_act), *out)
             else:
-                assert B > 0 and P % B == 0, "mus must hold B*N rows"
-                N = P // B
-                fwd = None if bin_points is None else _dev(bin_points, torch.float32, "cam_fwd")
                 nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
                 ws = _workspace(dev, nbytes)
-                rc = lib.voge_trace_topk_fwd(
-                    _p(mus_c), _p(isg_c), _p(rays_c), _p(fwd), _p(cones_of(rays_c, B, H, W)), B, N, H, W, K, float(thr_act), _p(ws), nbytes,
-                    _p(sel_idx), _p(sel_len), _p(sel_act), _p(sel_dsd), _p(cnt), _stream())
-                _lib.check(rc, "voge_trace_topk_fwd")
-        ctx.save_for_backward(mus_c, isg_c, rays_c)
-        ctx.sel_idx = sel_idx
-        ctx.cnt = cnt
-        _tag_index(sel_idx, cnt, P)
-        ctx.mark_non_differentiable(sel_idx)
-        ctx.set_materialize_grads(False)
-        return sel_idx, sel_len, sel_act, sel_dsd
-
-    @staticmethod
-    def backward(ctx, grad_sel_idx, grad_sel_len, grad_sel_act, grad_sel_dsd):
-        lib = _lib.load()
-        mus, isg, rays = ctx.saved_tensors
-        sel_idx = ctx.sel_idx
-        B, H, W, K = sel_idx.shape
-        P = mus.shape[0]
-        zeros = None
-
-        def g(t):
-            nonlocal zeros
-            if t is None:
-                if zeros is None:
-                    zeros = torch.zeros(sel_idx.shape, dtype=torch.float32, device=sel_idx.device)
-                return zeros
-            return _dev(t, torch.float32, "grad")
-        gl, ga, gd = g(grad_sel_len), g(grad_sel_act), g(grad_sel_dsd)
-        g_ray = torch.empty_like(rays) if ctx.needs_input_grad[2] else None
-        g_mus = torch.empty_like(mus)
-        g_isg = torch.empty_like(isg)
-        with _on(rays.device):
-            nbytes = lib.voge_trace_bwd_workspace_bytes(P)
-            ws = _workspace(rays.device, nbytes)
-            rc = lib.voge_trace_bwd(_p(mus), _p(isg), _p(rays), _p(sel_idx), _p(ctx.cnt), _p(gl), _p(ga), _p(gd), P,
-                                    B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g_mus), _p(g_isg), _stream())
-        _lib.check(rc, "voge_trace_bwd")
-        return g_mus, g_isg, g_ray, None, None, None, None
-
-
-class _RayTraceVoGEIso(torch.autograd.Function):
-    """The same trace for isotropic Gaussians given as ONE scalar each (A = a I): what
-    expend_sigma((N,)) followed by 2*sigma (Aggregation.py:155-157, Renderer.py:133) describes.
-    forward(mus [P,3], a [P], rays [B,H,W,3], cam_fwd | None, thr_act, n_assign); the backward
-    returns the gradient of the scalar directly (four sums per Gaussian instead of twelve)."""
-
-    @staticmethod
-    def forward(ctx, mus, a, rays, cam_fwd, thr_act, n_assign):
-        lib = _lib.load()
-        mus_c = _dev(mus, torch.float32, "mus")
-        a_c = _dev(a, torch.float32, "a")
-        rays_c = _dev(rays, torch.float32, "rays")
-        assert mus_c.dim() == 2 and mus_c.shape[1] == 3 and a_c.dim() == 1 and a_c.shape[0] == mus_c.shape[0]
-        assert rays_c.dim() == 4 and rays_c.shape[3] == 3
-        B, H, W, _ = rays_c.shape
-        P = mus_c.shape[0]
-        assert B > 0 and P % B == 0, "mus must hold B*N rows"
-        N, K, dev = P // B, int(n_assign), rays_c.device
-        sel_idx = torch.empty((B, H, W, K), dtype=torch.int32, device=dev)
-        sel_len = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
-        sel_act = torch.empty_like(sel_len)
-        sel_dsd = torch.empty_like(sel_len)
-        cnt = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-        fwd = None if cam_fwd is None else _dev(cam_fwd, torch.float32, "cam_fwd")
-        with _on(dev):
-            nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
-            ws = _workspace(dev, nbytes)
-            rc = lib.voge_trace_topk_fwd_iso(
-                _p(mus_c), _p(a_c), _p(rays_c), _p(fwd), _p(cones_of(rays_c, B, H, W)), B, N, H, W, K, float(thr_act), _p(ws), nbytes,
-                _p(sel_idx), _p(sel_len), _p(sel_act), _p(sel_dsd), _p(cnt), _stream())
-        _lib.check(rc, "voge_trace_topk_fwd_iso")
-        ctx.save_for_backward(mus_c, a_c, rays_c)
+                sweep = (_p(fwd), _p(cones_of(rays_c, B, H, W)), B, N, H, W, K, float(thr_act), _p(ws), nbytes, *out)
+                if mode == 2:
+                    rc = lib.voge_trace_topk_fwd_iso_view(_p(p0_c), _p(p1_c), _p(o_c), int(shared), int(sigma_mode), _p(rays_c), *sweep)
+                elif mode == 1:
+                    rc = lib.voge_trace_topk_fwd_iso(_p(p0_c), _p(p1_c), _p(rays_c), *sweep)
+                else:
+                    rc = lib.voge_trace_topk_fwd(_p(p0_c), _p(p1_c), _p(rays_c), *sweep)
+        _lib.check(rc, "voge_trace_topk_fwd")
+        ctx.save_for_backward(p0_c, p1_c, o_c, rays_c)
         ctx.sel_idx = sel_idx      # may later be rewritten in place by merge_final; cnt marks the filled slots
         ctx.cnt = cnt
-        _tag_index(sel_idx, cnt, P)
+        ctx.meta = (int(mode), int(sigma_mode), shared)
+        _tag_index(sel_idx, cnt, B * N if mode == 2 else p0_c.shape[0])
         ctx.mark_non_differentiable(sel_idx)
         ctx.set_materialize_grads(False)
         return sel_idx, sel_len, sel_act, sel_dsd
 
     @staticmethod
     def backward(ctx, grad_sel_idx, grad_sel_len, grad_sel_act, grad_sel_dsd):
-        lib = _lib.load()
-        mus, a, rays = ctx.saved_tensors
-        sel_idx = ctx.sel_idx
-        B, H, W, K = sel_idx.shape
-        P = mus.shape[0]
-        zeros = None
-
-        def g(t):
-            nonlocal zeros
-            if t is None:
-                if zeros is None:
-                    zeros = torch.zeros(sel_idx.shape, dtype=torch.float32, device=sel_idx.device)
-                return zeros
-            return _dev(t, torch.float32, "grad")
-        gl, ga, gd = g(grad_sel_len), g(grad_sel_act), g(grad_sel_dsd)
-        g_ray = torch.empty_like(rays) if ctx.needs_input_grad[2] else None
-        g_mus = torch.empty_like(mus)
-        g_a = torch.empty_like(a)
-        with _on(rays.device):
-            nbytes = lib.voge_trace_bwd_iso_workspace_bytes(P)
-            ws = _workspace(rays.device, nbytes)
-            rc = lib.voge_trace_bwd_iso(_p(mus), _p(a), _p(rays), _p(sel_idx), _p(ctx.cnt), _p(gl), _p(ga), _p(gd), P,
-                                        B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g_mus), _p(g_a), _stream())
-        _lib.check(rc, "voge_trace_bwd_iso")
-        return g_mus, g_a, g_ray, None, None, None
-
-
-class _RayTraceVoGEIsoView(torch.autograd.Function):
-    """_RayTraceVoGEIso with the renderer's elementwise preamble folded into the kernels
-    (Renderer.py:130-137): forward(verts [N,3] | [B,N,3], sigmas [N] | [B,N], origin [B,3], rays [B,H,W,3],
-    cam_fwd | None, thr_act, n_assign, sigma_mode) where the Gaussian seen by view b is
-    (verts - origin[b], a = 2 sigma (mode 1) | 2 / sigma (mode 2) | sigma (mode 0)).  No gradient for
-    origin: callers that optimise the camera use the unfused form."""
-
-    @staticmethod
-    def forward(ctx, verts, sigmas, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode):
-        lib = _lib.load()
-        v_c = _dev(verts, torch.float32, "verts")
-        s_c = _dev(sigmas, torch.float32, "sigmas")
-        o_c = _dev(origin, torch.float32, "origin")
-        rays_c = _dev(rays, torch.float32, "rays")
-        assert rays_c.dim() == 4 and rays_c.shape[3] == 3
-        B, H, W, _ = rays_c.shape
-        shared = v_c.dim() == 2
-        assert v_c.shape[-1] == 3 and (shared or v_c.shape[0] == B) and s_c.shape == v_c.shape[:-1]
-        assert o_c.shape == (B, 3)
-        N, K, dev = v_c.shape[-2], int(n_assign), rays_c.device
-        sel_idx = torch.empty((B, H, W, K), dtype=torch.int32, device=dev)
-        sel_len = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
-        sel_act = torch.empty_like(sel_len)
-        sel_dsd = torch.empty_like(sel_len)
-        cnt = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-        fwd = None if cam_fwd is None else _dev(cam_fwd, torch.float32, "cam_fwd")
-        with _on(dev):
-            nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
-            ws = _workspace(dev, nbytes)
-            rc = lib.voge_trace_topk_fwd_iso_view(
-                _p(v_c), _p(s_c), _p(o_c), int(shared), int(sigma_mode), _p(rays_c), _p(fwd), _p(cones_of(rays_c, B, H, W)), B, N, H, W, K,
-                float(thr_act), _p(ws), nbytes, _p(sel_idx), _p(sel_len), _p(sel_act), _p(sel_dsd), _p(cnt), _stream())
-        _lib.check(rc, "voge_trace_topk_fwd_iso_view")
-        ctx.save_for_backward(v_c, s_c, o_c, rays_c)
-        ctx.sel_idx, ctx.cnt, ctx.mode, ctx.shared = sel_idx, cnt, int(sigma_mode), shared
-        _tag_index(sel_idx, cnt, B * N)
-        ctx.mark_non_differentiable(sel_idx)
-        ctx.set_materialize_grads(False)
-        return sel_idx, sel_len, sel_act, sel_dsd
-
-    @staticmethod
-    def backward(ctx, grad_sel_idx, grad_sel_len, grad_sel_act, grad_sel_dsd):
-        lib = _lib.load()
-        verts, sigmas, origin, rays = ctx.saved_tensors
-        if ctx.needs_input_grad[2]:
+        p0, p1, origin, rays = ctx.saved_tensors
+        mode, sigma_mode, shared = ctx.meta
+        if mode == 2 and ctx.needs_input_grad[3]:
             raise _lib.VogeHipError("the fused view form has no gradient for the camera centre; "
                                     "use ray_tracing_iso on centred vertices")
         sel_idx = ctx.sel_idx
-        B, H, W, K = sel_idx.shape
-        N = verts.shape[-2]
         zeros = None
 
         def g(t):
@@ -448,17 +370,40 @@ class _RayTraceVoGEIsoView(torch.autograd.Function):
                 return zeros
             return _dev(t, torch.float32, "grad")
         gl, ga, gd = g(grad_sel_len), g(grad_sel_act), g(grad_sel_dsd)
-        g_ray = torch.empty_like(rays) if ctx.needs_input_grad[3] else None
-        g_verts = torch.empty_like(verts)
-        g_sig = torch.empty_like(sigmas)
-        with _on(rays.device):
-            nbytes = lib.voge_trace_bwd_iso_workspace_bytes(B * N)
-            ws = _workspace(rays.device, nbytes)
-            rc = lib.voge_trace_bwd_iso_view(_p(verts), _p(sigmas), _p(origin), int(ctx.shared), ctx.mode, _p(rays),
-                                             _p(sel_idx), _p(ctx.cnt), _p(gl), _p(ga), _p(gd), B, N, B * H, W, K,
-                                             _p(ws), nbytes, _p(g_ray), _p(g_verts), _p(g_sig), _stream())
-        _lib.check(rc, "voge_trace_bwd_iso_view")
-        return g_verts, g_sig, None, g_ray, None, None, None, None
+        g0, g1, g_ray = _trace_bwd(mode, p0, p1, origin, shared, sigma_mode, rays, sel_idx, ctx.cnt, gl, ga, gd, ctx.needs_input_grad[4])
+        return None, g0, g1, None, g_ray, None, None, None, None, None, None
+
+
+class _RayTraceVoGE:
+    """_RayTrace of the general 3x3 forms: apply(mus [P,3], isigmas [P,3,3], rays [B,H,W,3], bin_points, thr_act, bin_size,
+    n_assign).  bin_points: None (every Gaussian of the batch element), a float [B,3] view axis per batch element (the
+    candidates in front of the camera), or int explicit candidate lists [B,BH,BW,M]."""
+
+    @staticmethod
+    def apply(mus, isigmas, rays, bin_points, thr_act, bin_size, n_assign):
+        if bin_points is not None and bin_points.dtype in (torch.int32, torch.int64):
+            return _RayTrace.apply(0, mus, isigmas, None, rays, None, thr_act, n_assign, 0, bin_points, bin_size)
+        return _RayTrace.apply(0, mus, isigmas, None, rays, bin_points, thr_act, n_assign, 0, None, bin_size)
+
+
+class _RayTraceVoGEIso:
+    """_RayTrace for isotropic Gaussians given as ONE scalar each (A = a I): what expend_sigma((N,)) followed by 2*sigma
+    (Aggregation.py:155-157, Renderer.py:133) describes.  apply(mus [P,3], a [P], rays [B,H,W,3], cam_fwd | None, thr_act,
+    n_assign)."""
+
+    @staticmethod
+    def apply(mus, a, rays, cam_fwd, thr_act, n_assign):
+        return _RayTrace.apply(1, mus, a, None, rays, cam_fwd, thr_act, n_assign, 0, None, 0)
+
+
+class _RayTraceVoGEIsoView:
+    """_RayTraceVoGEIso with the renderer's elementwise preamble folded into the kernels (Renderer.py:130-137):
+    apply(verts [N,3] | [B,N,3], sigmas [N] | [B,N], origin [B,3], rays [B,H,W,3], cam_fwd | None, thr_act, n_assign,
+    sigma_mode).  No gradient for origin."""
+
+    @staticmethod
+    def apply(verts, sigmas, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode):
+        return _RayTrace.apply(2, verts, sigmas, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode, None, 0)
 
 
 # VOGE_THREE_KERNEL_BACKWARD=1: _Fragments.backward runs voge_composite_bwd + voge_trace_bwd* (the round-1 chain, with
@@ -480,14 +425,71 @@ def _grad_weight_layout(g, K):
     return _dev(g, torch.float32, "grad_weight"), K, 1
 
 
+def _grad_layout(g, C):
+    """How the fused backwards read the gradient of a [.., C] image: (tensor, stride_pix, stride_c) in elements.  Autograd's
+    broadcast scalar (sum / mean losses) is read in place as (g, 0, 0); anything else is made contiguous, (C, 1)."""
+    if g.dtype == torch.float32 and g.is_cuda and all(s == 0 for s in g.stride()):
+        return g, 0, 0
+    return _dev(g, torch.float32, "grad_image"), C, 1
+
+
+def _fragment_bwd(mode, p0, p1, records, shared, sigma_mode, rays, idx, cnt, B, N, like, weight, act, ln, dsd, g_weight, g_len, occ):
+    """Composite + trace backward in ONE pass (voge_fragment_bwd / _iso: the composite's closed form and the trace's chain rule per
+    slot in registers, per-Gaussian sums in a wave-private table) for the gradients of the weights and of len, either of which may
+    be None (without g_weight, `weight` is read but multiplies zero) -> (g0, g1) shaped like like[0] / like[1].  Mode 0 reads the
+    means p0, the scalar forms their records; p1 is the sigmas."""
+    lib = _lib.load()
+    _, H, W, K = idx.shape
+    gw, gs_pix, gs_k = _grad_weight_layout(g_weight, K)
+    gh = None if g_len is None else _dev(g_len, torch.float32, "grad_hit_length")
+    dev = rays.device
+    g0 = torch.empty(like[0].shape, dtype=torch.float32, device=dev)
+    g1 = torch.empty(like[1].shape, dtype=torch.float32, device=dev)
+    slots = (_p(idx), _p(cnt), _p(weight), _p(act), _p(ln), _p(dsd), _p(gw), gs_pix, gs_k, _p(gh), occ)
+    with _on(dev):
+        nbytes = lib.voge_fragment_bwd_workspace_bytes(B * N)
+        ws = _workspace(dev, nbytes)
+        out = (B * H, W, K, _p(ws), nbytes, _p(g0), _p(g1), _stream())
+        if mode == 0:
+            rc = lib.voge_fragment_bwd(_p(p0), _p(p1), _p(rays), *slots, B * N, *out)
+        else:
+            rc = lib.voge_fragment_bwd_iso(_p(records), _p(p1), int(shared), sigma_mode, _p(rays), *slots, B, N, *out)
+    _lib.check(rc, "voge_fragment_bwd")
+    return g0, g1
+
+
+def _sweep(mode, p0, p1, origin, shared, sigma_mode, rays, fwd, B, N, H, W, K, thr_act, occ, sel_idx, sel_len, act, dsd, cnt,
+           weight, valid, records):
+    """The fine sweep of _trace_inputs' forms with the composite in its epilogue (voge_fragments_fwd / _iso / _iso_view), or, with
+    None in act, dsd, weight and valid, the trace alone (the same entries; mode 0: voge_trace_lean_fwd)."""
+    lib = _lib.load()
+    dev = rays.device
+    with _on(dev):
+        nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
+        ws = _workspace(dev, nbytes)
+        cones = _p(cones_of(rays, B, H, W))
+        if mode == 0 and weight is None:
+            rc = lib.voge_trace_lean_fwd(_p(p0), _p(p1), _p(rays), _p(fwd), cones, B, N, H, W, K, float(thr_act), _p(ws), nbytes,
+                                         _p(sel_idx), _p(sel_len), _p(cnt), _p(records), _stream())
+        else:
+            tail = (B, N, H, W, K, float(thr_act), float(occ), _p(ws), nbytes, _p(sel_idx), _p(sel_len), _p(act), _p(dsd), _p(cnt),
+                    _p(weight), _p(valid))
+            if mode == 2:
+                rc = lib.voge_fragments_fwd_iso_view(_p(p0), _p(p1), _p(origin), int(shared), int(sigma_mode), _p(rays), _p(fwd), cones,
+                                                     *tail, _p(records), _stream())
+            elif mode == 1:
+                rc = lib.voge_fragments_fwd_iso(_p(p0), _p(p1), _p(rays), _p(fwd), cones, *tail, _p(records), _stream())
+            else:
+                rc = lib.voge_fragments_fwd(_p(p0), _p(p1), _p(rays), _p(fwd), cones, *tail, _stream())
+    _lib.check(rc, "voge_fragments_fwd")
+
+
 class _Fragments(torch.autograd.Function):
     """Trace + composite in one launch chain (voge_fragments_fwd*): what GaussianRenderer.forward needs from
     ray_tracing (RayTracing.py:12-30) followed by aggregation (Aggregation.py:82-107).
     forward(mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode, occ)
         -> weight, sel_idx, valid_num, sel_len | cnt, records, act, dsd  (the call's bookkeeping, non-differentiable)
-      mode 0: p0 = mus [P,3], p1 = isigmas [P,3,3]           (general 3x3 forms)
-      mode 1: p0 = mus [P,3], p1 = a [P]                     (A = a I)
-      mode 2: p0 = verts [N,3] | [B,N,3], p1 = sigmas [N] | [B,N], origin [B,3]   (the renderer's preamble folded in)
+    with the Gaussians in one of _trace_inputs' forms (mode 0 general 3x3, 1 A = a I, 2 the renderer's preamble folded in).
     The backward is ONE pass over the fragments (voge_fragment_bwd*: the composite's closed form and the trace's chain
     rule, nothing exchanged through memory) for whatever gradient reaches the weights and vert_hit_length -- the
     reference's training loops differentiate through interpolate_attr + get_silhouette (demo/ShapeFitting.py:217,295).
@@ -495,23 +497,8 @@ class _Fragments(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode, occ):
-        lib = _lib.load()
-        p0_c, p1_c = _dev(p0, torch.float32, "means"), _dev(p1, torch.float32, "sigmas")
-        rays_c = _dev(rays, torch.float32, "rays")
-        assert rays_c.dim() == 4 and rays_c.shape[3] == 3
-        B, H, W, _ = rays_c.shape
+        p0_c, p1_c, o_c, rays_c, fwd, B, N, H, W, shared = _trace_inputs(mode, p0, p1, origin, rays, cam_fwd)
         K, dev = int(n_assign), rays_c.device
-        o_c, shared = None, False
-        if mode == 2:
-            o_c = _dev(origin, torch.float32, "origin")
-            shared = p0_c.dim() == 2
-            assert p0_c.shape[-1] == 3 and (shared or p0_c.shape[0] == B) and p1_c.shape == p0_c.shape[:-1]
-            assert o_c.shape == (B, 3)
-            N = p0_c.shape[-2]
-        else:
-            assert p0_c.dim() == 2 and p0_c.shape[1] == 3 and p0_c.shape[0] % max(B, 1) == 0
-            assert p1_c.shape[0] == p0_c.shape[0] and (p1_c.dim() == 1 if mode == 1 else p1_c.shape[1:] == (3, 3))
-            N = p0_c.shape[0] // B
         sel_idx = torch.empty((B, H, W, K), dtype=torch.int32, device=dev)
         sel_len = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
         weight = torch.empty_like(sel_len)
@@ -525,21 +512,8 @@ class _Fragments(torch.autograd.Function):
         valid = torch.empty((B, H, W), dtype=torch.int64, device=dev)
         # scalar forms: the per-Gaussian (centred mean, a) records outlive the call -- the fused backward reads them
         records = torch.empty((B * N, 4), dtype=torch.float32, device=dev) if mode != 0 else None
-        fwd = None if cam_fwd is None else _dev(cam_fwd, torch.float32, "cam_fwd")
-        with _on(dev):
-            nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
-            ws = _workspace(dev, nbytes)
-            tail = (B, N, H, W, K, float(thr_act), float(occ), _p(ws), nbytes, _p(sel_idx), _p(sel_len), _p(sel_act),
-                    _p(sel_dsd), _p(cnt), _p(weight), _p(valid))
-            cones = _p(cones_of(rays_c, B, H, W))
-            if mode == 2:
-                rc = lib.voge_fragments_fwd_iso_view(_p(p0_c), _p(p1_c), _p(o_c), int(shared), int(sigma_mode), _p(rays_c),
-                                                     _p(fwd), cones, *tail, _p(records), _stream())
-            elif mode == 1:
-                rc = lib.voge_fragments_fwd_iso(_p(p0_c), _p(p1_c), _p(rays_c), _p(fwd), cones, *tail, _p(records), _stream())
-            else:
-                rc = lib.voge_fragments_fwd(_p(p0_c), _p(p1_c), _p(rays_c), _p(fwd), cones, *tail, _stream())
-        _lib.check(rc, "voge_fragments_fwd")
+        _sweep(mode, p0_c, p1_c, o_c, shared, sigma_mode, rays_c, fwd, B, N, H, W, K, thr_act, occ, sel_idx, sel_len, sel_act, sel_dsd,
+               cnt, weight, valid, records)
         ctx.save_for_backward(p0_c, p1_c, rays_c, sel_len, weight)
         # (only tensors that are NOT differentiable outputs of this node may hang on ctx as plain attributes: an output
         # with a grad_fn kept here would close the cycle ctx -> tensor -> grad_fn -> ctx and leave the frame's buffers to
@@ -559,72 +533,33 @@ class _Fragments(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_weight, _g_idx, _g_valid, g_hitlen, *_unused):
-        lib = _lib.load()
         p0, p1, rays, ln, weight = ctx.saved_tensors
         mode, sigma_mode, shared, occ, B, N = ctx.meta
         if g_weight is None and g_hitlen is None:      # nothing reached the fragments (e.g. _ShadeThrough took the frame)
             return (None,) * 10
         sel_idx, cnt = ctx.sel_idx, ctx.cnt
-        _, H, W, K = sel_idx.shape
-        npix = B * H * W
-        dev = rays.device
         if mode == 2 and ctx.needs_input_grad[3]:
             raise _lib.VogeHipError("the fused view form has no gradient for the camera centre; "
                                     "use ray_tracing_iso on centred vertices")
-        g0, g1 = torch.empty_like(p0), torch.empty_like(p1)
         # (the one-pass kernel adds a pixel's slots to its table without arbitration -- a pixel's Gaussians are distinct
         #  as the trace wrote them.  A list somebody edited through torch since is no longer known to be: it takes the stand-alone
         #  kernels, whose table elects one writer per key)
         edited = sel_idx._version != ctx.idx_version
         if not (ctx.needs_input_grad[4] or THREE_KERNEL_BACKWARD or B * N >= (1 << 26) or edited):
-            # ONE pass: composite backward + trace backward per slot in registers, per-Gaussian sums in a wave-private
-            # table (fragment_bwd.hip, SRC = 1).  No act / dsd arrays, no g_len / g_act / g_dsd.
-            gw, gs_pix, gs_k = _grad_weight_layout(g_weight, K)
-            gh = None if g_hitlen is None else _dev(g_hitlen, torch.float32, "grad_hit_length")
+            # ONE pass (fragment_bwd.hip, SRC = 1): no act / dsd arrays, no g_len / g_act / g_dsd
             act, dsd = ctx.act_dsd
-            with _on(dev):
-                nbytes = lib.voge_fragment_bwd_workspace_bytes(B * N)
-                ws = _workspace(dev, nbytes)
-                if mode == 0:
-                    rc = lib.voge_fragment_bwd(_p(p0), _p(p1), _p(rays), _p(sel_idx), _p(cnt), _p(weight), _p(act), _p(ln), _p(dsd),
-                                               _p(gw), gs_pix, gs_k, _p(gh), occ, B * N, B * H, W, K, _p(ws), nbytes, _p(g0), _p(g1),
-                                               _stream())
-                else:
-                    rc = lib.voge_fragment_bwd_iso(_p(ctx.records), _p(p1), int(shared), sigma_mode, _p(rays), _p(sel_idx), _p(cnt),
-                                                   _p(weight), _p(act), _p(ln), _p(dsd), _p(gw), gs_pix, gs_k, _p(gh), occ, B, N,
-                                                   B * H, W, K, _p(ws), nbytes, _p(g0), _p(g1), _stream())
-            _lib.check(rc, "voge_fragment_bwd")
+            g0, g1 = _fragment_bwd(mode, p0, p1, ctx.records, shared, sigma_mode, rays, sel_idx, cnt, B, N, (p0, p1), weight, act, ln,
+                                   dsd, g_weight, g_hitlen, occ)
             return None, g0, g1, None, None, None, None, None, None, None
         act, dsd = _act_dsd(ctx.act_dsd, ctx.records, rays, sel_idx, ln, cnt, B * N)
-        g_act, g_len, g_dsd = torch.empty_like(act), torch.empty_like(act), torch.empty_like(act)
-        with _on(dev):
-            if g_weight is None:
-                g_act.zero_(); g_len.zero_(); g_dsd.zero_()
-            else:
-                gw = _dev(g_weight, torch.float32, "grad_weight")
-                rc = lib.voge_composite_bwd(_p(act), _p(ln), _p(dsd), _p(weight), _p(cnt), _p(gw), occ, npix, K, _p(g_act),
-                                            _p(g_len), _p(g_dsd), _stream())
-                _lib.check(rc, "voge_composite_bwd")
-            if g_hitlen is not None:      # vert_hit_length is the trace's len itself (Aggregation.py:107)
-                g_len = g_len + _dev(g_hitlen, torch.float32, "grad_hit_length")
-            g_ray = torch.empty_like(rays) if ctx.needs_input_grad[4] else None
-            if mode == 2:
-                nbytes = lib.voge_trace_bwd_iso_workspace_bytes(B * N)
-                ws = _workspace(dev, nbytes)
-                rc = lib.voge_trace_bwd_iso_view(_p(p0), _p(p1), _p(ctx.origin), int(shared), sigma_mode, _p(rays), _p(sel_idx),
-                                                 _p(cnt), _p(g_len), _p(g_act), _p(g_dsd), B, N, B * H, W, K, _p(ws), nbytes,
-                                                 _p(g_ray), _p(g0), _p(g1), _stream())
-            elif mode == 1:
-                nbytes = lib.voge_trace_bwd_iso_workspace_bytes(B * N)
-                ws = _workspace(dev, nbytes)
-                rc = lib.voge_trace_bwd_iso(_p(p0), _p(p1), _p(rays), _p(sel_idx), _p(cnt), _p(g_len), _p(g_act), _p(g_dsd), B * N,
-                                            B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g0), _p(g1), _stream())
-            else:
-                nbytes = lib.voge_trace_bwd_workspace_bytes(B * N)
-                ws = _workspace(dev, nbytes)
-                rc = lib.voge_trace_bwd(_p(p0), _p(p1), _p(rays), _p(sel_idx), _p(cnt), _p(g_len), _p(g_act), _p(g_dsd), B * N,
-                                        B * H, W, K, _p(ws), nbytes, _p(g_ray), _p(g0), _p(g1), _stream())
-        _lib.check(rc, "voge_trace_bwd")
+        if g_weight is None:
+            g_act, g_len, g_dsd = torch.zeros_like(act), torch.zeros_like(act), torch.zeros_like(act)
+        else:
+            g_act, g_len, g_dsd = _composite_bwd(act, ln, dsd, weight, cnt, g_weight, occ)
+        if g_hitlen is not None:      # vert_hit_length is the trace's len itself (Aggregation.py:107)
+            g_len = g_len + _dev(g_hitlen, torch.float32, "grad_hit_length")
+        g0, g1, g_ray = _trace_bwd(mode, p0, p1, ctx.origin, shared, sigma_mode, rays, sel_idx, cnt, g_len, g_act, g_dsd,
+                                   ctx.needs_input_grad[4])
         return None, g0, g1, None, g_ray, None, None, None, None, None
 
 
@@ -676,52 +611,20 @@ LAZY_COMPOSITE = os.environ.get("VOGE_LAZY_COMPOSITE", "1") != "0"
 
 
 class _TraceLean(torch.autograd.Function):
-    """The fine trace alone, without act / dsd (voge_fragments_fwd_iso* in trace-only form):
-    forward(mode 1 | 2, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode) -> sel_idx, sel_len, cnt, records.
-    backward: only vert_hit_length can carry a gradient here (voge_fragment_bwd_iso with g_weight = NULL)."""
+    """The fine trace alone, without act / dsd (_sweep's trace-only form):
+    forward(mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode) -> sel_idx, sel_len, cnt, records (mode 0: the
+    packed (mu, A)).  backward: only vert_hit_length can carry a gradient here (voge_fragment_bwd* with g_weight = NULL)."""
 
     @staticmethod
     def forward(ctx, mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode):
-        lib = _lib.load()
-        p0_c, p1_c = _dev(p0, torch.float32, "means"), _dev(p1, torch.float32, "sigmas")
-        rays_c = _dev(rays, torch.float32, "rays")
-        assert rays_c.dim() == 4 and rays_c.shape[3] == 3 and mode in (0, 1, 2)
-        B, H, W, _ = rays_c.shape
+        p0_c, p1_c, o_c, rays_c, fwd, B, N, H, W, shared = _trace_inputs(mode, p0, p1, origin, rays, cam_fwd)
         K, dev = int(n_assign), rays_c.device
-        o_c, shared = None, False
-        if mode == 0:      # full 3x3 forms: (mus [P,3], isigmas [P,3,3]); records = the packed (mu, A)
-            assert p0_c.dim() == 2 and p0_c.shape[1] == 3 and p0_c.shape[0] % max(B, 1) == 0
-            assert p1_c.shape == (p0_c.shape[0], 3, 3)
-            N = p0_c.shape[0] // B
-        elif mode == 2:
-            o_c = _dev(origin, torch.float32, "origin")
-            shared = p0_c.dim() == 2
-            assert p0_c.shape[-1] == 3 and (shared or p0_c.shape[0] == B) and p1_c.shape == p0_c.shape[:-1]
-            assert o_c.shape == (B, 3)
-            N = p0_c.shape[-2]
-        else:
-            assert p0_c.dim() == 2 and p0_c.shape[1] == 3 and p0_c.shape[0] % max(B, 1) == 0
-            assert p1_c.shape[0] == p0_c.shape[0] and p1_c.dim() == 1
-            N = p0_c.shape[0] // B
         sel_idx = torch.empty((B, H, W, K), dtype=torch.int32, device=dev)
         sel_len = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
         cnt = torch.empty((B, H, W), dtype=torch.int32, device=dev)
         records = torch.empty((B * N, 12 if mode == 0 else 4), dtype=torch.float32, device=dev)
-        fwd = None if cam_fwd is None else _dev(cam_fwd, torch.float32, "cam_fwd")
-        with _on(dev):
-            nbytes = lib.voge_trace_workspace_bytes(B, N, H, W)
-            ws = _workspace(dev, nbytes)
-            tail = (B, N, H, W, K, float(thr_act), 1.0, _p(ws), nbytes, _p(sel_idx), _p(sel_len), None, None, _p(cnt), None, None)
-            cones = _p(cones_of(rays_c, B, H, W))
-            if mode == 0:
-                rc = lib.voge_trace_lean_fwd(_p(p0_c), _p(p1_c), _p(rays_c), _p(fwd), cones, B, N, H, W, K, float(thr_act), _p(ws),
-                                             nbytes, _p(sel_idx), _p(sel_len), _p(cnt), _p(records), _stream())
-            elif mode == 2:
-                rc = lib.voge_fragments_fwd_iso_view(_p(p0_c), _p(p1_c), _p(o_c), int(shared), int(sigma_mode), _p(rays_c),
-                                                     _p(fwd), cones, *tail, _p(records), _stream())
-            else:
-                rc = lib.voge_fragments_fwd_iso(_p(p0_c), _p(p1_c), _p(rays_c), _p(fwd), cones, *tail, _p(records), _stream())
-        _lib.check(rc, "voge_fragments_fwd (trace only)")
+        _sweep(mode, p0_c, p1_c, o_c, shared, sigma_mode, rays_c, fwd, B, N, H, W, K, thr_act, 1.0, sel_idx, sel_len, None, None, cnt,
+               None, None, records)
         ctx.save_for_backward(p0_c, p1_c, rays_c, sel_len)
         ctx.sel_idx, ctx.cnt, ctx.records = sel_idx, cnt, records
         ctx.meta = (int(mode), int(sigma_mode), bool(shared), B, N)
@@ -734,28 +637,14 @@ class _TraceLean(torch.autograd.Function):
     def backward(ctx, _g_idx, g_len, _g_cnt, _g_rec):
         if g_len is None:
             return (None,) * 9
-        lib = _lib.load()
         p0, p1, rays, ln = ctx.saved_tensors
         mode, sigma_mode, shared, B, N = ctx.meta
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[3]:
             raise _lib.VogeHipError("deferred-composite fragments carry no gradient for the rays / the camera centre; "
                                     "VOGE_LAZY_COMPOSITE=0 (or rays that require grad at render time) selects the eager chain")
-        sel_idx, cnt = ctx.sel_idx, ctx.cnt
-        _, H, W, K = sel_idx.shape
-        gh = _dev(g_len, torch.float32, "grad_hit_length")
-        g0, g1 = torch.empty_like(p0), torch.empty_like(p1)
-        with _on(rays.device):
-            nbytes = lib.voge_fragment_bwd_workspace_bytes(B * N)
-            ws = _workspace(rays.device, nbytes)
-            # (g_weight = NULL: u = 0 everywhere, the `weight` operand is read but multiplies zero -- len stands in)
-            if mode == 0:
-                rc = lib.voge_fragment_bwd(_p(p0), _p(p1), _p(rays), _p(sel_idx), _p(cnt), _p(ln), None, _p(ln), None, None, 0, 0,
-                                           _p(gh), 1.0, B * N, B * H, W, K, _p(ws), nbytes, _p(g0), _p(g1), _stream())
-            else:
-                rc = lib.voge_fragment_bwd_iso(_p(ctx.records), _p(p1), int(shared), sigma_mode, _p(rays), _p(sel_idx), _p(cnt), _p(ln),
-                                               None, _p(ln), None, None, 0, 0, _p(gh), 1.0, B, N, B * H, W, K, _p(ws), nbytes, _p(g0),
-                                               _p(g1), _stream())
-        _lib.check(rc, "voge_fragment_bwd")
+        # (g_weight = NULL: u = 0 everywhere, the `weight` operand is read but multiplies zero -- len stands in)
+        g0, g1 = _fragment_bwd(mode, p0, p1, ctx.records, shared, sigma_mode, rays, ctx.sel_idx, ctx.cnt, B, N, (p0, p1), ln, None, ln,
+                               None, None, g_len, 1.0)
         return None, g0, g1, None, None, None, None, None, None
 
 
@@ -769,6 +658,58 @@ def _plain(t_, dtype, name):
     return t_
 
 
+def _sigma_kind(sigmas):
+    """(kind, shared) of a general sigma tensor: kind 1 = per-axis [.., N, 3], kind 2 = [.., N, 3, 3] (_GeneralPreamble's rule)."""
+    kind = 2 if tuple(sigmas.shape[-2:]) == (3, 3) and sigmas.dim() >= 3 else 1
+    return kind, sigmas.dim() == (3 if kind == 2 else 2)
+
+
+def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out, gen):
+    """frame_trace (gen False: voge_frame_trace_fwd_iso) and frame_trace_gen (gen True: voge_frame_trace_fwd_gen)."""
+    lib = _lib.load()
+    v_c, s_c = _plain(verts, torch.float32, "verts"), _plain(sigmas, torch.float32, "sigmas")
+    R_c, T_c = _plain(R, torch.float32, "R"), _plain(T, torch.float32, "T")
+    f_c, p_c = _plain(focal, torch.float32, "focal_length"), _plain(pp, torch.float32, "principal_point")
+    B = R_c.shape[0]
+    row0, h, stripe_h, pitch = band
+    shared = v_c.dim() == 2
+    N, K, dev = v_c.shape[-2], int(n_assign), v_c.device
+    assert R_c.shape == (B, 3, 3) and T_c.shape == (B, 3) and f_c.shape == (B, 2) and p_c.shape == (B, 2)
+    assert v_c.shape[-1] == 3 and (shared or v_c.shape[0] == B)
+    if gen:
+        kind, shared_s = _sigma_kind(s_c)
+        assert s_c.shape[-(kind + 1)] == N and s_c.shape[-1] == 3 and (shared_s or s_c.shape[0] == B)
+        nrec, form = (8 if kind == 1 else 12), (0, 0, False, (kind, int(shared), int(shared_s)))      # (kind 1: compact per-axis records)
+    else:
+        assert s_c.shape == v_c.shape[:-1]
+        nrec, form = 4, (2, int(sigma_mode), shared, None)
+    empty = torch.empty
+    sel_idx = empty((B, h, W, K), dtype=torch.int32, device=dev)
+    sel_len = empty((B, h, W, K), dtype=torch.float32, device=dev)
+    cnt = empty((B, h, W), dtype=torch.int32, device=dev)
+    records = empty((B * N, nrec), dtype=torch.float32, device=dev)
+    rays = empty((B, h, W, 3), dtype=torch.float32, device=dev)
+    with _on(dev):
+        nbytes = lib.voge_trace_workspace_bytes(B, N, h, W)
+        ws = _workspace(dev, nbytes)
+        cam = (R_c.data_ptr(), T_c.data_ptr(), f_c.data_ptr(), p_c.data_ptr(), int(row0), int(stripe_h), int(pitch), int(bool(behind)), B,
+               N, int(h), int(W), K, float(thr_act), ws.data_ptr(), nbytes, sel_idx.data_ptr(), sel_len.data_ptr(), cnt.data_ptr(),
+               records.data_ptr(), rays.data_ptr(), _p(origin_out), _stream())
+        if gen:
+            rc = lib.voge_frame_trace_fwd_gen(v_c.data_ptr(), s_c.data_ptr(), int(shared), int(shared_s), kind, *cam)
+        else:
+            rc = lib.voge_frame_trace_fwd_iso(v_c.data_ptr(), s_c.data_ptr(), int(shared), int(sigma_mode), *cam)
+    if rc:
+        _lib.check(rc, "voge_frame_trace_fwd")
+    _tag_index(sel_idx, cnt, B * N)
+    lz = LazyComposite.__new__(LazyComposite)      # (slots assigned directly: the cheapest construction, once a frame)
+    lz.mode, lz.sigma_mode, lz.shared, lz.gen = form
+    (lz.occ, lz.B, lz.N, lz.K, lz.p0, lz.p1, lz.sel_idx, lz.sel_len, lz.cnt, lz.records, lz.rays, lz.rays_version, lz.grad_mode,
+     lz.idx_version, lz.p0_version, lz.frame) = (float(occ), B, N, K, verts, sigmas, sel_idx, sel_len, cnt, records, rays, 0,
+                                                 torch.is_grad_enabled(), sel_idx._version, verts._version, True)
+    return sel_idx, sel_len, lz
+
+
 def frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out=None):
     """Round 6: the renderer's forward up to the sweep with the CAMERA as input (voge_frame_trace_fwd_iso): no ray-generation
     launch and no autograd node at all -- the trace's three kernels make rays, cones, camera centre and view axis from
@@ -778,44 +719,7 @@ def frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assi
     origin_out: None | a contiguous fp32 [B,3] tensor that receives the camera centres.
     -> (sel_idx, sel_len, LazyComposite): sel_len carries NO grad_fn here; whoever reads Fragments.vert_hit_length gets a
     differentiable alias on demand (LazyComposite.hit_length, _HitLength) -- the weights' consumers never pay for that node."""
-    lib = _lib.load()
-    v_c, s_c = _plain(verts, torch.float32, "verts"), _plain(sigmas, torch.float32, "sigmas")
-    R_c, T_c = _plain(R, torch.float32, "R"), _plain(T, torch.float32, "T")
-    f_c, p_c = _plain(focal, torch.float32, "focal_length"), _plain(pp, torch.float32, "principal_point")
-    B = R_c.shape[0]
-    row0, h, stripe_h, pitch = band
-    shared = v_c.dim() == 2
-    assert R_c.shape == (B, 3, 3) and T_c.shape == (B, 3) and f_c.shape == (B, 2) and p_c.shape == (B, 2)
-    assert v_c.shape[-1] == 3 and (shared or v_c.shape[0] == B) and s_c.shape == v_c.shape[:-1]
-    N, K, dev = v_c.shape[-2], int(n_assign), v_c.device
-    empty = torch.empty
-    sel_idx = empty((B, h, W, K), dtype=torch.int32, device=dev)
-    sel_len = empty((B, h, W, K), dtype=torch.float32, device=dev)
-    cnt = empty((B, h, W), dtype=torch.int32, device=dev)
-    records = empty((B * N, 4), dtype=torch.float32, device=dev)
-    rays = empty((B, h, W, 3), dtype=torch.float32, device=dev)
-    with _on(dev):
-        nbytes = lib.voge_trace_workspace_bytes(B, N, h, W)
-        ws = _workspace(dev, nbytes)
-        rc = lib.voge_frame_trace_fwd_iso(v_c.data_ptr(), s_c.data_ptr(), int(shared), int(sigma_mode), R_c.data_ptr(), T_c.data_ptr(),
-                                          f_c.data_ptr(), p_c.data_ptr(), int(row0), int(stripe_h), int(pitch), int(bool(behind)), B, N,
-                                          int(h), int(W), K, float(thr_act), ws.data_ptr(), nbytes, sel_idx.data_ptr(),
-                                          sel_len.data_ptr(), cnt.data_ptr(), records.data_ptr(), rays.data_ptr(), _p(origin_out), _stream())
-    if rc:
-        _lib.check(rc, "voge_frame_trace_fwd_iso")
-    _tag_index(sel_idx, cnt, B * N)
-    lz = LazyComposite.__new__(LazyComposite)
-    (lz.mode, lz.sigma_mode, lz.shared, lz.occ, lz.B, lz.N, lz.K, lz.p0, lz.p1, lz.sel_idx, lz.sel_len, lz.cnt, lz.records, lz.rays,
-     lz.rays_version, lz.grad_mode, lz.idx_version, lz.p0_version, lz.frame, lz.hit_len, lz.gen) = (
-        2, int(sigma_mode), shared, float(occ), B, N, K, verts, sigmas, sel_idx, sel_len, cnt, records, rays, 0, torch.is_grad_enabled(),
-        sel_idx._version, verts._version, True, None, None)
-    return sel_idx, sel_len, lz
-
-
-def _sigma_kind(sigmas):
-    """(kind, shared) of a general sigma tensor: kind 1 = per-axis [.., N, 3], kind 2 = [.., N, 3, 3] (_GeneralPreamble's rule)."""
-    kind = 2 if tuple(sigmas.shape[-2:]) == (3, 3) and sigmas.dim() >= 3 else 1
-    return kind, sigmas.dim() == (3 if kind == 2 else 2)
+    return _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out, False)
 
 
 def frame_trace_gen(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, occ, origin_out=None):
@@ -824,44 +728,14 @@ def frame_trace_gen(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_
     node).  verts [N,3] | [B,N,3]; sigmas [N,3] | [N,3,3] | [B,N,3] | [B,N,3,3].  -> (sel_idx, sel_len, LazyComposite) with
     mode 0, lz.gen = (kind, shared_verts, shared_sigmas) and lz.p0 / lz.p1 the USER's tensors: every backward route of such
     fragments goes through voge_frame_bwd_gen, which hands the gradients to exactly those."""
-    lib = _lib.load()
-    v_c, s_c = _plain(verts, torch.float32, "verts"), _plain(sigmas, torch.float32, "sigmas")
-    R_c, T_c = _plain(R, torch.float32, "R"), _plain(T, torch.float32, "T")
-    f_c, p_c = _plain(focal, torch.float32, "focal_length"), _plain(pp, torch.float32, "principal_point")
-    B = R_c.shape[0]
-    row0, h, stripe_h, pitch = band
-    shared_v = v_c.dim() == 2
-    kind, shared_s = _sigma_kind(s_c)
-    N, K, dev = v_c.shape[-2], int(n_assign), v_c.device
-    assert R_c.shape == (B, 3, 3) and T_c.shape == (B, 3) and f_c.shape == (B, 2) and p_c.shape == (B, 2)
-    assert v_c.shape[-1] == 3 and (shared_v or v_c.shape[0] == B)
-    assert s_c.shape[-(kind + 1)] == N and s_c.shape[-1] == 3 and (shared_s or s_c.shape[0] == B)
-    empty = torch.empty
-    sel_idx = empty((B, h, W, K), dtype=torch.int32, device=dev)
-    sel_len = empty((B, h, W, K), dtype=torch.float32, device=dev)
-    cnt = empty((B, h, W), dtype=torch.int32, device=dev)
-    records = empty((B * N, 8 if kind == 1 else 12), dtype=torch.float32, device=dev)      # (kind 1: the compact per-axis records)
-    rays = empty((B, h, W, 3), dtype=torch.float32, device=dev)
-    with _on(dev):
-        nbytes = lib.voge_trace_workspace_bytes(B, N, h, W)
-        ws = _workspace(dev, nbytes)
-        rc = lib.voge_frame_trace_fwd_gen(v_c.data_ptr(), s_c.data_ptr(), int(shared_v), int(shared_s), kind, R_c.data_ptr(), T_c.data_ptr(),
-                                          f_c.data_ptr(), p_c.data_ptr(), int(row0), int(stripe_h), int(pitch), int(bool(behind)), B, N,
-                                          int(h), int(W), K, float(thr_act), ws.data_ptr(), nbytes, sel_idx.data_ptr(),
-                                          sel_len.data_ptr(), cnt.data_ptr(), records.data_ptr(), rays.data_ptr(), _p(origin_out), _stream())
-    if rc:
-        _lib.check(rc, "voge_frame_trace_fwd_gen")
-    _tag_index(sel_idx, cnt, B * N)
-    lz = LazyComposite(mode=0, sigma_mode=0, shared=False, occ=float(occ), B=B, N=N, K=K, p0=verts, p1=sigmas, sel_idx=sel_idx,
-                       sel_len=sel_len, cnt=cnt, records=records, rays=rays, rays_version=0, grad_mode=torch.is_grad_enabled(),
-                       idx_version=sel_idx._version, p0_version=verts._version, frame=True, gen=(kind, int(shared_v), int(shared_s)))
-    return sel_idx, sel_len, lz
+    return _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, 0, occ, origin_out, True)
 
 
-def _frame_gen_bwd(lib, lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, gs0, gs1, g_hitlen, acc=None):
+def _frame_gen_bwd(lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, gs0, gs1, g_hitlen, acc=None):
     """voge_frame_bwd_gen on fragments of frame_trace_gen: -> (g_p0, g_p1, g_attr | None), the gradients of the user's verts / sigmas
     (and attributes).  acc: the accumulator the composite zeroed on its way (good for one call), or None (scratch, filled here)."""
     lz.check()
+    lib = _lib.load()
     kind, shared_v, shared_s = lz.gen
     dev = ln.device
     B, H, W = lz.cnt.shape
@@ -888,7 +762,7 @@ def _frame_gen_bwd(lib, lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, g
 class _HitLength(torch.autograd.Function):
     """Fragments.vert_hit_length of the camera-input trace as a differentiable tensor (the reference's is: the trace's len itself,
     Aggregation.py:107): forward(verts, sigmas, sel_len, lz) -> an alias of sel_len with this node behind it; backward: the
-    trace's chain rule for a gradient of len alone (voge_fragment_bwd_iso with g_weight = NULL), as _TraceLean.backward."""
+    trace's chain rule for a gradient of len alone (the weights' backward with g_weight = NULL), as _TraceLean.backward."""
 
     @staticmethod
     def forward(ctx, p0, p1, sel_len, lz):
@@ -901,27 +775,12 @@ class _HitLength(torch.autograd.Function):
     def backward(ctx, g_len):
         if g_len is None:
             return None, None, None, None
-        lib = _lib.load()
         lz = ctx.lz
-        lz.check()
-        if lz.gen is not None:      # (general forms: the weights' form with g_weight = NULL -- `weight` is read but multiplies zero)
-            gh = _dev(g_len, torch.float32, "grad_hit_length")
-            g0, g1, _ = _frame_gen_bwd(lib, lz, 2, None, lz.sel_len, (None, None), lz.sel_len, None, None, None, -1.0, None, 0, 0, gh)
-            return g0, g1, None, None
         (p1,) = ctx.saved_tensors
-        p1 = _dev(p1, torch.float32, "sigmas")
-        ln, sel_idx = lz.sel_len, lz.sel_idx
-        B, H, W, K = sel_idx.shape
-        gh = _dev(g_len, torch.float32, "grad_hit_length")
-        g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=ln.device)
-        g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=ln.device)
-        with _on(ln.device):
-            nbytes = lib.voge_fragment_bwd_workspace_bytes(lz.B * lz.N)
-            ws = _workspace(ln.device, nbytes)
-            rc = lib.voge_fragment_bwd_iso(_p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(sel_idx), _p(lz.cnt),
-                                           _p(ln), None, _p(ln), None, None, 0, 0, _p(gh), 1.0, lz.B, lz.N, B * H, W, K, _p(ws), nbytes,
-                                           _p(g0), _p(g1), _stream())
-        _lib.check(rc, "voge_fragment_bwd")
+        if lz.gen is None:      # (general forms read their records: the user's sigmas are not an operand)
+            p1 = _dev(p1, torch.float32, "sigmas")
+        # (`weight` is read but multiplies zero -- len stands in; the trace-only form's absorptivity 1.0)
+        g0, g1 = _lazy_fragment_bwd(lz, p1, lz.sel_len, lz.sel_len, None, g_len=g_len, occ=1.0)
         return g0, g1, None, None
 
 
@@ -949,11 +808,10 @@ class LazyComposite:
     """What the deferred composite needs from a _TraceLean call (nothing in it has a grad_fn except sel_len, which the
     composite nodes take as an input)."""
     __slots__ = ("mode", "sigma_mode", "shared", "occ", "B", "N", "K", "p0", "p1", "sel_idx", "sel_len", "cnt", "records", "rays",
-                 "rays_version", "grad_mode", "idx_version", "p0_version", "frame", "hit_len", "gen")
+                 "rays_version", "grad_mode", "idx_version", "p0_version", "frame", "gen")
 
     def __init__(self, **kw):
         self.frame = False      # (made by frame_trace: the shade stage may take the frame entries of ABI 7)
-        self.hit_len = None     # (unused; kept for pickles of round 6's first builds)
         self.gen = None         # (frame_trace_gen: (kind, shared_verts, shared_sigmas) -- p0 / p1 are the USER's verts / sigmas)
         for k, v in kw.items():
             setattr(self, k, v)
@@ -1041,30 +899,59 @@ def _general_act_dsd(lz, sel_len, need):
     return (torch.empty_like(sel_len), torch.empty_like(sel_len))
 
 
-def _lazy_fragment_bwd(lib, lz, p1, weight, ln, g_weight, K, ad=(None, None)):
-    """composite + trace backward in one pass for a deferred composite: -> (g_p0, g_p1)."""
+def _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ad=(None, None), g_len=None, occ=None):
+    """_fragment_bwd on deferred-composite fragments (frame_trace_gen's: voge_frame_bwd_gen) -> (g_p0, g_p1).  occ: the absorptivity
+    the kernel is handed (default lz.occ)."""
     if lz.gen is not None:
-        gw, gs_pix, gs_k = _grad_weight_layout(g_weight, K)
-        g0, g1, _ = _frame_gen_bwd(lib, lz, 2, None, weight, ad, ln, None, None, None, -1.0, gw, gs_pix, gs_k, None)
+        gw, gs_pix, gs_k = _grad_weight_layout(g_weight, lz.K)
+        gh = None if g_len is None else _dev(g_len, torch.float32, "grad_hit_length")
+        g0, g1, _ = _frame_gen_bwd(lz, 2, None, weight, ad, ln, None, None, None, -1.0, gw, gs_pix, gs_k, gh)
         return g0, g1
     lz.check()
-    gw, gs_pix, gs_k = _grad_weight_layout(g_weight, K)
-    g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=ln.device)
-    g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=ln.device)
-    B, H, W = lz.cnt.shape
-    with _on(ln.device):
-        nbytes = lib.voge_fragment_bwd_workspace_bytes(lz.B * lz.N)
-        ws = _workspace(ln.device, nbytes)
-        if lz.mode == 0:
-            rc = lib.voge_fragment_bwd(_p(lz.means()), _p(p1), _p(lz.rays), _p(lz.sel_idx), _p(lz.cnt), _p(weight), _p(ad[0]), _p(ln),
-                                       _p(ad[1]), _p(gw), gs_pix, gs_k, None, lz.occ, lz.B * lz.N, B * H, W, K, _p(ws), nbytes, _p(g0),
-                                       _p(g1), _stream())
+    return _fragment_bwd(lz.mode, lz.means() if lz.mode == 0 else None, p1, lz.records, lz.shared, lz.sigma_mode, lz.rays, lz.sel_idx,
+                         lz.cnt, lz.B, lz.N, (lz.p0, lz.p1), weight, ad[0], ln, ad[1], g_weight, g_len, lz.occ if occ is None else occ)
+
+
+def _frame_acc(lz, need):
+    """(round 6) Fragments of the camera-input trace: the accumulator of the coming backward, allocated by the forward whose launch
+    zeroes it on its way -- no fill launch in front of that backward (voge_frame_*_bwd_*).  None when that does not apply."""
+    if lz.frame and need and lz.K <= 128 and FRAME_DIRECT_BWD:
+        return torch.empty((lz.B * lz.N * (32 if lz.gen is None else (48 if lz.gen[0] == 1 else 64)),), dtype=torch.uint8,
+                           device=lz.sel_idx.device)
+    return None
+
+
+def _composite_fwd(lz, sel_len, need, attr=None, bg=None, thr=-1.0, rgb=None, img=None, wsum=None, sil=None, acc=None):
+    """The deferred composite from the sweep's records in ONE launch -> (weight, valid_num, (act, dsd)): the weights alone, or with
+    attr also the merged attributes rgb, their weight sum and (bg given) the image.  The frame entries also write the silhouette sil
+    and zero the accumulator acc (_frame_acc); (act, dsd) is what the general composite keeps for its backward (_general_act_dsd,
+    need: whether a backward may run), left on the weights as voge_act_dsd."""
+    lib = _lib.load()
+    idx, K = lz.sel_idx, lz.K
+    npix = idx.numel() // K
+    C, Nattr = (0, 0) if attr is None else (attr.shape[1], attr.shape[0])
+    nacc = 0 if acc is None else acc.numel()
+    weight = torch.empty_like(sel_len)
+    valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=idx.device)
+    with _on(idx.device):
+        ad = _general_act_dsd(lz, sel_len, need)
+        src = (_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ)
+        args = src + (_p(attr), _p(bg), float(thr), npix, K, C, Nattr, _p(weight), _p(valid), _p(rgb), _p(img), _p(wsum))
+        if lz.gen is not None:
+            rc = lib.voge_frame_shade_fwd_rec(lz.gen[0], *args, _p(sil), _p(ad[0]), _p(ad[1]), _p(acc), nacc, _stream())
+        elif attr is None and lz.mode == 0:
+            rc = lib.voge_composite_fwd_rec(*src, npix, K, _p(weight), _p(valid), _p(ad[0]), _p(ad[1]), _stream())
+        elif attr is None:
+            rc = lib.voge_composite_fwd_iso(*src, npix, K, _p(weight), _p(valid), _stream())
+        elif lz.mode == 0:
+            rc = lib.voge_composite_shade_fwd_rec(*args, _p(ad[0]), _p(ad[1]), _stream())
+        elif sil is not None or acc is not None:
+            rc = lib.voge_frame_shade_fwd_iso(*args, _p(sil), _p(acc), nacc, _stream())
         else:
-            rc = lib.voge_fragment_bwd_iso(_p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(lz.sel_idx), _p(lz.cnt),
-                                           _p(weight), None, _p(ln), None, _p(gw), gs_pix, gs_k, None, lz.occ, lz.B, lz.N, B * H, W, K,
-                                           _p(ws), nbytes, _p(g0), _p(g1), _stream())
-    _lib.check(rc, "voge_fragment_bwd")
-    return g0, g1
+            rc = lib.voge_composite_shade_fwd_iso(*args, _stream())
+    _lib.check(rc, "voge_composite_fwd (from the records)")
+    weight.voge_act_dsd = ad
+    return weight, valid, ad
 
 
 class _CompositeLean(torch.autograd.Function):
@@ -1074,24 +961,7 @@ class _CompositeLean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, p0, p1, sel_len, lz):
-        lib = _lib.load()
-        idx, K = lz.sel_idx, lz.K
-        weight = torch.empty_like(sel_len)
-        valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=idx.device)
-        with _on(idx.device):
-            ctx.ad = _general_act_dsd(lz, sel_len, any(ctx.needs_input_grad))
-            if lz.gen is not None:
-                rc = lib.voge_frame_shade_fwd_rec(lz.gen[0], _p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, None, None,
-                                                  -1.0, idx.numel() // K, K, 0, 0, _p(weight), _p(valid), None, None, None, None,
-                                                  _p(ctx.ad[0]), _p(ctx.ad[1]), None, 0, _stream())
-            elif lz.mode == 0:
-                rc = lib.voge_composite_fwd_rec(_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, idx.numel() // K,
-                                                K, _p(weight), _p(valid), _p(ctx.ad[0]), _p(ctx.ad[1]), _stream())
-            else:
-                rc = lib.voge_composite_fwd_iso(_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, idx.numel() // K,
-                                                K, _p(weight), _p(valid), _stream())
-        _lib.check(rc, "voge_composite_fwd (from the records)")
-        weight.voge_act_dsd = ctx.ad
+        weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad))
         ctx.save_for_backward(_dev(p1, torch.float32, "sigmas"), sel_len, weight)
         ctx.lz = lz
         ctx.mark_non_differentiable(valid)
@@ -1103,8 +973,40 @@ class _CompositeLean(torch.autograd.Function):
         if g_weight is None:
             return None, None, None, None
         p1, ln, weight = ctx.saved_tensors
-        g0, g1 = _lazy_fragment_bwd(_lib.load(), ctx.lz, p1, weight, ln, g_weight, ctx.lz.K, ctx.ad)
+        g0, g1 = _lazy_fragment_bwd(ctx.lz, p1, weight, ln, g_weight, ctx.ad)
         return g0, g1, None, None
+
+
+def _shade_bwd(mode, means, sigmas, records, shared, sigma_mode, rays, cnt, occ, B, N, like, attr, idx, weight, act, ln, dsd, rgb,
+               wsum, bg, thr, go, gs_pix, gs_c, acc=None):
+    """The image's gradient go (strides gs_pix, gs_c: _grad_layout) through shade + composite + trace in ONE kernel -> (g0, g1, g_attr),
+    g0 / g1 shaped like like[0] / like[1]: voge_fragment_shade_bwd (mode 0: the means), _iso (the records), or, on the accumulator
+    acc that the forward zeroed (_frame_acc), voge_frame_shade_bwd_iso."""
+    lib = _lib.load()
+    _, H, W, K = idx.shape
+    Nattr, C = attr.shape
+    dev = idx.device
+    g_attr = torch.empty_like(attr)
+    g0 = torch.empty(like[0].shape, dtype=torch.float32, device=dev)
+    g1 = torch.empty(like[1].shape, dtype=torch.float32, device=dev)
+    image = (_p(rgb), _p(wsum), _p(bg), thr, _p(go), gs_pix, gs_c, occ)
+    sizes = (B * H, W, K, C, Nattr)
+    grads = (_p(g0), _p(g1), _p(g_attr))
+    with _on(dev):
+        if acc is not None:
+            rc = lib.voge_frame_shade_bwd_iso(_p(records), _p(sigmas), int(shared), sigma_mode, _p(rays), _p(attr), _p(idx), _p(cnt),
+                                              _p(weight), _p(ln), *image, B, N, *sizes, _p(acc), acc.numel(), *grads, _stream())
+        else:
+            nbytes = lib.voge_fragment_bwd_workspace_bytes(B * N)
+            ws = _workspace(dev, nbytes)
+            slots = (_p(attr), _p(idx), _p(cnt), _p(weight), _p(act), _p(ln), _p(dsd), *image)
+            if mode == 0:
+                rc = lib.voge_fragment_shade_bwd(_p(means), _p(sigmas), _p(rays), *slots, B * N, *sizes, _p(ws), nbytes, *grads, _stream())
+            else:
+                rc = lib.voge_fragment_shade_bwd_iso(_p(records), _p(sigmas), int(shared), sigma_mode, _p(rays), *slots, B, N, *sizes,
+                                                     _p(ws), nbytes, *grads, _stream())
+    _lib.check(rc, "voge_fragment_shade_bwd")
+    return g0, g1, g_attr
 
 
 class _CompositeShade(torch.autograd.Function):
@@ -1115,38 +1017,17 @@ class _CompositeShade(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, p0, p1, sel_len, lz, bg, thr):
-        lib = _lib.load()
         attr_c = _dev(attr, torch.float32, "colors")
         bg_c = _dev(bg, torch.float32, "background_color")
-        idx, K = lz.sel_idx, lz.K
+        idx = lz.sel_idx
         Nattr, C = attr_c.shape
         assert bg_c.numel() == C
         check_index_range(idx, Nattr)
-        weight = torch.empty_like(sel_len)
-        valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=idx.device)
         rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
         img = torch.empty_like(rgb)
         wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
-        # (round 6) fragments of the camera-input trace: the accumulator of the coming backward is allocated here and this launch
-        # zeroes it on its way -- no fill launch in front of that backward (voge_frame_shade_bwd_iso)
-        ctx.gbuf = None
-        if lz.frame and any(ctx.needs_input_grad[:3]) and K <= 128 and FRAME_DIRECT_BWD:
-            ctx.gbuf = torch.empty((lz.B * lz.N * (32 if lz.gen is None else (48 if lz.gen[0] == 1 else 64)),), dtype=torch.uint8, device=idx.device)
-        with _on(idx.device):
-            ctx.ad = _general_act_dsd(lz, sel_len, any(ctx.needs_input_grad))
-            args = (_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, _p(attr_c), _p(bg_c), float(thr),
-                    idx.numel() // K, K, C, Nattr, _p(weight), _p(valid), _p(rgb), _p(img), _p(wsum))
-            if lz.gen is not None:
-                rc = lib.voge_frame_shade_fwd_rec(lz.gen[0], *args, None, _p(ctx.ad[0]), _p(ctx.ad[1]), _p(ctx.gbuf),
-                                                  0 if ctx.gbuf is None else ctx.gbuf.numel(), _stream())
-            elif lz.mode == 0:
-                rc = lib.voge_composite_shade_fwd_rec(*args, _p(ctx.ad[0]), _p(ctx.ad[1]), _stream())
-            elif ctx.gbuf is not None:
-                rc = lib.voge_frame_shade_fwd_iso(*args, None, _p(ctx.gbuf), ctx.gbuf.numel(), _stream())
-            else:
-                rc = lib.voge_composite_shade_fwd_iso(*args, _stream())
-        _lib.check(rc, "voge_composite_shade_fwd")
-        weight.voge_act_dsd = ctx.ad
+        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]))
+        weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad), attr_c, bg_c, thr, rgb, img, wsum, acc=ctx.gbuf)
         ctx.save_for_backward(attr_c, _dev(p1, torch.float32, "sigmas"), sel_len, weight, rgb, bg_c, wsum)
         ctx.lz, ctx.thr = lz, float(thr)
         ctx.mark_non_differentiable(valid)
@@ -1155,55 +1036,58 @@ class _CompositeShade(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_img, g_weight, _g_valid):
-        lib = _lib.load()
         attr, p1, ln, weight, rgb, bg, wsum = ctx.saved_tensors
         lz = ctx.lz
         lz.check()
-        idx = lz.sel_idx
-        B, H, W, K = idx.shape
-        Nattr, C = attr.shape
         g_attr = g0 = g1 = None
         if g_img is not None:
-            if g_img.dtype == torch.float32 and g_img.is_cuda and all(s == 0 for s in g_img.stride()):
-                go, gs_pix, gs_c = g_img, 0, 0      # autograd's broadcast scalar (sum / mean losses), read in place
-            else:
-                go, gs_pix, gs_c = _dev(g_img, torch.float32, "grad_image"), C, 1
+            go, gs_pix, gs_c = _grad_layout(g_img, attr.shape[1])
             gbuf, ctx.gbuf = ctx.gbuf, None      # (zeroed by the forward, good for ONE backward: a second one takes the scratch form)
             if lz.gen is not None:      # (general forms of the frame path: the user's verts / sigmas get their gradients directly)
-                g0, g1, g_attr = _frame_gen_bwd(lib, lz, 0, attr, weight, ctx.ad, ln, rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, None, acc=gbuf)
-            elif gbuf is not None:
-                g_attr = torch.empty_like(attr)
-                g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=idx.device)
-                g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=idx.device)
-                with _on(idx.device):
-                    rc = lib.voge_frame_shade_bwd_iso(
-                        _p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight),
-                        _p(ln), _p(rgb), _p(wsum), _p(bg), ctx.thr, _p(go), gs_pix, gs_c, lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr,
-                        _p(gbuf), gbuf.numel(), _p(g0), _p(g1), _p(g_attr), _stream())
-                _lib.check(rc, "voge_frame_shade_bwd_iso")
-        if g_img is not None and g0 is None:
-            g_attr = torch.empty_like(attr)
-            g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=idx.device)
-            g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=idx.device)
-            with _on(idx.device):
-                nbytes = lib.voge_fragment_bwd_workspace_bytes(lz.B * lz.N)
-                ws = _workspace(idx.device, nbytes)
-                if lz.mode == 0:
-                    rc = lib.voge_fragment_shade_bwd(
-                        _p(lz.means()), _p(p1), _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight), _p(ctx.ad[0]), _p(ln),
-                        _p(ctx.ad[1]), _p(rgb), _p(wsum), _p(bg), ctx.thr, _p(go), gs_pix, gs_c, lz.occ, lz.B * lz.N, B * H, W, K, C, Nattr,
-                        _p(ws), nbytes, _p(g0), _p(g1), _p(g_attr), _stream())
-                else:
-                    rc = lib.voge_fragment_shade_bwd_iso(
-                        _p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight), None,
-                        _p(ln), None, _p(rgb), _p(wsum), _p(bg), ctx.thr, _p(go), gs_pix, gs_c, lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr,
-                        _p(ws), nbytes, _p(g0), _p(g1), _p(g_attr), _stream())
-            _lib.check(rc, "voge_fragment_shade_bwd")
+                g0, g1, g_attr = _frame_gen_bwd(lz, 0, attr, weight, ctx.ad, ln, rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, None, acc=gbuf)
+            else:
+                g0, g1, g_attr = _shade_bwd(lz.mode, lz.means() if lz.mode == 0 else None, p1, lz.records, lz.shared, lz.sigma_mode,
+                                            lz.rays, lz.cnt, lz.occ, lz.B, lz.N, (lz.p0, lz.p1), attr, lz.sel_idx, weight, ctx.ad[0], ln,
+                                            ctx.ad[1], rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, gbuf)
         if g_weight is not None:
-            h0, h1 = _lazy_fragment_bwd(lib, lz, p1, weight, ln, g_weight, K, ctx.ad)
+            h0, h1 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
             g0, g1 = (h0, h1) if g0 is None else (g0 + h0, g1 + h1)
         need = ctx.needs_input_grad
         return (g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None, None, None
+
+
+def _merge_bwd(lz, p1, attr, weight, ad, ln, go, gs_pix, gs_c, gws, wsum_fwd, acc):
+    """The gradients of the merged attributes (go: _grad_layout) and of their weight sum (gws) through merge + composite + trace in
+    ONE kernel -> (g0, g1, g_attr): voge_fragment_merge_bwd (mode 0), _iso, or, on the accumulator acc that the forward zeroed,
+    voge_frame_merge_bwd_iso -- which also takes the silhouette's gradient as gws, with the forward's sums wsum_fwd."""
+    lib = _lib.load()
+    idx = lz.sel_idx
+    B, H, W, K = idx.shape
+    Nattr, C = attr.shape
+    dev = idx.device
+    g_attr = torch.empty_like(attr)
+    g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=dev)
+    g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=dev)
+    grad = (_p(go), gs_pix, gs_c, _p(gws))
+    sizes = (B * H, W, K, C, Nattr)
+    grads = (_p(g0), _p(g1), _p(g_attr))
+    with _on(dev):
+        if acc is not None:
+            rc = lib.voge_frame_merge_bwd_iso(_p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(attr), _p(idx),
+                                              _p(lz.cnt), _p(weight), _p(ln), *grad, _p(wsum_fwd), lz.occ, lz.B, lz.N, *sizes, _p(acc),
+                                              acc.numel(), *grads, _stream())
+        else:
+            nbytes = lib.voge_fragment_bwd_workspace_bytes(lz.B * lz.N)
+            ws = _workspace(dev, nbytes)
+            slots = (_p(attr), _p(idx), _p(lz.cnt), _p(weight), _p(ad[0]), _p(ln), _p(ad[1]), *grad, lz.occ)
+            if lz.mode == 0:
+                rc = lib.voge_fragment_merge_bwd(_p(lz.means()), _p(p1), _p(lz.rays), *slots, lz.B * lz.N, *sizes, _p(ws), nbytes, *grads,
+                                                 _stream())
+            else:
+                rc = lib.voge_fragment_merge_bwd_iso(_p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), *slots, lz.B,
+                                                     lz.N, *sizes, _p(ws), nbytes, *grads, _stream())
+    _lib.check(rc, "voge_fragment_merge_bwd")
+    return g0, g1, g_attr
 
 
 class _CompositeMerge(torch.autograd.Function):
@@ -1215,36 +1099,17 @@ class _CompositeMerge(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, p0, p1, sel_len, lz):
-        lib = _lib.load()
         attr_c = _dev(attr, torch.float32, "vert_attr")
-        idx, K = lz.sel_idx, lz.K
+        idx = lz.sel_idx
         Nattr, C = attr_c.shape
         check_index_range(idx, Nattr)
-        weight = torch.empty_like(sel_len)
-        valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=idx.device)
         rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
         wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
         # (frame path: the composite writes get_silhouette = min(weight sum, 1) next to the sum, a differentiable OUTPUT of this
         #  node -- the training pattern's silhouette costs no launch forward and none backward: see backward)
         sil = torch.empty_like(wsum) if lz.frame else None
-        ctx.gbuf = None      # (see _CompositeShade: the frame path's backward without a fill launch)
-        if lz.frame and any(ctx.needs_input_grad[:3]) and K <= 128 and FRAME_DIRECT_BWD:
-            ctx.gbuf = torch.empty((lz.B * lz.N * (32 if lz.gen is None else (48 if lz.gen[0] == 1 else 64)),), dtype=torch.uint8, device=idx.device)
-        with _on(idx.device):
-            ctx.ad = _general_act_dsd(lz, sel_len, any(ctx.needs_input_grad))
-            args = (_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, _p(attr_c), None, -1.0, idx.numel() // K, K,
-                    C, Nattr, _p(weight), _p(valid), _p(rgb), None, _p(wsum))
-            nacc = 0 if ctx.gbuf is None else ctx.gbuf.numel()
-            if lz.gen is not None:
-                rc = lib.voge_frame_shade_fwd_rec(lz.gen[0], *args, _p(sil), _p(ctx.ad[0]), _p(ctx.ad[1]), _p(ctx.gbuf), nacc, _stream())
-            elif lz.mode == 0:
-                rc = lib.voge_composite_shade_fwd_rec(*args, _p(ctx.ad[0]), _p(ctx.ad[1]), _stream())
-            elif lz.frame:
-                rc = lib.voge_frame_shade_fwd_iso(*args, _p(sil), _p(ctx.gbuf), nacc, _stream())
-            else:
-                rc = lib.voge_composite_shade_fwd_iso(*args, _stream())
-        _lib.check(rc, "voge_composite_shade_fwd")
-        weight.voge_act_dsd = ctx.ad
+        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]))
+        weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad), attr_c, None, -1.0, rgb, None, wsum, sil, ctx.gbuf)
         ctx.save_for_backward(attr_c, _dev(p1, torch.float32, "sigmas"), sel_len, weight, wsum)
         ctx.lz = lz
         ctx.mark_non_differentiable(valid)
@@ -1253,13 +1118,11 @@ class _CompositeMerge(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_wsum, g_weight, _g_valid, g_sil=None):
-        lib = _lib.load()
         attr, p1, ln, weight, wsum = ctx.saved_tensors
         lz = ctx.lz
         lz.check()
         idx = lz.sel_idx
-        B, H, W, K = idx.shape
-        Nattr, C = attr.shape
+        C = attr.shape[1]
         g_attr = g0 = g1 = None
         # the silhouette's gradient: handed to the fused kernel as it is (with the forward's sums, which say where min(sum, 1)
         # passes it on) when that kernel runs on the forward's accumulator; any other combination turns it into the sum's own
@@ -1273,44 +1136,15 @@ class _CompositeMerge(torch.autograd.Function):
         if g_rgb is not None or g_wsum is not None:
             if g_rgb is None:
                 g_rgb = torch.zeros(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
-            if g_rgb.dtype == torch.float32 and g_rgb.is_cuda and all(s == 0 for s in g_rgb.stride()):
-                go, gs_pix, gs_c = g_rgb, 0, 0
-            else:
-                go, gs_pix, gs_c = _dev(g_rgb, torch.float32, "grad_out"), C, 1
+            go, gs_pix, gs_c = _grad_layout(g_rgb, C)
             gws = None if g_wsum is None else _dev(g_wsum, torch.float32, "grad_weight_sum")
             gbuf, ctx.gbuf = ctx.gbuf, None      # (zeroed by the forward, good for ONE backward)
             if lz.gen is not None:
-                g0, g1, g_attr = _frame_gen_bwd(lib, lz, 1, attr, weight, ctx.ad, ln, wsum_fwd, gws, None, -1.0, go, gs_pix, gs_c, None, acc=gbuf)
-            elif gbuf is not None:
-                g_attr = torch.empty_like(attr)
-                g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=idx.device)
-                g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=idx.device)
-                with _on(idx.device):
-                    rc = lib.voge_frame_merge_bwd_iso(
-                        _p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight),
-                        _p(ln), _p(go), gs_pix, gs_c, _p(gws), _p(wsum_fwd), lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr, _p(gbuf),
-                        gbuf.numel(), _p(g0), _p(g1), _p(g_attr), _stream())
-                _lib.check(rc, "voge_frame_merge_bwd_iso")
-        if (g_rgb is not None or g_wsum is not None) and g0 is None:
-            g_attr = torch.empty_like(attr)
-            g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=idx.device)
-            g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=idx.device)
-            with _on(idx.device):
-                nbytes = lib.voge_fragment_bwd_workspace_bytes(lz.B * lz.N)
-                ws = _workspace(idx.device, nbytes)
-                if lz.mode == 0:
-                    rc = lib.voge_fragment_merge_bwd(
-                        _p(lz.means()), _p(p1), _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight), _p(ctx.ad[0]), _p(ln),
-                        _p(ctx.ad[1]), _p(go), gs_pix, gs_c, _p(gws), lz.occ, lz.B * lz.N, B * H, W, K, C, Nattr, _p(ws), nbytes, _p(g0),
-                        _p(g1), _p(g_attr), _stream())
-                else:
-                    rc = lib.voge_fragment_merge_bwd_iso(
-                        _p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(attr), _p(idx), _p(lz.cnt), _p(weight), None,
-                        _p(ln), None, _p(go), gs_pix, gs_c, _p(gws), lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr, _p(ws), nbytes, _p(g0),
-                        _p(g1), _p(g_attr), _stream())
-            _lib.check(rc, "voge_fragment_merge_bwd")
+                g0, g1, g_attr = _frame_gen_bwd(lz, 1, attr, weight, ctx.ad, ln, wsum_fwd, gws, None, -1.0, go, gs_pix, gs_c, None, acc=gbuf)
+            else:
+                g0, g1, g_attr = _merge_bwd(lz, p1, attr, weight, ctx.ad, ln, go, gs_pix, gs_c, gws, wsum_fwd, gbuf)
         if g_weight is not None:
-            h0, h1 = _lazy_fragment_bwd(lib, lz, p1, weight, ln, g_weight, K, ctx.ad)
+            h0, h1 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
             g0, g1 = (h0, h1) if g0 is None else (g0 + h0, g1 + h1)
         need = ctx.needs_input_grad
         return (g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None
@@ -1377,6 +1211,30 @@ def composite_shade(lz, attr, bg, thr):
     return img, lz.through(weight), valid
 
 
+def _shade_fwd(attr, weight, idx, valid_num, bg, thr):
+    """interpolate_attr + get_silhouette + to_colored_background of composited fragments, one kernel (voge_shade_fwd)
+    -> (attr, weight, valid_num, bg as the kernel read them; rgb, img, wsum)."""
+    lib = _lib.load()
+    attr_c = _dev(attr, torch.float32, "colors")
+    w = _dev(weight, torch.float32, "weight")
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
+        raise _lib.VogeHipError("vert_index must be a contiguous int32 tensor on the HIP device")
+    vn = _dev(valid_num, torch.int64, "valid_num")
+    bg_c = _dev(bg, torch.float32, "background_color")
+    K = idx.shape[-1]
+    Nattr, C = attr_c.shape
+    assert C <= 4 and bg_c.numel() == C
+    check_index_range(idx, Nattr)
+    rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
+    img = torch.empty_like(rgb)
+    wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
+    with _on(idx.device):
+        rc = lib.voge_shade_fwd(_p(attr_c), _p(idx), _p(w), _p(vn), _p(bg_c), float(thr), idx.numel() // max(K, 1), K, C, Nattr, 1,
+                                _p(rgb), _p(img), None, _p(wsum), _stream())
+    _lib.check(rc, "voge_shade_fwd")
+    return attr_c, w, vn, bg_c, rgb, img, wsum
+
+
 class _ShadeThrough(torch.autograd.Function):
     """to_colored_background on fragments this renderer made: the forward is _Shade's, the
     backward runs shade -> composite -> trace as ONE kernel (voge_fragment_shade_bwd_iso for scalar sigmas,
@@ -1388,63 +1246,23 @@ class _ShadeThrough(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, weight, p0, p1, th, idx, valid_num, bg, thr):
-        lib = _lib.load()
-        attr_c = _dev(attr, torch.float32, "colors")
-        w = _dev(weight, torch.float32, "weight")
-        vn = _dev(valid_num, torch.int64, "valid_num")
-        bg_c = _dev(bg, torch.float32, "background_color")
-        K = idx.shape[-1]
-        npix = idx.numel() // max(K, 1)
-        Nattr, C = attr_c.shape
-        assert C <= 4 and bg_c.numel() == C
-        check_index_range(idx, Nattr)
-        rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
-        img = torch.empty_like(rgb)
-        wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
-        with _on(idx.device):
-            rc = lib.voge_shade_fwd(_p(attr_c), _p(idx), _p(w), _p(vn), _p(bg_c), float(thr), npix, K, C, Nattr, 1,
-                                    _p(rgb), _p(img), None, _p(wsum), _stream())
-        _lib.check(rc, "voge_shade_fwd")
+        attr_c, w, _, bg_c, rgb, img, wsum = _shade_fwd(attr, weight, idx, valid_num, bg, thr)
         ctx.save_for_backward(attr_c, w, rgb, bg_c, wsum)
         ctx.th, ctx.idx, ctx.thr = th, idx, float(thr)
         return img
 
     @staticmethod
     def backward(ctx, g_img):
-        lib = _lib.load()
         attr, w, rgb, bg, wsum = ctx.saved_tensors
         th, idx = ctx.th, ctx.idx
         # what the kernel reads outside save_for_backward must still be what the forward saw
         if (th["len"]._version, th["rays"]._version) != th["versions"][1:3]:
             raise RuntimeError("vert_hit_length or the rays were modified in place after to_colored_background: "
                                "the fused backward would read the changed values (as autograd's own check for saved tensors)")
-        B, H, W, K = idx.shape
-        Nattr, C = attr.shape
-        # the gradient as it comes: a contiguous image, or autograd's broadcast scalar (sum / mean losses) read in place
-        if g_img.dtype == torch.float32 and g_img.is_cuda and all(s == 0 for s in g_img.stride()):
-            go, gs_pix, gs_c = g_img, 0, 0
-        else:
-            go, gs_pix, gs_c = _dev(g_img, torch.float32, "grad_image"), C, 1
-        g_attr = torch.empty_like(attr)
-        p0, p1 = th["p0"], th["p1"]
-        g0 = torch.empty(p0.shape, dtype=torch.float32, device=idx.device)
-        g1 = torch.empty(p1.shape, dtype=torch.float32, device=idx.device)
-        P = th["B"] * th["N"]
-        with _on(idx.device):
-            nbytes = lib.voge_fragment_bwd_workspace_bytes(P)
-            ws = _workspace(idx.device, nbytes)
-            if th["mode"] == 0:      # full 3x3 forms: gradients of (mus, isigmas) as given
-                rc = lib.voge_fragment_shade_bwd(
-                    _p(th["means"]), _p(th["sigmas"]), _p(th["rays"]), _p(attr), _p(idx), _p(th["cnt"]), _p(w), _p(th["act"]),
-                    _p(th["len"]), _p(th["dsd"]), _p(rgb), _p(wsum), _p(bg), ctx.thr, _p(go), gs_pix, gs_c, th["occ"], P, B * H, W, K,
-                    C, Nattr, _p(ws), nbytes, _p(g0), _p(g1), _p(g_attr), _stream())
-            else:
-                rc = lib.voge_fragment_shade_bwd_iso(
-                    _p(th["records"]), _p(th["sigmas"]), int(th["shared"]), th["sigma_mode"], _p(th["rays"]), _p(attr), _p(idx),
-                    _p(th["cnt"]), _p(w), _p(th["act"]), _p(th["len"]), _p(th["dsd"]), _p(rgb), _p(wsum), _p(bg), ctx.thr, _p(go),
-                    gs_pix, gs_c, th["occ"], th["B"], th["N"], B * H, W, K, C, Nattr, _p(ws), nbytes, _p(g0), _p(g1), _p(g_attr),
-                    _stream())
-        _lib.check(rc, "voge_fragment_shade_bwd")
+        go, gs_pix, gs_c = _grad_layout(g_img, attr.shape[1])
+        g0, g1, g_attr = _shade_bwd(th["mode"], th["means"], th["sigmas"], th["records"], th["shared"], th["sigma_mode"], th["rays"],
+                                    th["cnt"], th["occ"], th["B"], th["N"], (th["p0"], th["p1"]), attr, idx, w, th["act"], th["len"],
+                                    th["dsd"], rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c)
         need = ctx.needs_input_grad
         return (g_attr if need[0] else None), None, (g0 if need[2] else None), (g1 if need[3] else None), None, None, None, None, None
 
@@ -1517,20 +1335,10 @@ class _Composite(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_weight, _g_valid):
-        lib = _lib.load()
         if g_weight is None:
             return None, None, None, None, None
         act, ln, dsd, weight = ctx.saved_tensors
-        K = act.shape[-1]
-        npix = act.numel() // max(K, 1)
-        gw = _dev(g_weight, torch.float32, "grad_weight")
-        g_act = torch.empty_like(act)
-        g_len = torch.empty_like(act)
-        g_dsd = torch.empty_like(act)
-        with _on(act.device):
-            rc = lib.voge_composite_bwd(_p(act), _p(ln), _p(dsd), _p(weight), _p(ctx.cnt), _p(gw), ctx.occ, npix, K, _p(g_act), _p(g_len),
-                                        _p(g_dsd), _stream())
-        _lib.check(rc, "voge_composite_bwd")
+        g_act, g_len, g_dsd = _composite_bwd(act, ln, dsd, weight, ctx.cnt, g_weight, ctx.occ)
         return None, g_act, g_len, g_dsd, None
 
 
@@ -1624,25 +1432,7 @@ class _Shade(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attr, weight, idx, valid_num, bg, thr):
-        lib = _lib.load()
-        attr_c = _dev(attr, torch.float32, "colors")
-        w = _dev(weight, torch.float32, "weight")
-        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
-            raise _lib.VogeHipError("vert_index must be a contiguous int32 tensor on the HIP device")
-        vn = _dev(valid_num, torch.int64, "valid_num")
-        bg_c = _dev(bg, torch.float32, "background_color")
-        K = idx.shape[-1]
-        npix = idx.numel() // max(K, 1)
-        Nattr, C = attr_c.shape
-        assert C <= 4 and bg_c.numel() == C
-        check_index_range(idx, Nattr)
-        rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
-        img = torch.empty_like(rgb)
-        wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
-        with _on(idx.device):
-            rc = lib.voge_shade_fwd(_p(attr_c), _p(idx), _p(w), _p(vn), _p(bg_c), float(thr), npix, K, C, Nattr, 1,
-                                    _p(rgb), _p(img), None, _p(wsum), _stream())
-        _lib.check(rc, "voge_shade_fwd")
+        attr_c, w, vn, bg_c, rgb, img, wsum = _shade_fwd(attr, weight, idx, valid_num, bg, thr)
         ctx.save_for_backward(attr_c, w, vn, rgb, bg_c, wsum)
         ctx.idx = idx      # see _Merge: kept outside the version counter on purpose
         ctx.thr = float(thr)
@@ -1711,10 +1501,7 @@ class _BlendBackground(torch.autograd.Function):
         H, W, C = shape[-3:]
         e = _bg_view(bg, shape)
         B = e.shape[0]
-        if g_img.dtype == torch.float32 and g_img.is_cuda and all(st == 0 for st in g_img.stride()):
-            go, gs_pix, gs_c = g_img, 0, 0      # autograd's broadcast scalar (sum / mean losses), read in place
-        else:
-            go, gs_pix, gs_c = _dev(g_img, torch.float32, "grad_image"), C, 1
+        go, gs_pix, gs_c = _grad_layout(g_img, C)
         out, gst, dense, ws, nbytes = None, (0, 0, 0, 0), None, None, 0
         if need[2]:
             bs = (1,) * (len(shape) - bg.dim()) + tuple(bg.shape)      # bg's shape aligned with the image's
