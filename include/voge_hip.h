@@ -395,6 +395,35 @@ int voge_frame_bwd_gen(int form, const float *records, int shared_verts, int sha
                        long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
                        float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream);
 
+/*
+ * ABI 7 (additive), the frame path for ORIENTED Gaussians: three scales and a rotation per Gaussian instead of a [3][3] form.
+ * Replaces: S = R(q) diag(s) R(q)^T composed in torch in front of voge_frame_trace_fwd_gen(kind 2) -- the host-side product of
+ * VoGE/Converter/Converters.py:35-71 (rot @ shape @ rot^T), Aggregation.py:144-175 and Renderer.py:133-137 (A = 2 S, or A = 2 S^-1
+ * under inverse_sigma) -- and autograd through it behind voge_frame_bwd_gen.
+ *   scales [N | B*N][3] (> 0), quats [N | B*N][4] = (w, x, y, z), 16-byte aligned, need not be unit: qh = q / |q|; a quaternion
+ *   whose squared norm, computed in fp32, is not a positive finite number (zero or underflowed, NaN, infinite or overflowed) is the
+ *   identity rotation in the forward AND gets a zero gradient in the backward.  shared_sigmas covers both.
+ *   R(qh) = [[1-2(y^2+z^2), 2(xy-wz), 2(xz+wy)], [2(xy+wz), 1-2(x^2+z^2), 2(yz-wx)], [2(xz-wy), 2(yz+wx), 1-2(x^2+y^2)]];
+ *   A_ij = sum_k (d_k R_ik) R_jk for i <= j, mirrored (bitwise symmetric); sigma_mode 1: d = 2 s, 2: d = 2 / s (inverse_sigma).
+ * voge_frame_trace_fwd_ori: voge_frame_trace_fwd_gen's contract and remaining arguments; records = kind 2's packed (centred mu, A)
+ *   [B*N][12], so voge_frame_shade_fwd_rec(kind = 2, ...) composites them and nothing behind the record pass differs.
+ * voge_frame_bwd_ori: voge_frame_bwd_gen(kind 2)'s forms, inputs and accumulator (voge_frame_bwd_gen_acc_bytes); the finishing pass
+ *   turns the raw 3x3 sums G into g_scales [N | B*N][3] (g_d[k] = r_k^T G r_k; 2 g_d or -2 g_d / s^2) and g_quats [N | B*N][4]
+ *   (through g_R = (G + G^T) R diag(d) and the normalisation: orthogonal to q), a shared set summing its views in a fixed order.
+ *   g_scales and g_quats: both or neither; g_verts as voge_frame_bwd_gen.
+ */
+int voge_frame_trace_fwd_ori(const float *verts, const float *scales, const float *quats, int shared_verts, int shared_sigmas,
+                             int sigma_mode, const float *R, const float *T, const float *focal, const float *pp, int row0,
+                             int stripe_h, int pitch, int behind, int B, int N, int h, int W, int K, float thr_act, void *workspace,
+                             size_t workspace_bytes, int32_t *idx, float *len, int32_t *cnt, float *records, float *rays,
+                             float *origin, voge_stream_t stream);
+int voge_frame_bwd_ori(int form, const float *records, const float *scales, const float *quats, int shared_verts, int shared_sigmas,
+                       int sigma_mode, const float *rays, const float *attr, const int32_t *idx, const int32_t *cnt,
+                       const float *weight, const float *act, const float *len, const float *dsd, const float *rgb, const float *wsum,
+                       const float *bg, float thr, const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ,
+                       int B, int N, long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
+                       float *g_verts, float *g_scales, float *g_quats, float *g_attr, voge_stream_t stream);
+
 /* interpolate_attr (+ get_silhouette) on fragments of this renderer, backward: merge_final's own backward
  * (VoGE/Aggregation.py:111-141; g_rgb = the gradient of the merged attributes [nrows*W,C], strides as g_img above), plus
  * g_wsum [nrows*W] or NULL = the gradient of the per-pixel weight sum (get_silhouette = min(sum, 1) of the same fragments),

@@ -49,12 +49,36 @@ def naive_vertices_converter(vertices, faces, percentage=0.5, max_sig_rate=-1):
     return vertices, isigma, None
 
 
-def normal_mesh_converter(vertices, faces, normals, percentage=0.5, shape_ratio=0.5, max_sig_rate=-1, auto_fix=True):
+def matrix_to_quaternion(rot):
+    """[n,3,3] rotation matrices -> [n,4] unit quaternions (w, x, y, z), numpy fp64: the eigenvector of the largest eigenvalue of
+    the symmetric 4x4 matrix K(R) (Bar-Itzhack), with w >= 0.  For a proper rotation Aggregation.quaternion_to_matrix gives the
+    matrix back; an improper or non-orthogonal matrix gets the nearest rotation's quaternion."""
+    m = np.asarray(rot, dtype=np.float64).reshape(-1, 3, 3)
+    k = np.empty((m.shape[0], 4, 4))
+    k[:, 0, 0] = m[:, 0, 0] + m[:, 1, 1] + m[:, 2, 2]
+    k[:, 0, 1] = k[:, 1, 0] = m[:, 2, 1] - m[:, 1, 2]
+    k[:, 0, 2] = k[:, 2, 0] = m[:, 0, 2] - m[:, 2, 0]
+    k[:, 0, 3] = k[:, 3, 0] = m[:, 1, 0] - m[:, 0, 1]
+    k[:, 1, 1] = m[:, 0, 0] - m[:, 1, 1] - m[:, 2, 2]
+    k[:, 1, 2] = k[:, 2, 1] = m[:, 0, 1] + m[:, 1, 0]
+    k[:, 1, 3] = k[:, 3, 1] = m[:, 0, 2] + m[:, 2, 0]
+    k[:, 2, 2] = m[:, 1, 1] - m[:, 0, 0] - m[:, 2, 2]
+    k[:, 2, 3] = k[:, 3, 2] = m[:, 1, 2] + m[:, 2, 1]
+    k[:, 3, 3] = m[:, 2, 2] - m[:, 0, 0] - m[:, 1, 1]
+    q = np.linalg.eigh(k / 3.0)[1][:, :, -1]
+    return q * np.where(q[:, :1] < 0, -1.0, 1.0)
+
+
+def normal_mesh_converter(vertices, faces, normals, percentage=0.5, shape_ratio=0.5, max_sig_rate=-1, auto_fix=True, oriented=False):
     """One Gaussian per mesh vertex, flattened along the vertex normal (Converters.py:35-71): in the frame whose third
     axis is the normal, Sigma^-1 = s * diag(1, 1, shape_ratio) with s the isotropic scale of naive_vertices_converter;
     the frame is look_at_rotation(-normal) (third column = normal; PyTorch3D's convention, cameras.look_at_rotation
-    here).  Returns (verts, isigma [n,3,3], None)."""
+    here).  Returns (verts, isigma [n,3,3], None); oriented=True: (verts, scales [n,3], quats [n,4]) -- the same frame and the
+    same (s, s, shape_ratio * s) without multiplying them out (Meshes.OrientedGaussianMeshes; Aggregation.oriented_sigma gives
+    isigma back), degenerate frames becoming (s, s, s) with the identity under auto_fix."""
     from ..cameras import look_at_rotation
+    if oriented and max_sig_rate > 0:
+        raise ValueError("max_sig_rate clamps the matrix elementwise, which has no oriented form: use oriented=False")
     is_torch = torch.is_tensor(vertices)
     if is_torch:
         vertices, faces = vertices.numpy(), faces.numpy()
@@ -66,6 +90,18 @@ def normal_mesh_converter(vertices, faces, normals, percentage=0.5, shape_ratio=
     assert torch.max(n2) < 1.1 and torch.min(n2) > 0.9
     shape = np.array([[1, 0, 0], [0, 1, 0], [0, 0, shape_ratio]])[None] * base.reshape(-1, 1, 1)
     rot = look_at_rotation(-normals.type(torch.float32)).numpy()
+    if oriented:
+        scales = base.reshape(-1, 1) * np.array([[1.0, 1.0, shape_ratio]])
+        quats = matrix_to_quaternion(rot)
+        # (look_at_rotation's frames are right-handed rotations, or all zeros when the normal is parallel to its up axis)
+        flat = np.linalg.det(rot) < 0.5
+        if auto_fix:
+            scales[flat] = base[flat].reshape(-1, 1)
+            quats[flat] = np.array([1.0, 0.0, 0.0, 0.0])
+        if is_torch:
+            return (torch.from_numpy(vertices).type(torch.float32), torch.from_numpy(scales).type(torch.float32),
+                    torch.from_numpy(quats).type(torch.float32))
+        return vertices, scales, quats
     isigma = rot @ shape @ rot.transpose(0, 2, 1)
     if auto_fix:
         flat = np.linalg.det(isigma) == 0

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .Aggregation import aggregation, expend_sigma, merge_final
+from .Aggregation import aggregation, expend_sigma, merge_final, oriented_sigma
 from . import RayTracing
 from .RayTracing import _view_axis
 from .cameras import camera_tensors, pixel_rays
@@ -140,6 +140,16 @@ class GaussianRenderSettings:
         return getattr(self, item)
 
 
+class _Overridden:
+    """Render settings with some entries replaced for one call (the settings object itself is the caller's)."""
+
+    def __init__(self, base, **over):
+        self._base, self._over = base, over
+
+    def __getitem__(self, item):
+        return self._over[item] if item in self._over else self._base[item]
+
+
 class GaussianRenderer(nn.Module):
     to_set_args = ['R', 'T', 'focal', 'principal']
 
@@ -179,7 +189,8 @@ class GaussianRenderer(nn.Module):
         return cam
 
     def forward(self, gmeshes, **kwargs):
-        """gmeshes() -> (verts [N,3] | [B,N,3], sigmas [N] | [N,3] | [N,3,3], radians);
+        """gmeshes() -> (verts [N,3] | [B,N,3], sigmas [N] | [N,3] | [N,3,3], radians), or, from a mesh with `oriented`
+        (Meshes.OrientedGaussianMeshes), (verts, scales [..,N,3], quats [..,N,4]);
         R=, T= (and the inert focal=, principal=) keywords are stored on the camera object
         (Renderer.py:104-109).  `rows=(r0, r1)` (extension) renders only that pixel-row band."""
         cams = self.cameras
@@ -192,6 +203,25 @@ class GaussianRenderer(nn.Module):
         image_size = st['image_size']
 
         verts, sigmas, _radians = gmeshes()
+        if getattr(gmeshes, 'oriented', False):
+            # oriented Gaussians: (verts, scales [..,N,3], quats [..,N,4]) -- the frame path takes them as they are
+            # (ops.frame_trace_ori); every other route sees S = R diag(s) R^T as an (N,3,3) sigma below
+            scales, quats = sigmas, _radians
+            if scales.shape[-1] != 3 or quats.shape[-1] != 4 or scales.shape[:-1] != quats.shape[:-1] or scales.dim() not in (2, 3):
+                raise ValueError('oriented Gaussians take scales[..,3] and quats[..,4] with the same leading dims, got '
+                                 f'{tuple(scales.shape)} and {tuple(quats.shape)}')
+            if (FUSED_PREAMBLE and verts.is_cuda and scales.dtype == quats.dtype == verts.dtype == torch.float32
+                    and quats.is_cuda and not (st['max_point_per_bin'] != -1 and RayTracing.REFERENCE_CANDIDATES)
+                    and os.environ.get("VOGE_LAZY_GENERAL", "1") != "0"):
+                cam = self._frame_camera(cams, image_size, kwargs.get('rows'))
+                if cam is not None and ops.frame_eligible(verts, scales, *cam[:4], st['max_assign'], cam[4][1] * cam[5]):
+                    index, hit_len, lz = ops.frame_trace_ori(
+                        verts, scales, quats, *cam[:4], cam[4], cam[5], st['max_point_per_bin'] != -1,
+                        -math.log(st['thr_activation'] + 1 / 1e10), st['max_assign'], 2 if st['inverse_sigma'] else 1, st['absorptivity'])
+                    return Fragments(None, index, None, hit_len, _lazy=lz)
+            sigmas = oriented_sigma(scales, quats)
+            if st['inverse_sigma']:      # (the (N,3,3) fused routes take no inverse_sigma: invert here, render as given)
+                sigmas, st = torch.inverse(sigmas), _Overridden(st, inverse_sigma=False)
         shared_verts = verts.dim() == 2
         verts2d = verts                      # (the [N,3] parameter itself: indexing it back out of verts[None] would put a
         if shared_verts:                     #  select + zero-fill + copy into every backward)

@@ -815,6 +815,24 @@ extern "C" int voge_frame_merge_bwd_iso(const float *records, const float *sigma
 // 2 everywhere for [3][3] ones) -- no general_preamble_bwd launch behind it.
 //   form 0: the image's gradient (to_colored_background: rgb, wsum, bg, thr, g = g_img);   form 1: merge_final's (interpolate_attr:
 //   g = g_rgb, wsum = g_wsum | NULL -- or, with rgb = the forward's weight sums [pix], the gradient of get_silhouette);   form 2: the weights' own (g = g_weight with strides, g_hitlen | NULL; C = 0, no attr).
+// thread t of a finishing pass: the attributes' gradient (acc[..][attr_at ..]) and the vertices' (acc[..][0..2]; a shared set: its
+// views in a fixed order)
+__device__ __forceinline__ void finish_attr_verts(const float *__restrict__ acc, const int S, const int P, const int N, const int B,
+                                                  const int shared_v, const int attr_at, const int C, const long Nattr,
+                                                  float *__restrict__ g_verts, float *__restrict__ g_attr, const long t) {
+  if (g_attr != nullptr && t < Nattr) {
+    for (int c = 0; c < C; ++c) g_attr[t * C + c] = (t < P) ? acc[t * S + attr_at + c] : 0.0f;
+  }
+  if (g_verts != nullptr && t < (shared_v ? N : P)) {
+    float v[3] = {0.f, 0.f, 0.f};
+    for (int b = 0; b < (shared_v ? B : 1); ++b) {
+      const float *a = acc + ((long)b * N + t) * S;
+      v[0] += a[0]; v[1] += a[1]; v[2] += a[2];
+    }
+    g_verts[3 * t] = v[0]; g_verts[3 * t + 1] = v[1]; g_verts[3 * t + 2] = v[2];
+  }
+}
+
 __global__ void __launch_bounds__(256)
 fragment_bwd_finish_view_kernel(const float *__restrict__ acc, const int S, const int P, const int N, const int B, const int shared_v,
                                 const int shared_s, const int kind, const int C, const long Nattr, float *__restrict__ g_verts,
@@ -822,17 +840,7 @@ fragment_bwd_finish_view_kernel(const float *__restrict__ acc, const int S, cons
   // acc per Gaussian -- kind 2 (S = 16 | 12): g_mu [0..2], g_A [3..11], w g_rgb [12..15]; kind 1, the per-axis kernel's entries
   // (S = 12 | 8): g_mu [0..2], g_A00 [3], g_A11 [4], g_A22 [5], w g_rgb [6..9]
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g_attr != nullptr && t < Nattr) {
-    for (int c = 0; c < C; ++c) g_attr[t * C + c] = (t < P) ? acc[t * S + (kind == 1 ? 6 : 12) + c] : 0.0f;
-  }
-  if (g_verts != nullptr && t < (shared_v ? N : P)) {
-    float v[3] = {0.f, 0.f, 0.f};
-    for (int b = 0; b < (shared_v ? B : 1); ++b) {      // (a shared set: its views in a fixed order)
-      const float *a = acc + ((long)b * N + t) * S;
-      v[0] += a[0]; v[1] += a[1]; v[2] += a[2];
-    }
-    g_verts[3 * t] = v[0]; g_verts[3 * t + 1] = v[1]; g_verts[3 * t + 2] = v[2];
-  }
+  finish_attr_verts(acc, S, P, N, B, shared_v, kind == 1 ? 6 : 12, C, Nattr, g_verts, g_attr, t);
   if (g_sigmas != nullptr && kind == 1 && t < (shared_s ? N : P)) {
     float v[3] = {0.f, 0.f, 0.f};
     for (int b = 0; b < (shared_s ? B : 1); ++b) {
@@ -856,22 +864,80 @@ fragment_bwd_finish_view_kernel(const float *__restrict__ acc, const int S, cons
 
 extern "C" size_t voge_frame_bwd_gen_acc_bytes(int P) { return P <= 0 ? 0 : (size_t)P * 64; }      // (kind 1 uses 48 | 32 of them)
 
-extern "C" int voge_frame_bwd_gen(int form, const float *records, int shared_verts, int shared_sigmas, int kind, const float *rays,
-                                  const float *attr, const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
-                                  const float *len, const float *dsd, const float *rgb, const float *wsum, const float *bg, float thr,
-                                  const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ, int B, int N,
-                                  long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
-                                  float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream) {
+// The oriented form's finishing pass (voge_frame_bwd_ori): kind 2's accumulator, G = the raw 3x3 sums acc[..][3..11] (a shared
+// set: its views in a fixed order), through A = R diag(d) R^T backwards -- g_d[k] = r_k^T G r_k (r_k: column k of R), g_s = 2 g_d
+// or -2 g_d / s^2, g_R = (G + G^T) R diag(d), g_qh by the derivative of quat_rotation's matrix, g_q = (g_qh - qh (qh . g_qh)) / |q|
+// (zero for a quaternion without a usable norm: quat_usable, the record pass' decision).  One thread per Gaussian, R recomputed from
+// q; P-sized work, done in fp64 from the fp32 sums (~150 DP operations, a square root and a few divisions per Gaussian: 5.3 us at
+// 50 000 Gaussians, where the [3][3] form's finishing pass takes 5.2 -- profiles/r8_oriented_frame.txt; larger sets not measured).
+__global__ void __launch_bounds__(256)
+fragment_bwd_finish_ori_kernel(const float *__restrict__ acc, const int S, const int P, const int N, const int B, const int shared_v,
+                               const int shared_s, const int sigma_mode, const float *__restrict__ scales,
+                               const float *__restrict__ quats, const int C, const long Nattr, float *__restrict__ g_verts,
+                               float *__restrict__ g_scales, float *__restrict__ g_quats, float *__restrict__ g_attr) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  finish_attr_verts(acc, S, P, N, B, shared_v, 12, C, Nattr, g_verts, g_attr, t);
+  if (g_scales == nullptr || t >= (shared_s ? N : P)) return;
+  double G[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) G[i] = 0.0;
+  for (int b = 0; b < (shared_s ? B : 1); ++b) {
+    const float *a = acc + ((long)b * N + t) * S + 3;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) G[i] += (double)a[i];
+  }
+  const float4 q = reinterpret_cast<const float4 *>(quats)[t];
+  double R[9], qh[4], inv;
+  const bool ok = quat_usable(q.x, q.y, q.z, q.w);      // (the forward's own fp32 decision)
+  quat_rotation<double>(ok, q.x, q.y, q.z, q.w, R, qh, inv);
+  double d[3], gR[9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double s = (double)scales[3 * t + k];
+    d[k] = sigma_mode == 2 ? 2.0 / s : 2.0 * s;
+    double gd = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      // (G + G^T) r_k, row i: g_R[i][k] = d_k * that; g_d[k] = r_k^T G r_k = half of r_k^T (G + G^T) r_k
+      const double m = (G[3 * i] + G[i]) * R[k] + (G[3 * i + 1] + G[3 + i]) * R[3 + k] + (G[3 * i + 2] + G[6 + i]) * R[6 + k];
+      gR[3 * i + k] = d[k] * m;
+      gd += R[3 * i + k] * m;
+    }
+    gd *= 0.5;
+    g_scales[3 * t + k] = (float)(sigma_mode == 2 ? -2.0 * gd / (s * s) : 2.0 * gd);
+  }
+  const double w = qh[0], x = qh[1], y = qh[2], z = qh[3];
+  const double gw = 2.0 * (-z * gR[1] + y * gR[2] + z * gR[3] - x * gR[5] - y * gR[6] + x * gR[7]);
+  const double gx = 2.0 * (y * gR[1] + z * gR[2] + y * gR[3] - 2.0 * x * gR[4] - w * gR[5] + z * gR[6] + w * gR[7] - 2.0 * x * gR[8]);
+  const double gy = 2.0 * (-2.0 * y * gR[0] + x * gR[1] + w * gR[2] + x * gR[3] + z * gR[5] - w * gR[6] + z * gR[7] - 2.0 * y * gR[8]);
+  const double gz = 2.0 * (-2.0 * z * gR[0] - w * gR[1] + x * gR[2] + w * gR[3] - 2.0 * z * gR[4] + y * gR[5] + x * gR[6] + y * gR[7]);
+  const double along = w * gw + x * gx + y * gy + z * gz;
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (ok) out = make_float4((float)((gw - w * along) * inv), (float)((gx - x * along) * inv), (float)((gy - y * along) * inv),
+                            (float)((gz - z * along) * inv));
+  reinterpret_cast<float4 *>(g_quats)[t] = out;
+}
+
+static int frame_bwd_gen_impl(int form, const float *records, int shared_verts, int shared_sigmas, int kind, const float *rays,
+                              const float *attr, const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
+                              const float *len, const float *dsd, const float *rgb, const float *wsum, const float *bg, float thr,
+                              const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ, int B, int N,
+                              long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
+                              float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream,
+                              // (the oriented form: kind 2 with g_sigmas = the scales' gradient [.., 3], finished by fragment_bwd_finish_ori_kernel)
+                              const float *ori_scales = nullptr, const float *ori_quats = nullptr, int ori_mode = 0, float *g_quats = nullptr) {
+  const bool ori = ori_mode != 0;
   if (form < 0 || form > 2 || (kind != 1 && kind != 2) || B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || Nattr < 0) return VOGE_ERR_BAD_ARG;
   if (form != 2 && (C <= 0 || C > 4)) return VOGE_ERR_BAD_ARG;
   if (K > (form == 2 ? VOGE_MAX_K : 128)) return VOGE_ERR_K_TOO_LARGE;
   const int P = B * N;
   hipStream_t st = (hipStream_t)stream;
-  const long nv = shared_verts ? N : P, ns = (long)(shared_sigmas ? N : P) * (kind == 1 ? 3 : 9);
+  const long nv = shared_verts ? N : P, ns = (long)(shared_sigmas ? N : P) * (kind == 1 || ori ? 3 : 9);
   if (P == 0 || nrows * W == 0) {      // nothing was traced: zero gradients
     hipError_t e = hipSuccess;
     if (g_verts && nv > 0) e = voge_fill_async(g_verts, 0, sizeof(float) * 3 * (size_t)nv, st);
     if (e == hipSuccess && g_sigmas && ns > 0) e = voge_fill_async(g_sigmas, 0, sizeof(float) * (size_t)ns, st);
+    if (e == hipSuccess && g_quats && ns > 0) e = voge_fill_async(g_quats, 0, sizeof(float) * (size_t)(ns / 3) * 4, st);
     if (e == hipSuccess && g_attr && Nattr > 0 && form != 2) e = voge_fill_async(g_attr, 0, sizeof(float) * (size_t)Nattr * C, st);
     return (int)e;
   }
@@ -906,10 +972,46 @@ extern "C" int voge_frame_bwd_gen(int form, const float *records, int shared_ver
     }
   }
   const long n_fin = (form != 2 && Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_view_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, accf, S, P, N, B,
-                     shared_verts ? 1 : 0, shared_sigmas ? 1 : 0, kind, form == 2 ? 0 : C, form == 2 ? 0l : Nattr, g_verts, g_sigmas,
-                     form == 2 ? nullptr : g_attr);
+  if (ori)
+    hipLaunchKernelGGL(fragment_bwd_finish_ori_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, accf, S, P, N, B,
+                       shared_verts ? 1 : 0, shared_sigmas ? 1 : 0, ori_mode, ori_scales, ori_quats, form == 2 ? 0 : C,
+                       form == 2 ? 0l : Nattr, g_verts, g_sigmas, g_quats, form == 2 ? nullptr : g_attr);
+  else
+    hipLaunchKernelGGL(fragment_bwd_finish_view_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, accf, S, P, N, B,
+                       shared_verts ? 1 : 0, shared_sigmas ? 1 : 0, kind, form == 2 ? 0 : C, form == 2 ? 0l : Nattr, g_verts, g_sigmas,
+                       form == 2 ? nullptr : g_attr);
   return launch_status();
+}
+
+extern "C" int voge_frame_bwd_gen(int form, const float *records, int shared_verts, int shared_sigmas, int kind, const float *rays,
+                                  const float *attr, const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
+                                  const float *len, const float *dsd, const float *rgb, const float *wsum, const float *bg, float thr,
+                                  const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ, int B, int N,
+                                  long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
+                                  float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream) {
+  return frame_bwd_gen_impl(form, records, shared_verts, shared_sigmas, kind, rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg,
+                            thr, g, g_stride0, g_stride1, g_hitlen, occ, B, N, nrows, W, K, C, Nattr, acc, acc_bytes, acc_is_zero, g_verts,
+                            g_sigmas, g_attr, stream);
+}
+
+// Every backward route of fragments made by voge_frame_trace_fwd_ori: voge_frame_bwd_gen(kind 2)'s fused kernel as it is, on the
+// same records and accumulator (voge_frame_bwd_gen_acc_bytes), then the oriented finishing pass -- the gradients of verts, scales
+// and quats as the user holds them, in place of the [3][3] gradient and autograd through R diag(s) R^T composed in torch.
+extern "C" int voge_frame_bwd_ori(int form, const float *records, const float *scales, const float *quats, int shared_verts,
+                                  int shared_sigmas, int sigma_mode, const float *rays, const float *attr, const int32_t *idx,
+                                  const int32_t *cnt, const float *weight, const float *act, const float *len, const float *dsd,
+                                  const float *rgb, const float *wsum, const float *bg, float thr, const float *g, long g_stride0,
+                                  long g_stride1, const float *g_hitlen, float occ, int B, int N, long nrows, int W, int K, int C,
+                                  long Nattr, void *acc, size_t acc_bytes, int acc_is_zero, float *g_verts, float *g_scales,
+                                  float *g_quats, float *g_attr, voge_stream_t stream) {
+  if (sigma_mode != 1 && sigma_mode != 2) return VOGE_ERR_BAD_ARG;
+  if ((g_scales == nullptr) != (g_quats == nullptr)) return VOGE_ERR_BAD_ARG;
+  if (g_scales != nullptr && (long)B * N > 0 &&
+      (!scales || !quats || ((reinterpret_cast<uintptr_t>(quats) | reinterpret_cast<uintptr_t>(g_quats)) & 15) != 0))
+    return VOGE_ERR_BAD_ARG;
+  return frame_bwd_gen_impl(form, records, shared_verts, shared_sigmas, 2, rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr,
+                            g, g_stride0, g_stride1, g_hitlen, occ, B, N, nrows, W, K, C, Nattr, acc, acc_bytes, acc_is_zero, g_verts,
+                            g_scales, g_attr, stream, scales, quats, sigma_mode, g_quats);
 }
 
 extern "C" int voge_fragment_shade_bwd(const float *mus, const float *isigmas, const float *rays, const float *colors,

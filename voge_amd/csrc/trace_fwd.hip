@@ -67,6 +67,23 @@ __device__ __forceinline__ void prep_one(const int g, const float *__restrict__ 
     const float *sg = isg + 9 * (size_t)(view.sigma_shared ? g % N : g);
 #pragma unroll
     for (int i = 0; i < 9; ++i) A[i] = 2.0f * sg[i];
+  } else if (view.gen_kind == 3) {      // the user's (scales, quaternion): A = R diag(d) R^T, six entries computed, mirrored
+    const size_t so = view.sigma_shared ? g % N : g;
+    const float *sg = isg + 3 * so;
+    const float4 q = reinterpret_cast<const float4 *>(view.quats)[so];      // (w, x, y, z): one 16-byte load
+    float Rm[9], qh[4], inv;
+    quat_rotation<float>(quat_usable(q.x, q.y, q.z, q.w), q.x, q.y, q.z, q.w, Rm, qh, inv);
+    float d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = view.ori_mode == 2 ? 2.0f / sg[k] : 2.0f * sg[k];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = i; j < 3; ++j) {
+        const float a = ((d[0] * Rm[3 * i]) * Rm[3 * j] + (d[1] * Rm[3 * i + 1]) * Rm[3 * j + 1]) + (d[2] * Rm[3 * i + 2]) * Rm[3 * j + 2];
+        A[3 * i + j] = a; A[3 * j + i] = a;
+      }
+    }
   } else {
 #pragma unroll
     for (int i = 0; i < 9; ++i) A[i] = isg[9 * (size_t)g + i];
@@ -1379,11 +1396,12 @@ static int trace_topk_fwd_impl(const int iso_in, const IsoView view, const float
   const size_t nst = (size_t)((W + kST - 1) / kST) * ((H + kST - 1) / kST);
   const size_t stride_mu = view.shared ? 0 : (size_t)N * 3;
   const size_t stride_sg = iso_in ? (view.shared ? 0 : (size_t)N)
-                                  : (view.gen_kind ? (view.sigma_shared ? 0 : (size_t)N * (view.gen_kind == 1 ? 3 : 9)) : (size_t)N * 9);
+                                  : (view.gen_kind ? (view.sigma_shared ? 0 : (size_t)N * (view.gen_kind == 2 ? 9 : 3)) : (size_t)N * 9);
   for (int b0 = 0; b0 < B; b0 += per) {
     const int nb = (B - b0 < per) ? B - b0 : per;
     IsoView v = view;
     if (v.origin != nullptr) v.origin += 3 * (size_t)b0;
+    if (v.quats != nullptr && !v.sigma_shared) v.quats += 4 * (size_t)b0 * N;
     auto at = [&](auto *p, const size_t per_view) { return p ? p + (size_t)b0 * per_view : p; };
     if (cam.R != nullptr) v.cam_origin = 1;
     CamView cv = cam;
@@ -1615,5 +1633,25 @@ extern "C" int voge_frame_trace_fwd_gen(const float *verts, const float *sigmas,
   IsoView view{nullptr, shared_verts ? 1 : 0, 0};
   view.gen_kind = kind; view.sigma_shared = shared_sigmas ? 1 : 0;
   return trace_topk_fwd_impl(0, view, verts, sigmas, nullptr, nullptr, nullptr, B, N, h, W, K, thr_act, workspace, workspace_bytes, idx, len,
+                             nullptr, nullptr, cnt, stream, 1.0f, nullptr, nullptr, records, cam);
+}
+
+// ... and for ORIENTED Gaussians: scales [N | B*N][3] and unit-or-not quaternions [N | B*N][4] (w, x, y, z; 16-byte aligned) in
+// place of a [3][3] form -- what a caller of voge_frame_trace_fwd_gen(kind 2) composes in torch in front of it, S = R diag(s) R^T
+// (Renderer.py:133-137 then doubles it, or inverts and doubles it: sigma_mode 1: d = 2 s, 2: d = 2 / s).  The record pass builds
+// A = R diag(d) R^T itself (voge_common.h: quat_rotation), bitwise symmetric; records = kind 2's packed (centred mu, A) [B*N][12],
+// so everything behind the record pass is kind 2's, unchanged.
+extern "C" int voge_frame_trace_fwd_ori(const float *verts, const float *scales, const float *quats, int shared_verts,
+                                        int shared_sigmas, int sigma_mode, const float *R, const float *T, const float *focal,
+                                        const float *pp, int row0, int stripe_h, int pitch, int behind, int B, int N, int h, int W,
+                                        int K, float thr_act, void *workspace, size_t workspace_bytes, int32_t *idx, float *len,
+                                        int32_t *cnt, float *records, float *rays, float *origin, voge_stream_t stream) {
+  if ((sigma_mode != 1 && sigma_mode != 2) || !cnt || !records || !R || !T || !focal || !pp || stripe_h <= 0 || pitch < 0) return VOGE_ERR_BAD_ARG;
+  if ((size_t)B * h * W > 0 && !rays) return VOGE_ERR_BAD_ARG;
+  if (N > 0 && (!quats || (reinterpret_cast<uintptr_t>(quats) & 15) != 0)) return VOGE_ERR_BAD_ARG;
+  const CamView cam{R, T, focal, pp, row0, stripe_h, pitch, h, W, behind ? 1 : 0, origin, rays};
+  IsoView view{nullptr, shared_verts ? 1 : 0, 0};
+  view.gen_kind = 3; view.sigma_shared = shared_sigmas ? 1 : 0; view.quats = quats; view.ori_mode = sigma_mode;
+  return trace_topk_fwd_impl(0, view, verts, scales, nullptr, nullptr, nullptr, B, N, h, W, K, thr_act, workspace, workspace_bytes, idx, len,
                              nullptr, nullptr, cnt, stream, 1.0f, nullptr, nullptr, records, cam);
 }

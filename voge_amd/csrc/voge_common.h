@@ -51,9 +51,36 @@ struct IsoView {
   // per-axis sigmas [N | B*N][3], A = 2 diag(s); 2: the user's [N | B*N][3][3], A = 2 S (Renderer.py:133 + Aggregation.py:144-175);
   // sigma_shared: one [N, ...] set seen by every view.  `shared` above then says the same for the centres.
   int gen_kind = 0, sigma_shared = 0;
+  // gen_kind 3 (voge_frame_trace_fwd_ori): `isg` holds the user's scales [N | B*N][3] and quats their rotations [N | B*N][4]
+  // (w, x, y, z; sigma_shared covers both); A = R diag(d) R^T with d = 2 s (ori_mode 1) or 2 / s (ori_mode 2)
+  const float *quats = nullptr;
+  int ori_mode = 1;
 };
 __device__ __forceinline__ float iso_view_a(const float s, const int mode) {
   return mode == 1 ? 2.0f * s : (mode == 2 ? 2.0f / s : s);
+}
+
+// Whether a quaternion (w, x, y, z) has a usable norm: its squared norm AS fp32 COMPUTES IT is a positive finite number (not zero
+// or underflowed, not NaN, not infinite or overflowed).  Decided once, in fp32, for the record pass and the finishing pass alike:
+// the backward differentiates the rotation the forward rendered.
+__device__ __forceinline__ bool quat_usable(const float qw, const float qx, const float qy, const float qz) {
+  const float n2 = qw * qw + qx * qx + qy * qy + qz * qz;
+  return n2 > 0.0f && n2 < INFINITY;
+}
+
+// Rotation matrix of a quaternion (w, x, y, z) that need not be unit: qh = q / |q|, inv = 1 / |q|, R (row-major) = the standard
+// matrix of qh.  ok = quat_usable(q): a quaternion without a usable norm is the identity (inv = 0) -- its gradient is zero.
+// T = float: the record pass; T = double: the backward's finishing pass.  Correctly rounded division and square root, no
+// contraction: (1, 0, 0, 0) gives the identity matrix exactly.
+template <typename T>
+__device__ __forceinline__ void quat_rotation(const bool ok, const T qw, const T qx, const T qy, const T qz, T R[9], T qh[4], T &inv) {
+  const T n2 = qw * qw + qx * qx + qy * qy + qz * qz;
+  inv = ok ? (T)1 / sqrt(n2) : (T)0;
+  const T w = ok ? qw * inv : (T)1, x = ok ? qx * inv : (T)0, y = ok ? qy * inv : (T)0, z = ok ? qz * inv : (T)0;
+  qh[0] = w; qh[1] = x; qh[2] = y; qh[3] = z;
+  R[0] = (T)1 - (T)2 * (y * y + z * z); R[1] = (T)2 * (x * y - w * z); R[2] = (T)2 * (x * z + w * y);
+  R[3] = (T)2 * (x * y + w * z); R[4] = (T)1 - (T)2 * (x * x + z * z); R[5] = (T)2 * (y * z - w * x);
+  R[6] = (T)2 * (x * z - w * y); R[7] = (T)2 * (y * z + w * x); R[8] = (T)1 - (T)2 * (x * x + y * y);
 }
 
 struct PairOut {

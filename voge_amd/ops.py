@@ -664,8 +664,15 @@ def _sigma_kind(sigmas):
     return kind, sigmas.dim() == (3 if kind == 2 else 2)
 
 
-def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out, gen):
-    """frame_trace (gen False: voge_frame_trace_fwd_iso) and frame_trace_gen (gen True: voge_frame_trace_fwd_gen)."""
+def _plain16(t_, name):
+    """_plain for an array the kernels read with 16-byte loads (a view into a larger buffer may start anywhere)."""
+    t_ = _plain(t_, torch.float32, name)
+    return t_ if t_.data_ptr() % 16 == 0 else t_.detach().clone()
+
+
+def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out, gen, quats=None):
+    """frame_trace (gen False: voge_frame_trace_fwd_iso), frame_trace_gen (gen True: voge_frame_trace_fwd_gen) and frame_trace_ori
+    (quats given, sigmas = the scales: voge_frame_trace_fwd_ori)."""
     lib = _lib.load()
     v_c, s_c = _plain(verts, torch.float32, "verts"), _plain(sigmas, torch.float32, "sigmas")
     R_c, T_c = _plain(R, torch.float32, "R"), _plain(T, torch.float32, "T")
@@ -676,7 +683,13 @@ def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_ass
     N, K, dev = v_c.shape[-2], int(n_assign), v_c.device
     assert R_c.shape == (B, 3, 3) and T_c.shape == (B, 3) and f_c.shape == (B, 2) and p_c.shape == (B, 2)
     assert v_c.shape[-1] == 3 and (shared or v_c.shape[0] == B)
-    if gen:
+    if quats is not None:
+        q_c = _plain16(quats, "quats")
+        shared_s = s_c.dim() == 2
+        assert tuple(s_c.shape[-2:]) == (N, 3) and q_c.shape == s_c.shape[:-1] + (4,) and (shared_s or s_c.shape[0] == B)
+        assert sigma_mode in (1, 2)
+        nrec, form = 12, (0, int(sigma_mode), False, (3, int(shared), int(shared_s)))      # (kind 2's records; gen[0] 3: oriented)
+    elif gen:
         kind, shared_s = _sigma_kind(s_c)
         assert s_c.shape[-(kind + 1)] == N and s_c.shape[-1] == 3 and (shared_s or s_c.shape[0] == B)
         nrec, form = (8 if kind == 1 else 12), (0, 0, False, (kind, int(shared), int(shared_s)))      # (kind 1: compact per-axis records)
@@ -695,7 +708,9 @@ def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_ass
         cam = (R_c.data_ptr(), T_c.data_ptr(), f_c.data_ptr(), p_c.data_ptr(), int(row0), int(stripe_h), int(pitch), int(bool(behind)), B,
                N, int(h), int(W), K, float(thr_act), ws.data_ptr(), nbytes, sel_idx.data_ptr(), sel_len.data_ptr(), cnt.data_ptr(),
                records.data_ptr(), rays.data_ptr(), _p(origin_out), _stream())
-        if gen:
+        if quats is not None:
+            rc = lib.voge_frame_trace_fwd_ori(v_c.data_ptr(), s_c.data_ptr(), q_c.data_ptr(), int(shared), int(shared_s), int(sigma_mode), *cam)
+        elif gen:
             rc = lib.voge_frame_trace_fwd_gen(v_c.data_ptr(), s_c.data_ptr(), int(shared), int(shared_s), kind, *cam)
         else:
             rc = lib.voge_frame_trace_fwd_iso(v_c.data_ptr(), s_c.data_ptr(), int(shared), int(sigma_mode), *cam)
@@ -707,6 +722,8 @@ def _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_ass
     (lz.occ, lz.B, lz.N, lz.K, lz.p0, lz.p1, lz.sel_idx, lz.sel_len, lz.cnt, lz.records, lz.rays, lz.rays_version, lz.grad_mode,
      lz.idx_version, lz.p0_version, lz.frame) = (float(occ), B, N, K, verts, sigmas, sel_idx, sel_len, cnt, records, rays, 0,
                                                  torch.is_grad_enabled(), sel_idx._version, verts._version, True)
+    lz.p2 = quats
+    lz.p12_version = None if quats is None else (sigmas._version, quats._version)
     return sel_idx, sel_len, lz
 
 
@@ -731,9 +748,21 @@ def frame_trace_gen(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_
     return _frame_trace(verts, sigmas, R, T, focal, pp, band, W, behind, thr_act, n_assign, 0, occ, origin_out, True)
 
 
+def frame_trace_ori(verts, scales, quats, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out=None):
+    """frame_trace_gen for ORIENTED Gaussians (voge_frame_trace_fwd_ori): verts [N,3] | [B,N,3], scales [N,3] | [B,N,3], quats
+    [N,4] | [B,N,4] = (w, x, y, z), not necessarily unit -- the record pass builds A = R diag(d) R^T (sigma_mode 1: d = 2 s;
+    2, inverse_sigma: d = 2 / s) into kind 2's records, so the composite is the [N,3,3] frame's.  -> (sel_idx, sel_len,
+    LazyComposite) with mode 0, lz.gen = (3, shared_verts, shared_sigmas) and lz.p0 / lz.p1 / lz.p2 the USER's verts / scales /
+    quats: every backward route goes through voge_frame_bwd_ori, which hands the gradients to exactly those.  The kernels read a
+    quaternion with one 16-byte load: a quats tensor whose storage does not start on a 16-byte boundary (a view into a larger
+    buffer) is copied, once here and once in every backward (_plain16) -- any tensor torch allocated itself is read in place."""
+    return _frame_trace(verts, scales, R, T, focal, pp, band, W, behind, thr_act, n_assign, sigma_mode, occ, origin_out, True, quats)
+
+
 def _frame_gen_bwd(lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, gs0, gs1, g_hitlen, acc=None):
-    """voge_frame_bwd_gen on fragments of frame_trace_gen: -> (g_p0, g_p1, g_attr | None), the gradients of the user's verts / sigmas
-    (and attributes).  acc: the accumulator the composite zeroed on its way (good for one call), or None (scratch, filled here)."""
+    """voge_frame_bwd_gen on fragments of frame_trace_gen (frame_trace_ori: voge_frame_bwd_ori): -> (g_p0, g_p1, g_p2 | None,
+    g_attr | None), the gradients of the user's verts / sigmas (oriented: scales, quats) and attributes.  acc: the accumulator the
+    composite zeroed on its way (good for one call), or None (scratch, filled here)."""
     lz.check()
     lib = _lib.load()
     kind, shared_v, shared_s = lz.gen
@@ -743,6 +772,7 @@ def _frame_gen_bwd(lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, gs0, g
     g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=dev)
     g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=dev)
     g_attr = None if attr is None else torch.empty_like(attr)
+    g2 = None
     C, Nattr = (0, 0) if attr is None else (attr.shape[1], attr.shape[0])
     with _on(dev):
         zeroed = acc is not None
@@ -751,12 +781,17 @@ def _frame_gen_bwd(lz, form, attr, weight, ad, ln, rgb, wsum, bg, thr, g, gs0, g
             acc = _workspace(dev, nbytes)
         else:
             nbytes = acc.numel()
-        rc = lib.voge_frame_bwd_gen(form, _p(lz.records), shared_v, shared_s, kind, _p(lz.rays), _p(attr), _p(lz.sel_idx), _p(lz.cnt),
-                                    _p(weight), _p(ad[0]), _p(ln), _p(ad[1]), _p(rgb), _p(wsum), _p(bg), float(thr), _p(g), gs0, gs1,
-                                    _p(g_hitlen), lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr, _p(acc), nbytes, int(zeroed), _p(g0), _p(g1),
-                                    _p(g_attr), _stream())
-    _lib.check(rc, "voge_frame_bwd_gen")
-    return g0, g1, g_attr
+        tail = (_p(lz.rays), _p(attr), _p(lz.sel_idx), _p(lz.cnt), _p(weight), _p(ad[0]), _p(ln), _p(ad[1]), _p(rgb), _p(wsum), _p(bg),
+                float(thr), _p(g), gs0, gs1, _p(g_hitlen), lz.occ, lz.B, lz.N, B * H, W, K, C, Nattr, _p(acc), nbytes, int(zeroed), _p(g0),
+                _p(g1))
+        if kind == 3:
+            g2 = torch.empty(lz.p2.shape, dtype=torch.float32, device=dev)
+            rc = lib.voge_frame_bwd_ori(form, _p(lz.records), _p(_plain(lz.p1, torch.float32, "scales")), _p(_plain16(lz.p2, "quats")),
+                                        shared_v, shared_s, lz.sigma_mode, *tail, _p(g2), _p(g_attr), _stream())
+        else:
+            rc = lib.voge_frame_bwd_gen(form, _p(lz.records), shared_v, shared_s, kind, *tail, _p(g_attr), _stream())
+    _lib.check(rc, "voge_frame_bwd_ori" if kind == 3 else "voge_frame_bwd_gen")
+    return g0, g1, g2, g_attr
 
 
 class _HitLength(torch.autograd.Function):
@@ -765,7 +800,7 @@ class _HitLength(torch.autograd.Function):
     trace's chain rule for a gradient of len alone (the weights' backward with g_weight = NULL), as _TraceLean.backward."""
 
     @staticmethod
-    def forward(ctx, p0, p1, sel_len, lz):
+    def forward(ctx, p0, p1, sel_len, lz, p2=None):
         ctx.lz = lz
         ctx.save_for_backward(p1)
         ctx.set_materialize_grads(False)
@@ -774,14 +809,14 @@ class _HitLength(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_len):
         if g_len is None:
-            return None, None, None, None
+            return None, None, None, None, None
         lz = ctx.lz
         (p1,) = ctx.saved_tensors
         if lz.gen is None:      # (general forms read their records: the user's sigmas are not an operand)
             p1 = _dev(p1, torch.float32, "sigmas")
         # (`weight` is read but multiplies zero -- len stands in; the trace-only form's absorptivity 1.0)
-        g0, g1 = _lazy_fragment_bwd(lz, p1, lz.sel_len, lz.sel_len, None, g_len=g_len, occ=1.0)
-        return g0, g1, None, None
+        g0, g1, g2 = _lazy_fragment_bwd(lz, p1, lz.sel_len, lz.sel_len, None, g_len=g_len, occ=1.0)
+        return g0, g1, None, None, g2
 
 
 # VOGE_FRAME_PATH=0 (or ops.FRAME_PATH = False): the renderer generates its ray bundle with voge_rays_fwd and traces through the
@@ -808,11 +843,13 @@ class LazyComposite:
     """What the deferred composite needs from a _TraceLean call (nothing in it has a grad_fn except sel_len, which the
     composite nodes take as an input)."""
     __slots__ = ("mode", "sigma_mode", "shared", "occ", "B", "N", "K", "p0", "p1", "sel_idx", "sel_len", "cnt", "records", "rays",
-                 "rays_version", "grad_mode", "idx_version", "p0_version", "frame", "gen")
+                 "rays_version", "grad_mode", "idx_version", "p0_version", "frame", "gen", "p2", "p12_version")
 
     def __init__(self, **kw):
         self.frame = False      # (made by frame_trace: the shade stage may take the frame entries of ABI 7)
         self.gen = None         # (frame_trace_gen: (kind, shared_verts, shared_sigmas) -- p0 / p1 are the USER's verts / sigmas)
+        self.p2 = None          # (frame_trace_ori: gen = (3, ..), p1 the USER's scales, p2 the USER's quaternions)
+        self.p12_version = None
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -822,10 +859,13 @@ class LazyComposite:
         if not self.frame:
             return self.sel_len
         # (NOT remembered here: the alias' grad_fn holds this object -- the Fragments that asked keeps what it gets)
-        if self.grad_mode and (self.p0.requires_grad or self.p1.requires_grad):
+        if self.grad_mode and self.wants_grad():
             with torch.enable_grad():
-                return _HitLength.apply(self.p0, self.p1, self.sel_len, self)
+                return _HitLength.apply(self.p0, self.p1, self.sel_len, self, self.p2)
         return self.sel_len
+
+    def wants_grad(self):
+        return self.p0.requires_grad or self.p1.requires_grad or (self.p2 is not None and self.p2.requires_grad)
 
     def means(self):
         """(general forms) the centres as the trace saw them: contiguous fp32, no grad_fn."""
@@ -848,6 +888,9 @@ class LazyComposite:
         if self.mode == 0 and self.p0._version != self.p0_version:
             raise RuntimeError("the Gaussians' centres were modified in place after the fragments were traced (an optimizer "
                                "step between forward and backward?): the backward would read the changed values")
+        if self.p12_version is not None and self.p12_version != (self.p1._version, self.p2._version):
+            raise RuntimeError("the Gaussians' scales or quaternions were modified in place after the fragments were traced: the "
+                               "backward's finishing pass would read the changed values")
 
     def grad(self):
         """The autograd mode the RENDER ran under, for whoever composites these fragments later: the reference computes the
@@ -900,16 +943,16 @@ def _general_act_dsd(lz, sel_len, need):
 
 
 def _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ad=(None, None), g_len=None, occ=None):
-    """_fragment_bwd on deferred-composite fragments (frame_trace_gen's: voge_frame_bwd_gen) -> (g_p0, g_p1).  occ: the absorptivity
-    the kernel is handed (default lz.occ)."""
+    """_fragment_bwd on deferred-composite fragments (frame_trace_gen's: voge_frame_bwd_gen) -> (g_p0, g_p1, g_p2 | None).  occ: the
+    absorptivity the kernel is handed (default lz.occ)."""
     if lz.gen is not None:
         gw, gs_pix, gs_k = _grad_weight_layout(g_weight, lz.K)
         gh = None if g_len is None else _dev(g_len, torch.float32, "grad_hit_length")
-        g0, g1, _ = _frame_gen_bwd(lz, 2, None, weight, ad, ln, None, None, None, -1.0, gw, gs_pix, gs_k, gh)
-        return g0, g1
+        g0, g1, g2, _ = _frame_gen_bwd(lz, 2, None, weight, ad, ln, None, None, None, -1.0, gw, gs_pix, gs_k, gh)
+        return g0, g1, g2
     lz.check()
-    return _fragment_bwd(lz.mode, lz.means() if lz.mode == 0 else None, p1, lz.records, lz.shared, lz.sigma_mode, lz.rays, lz.sel_idx,
-                         lz.cnt, lz.B, lz.N, (lz.p0, lz.p1), weight, ad[0], ln, ad[1], g_weight, g_len, lz.occ if occ is None else occ)
+    return (*_fragment_bwd(lz.mode, lz.means() if lz.mode == 0 else None, p1, lz.records, lz.shared, lz.sigma_mode, lz.rays, lz.sel_idx,
+                           lz.cnt, lz.B, lz.N, (lz.p0, lz.p1), weight, ad[0], ln, ad[1], g_weight, g_len, lz.occ if occ is None else occ), None)
 
 
 def _frame_acc(lz, need):
@@ -938,7 +981,7 @@ def _composite_fwd(lz, sel_len, need, attr=None, bg=None, thr=-1.0, rgb=None, im
         src = (_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ)
         args = src + (_p(attr), _p(bg), float(thr), npix, K, C, Nattr, _p(weight), _p(valid), _p(rgb), _p(img), _p(wsum))
         if lz.gen is not None:
-            rc = lib.voge_frame_shade_fwd_rec(lz.gen[0], *args, _p(sil), _p(ad[0]), _p(ad[1]), _p(acc), nacc, _stream())
+            rc = lib.voge_frame_shade_fwd_rec(1 if lz.gen[0] == 1 else 2, *args, _p(sil), _p(ad[0]), _p(ad[1]), _p(acc), nacc, _stream())
         elif attr is None and lz.mode == 0:
             rc = lib.voge_composite_fwd_rec(*src, npix, K, _p(weight), _p(valid), _p(ad[0]), _p(ad[1]), _stream())
         elif attr is None:
@@ -960,7 +1003,7 @@ class _CompositeLean(torch.autograd.Function):
     one pass: voge_fragment_bwd_iso) can hand them the gradient directly; sel_len gets none from here."""
 
     @staticmethod
-    def forward(ctx, p0, p1, sel_len, lz):
+    def forward(ctx, p0, p1, sel_len, lz, p2=None):
         weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad))
         ctx.save_for_backward(_dev(p1, torch.float32, "sigmas"), sel_len, weight)
         ctx.lz = lz
@@ -971,10 +1014,10 @@ class _CompositeLean(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_weight, _g_valid):
         if g_weight is None:
-            return None, None, None, None
+            return None, None, None, None, None
         p1, ln, weight = ctx.saved_tensors
-        g0, g1 = _lazy_fragment_bwd(ctx.lz, p1, weight, ln, g_weight, ctx.ad)
-        return g0, g1, None, None
+        g0, g1, g2 = _lazy_fragment_bwd(ctx.lz, p1, weight, ln, g_weight, ctx.ad)
+        return g0, g1, None, None, g2
 
 
 def _shade_bwd(mode, means, sigmas, records, shared, sigma_mode, rays, cnt, occ, B, N, like, attr, idx, weight, act, ln, dsd, rgb,
@@ -1016,7 +1059,7 @@ class _CompositeShade(torch.autograd.Function):
     that reaches the weights from elsewhere (a silhouette loss on the same fragments) through voge_fragment_bwd_iso."""
 
     @staticmethod
-    def forward(ctx, attr, p0, p1, sel_len, lz, bg, thr):
+    def forward(ctx, attr, p0, p1, sel_len, lz, bg, thr, p2=None):
         attr_c = _dev(attr, torch.float32, "colors")
         bg_c = _dev(bg, torch.float32, "background_color")
         idx = lz.sel_idx
@@ -1026,7 +1069,7 @@ class _CompositeShade(torch.autograd.Function):
         rgb = torch.empty(idx.shape[:-1] + (C,), dtype=torch.float32, device=idx.device)
         img = torch.empty_like(rgb)
         wsum = torch.empty(idx.shape[:-1], dtype=torch.float32, device=idx.device)
-        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]))
+        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[-1])
         weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad), attr_c, bg_c, thr, rgb, img, wsum, acc=ctx.gbuf)
         ctx.save_for_backward(attr_c, _dev(p1, torch.float32, "sigmas"), sel_len, weight, rgb, bg_c, wsum)
         ctx.lz, ctx.thr = lz, float(thr)
@@ -1039,21 +1082,22 @@ class _CompositeShade(torch.autograd.Function):
         attr, p1, ln, weight, rgb, bg, wsum = ctx.saved_tensors
         lz = ctx.lz
         lz.check()
-        g_attr = g0 = g1 = None
+        g_attr = g0 = g1 = g2 = None
         if g_img is not None:
             go, gs_pix, gs_c = _grad_layout(g_img, attr.shape[1])
             gbuf, ctx.gbuf = ctx.gbuf, None      # (zeroed by the forward, good for ONE backward: a second one takes the scratch form)
             if lz.gen is not None:      # (general forms of the frame path: the user's verts / sigmas get their gradients directly)
-                g0, g1, g_attr = _frame_gen_bwd(lz, 0, attr, weight, ctx.ad, ln, rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, None, acc=gbuf)
+                g0, g1, g2, g_attr = _frame_gen_bwd(lz, 0, attr, weight, ctx.ad, ln, rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, None, acc=gbuf)
             else:
                 g0, g1, g_attr = _shade_bwd(lz.mode, lz.means() if lz.mode == 0 else None, p1, lz.records, lz.shared, lz.sigma_mode,
                                             lz.rays, lz.cnt, lz.occ, lz.B, lz.N, (lz.p0, lz.p1), attr, lz.sel_idx, weight, ctx.ad[0], ln,
                                             ctx.ad[1], rgb, wsum, bg, ctx.thr, go, gs_pix, gs_c, gbuf)
         if g_weight is not None:
-            h0, h1 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
-            g0, g1 = (h0, h1) if g0 is None else (g0 + h0, g1 + h1)
+            h0, h1, h2 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
+            g0, g1, g2 = (h0, h1, h2) if g0 is None else (g0 + h0, g1 + h1, None if h2 is None else g2 + h2)
         need = ctx.needs_input_grad
-        return (g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None, None, None
+        return ((g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None, None, None,
+                (g2 if need[7] else None))
 
 
 def _merge_bwd(lz, p1, attr, weight, ad, ln, go, gs_pix, gs_c, gws, wsum_fwd, acc):
@@ -1098,7 +1142,7 @@ class _CompositeMerge(torch.autograd.Function):
     kernel backward (voge_fragment_merge_bwd_iso: merge backward + the sum's gradient + composite + trace)."""
 
     @staticmethod
-    def forward(ctx, attr, p0, p1, sel_len, lz):
+    def forward(ctx, attr, p0, p1, sel_len, lz, p2=None):
         attr_c = _dev(attr, torch.float32, "vert_attr")
         idx = lz.sel_idx
         Nattr, C = attr_c.shape
@@ -1108,7 +1152,7 @@ class _CompositeMerge(torch.autograd.Function):
         # (frame path: the composite writes get_silhouette = min(weight sum, 1) next to the sum, a differentiable OUTPUT of this
         #  node -- the training pattern's silhouette costs no launch forward and none backward: see backward)
         sil = torch.empty_like(wsum) if lz.frame else None
-        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]))
+        ctx.gbuf = _frame_acc(lz, any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[-1])
         weight, valid, ctx.ad = _composite_fwd(lz, sel_len, any(ctx.needs_input_grad), attr_c, None, -1.0, rgb, None, wsum, sil, ctx.gbuf)
         ctx.save_for_backward(attr_c, _dev(p1, torch.float32, "sigmas"), sel_len, weight, wsum)
         ctx.lz = lz
@@ -1123,7 +1167,7 @@ class _CompositeMerge(torch.autograd.Function):
         lz.check()
         idx = lz.sel_idx
         C = attr.shape[1]
-        g_attr = g0 = g1 = None
+        g_attr = g0 = g1 = g2 = None
         # the silhouette's gradient: handed to the fused kernel as it is (with the forward's sums, which say where min(sum, 1)
         # passes it on) when that kernel runs on the forward's accumulator; any other combination turns it into the sum's own
         wsum_fwd = None
@@ -1140,14 +1184,14 @@ class _CompositeMerge(torch.autograd.Function):
             gws = None if g_wsum is None else _dev(g_wsum, torch.float32, "grad_weight_sum")
             gbuf, ctx.gbuf = ctx.gbuf, None      # (zeroed by the forward, good for ONE backward)
             if lz.gen is not None:
-                g0, g1, g_attr = _frame_gen_bwd(lz, 1, attr, weight, ctx.ad, ln, wsum_fwd, gws, None, -1.0, go, gs_pix, gs_c, None, acc=gbuf)
+                g0, g1, g2, g_attr = _frame_gen_bwd(lz, 1, attr, weight, ctx.ad, ln, wsum_fwd, gws, None, -1.0, go, gs_pix, gs_c, None, acc=gbuf)
             else:
                 g0, g1, g_attr = _merge_bwd(lz, p1, attr, weight, ctx.ad, ln, go, gs_pix, gs_c, gws, wsum_fwd, gbuf)
         if g_weight is not None:
-            h0, h1 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
-            g0, g1 = (h0, h1) if g0 is None else (g0 + h0, g1 + h1)
+            h0, h1, h2 = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ctx.ad)
+            g0, g1, g2 = (h0, h1, h2) if g0 is None else (g0 + h0, g1 + h1, None if h2 is None else g2 + h2)
         need = ctx.needs_input_grad
-        return (g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None
+        return (g_attr if need[0] else None), (g0 if need[1] else None), (g1 if need[2] else None), None, None, (g2 if need[5] else None)
 
 
 def composite_merge(lz, attr):
@@ -1158,7 +1202,7 @@ def composite_merge(lz, attr):
     if os.environ.get("VOGE_SHADE_THROUGH", "1") == "0":
         return None
     with lz.grad():
-        rgb, wsum, weight, valid, sil = _CompositeMerge.apply(attr, lz.p0, lz.p1, lz.sel_len, lz)
+        rgb, wsum, weight, valid, sil = _CompositeMerge.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, lz.p2)
     return rgb, wsum, lz.through(weight), valid, sil
 
 
@@ -1192,7 +1236,7 @@ def lazy_eligible(mode, p0, p1, origin, rays, n_assign):
 def composite_lean(lz):
     """-> weight, valid_num of a deferred composite (the weights carry `voge_through` like fragments()' do)."""
     with lz.grad():
-        weight, valid = _CompositeLean.apply(lz.p0, lz.p1, lz.sel_len, lz)
+        weight, valid = _CompositeLean.apply(lz.p0, lz.p1, lz.sel_len, lz, lz.p2)
     return lz.through(weight), valid
 
 
@@ -1204,10 +1248,10 @@ def composite_shade(lz, attr, bg, thr):
     if os.environ.get("VOGE_SHADE_THROUGH", "1") == "0":
         return None
     if torch.is_grad_enabled() == lz.grad_mode:      # (the usual case: no mode switch to pay for)
-        img, weight, valid = _CompositeShade.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, bg, thr)
+        img, weight, valid = _CompositeShade.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, bg, thr, lz.p2)
     else:
         with lz.grad():
-            img, weight, valid = _CompositeShade.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, bg, thr)
+            img, weight, valid = _CompositeShade.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, bg, thr, lz.p2)
     return img, lz.through(weight), valid
 
 
