@@ -340,6 +340,16 @@ int voge_fragment_shade_bwd_iso(const float *records, const float *sigmas, int s
  *   arrays was built and measured: one launch less, 30 us slower -- three atomic requests per table entry instead of one.)
  */
 size_t voge_frame_bwd_acc_bytes(int P);
+/*
+ * Diagnostic: the bounding cones the voge_frame_* entry points make from the camera inside their binning kernels, by the same
+ * device functions.  hier [B][nst * 21][8] floats: per view the super-tiles' (32x32 px) records, then [nst][4] quads (16x16 px,
+ * qy * 2 + qx), then [nst][16] tiles (8x8 px, ty * 4 + tx) -- voge_cones_floats' layout; regions [B][ceil(h/128) * ceil(W/128)][8]
+ * floats: the 128x128-px regions.  A record is (axis xyz, lower bound of the cosine, upper bound of the sine, ok, 2 pad); ok = -1:
+ * the block has no pixel in the band.  The band is h stacked rows of W pixels as in voge_frame_trace_fwd_iso.
+ */
+int voge_camera_cones(const float *R, const float *T, const float *focal, const float *pp, int row0, int stripe_h, int pitch,
+                      int B, int h, int W, float *hier, float *regions, voge_stream_t stream);
+
 int voge_frame_trace_fwd_iso(const float *verts, const float *sigmas, int shared, int sigma_mode, const float *R,
                              const float *T, const float *focal, const float *pp, int row0, int stripe_h, int pitch,
                              int behind, int B, int N, int h, int W, int K, float thr_act, void *workspace,

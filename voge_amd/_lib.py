@@ -42,6 +42,7 @@ SIGNATURES = {
     "voge_fragments_fwd_iso": (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_float, _c_float, _c_void_p, _c_size_t] + [_c_void_p] * 9),
     "voge_fragments_fwd_iso_view": (_c_int, [_c_void_p] * 3 + [_c_int] * 2 + [_c_void_p] * 3 + [_c_int] * 5
                                     + [_c_float, _c_float, _c_void_p, _c_size_t] + [_c_void_p] * 9),
+    "voge_camera_cones": (_c_int, [_c_void_p] * 4 + [_c_int] * 6 + [_c_void_p] * 3),
     "voge_frame_trace_fwd_iso": (_c_int, [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 4 + [_c_int] * 9
                                  + [_c_float, _c_void_p, _c_size_t] + [_c_void_p] * 7),
     "voge_frame_shade_fwd_iso": (_c_int, [_c_void_p] * 5 + [_c_float, _c_void_p, _c_void_p, _c_float, _c_long, _c_int, _c_int, _c_long]

@@ -44,7 +44,9 @@ static_assert(kCh * kCh == kBinThreads / 64, "one wave per super-tile of a regio
 // so  kappa - 1.13 * Rmax  (Rmax = largest finite reach in the bin) is a lower bound of len that
 // is MONOTONE in kappa -- what the sweep's early exit needs.
 __device__ __forceinline__ float depth_key(const float4 c, const Cone &k) {
-  const float nm = sqrtf(fmaf(c.z, c.z, fmaf(c.y, c.y, c.x * c.x)));
+  // (the hardware square root: an ulp of |mu| is 1.2e-7 of the key, bin_len_bound takes 1e-5 of it off every bound; the gather
+  //  and the tile filters both come through here, so an entry's key is the same bits wherever it is made)
+  const float nm = __builtin_amdgcn_sqrtf(fmaf(c.z, c.z, fmaf(c.y, c.y, c.x * c.x)));
   const float R = c.w;
   if (!(R < 3e38f) || !(nm < 3e38f)) return -INFINITY;
   float kappa = -nm;
@@ -223,7 +225,10 @@ binA_kernel(const ConeRec *__restrict__ cones /* [B][nst] */, const int nstx, co
   if (cam.R != nullptr) ck = cam_load(cam, b);      // (uniform)
   const BinAView V = binA_view<ISO_PREP>(b, cam_fwd, view, cam, &ck);
   if (cam.R != nullptr && cam.origin_out != nullptr && blockIdx.x == 0 && tid == 0) {
-    cam.origin_out[3 * b] = V.ox; cam.origin_out[3 * b + 1] = V.oy; cam.origin_out[3 * b + 2] = V.oz;
+    // (the view holds the centre only where the records are derived here: the prepared-records form makes it for this store)
+    float ox = V.ox, oy = V.oy, oz = V.oz;
+    if (!ISO_PREP) cam_origin(ck, cam.T + 3 * b, ox, oy, oz);
+    cam.origin_out[3 * b] = ox; cam.origin_out[3 * b + 1] = oy; cam.origin_out[3 * b + 2] = oz;
   }
   BinARaw raw[kRoundChunks];
   auto fetch_round = [&](const int j0) {      // (all of the round's loads go out together ...)

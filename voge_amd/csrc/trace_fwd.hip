@@ -1602,6 +1602,41 @@ extern "C" int voge_fragments_fwd_iso_view(const float *verts, const float *sigm
 // rows: the band is h stacked rows; stacked row i is image row row0 + (i / stripe_h) * pitch + i % stripe_h (a contiguous
 // band: stripe_h >= h, pitch 0; a rank's interleaved stripes: voge_rays_striped_fwd's meaning).  behind != 0: the reference's
 // "skip z < 0" candidate rule (rasterize_coarse.cu:35), the view axis being column 2 of R.
+// Diagnostic (tests/test_gpu_bin_cones.py): the cones the frame path's bin kernels make from the camera, by the calls they make --
+// binA's region (cam_rect_cone over kST0 pixels) and child cones (over kST), binB's quad and tile cones (cam_two_cones, one
+// workgroup per quad and one wave per tile, as in binB_kernel).
+namespace voge {
+__global__ void __launch_bounds__(kQT)
+camera_cones_kernel(const CamView cam, const int nstx, const int nsty, const int nst0x, const int nst0y,
+                    ConeRec *__restrict__ hier /* [B][nst * kConeRecsPerST] */, ConeRec *__restrict__ regions /* [B][nst0] */) {
+  const int tid = threadIdx.x, wave = tid >> 6, b = blockIdx.y;
+  const int binl = blockIdx.x >> 2, qq = blockIdx.x & 3;
+  const int stx = binl % nstx, sty = binl / nstx;
+  const size_t nst = (size_t)nstx * nsty;
+  const CamK ck = cam_load(cam, b);
+  const int tx = stx * (kST / 8) + (qq & 1) * 2 + (wave & 1), ty = sty * (kST / 8) + (qq >> 1) * 2 + (wave >> 1);
+  ConeRec tcr, qcr;
+  cam_two_cones(ck, cam, tx * 8, ty * 8, 8, stx * kST + (qq & 1) * kQuad, sty * kST + (qq >> 1) * kQuad, kQuad, tcr, qcr);
+  if ((tid & 63) == 0) hier[cone_tile_at(b, nst, binl, ((qq >> 1) * 2 + (wave >> 1)) * 4 + (qq & 1) * 2 + (wave & 1))] = tcr;
+  if (tid == 0) hier[cone_quad_at(b, nst, binl, qq)] = qcr;
+  if (tid == 0 && qq == 0) hier[cone_super_at(b, nst, binl)] = cam_rect_cone(ck, cam, stx * kST, stx * kST + kST - 1, sty * kST, sty * kST + kST - 1);
+  if (tid == 0 && qq == 1 && binl < nst0x * nst0y) {
+    const int rx = binl % nst0x, ry = binl / nst0x;
+    regions[(size_t)b * nst0x * nst0y + binl] = cam_rect_cone(ck, cam, rx * kST0, rx * kST0 + kST0 - 1, ry * kST0, ry * kST0 + kST0 - 1);
+  }
+}
+}  // namespace voge
+
+extern "C" int voge_camera_cones(const float *R, const float *T, const float *focal, const float *pp, int row0, int stripe_h, int pitch,
+                                 int B, int h, int W, float *hier, float *regions, voge_stream_t stream) {
+  if (!R || !T || !focal || !pp || !hier || !regions || stripe_h <= 0 || pitch < 0 || B <= 0 || h <= 0 || W <= 0) return VOGE_ERR_BAD_ARG;
+  const CamView cam{R, T, focal, pp, row0, stripe_h, pitch, h, W, 0, nullptr, nullptr};
+  const int nstx = (W + kST - 1) / kST, nsty = (h + kST - 1) / kST, nst0x = (W + kST0 - 1) / kST0, nst0y = (h + kST0 - 1) / kST0;
+  hipLaunchKernelGGL(camera_cones_kernel, dim3(nstx * nsty * 4, B), dim3(kQT), 0, (hipStream_t)stream, cam, nstx, nsty, nst0x, nst0y,
+                     reinterpret_cast<ConeRec *>(hier), reinterpret_cast<ConeRec *>(regions));
+  return launch_status();
+}
+
 extern "C" int voge_frame_trace_fwd_iso(const float *verts, const float *sigmas, int shared, int sigma_mode, const float *R,
                                         const float *T, const float *focal, const float *pp, int row0, int stripe_h, int pitch,
                                         int behind, int B, int N, int h, int W, int K, float thr_act, void *workspace,

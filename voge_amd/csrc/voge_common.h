@@ -445,11 +445,15 @@ struct Cone {
 // Conservative "this Gaussian cannot be hit by any line through the origin whose direction
 // lies in the cone".  c = (centre, reach).  Distance from the centre to the double cone is
 // >= q*cos - |p|*sin (p, q = axial / radial parts of the centre).
+// (round 7: the hardware square root, ~1 ulp.  The correctly rounded sqrtf is a dozen instructions -- scaling, v_sqrt, two
+// refinement steps -- in a test of two dozen that binA runs 17 times per Gaussian and binB once per candidate and tile, both
+// VALU-bound there.  An ulp of q moves `gap` by 1.2e-7 q cs <= 1.2e-7 |centre|; every reach carries a margin of 1e-5 |centre| or
+// more (iso_cull_record, prep_one) for exactly this kind of fp32 rounding -- p and r above round by as much already.)
 __device__ __forceinline__ bool cone_keep(const float4 c, const Cone &k) {
   if (c.w < 0.0f) return false;
   const float p = fmaf(c.z, k.az, fmaf(c.y, k.ay, c.x * k.ax));
   const float rx = fmaf(-p, k.ax, c.x), ry = fmaf(-p, k.ay, c.y), rz = fmaf(-p, k.az, c.z);
-  const float q = sqrtf(fmaf(rz, rz, fmaf(ry, ry, rx * rx)));
+  const float q = __builtin_amdgcn_sqrtf(fmaf(rz, rz, fmaf(ry, ry, rx * rx)));
   const float gap = fmaf(q, k.cs, -fabsf(p) * k.sn);
   return !k.ok || !(gap > c.w);
 }
