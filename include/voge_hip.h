@@ -374,6 +374,33 @@ int voge_frame_merge_bwd_iso(const float *records, const float *sigmas, int shar
                              float *g_sigmas, float *g_attr, voge_stream_t stream);
 
 /*
+ * Depth on the frame path (EXTENSION: the reference has no depth output).  With n = min(cnt, K) live slots of a pixel,
+ * A = sum_{k<n} w_k len_k and S = sum_{k<n} w_k:  depth = A / S where S > 0, else `background` (normalize != 0: the expected hit
+ * distance along the unit pixel ray), or A itself (normalize == 0; background ignored).  Not clamped; not view-space z.
+ * voge_frame_depth_fwd_iso   = voge_frame_shade_fwd_iso without a colour table: from idx, cnt, len, records and rays it writes
+ *   weight [npix][K], valid_num, depth [npix], wsum [npix] = S and sil [npix] = min(S, 1) (NULL: not wanted) in ONE launch, and
+ *   zeroes bwd_acc [bwd_acc_bytes, a multiple of 16, 16-byte aligned; NULL: nothing] on its way: the accumulator of the backward
+ *   below, 16 bytes per Gaussian (four sums, no colour term).  The index list is NOT rewritten (-1 stays -1).  K <= 128.
+ *   Replaces the torch expression (frag.vert_weight * frag.vert_hit_length).sum(-1) / frag.vert_weight.sum(-1) -- and the
+ *   composite launch in front of it.
+ * voge_frame_depth_bwd_iso   = its backward, modelled on voge_frame_merge_bwd_iso: acc_zeroed [>= 16 * B * N bytes, ZEROED, good
+ *   for one call], one fused launch, the finishing pass.  Per pixel it forms a = g_depth / S, b = -a depth (normalize, S > 0;
+ *   zero elsewhere) or a = g_depth, b = 0, adds the pass-through of g_sil [npix] (the gradient of min(S, 1); NULL: none) to b, and
+ *   feeds g_w[k] = a len_k + b and g_len[k] = a w_k to the composite + trace backward.  g_depth: element p at
+ *   g_depth[p * g_stride_pix] (1: contiguous, 0: one value for every pixel) or NULL when only g_sil is given.  Replaces autograd's
+ *   backward of that expression plus TWO voge_fragment_bwd_iso calls (one for g_weight, one for g_len).  K <= 128.
+ */
+int voge_frame_depth_fwd_iso(const int32_t *idx, const int32_t *cnt, const float *len, const float *records,
+                             const float *rays, float occ, int normalize, float background, long npix, int K,
+                             float *weight, int64_t *valid_num, float *depth, float *wsum, float *sil, void *bwd_acc,
+                             size_t bwd_acc_bytes, voge_stream_t stream);
+int voge_frame_depth_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
+                             const int32_t *idx, const int32_t *cnt, const float *weight, const float *len,
+                             const float *depth, const float *wsum, const float *g_depth, long g_stride_pix,
+                             const float *g_sil, int normalize, float occ, int B, int N, long nrows, int W, int K,
+                             void *acc_zeroed, size_t acc_bytes, float *g_verts, float *g_sigmas, voge_stream_t stream);
+
+/*
  * ABI 7, the frame path for (N,3) / (N,3,3) sigmas (Renderer.py:130-137 with Aggregation.py:144-175: A = 2 expend_sigma(sigmas);
  * no inverse_sigma).  voge_frame_trace_fwd_gen: voge_frame_trace_fwd_iso's contract with the USER's arrays as inputs -- verts
  * [N | B*N][3] (shared_verts: one set for all views), sigmas [N | B*N][3] (kind 1: per-axis) or [N | B*N][3][3] (kind 2) -- the record pass
@@ -550,6 +577,22 @@ int voge_blend_fwd(const float *rgb, const float *weight, const float *bg, float
  */
 int voge_silhouette_fwd(const float *weight, long npix, int K, float *sil, float *wsum, voge_stream_t stream);
 int voge_silhouette_bwd(const float *wsum, const float *g_sil, long npix, float *g_pix, voge_stream_t stream);
+
+/*
+ * Depth of composited fragments (EXTENSION: the reference has no depth output).  weight, len [npix][K], valid_num [npix]
+ * (int64); with n = min(max(valid_num, 0), K), A = sum_{k<n} weight_k len_k and S = sum_{k<n} weight_k:
+ *   depth [npix] = A / S where S > 0, else `background` (normalize != 0), or A (normalize == 0; background ignored);
+ *   wsum [npix] = S.  Slots k >= n never contribute.  The sums use a fixed association: the same bits on every run.
+ * Replaces the torch expression (weight * len).sum(-1) / weight.sum(-1), which is wrong on empty slots (len = 1e10 there).
+ * Backward: g_weight[k] = a len_k + b, g_len[k] = a weight_k for k < n and ZERO in the dead slots, with a = g_depth / S,
+ * b = -a depth where S > 0 and a = b = 0 elsewhere (normalize), or a = g_depth, b = 0 (depth / wsum may then be NULL).
+ * Replaces autograd's backward of that expression.  K <= VOGE_MAX_K.
+ */
+int voge_depth_fwd(const float *weight, const float *len, const int64_t *valid_num, long npix, int K, int normalize,
+                   float background, float *depth, float *wsum, voge_stream_t stream);
+int voge_depth_bwd(const float *weight, const float *len, const int64_t *valid_num, const float *depth,
+                   const float *wsum, const float *g_depth, long npix, int K, int normalize, float *g_weight,
+                   float *g_len, voge_stream_t stream);
 
 /*
  * Background blend backward: g_out [npix,C] -> g_rgb [npix,C] and the additive term

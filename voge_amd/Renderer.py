@@ -1,7 +1,7 @@
 """Host-side mirror of VoGE/Renderer.py: GaussianRenderer (:87-150), GaussianRenderSettings
 (:53-84), Fragments (:13-50), interpolate_attr (:153), get_silhouette (:157-159),
 to_colored_background (:162-171), to_white_background (:174-176) -- same names, same argument
-meaning.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
+meaning; get_depth is an extension.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
 tensors raises instead of falling back.
 """
 import math
@@ -42,11 +42,22 @@ class Fragments(object):
         # (the camera-input trace hands out vert_hit_length without a grad_fn; the differentiable alias is made when it is read)
         self._hl_src = _lazy if (_lazy is not None and _lazy.frame and _lazy.sel_len is vert_hit_length) else None
         self._wsum = None      # (per-pixel weight sum left by a one-pass composite + merge: see get_silhouette)
+        # (a reshaped view -- squeeze / unsqueeze -- of fragments whose composite is still pending: (its leading dimensions, the
+        #  number of leading dimensions of the trace's own tensors); what the deferred composite returns is viewed to that: _shaped)
+        self._lead = None
+
+    def _shaped(self, t_):
+        """A tensor the deferred composite made in the trace's own shape, as THESE fragments' view of it (the same memory;
+        ops.carry_tags hands the bookkeeping on)."""
+        if self._lead is None or t_ is None:
+            return t_
+        lead, nlead = self._lead
+        return ops.carry_tags(t_, t_.view(lead + tuple(t_.shape[nlead:])))
 
     @property
     def vert_hit_length(self):
         if self._hl_src is not None:
-            self._hit_length, self._hl_src = self._hl_src.hit_length(), None
+            self._hit_length, self._hl_src = self._shaped(self._hl_src.hit_length()), None
         return self._hit_length
 
     @vert_hit_length.setter
@@ -54,12 +65,11 @@ class Fragments(object):
         self._hit_length, self._hl_src = value, None
 
     def _composite(self):
-        lz, self._lazy = self._lazy, None
-        self._vert_weight, self._valid_num = ops.composite_lean(lz)
+        self._set_composite(*ops.composite_lean(self._lazy))
 
     def _set_composite(self, weight, valid_num):
         self._lazy = None
-        self._vert_weight, self._valid_num = weight, valid_num
+        self._vert_weight, self._valid_num = self._shaped(weight), self._shaped(valid_num)
 
     @property
     def vert_weight(self):
@@ -70,7 +80,7 @@ class Fragments(object):
     @vert_weight.setter
     def vert_weight(self, value):
         if self._lazy is not None and self._valid_num is None:      # (the reference's Fragments always has valid_num)
-            self._valid_num = self._lazy.cnt.to(torch.int64)
+            self._valid_num = self._shaped(self._lazy.cnt.to(torch.int64))
         self._lazy = None
         self._wsum = None
         self._vert_weight = value
@@ -78,7 +88,7 @@ class Fragments(object):
     @property
     def valid_num(self):
         if self._valid_num is None and self._lazy is not None:
-            self._valid_num = self._lazy.cnt.to(torch.int64)      # (= the trace's hit count; the composite writes the same)
+            self._valid_num = self._shaped(self._lazy.cnt.to(torch.int64))      # (= the trace's hit count; the composite writes the same)
         return self._valid_num
 
     @valid_num.setter
@@ -88,6 +98,17 @@ class Fragments(object):
     def _map(self, fn):
         # (views of the same memory keep the trace's bookkeeping -- ops.carry_tags -- so frag.copy(), frag.squeeze()
         #  and frag.unsqueeze() stay on the fast paths, as RenderBunny.py:45's to_white_background(frag.copy(), ...))
+        if self._lazy is not None:
+            # nothing composited yet: a reshaped view of the same memory (squeeze / unsqueeze / [0] of a one-view batch) stays
+            # deferred -- the one-pass forms remain open to it; a true slice composites now and goes on below
+            idx = self.vert_index
+            v = fn(idx)
+            if v.data_ptr() == idx.data_ptr() and v.numel() == idx.numel() and v.is_contiguous():
+                out = Fragments(None, ops.carry_tags(idx, v), None if self._valid_num is None else fn(self._valid_num),
+                                ops.carry_tags(self._hit_length, fn(self._hit_length)), _lazy=self._lazy)
+                out._hl_src = self._hl_src
+                out._lead = (tuple(v.shape[:-1]), self._lazy.sel_idx.dim() - 1)
+                return out
         return Fragments(**{k: ops.carry_tags(getattr(self, k), fn(getattr(self, k))) for k in self._fields})
 
     def __getitem__(self, item):
@@ -114,7 +135,9 @@ class Fragments(object):
 
     def copy(self):
         if self._lazy is not None:      # nothing to copy yet: the same deferred composite (tensors are shared either way,
-            return Fragments(None, self.vert_index, self._valid_num, self._hit_length, _lazy=self._lazy)   # .contiguous() is a no-op)
+            out = Fragments(None, self.vert_index, self._valid_num, self._hit_length, _lazy=self._lazy)   # .contiguous() is a no-op)
+            out._hl_src, out._lead = self._hl_src, self._lead
+            return out
         return self._map(lambda t: t.contiguous())
 
 
@@ -314,8 +337,9 @@ def interpolate_attr(fragments: Fragments, vert_attr: torch.Tensor):
         out = ops.composite_merge(lz, vert_attr)
         if out is not None:
             fragments._set_composite(out[2], out[3])
-            fragments._wsum = (out[1], out[2], out[2]._version, out[4])
-            return out[0]
+            w = fragments._vert_weight
+            fragments._wsum = (fragments._shaped(out[1]), w, w._version, fragments._shaped(out[4]))
+            return fragments._shaped(out[0])
     return merge_final(vert_attr=vert_attr, weight=fragments.vert_weight, valid_num=fragments.valid_num,
                        vert_assign=fragments.vert_index)
 
@@ -329,6 +353,40 @@ def get_silhouette(fragments: Fragments):
         # (torch.minimum splits the gradient at a tie like torch.min(a, b))
         return torch.minimum(ws[0], torch.ones_like(ws[0]))
     return ops.silhouette(fragments.vert_weight)
+
+
+def get_depth(fragments: Fragments, normalize: bool = True, background: float = 0.0):
+    """Depth map of the fragments (an extension: the reference has none) -> [..., H, W] fp32, the leading dimensions of
+    vert_index[..., 0].  For a pixel with n = min(valid_num, K) live slots, A = sum_{k<n} w_k len_k and S = sum_{k<n} w_k
+    (w = vert_weight, len = vert_hit_length); slots k >= n never contribute, forward or backward.
+
+    normalize=True:  the expected hit distance A / S where S > 0; elsewhere (nothing hit, or every weight underflowed) the
+                     result is `background`, a Python float, and the gradient is zero.  S is NOT bounded by 1 -- Gaussians
+                     overlap along a ray -- so the un-normalised sum is not a distance; this is.
+                     d/dw_k = (len_k - D) / S, d/dlen_k = w_k / S.
+    normalize=False: the accumulated A (0 where nothing was hit; `background` is ignored).  d/dw_k = len_k, d/dlen_k = w_k.
+
+    The result is not clamped.  It is a distance along the UNIT pixel ray from the camera centre, as vert_hit_length is, not
+    view-space z: multiply by the ray's cosine to the view axis (rays . view_axis, e.g. from cameras.pixel_rays) to get z.
+    The per-pixel sums use a fixed association: the same bits on every run.  vert_index is not rewritten (the -1 -> 0 of
+    empty slots is merge_final's).
+
+    Fragments whose composite is still pending (scalar sigmas on the frame path, K <= 128) get weights, depth, weight sum and
+    silhouette from ONE launch and ONE fused launch backward (ops._CompositeDepth); a get_silhouette on the same fragments then
+    costs nothing, forward or backward.  Everything else -- general and oriented Gaussians, ray-bundle traces, edited
+    fragments, K > 128, weights that already exist -- takes ops._Depth on the fragments' tensors.  For an RGB-D loss call
+    get_depth BEFORE to_colored_background: the colours then take the fused-backward shade on the finished weights (two
+    fused backward launches a step); the other order is just as correct, with the depth's gradient going through autograd's
+    [.., K] arrays."""
+    lz = getattr(fragments, "_lazy", None)
+    if lz is not None:
+        out = ops.composite_depth(lz, bool(normalize), float(background))
+        if out is not None:
+            fragments._set_composite(out[2], out[3])
+            w = fragments._vert_weight
+            fragments._wsum = (fragments._shaped(out[1]), w, w._version, fragments._shaped(out[4]))
+            return fragments._shaped(out[0])
+    return ops.depth(fragments.vert_weight, fragments.vert_hit_length, fragments.valid_num, normalize, background)
 
 
 _BG_CACHE = {}
@@ -375,7 +433,7 @@ def to_colored_background(fragments: Fragments, colors: torch.Tensor,
         out = ops.composite_shade(lz, colors, background_color, thr)
         if out is not None:
             fragments._set_composite(out[1], out[2])
-            return out[0]
+            return fragments._shaped(out[0])
     if colors.dim() == 2 and colors.shape[1] <= 4:
         # merge + silhouette + blend fused in one kernel; on fragments of this renderer the backward of the whole
         # pipeline (this blend, the composite, the trace) is one kernel as well (ops._ShadeThrough)

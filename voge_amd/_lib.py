@@ -51,6 +51,10 @@ SIGNATURES = {
                                  + [_c_int, _c_int, _c_long, _c_int, _c_int, _c_int, _c_long, _c_void_p, _c_size_t] + [_c_void_p] * 4),
     "voge_frame_merge_bwd_iso": (_c_int, [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 7 + [_c_long, _c_long, _c_void_p, _c_void_p, _c_float]
                                  + [_c_int, _c_int, _c_long, _c_int, _c_int, _c_int, _c_long, _c_void_p, _c_size_t] + [_c_void_p] * 4),
+    "voge_frame_depth_fwd_iso": (_c_int, [_c_void_p] * 5 + [_c_float, _c_int, _c_float, _c_long, _c_int] + [_c_void_p] * 6
+                                 + [_c_size_t, _c_void_p]),
+    "voge_frame_depth_bwd_iso": (_c_int, [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 8 + [_c_long, _c_void_p, _c_int, _c_float]
+                                 + [_c_int, _c_int, _c_long, _c_int, _c_int, _c_void_p, _c_size_t] + [_c_void_p] * 3),
     "voge_frame_bwd_acc_bytes": (_c_size_t, [_c_int]),
     "voge_frame_bwd_gen_acc_bytes": (_c_size_t, [_c_int]),
     "voge_frame_trace_fwd_gen": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_void_p] * 4 + [_c_int] * 9
@@ -106,6 +110,8 @@ SIGNATURES = {
     "voge_scatter_max": (_c_int, [_c_void_p] * 2 + [_c_long, _c_long] + [_c_void_p] * 2),
     "voge_silhouette_fwd": (_c_int, [_c_void_p, _c_long, _c_int] + [_c_void_p] * 3),
     "voge_silhouette_bwd": (_c_int, [_c_void_p] * 2 + [_c_long] + [_c_void_p] * 2),
+    "voge_depth_fwd": (_c_int, [_c_void_p] * 3 + [_c_long, _c_int, _c_int, _c_float] + [_c_void_p] * 3),
+    "voge_depth_bwd": (_c_int, [_c_void_p] * 6 + [_c_long, _c_int, _c_int] + [_c_void_p] * 3),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),
     "voge_blend_bg_fwd": (_c_int, [_c_void_p] * 3 + [_c_long] * 4 + [_c_float] + [_c_int] * 4 + [_c_void_p] * 2),
     "voge_blend_bg_bwd": (_c_int, [_c_void_p] * 3 + [_c_long] * 4 + [_c_float, _c_void_p, _c_long, _c_long] + [_c_int] * 4

@@ -355,7 +355,12 @@ struct CompShade {
   float4 *zero_p = nullptr;
   long zero_n4 = 0;
   float *sil = nullptr;      // (round 6) NULL | [npix]: get_silhouette = min(sum_k w_k, 1) (Renderer.py:157-159), written with the sum
+  // SC = -1, the DEPTH stage (voge_frame_depth_fwd_iso) reuses the fields instead of growing the struct, which every shade
+  // instantiation pays for in kernel-argument registers: rgb = depth [npix], Nattr = the normalize flag, thr = the background
+  // depth; colors, bg, img and idx_fix are not touched (get_depth does not rewrite the index list).
 };
+// SC = -1 (forward from the records, wave form): the DEPTH stage instead -- depth = sum_k w_k len_k / sum_k w_k over the live
+// slots (or the un-normalised sum), one more partial sum through the shade stage's reduction; no colour table, no index rewrite.
 // GEN (forward from the records): the records are the general path's packed (mu, A), three float4 per Gaussian
 // (voge_trace_lean_fwd); act / dsd come from make_eval + pair_eval, the operations of the sweep's own epilogue.
 // GEN 2 (round 6): the compact per-axis records (mu, a0, a1, a2, 0, 0), two float4 per Gaussian (voge_frame_trace_fwd_gen, kind 1);
@@ -370,9 +375,9 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
                   float *__restrict__ out2 /* g_dsd */, int64_t *__restrict__ valid_num,
                   const float4 *__restrict__ rec /* forward with act == NULL: [P] (mu, a) */, const float *__restrict__ rays,
                   const CompShade sh = CompShade{}) {
-  static_assert(SC == 0 || (MODE == 0 && WAVE && SC <= 4), "the shade stage rides in the wave-form forward only");
+  static_assert(SC == 0 || (MODE == 0 && WAVE && SC <= 4 && SC >= -1), "the shade stage rides in the wave-form forward only");
   constexpr bool BWD = MODE != 0;
-  if (SC > 0 && (long)blockIdx.x * blockDim.x < sh.zero_n4) {      // (uniform; the launch covers zero_n4: composite_shade_fwd_impl)
+  if (SC != 0 && (long)blockIdx.x * blockDim.x < sh.zero_n4) {      // (uniform; the launch covers zero_n4: composite_shade_fwd_impl)
     const long zi = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (zi < sh.zero_n4) sh.zero_p[zi] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
@@ -432,6 +437,11 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
             sh.rgb[pix * SC + c] = 0.0f;
             if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(sh.bg[c], 1.0f);
           }
+        }
+        if (SC < 0 && q == 0) {      // nothing was hit: the background depth (normalised) or an empty sum
+          sh.wsum[pix] = 0.0f;
+          if (sh.sil != nullptr) sh.sil[pix] = 0.0f;
+          sh.rgb[pix] = sh.Nattr != 0 ? sh.thr : 0.0f;
         }
       }
       return;
@@ -622,7 +632,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
     }
     if (SC > 0) {
       // ---- shade: sum_k w_k colour[idx_k] and sum_k w_k over the pixel's lanes; blend over the background ----
-      float part[SC + 1];
+      float part[(SC > 0 ? SC : 0) + 1];
 #pragma unroll
       for (int c = 0; c <= SC; ++c) part[c] = 0.0f;
 #pragma unroll
@@ -714,6 +724,32 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
             if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(fmaf(1.0f - sil, sh.bg[c], part[c]), 1.0f);
           }
         }
+      }
+    }
+    if (SC < 0) {
+      // ---- depth: sum_k w_k len_k and sum_k w_k over the pixel's LIVE slots (the lane holds both factors), summed towards
+      // the pixel's first lane like the shade stage's sums: a fixed association per pixel ----
+      float part[2] = {0.0f, 0.0f};
+#pragma unroll
+      for (int a = 0; a < NS; ++a) {
+        const bool on = k0 + a < lead;
+        part[0] = fmaf(on ? w[a] : 0.0f, on ? lm[a] : 0.0f, part[0]);
+        part[1] += on ? w[a] : 0.0f;
+      }
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        float x = part[c];
+        for (int o = 1; o < LP; o <<= 1) {
+          const float y = __shfl_down(x, o, 64);
+          if (q + o < LP && in_wg) x += y;
+        }
+        part[c] = x;
+      }
+      if (active && q == 0) {
+        const float ws = part[1];
+        sh.wsum[pix] = ws;
+        if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+        sh.rgb[pix] = sh.Nattr != 0 ? (ws > 0.0f ? part[0] / ws : sh.thr) : part[0];
       }
     }
     return;
@@ -1171,6 +1207,44 @@ extern "C" int voge_frame_shade_fwd_iso(int32_t *idx, const int32_t *cnt, const 
   if (npix == 0) return bwd_acc_bytes ? (int)voge_fill_async(bwd_acc, 0, bwd_acc_bytes, (hipStream_t)stream) : 0;      // (no launch to ride on)
   return composite_shade_fwd_impl(0, idx, cnt, len, records, rays, occ, colors, bg, thr, npix, K, C, Nattr, weight, valid_num,
                                   rgb, img, wsum, stream, nullptr, nullptr, bwd_acc, bwd_acc_bytes, sil);
+}
+
+// get_depth on the frame path (extension): voge_frame_shade_fwd_iso without a colour table -- weights, valid_num, the depth
+// (compositen_kernel's SC = -1 stage), the weight sum and the silhouette in ONE launch that also zeroes bwd_acc, the accumulator of
+// voge_frame_depth_bwd_iso (16 bytes per Gaussian: four sums, no colour term).  The index list is NOT rewritten.
+extern "C" int voge_frame_depth_fwd_iso(const int32_t *idx, const int32_t *cnt, const float *len, const float *records,
+                                        const float *rays, float occ, int normalize, float background, long npix, int K,
+                                        float *weight, int64_t *valid_num, float *depth, float *wsum, float *sil, void *bwd_acc,
+                                        size_t bwd_acc_bytes, voge_stream_t stream) {
+  if (npix < 0 || K <= 0) return VOGE_ERR_BAD_ARG;
+  if (K > 128) return VOGE_ERR_K_TOO_LARGE;      // (as the other one-pass entries: the backward's pixel fits one wave)
+  if (bwd_acc == nullptr) bwd_acc_bytes = 0;
+  if (bwd_acc_bytes > 0 && ((bwd_acc_bytes & 15) || (reinterpret_cast<uintptr_t>(bwd_acc) & 15))) return VOGE_ERR_BAD_ARG;
+  if (npix == 0) return bwd_acc_bytes ? (int)voge_fill_async(bwd_acc, 0, bwd_acc_bytes, (hipStream_t)stream) : 0;      // (no launch to ride on)
+  if (!idx || !cnt || !len || !records || !rays || !weight || !valid_num || !depth || !wsum) return VOGE_ERR_BAD_ARG;
+  constexpr int NS = 4;
+  const int tn = VOGE_COMP_WAVE_T;
+  const int ppwn = compn_pixels(K, NS, tn, true);
+  const dim3 gridn((unsigned)((npix + ppwn - 1) / ppwn)), blockn(tn);
+  const size_t ldsn = compn_lds_bytes(K, NS, false, tn, true);
+  CompShade sh{nullptr, nullptr, background, normalize ? 1L : 0L, depth, nullptr, wsum, nullptr};
+  sh.sil = sil;
+  if (bwd_acc_bytes > 0) {
+    sh.zero_p = reinterpret_cast<float4 *>(bwd_acc); sh.zero_n4 = (long)(bwd_acc_bytes / 16);
+    if ((long)gridn.x * tn < sh.zero_n4) {      // (more to zero than the launch has threads: a fill of its own)
+      const hipError_t e = voge_fill_async(bwd_acc, 0, bwd_acc_bytes, (hipStream_t)stream);
+      if (e != hipSuccess) return (int)e;
+      sh.zero_p = nullptr; sh.zero_n4 = 0;
+    }
+  }
+  const float4 *rec = reinterpret_cast<const float4 *>(records);
+  if ((double)npix * K < (double)(1l << 30))
+    hipLaunchKernelGGL((compositen_kernel<0, NS, true, uint32_t, -1, 0>), gridn, blockn, ldsn, (hipStream_t)stream, idx, nullptr, len,
+                       nullptr, nullptr, nullptr, cnt, occ, npix, K, ppwn, weight, nullptr, nullptr, valid_num, rec, rays, sh);
+  else
+    hipLaunchKernelGGL((compositen_kernel<0, NS, true, size_t, -1, 0>), gridn, blockn, ldsn, (hipStream_t)stream, idx, nullptr, len,
+                       nullptr, nullptr, nullptr, cnt, occ, npix, K, ppwn, weight, nullptr, nullptr, valid_num, rec, rays, sh);
+  return launch_status();
 }
 
 // ... and for the general forms (records = the packed (mu, A) of voge_frame_trace_fwd_gen / voge_trace_lean_fwd; act / dsd kept

@@ -78,6 +78,12 @@ struct FragBwdLds {
 //      element (p, k) at g_weight[p * gw_stride_pix + k * gw_stride_k] (K, 1 contiguous; (1, 0) for a per-pixel value
 //      broadcast over the slots, which is what a silhouette loss alone produces), plus the gradient of vert_hit_length
 //      (g_hitlen, contiguous or NULL) added to the trace's g_len; C = 0, no colour term.
+//   2: the DEPTH form (voge_frame_depth_bwd_iso; C = 0, no colour term, the weights-driven form's table): the gradient of the
+//      weights is g_w[k] = a len_k + b with two per-pixel scalars, formed here from operands the other forms do not use in this
+//      combination -- `rgb` = the forward's depth [pix], `wsum` = its weight sums [pix], g_img = the depth's gradient (element p at
+//      g_img[p * gs_pix]; NULL: none), `bg` = the SILHOUETTE's gradient [pix] | NULL, thr > 0: the normalised depth
+//      (a = g_D / S, b = -a D where S > 0) else the plain sum (a = g_D, b = 0); the silhouette's pass-through adds to b, and
+//      a w_k is added to the trace's g_len.  No kernel argument of its own.
 // NS: slots per lane (2; 4 for lists of more than 128 slots, so that a pixel's lanes still fit one wave).
 // OffT: uint32_t when every BYTE offset into the [pix][K] arrays fits 32 bits (the loads
 // then take scalar base + 32-bit lane offset and the address arithmetic leaves the vector unit), else size_t.
@@ -207,6 +213,12 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
     // the pixel's forward sums and upstream gradient (the shade stage), requested with the slots
     float gr[4] = {0.f, 0.f, 0.f, 0.f}, g_sum_w = 0.0f;
     float px_ws = 0.f, px_rgb[4] = {0.f, 0.f, 0.f, 0.f}, px_g[4] = {0.f, 0.f, 0.f, 0.f};
+    if (SRC == 2) {      // (depth form: the gradient of the depth, the forward's weight sum and depth, the silhouette's gradient)
+      if (g_img != nullptr) px_g[0] = g_img[(long)pix * gs_pix];
+      px_ws = at_bytes<float>(wsum, pix * (OffT)4);
+      px_rgb[0] = at_bytes<float>(rgb, pix * (OffT)4);
+      if (bg != nullptr) px_g[1] = at_bytes<float>(bg, pix * (OffT)4);
+    }
     if (SRC == 0) {
 #pragma unroll
       for (int c = 0; c < C; ++c) px_g[c] = g_img[(long)pix * gs_pix + c * gs_c];
@@ -306,12 +318,20 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
       }
       g_sum_w = g_mask * pass_s;
     }
+    float dp_a = 0.0f, dp_b = 0.0f;      // (SRC == 2) the pixel's two scalars: g_w[k] = dp_a len_k + dp_b, g_len[k] += dp_a w_k
+    if (SRC == 2) {
+      const bool hit = px_ws > 0.0f;
+      dp_a = thr > 0.0f ? (hit ? px_g[0] / px_ws : 0.0f) : px_g[0];
+      dp_b = (thr > 0.0f && hit) ? -dp_a * px_rgb[0] : 0.0f;
+      dp_b = fmaf(px_g[1], px_ws < 1.0f ? 1.0f : (px_ws == 1.0f ? 0.5f : 0.0f), dp_b);      // get_silhouette = min(S, 1) behind the same fragments
+    }
     // ---- shade backward: g_w of the slots; u = g_w w ----
     float um[NS];
 #pragma unroll
     for (int a = 0; a < NS; ++a) {
       float gw;
       if (SRC == 0) gw = live[a] ? fmaf(gr[3], col[a][3], fmaf(gr[2], col[a][2], fmaf(gr[1], col[a][1], fmaf(gr[0], col[a][0], g_sum_w)))) : 0.0f;
+      else if (SRC == 2) gw = live[a] ? fmaf(dp_a, lm[a], dp_b) : 0.0f;
       else gw = live[a] ? gwv[a] : 0.0f;
       um[a] = gw * wv[a];
     }
@@ -349,6 +369,11 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
 #pragma unroll
       for (int a = 0; a < NS; ++a)
         if (live[a]) gl[a] += at_bytes<float>(g_hitlen, fb + (OffT)(4 * a));
+    }
+    if (SRC == 2) {      // the depth's own gradient of len: a w_k
+#pragma unroll
+      for (int a = 0; a < NS; ++a)
+        if (live[a]) gl[a] = fmaf(dp_a, wv[a], gl[a]);
     }
     // ---- trace backward terms (isotropic: trace_bwd.hip) + the colour term, one table entry per Gaussian.  (The
     // (mu, a) records are gathered only now: held across the composite they cost the kernel a wave per SIMD.) ----
@@ -806,6 +831,40 @@ extern "C" int voge_frame_merge_bwd_iso(const float *records, const float *sigma
                                         float *g_sigmas, float *g_attr, voge_stream_t stream) {
   return frame_bwd_impl(true, records, sigmas, shared, sigma_mode, rays, attr, idx, cnt, weight, len, wsum_fwd, g_wsum, nullptr, -1.0f, g_rgb,
                         g_stride_pix, g_stride_c, occ, B, N, nrows, W, K, C, Nattr, acc_zeroed, acc_bytes, g_verts, g_sigmas, g_attr, stream);
+}
+
+// get_depth's backward on the frame path (extension): modelled on voge_frame_merge_bwd_iso -- the accumulator the forward
+// (voge_frame_depth_fwd_iso) zeroed, ONE fused launch (SRC = 2: the two per-pixel scalars are formed inside the kernel), the
+// finishing pass.  Four sums per Gaussian (g_mu, g_a): acc is [B * N][4] floats, 16 bytes per Gaussian.
+extern "C" int voge_frame_depth_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
+                                        const int32_t *idx, const int32_t *cnt, const float *weight, const float *len,
+                                        const float *depth, const float *wsum, const float *g_depth, long g_stride_pix,
+                                        const float *g_sil, int normalize, float occ, int B, int N, long nrows, int W, int K,
+                                        void *acc_zeroed, size_t acc_bytes, float *g_verts, float *g_sigmas, voge_stream_t stream) {
+  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || g_stride_pix < 0 || sigma_mode < 0 || sigma_mode > 2) return VOGE_ERR_BAD_ARG;
+  if (K > 128) return VOGE_ERR_K_TOO_LARGE;      // a lane owns a pair of slots; a pixel's lanes fit one wave
+  const int P = B * N;
+  hipStream_t st = (hipStream_t)stream;
+  const long n_out = shared ? N : P;
+  if (n_out == 0) return 0;      // no Gaussians: nothing to write
+  if (!g_verts || !g_sigmas) return VOGE_ERR_BAD_ARG;
+  if (P == 0 || nrows * W == 0) {
+    hipError_t e0 = voge_fill_async(g_verts, 0, sizeof(float) * 3 * (size_t)n_out, st);
+    if (e0 == hipSuccess) e0 = voge_fill_async(g_sigmas, 0, sizeof(float) * (size_t)n_out, st);
+    return (int)e0;
+  }
+  if (!records || !rays || !idx || !cnt || !weight || !len || !depth || !wsum || !acc_zeroed) return VOGE_ERR_BAD_ARG;
+  if ((!g_depth && !g_sil) || (sigma_mode == 2 && !sigmas)) return VOGE_ERR_BAD_ARG;
+  if (acc_bytes < (size_t)P * 16) return VOGE_ERR_WORKSPACE;
+  if (P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the record gathers
+  float *acc = reinterpret_cast<float *>(acc_zeroed);
+  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, nullptr, idx, cnt, weight, nullptr, len, nullptr, depth, wsum, g_sil,
+                 normalize ? 1.0f : -1.0f, g_depth, g_stride_pix, 0, nullptr, occ, P, nrows, W, K, 0, acc};
+  if ((double)nrows * W * K < (double)(1l << 30)) fb_launch<2, 0, 2, uint32_t, true, true>(a, st);      // (every byte offset fits 32 bits)
+  else fb_launch<2, 0, 2, size_t, true, true>(a, st);
+  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, 4, sigmas, P, N, B,
+                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, 0, 0l, g_verts, g_sigmas, (float *)nullptr);
+  return launch_status();
 }
 
 // ---- the general forms on the frame path: every backward route of fragments made by voge_frame_trace_fwd_gen.  The packed

@@ -570,6 +570,96 @@ silhouette_bwd_kernel(const float *__restrict__ wsum, const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------
+// Depth of composited fragments (extension: the reference has no depth output).  With n = min(valid_num, K) live slots,
+// A = sum_{k<n} w_k len_k and S = sum_{k<n} w_k:  depth = A / S where S > 0, else `background` (normalize), or A itself.
+// Streaming kernels, 8 bytes read per slot: a pixel owns LP consecutive lanes of ONE wave (LP a power of two, >= the pixel's
+// units, at most 64), a lane owns every LP-th unit -- VEC: a unit is four consecutive slots, one 16-byte load per array (K % 4 == 0,
+// aligned arrays); else one slot -- and the pixel's two sums are an xor butterfly over its lanes: a fixed association, the same
+// bits in every lane and on every run.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int depth_live(const int64_t *__restrict__ valid_num, const long pix, const int K) {
+  const int64_t v = valid_num[pix];
+  return (int)(v < 0 ? 0 : (v > K ? K : v));
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+depth_fwd_kernel(const float *__restrict__ weight, const float *__restrict__ len, const int64_t *__restrict__ valid_num,
+                 const long npix, const int K, const int LP, const int normalize, const float background,
+                 float *__restrict__ depth, float *__restrict__ wsum) {
+  const int lane = threadIdx.x & 63, q = lane & (LP - 1);
+  const long pix = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / LP) + lane / LP;
+  const bool ok = pix < npix;      // (no early exit: every lane takes part in the butterfly)
+  const int n = ok ? depth_live(valid_num, pix, K) : 0;
+  const float *const w = weight + pix * K, *const l = len + pix * K;
+  float A = 0.0f, S = 0.0f;
+  if (VEC) {
+    for (int k = 4 * q; k < n; k += 4 * LP) {
+      const float4 w4 = *reinterpret_cast<const float4 *>(w + k), l4 = *reinterpret_cast<const float4 *>(l + k);
+      const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, lv[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (k + j < n) { A = fmaf(wv[j], lv[j], A); S += wv[j]; }
+    }
+  } else {
+    for (int k = q; k < n; k += LP) { const float wv = w[k]; A = fmaf(wv, l[k], A); S += wv; }
+  }
+  for (int o = LP >> 1; o > 0; o >>= 1) { A += __shfl_xor(A, o, 64); S += __shfl_xor(S, o, 64); }
+  if (ok && q == 0) {
+    depth[pix] = normalize ? (S > 0.0f ? A / S : background) : A;
+    wsum[pix] = S;
+  }
+}
+
+// Its backward: g_w[k] = a len_k + b, g_len[k] = a w_k for k < n, zero in the dead slots, with the per-pixel
+//   normalize: a = g_D / S, b = -a D where S > 0 (else both zero: the background has no gradient);   else a = g_D, b = 0.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+depth_bwd_kernel(const float *__restrict__ weight, const float *__restrict__ len, const int64_t *__restrict__ valid_num,
+                 const float *__restrict__ depth, const float *__restrict__ wsum, const float *__restrict__ g_depth,
+                 const long npix, const int K, const int LP, const int normalize, float *__restrict__ g_weight,
+                 float *__restrict__ g_len) {
+  const int lane = threadIdx.x & 63, q = lane & (LP - 1);
+  const long pix = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / LP) + lane / LP;
+  if (pix >= npix) return;
+  const int n = depth_live(valid_num, pix, K);
+  float a = g_depth[pix], b = 0.0f;
+  if (normalize) {
+    const float S = wsum[pix];
+    a = S > 0.0f ? a / S : 0.0f;
+    b = S > 0.0f ? -a * depth[pix] : 0.0f;
+  }
+  const long base = pix * K;
+  if (VEC) {
+    for (int k = 4 * q; k < K; k += 4 * LP) {
+      float gw[4] = {0.f, 0.f, 0.f, 0.f}, gl[4] = {0.f, 0.f, 0.f, 0.f};
+      if (k < n) {
+        const float4 w4 = *reinterpret_cast<const float4 *>(weight + base + k), l4 = *reinterpret_cast<const float4 *>(len + base + k);
+        const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, lv[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (k + j < n) { gw[j] = fmaf(a, lv[j], b); gl[j] = a * wv[j]; }
+      }
+      *reinterpret_cast<float4 *>(g_weight + base + k) = make_float4(gw[0], gw[1], gw[2], gw[3]);
+      *reinterpret_cast<float4 *>(g_len + base + k) = make_float4(gl[0], gl[1], gl[2], gl[3]);
+    }
+  } else {
+    for (int k = q; k < K; k += LP) {
+      const bool live = k < n;
+      g_weight[base + k] = live ? fmaf(a, len[base + k], b) : 0.0f;
+      g_len[base + k] = live ? a * weight[base + k] : 0.0f;
+    }
+  }
+}
+
+// lanes per pixel of the two kernels above: the smallest power of two that holds the pixel's units, at most a wave
+static inline int depth_lanes(const int units) {
+  int lp = 1;
+  while (lp < units && lp < 64) lp <<= 1;
+  return lp;
+}
+
+// ------------------------------------------------------------------------------------------
 // Blend with a background that BROADCASTS to the image (to_colored_background with an image, a colour per view, a grey
 // level or a learnable colour: Renderer.py:162-171 as torch broadcasting evaluates it):
 //   img = min(rgb + (1 - m) bg, 1),  m = min(s, 1)  ([m > thr] when thr > 0).
@@ -822,6 +912,50 @@ extern "C" int voge_silhouette_bwd(const float *wsum, const float *g_sil, long n
   if (!wsum || !g_sil || !g_pix) return VOGE_ERR_BAD_ARG;
   hipLaunchKernelGGL(silhouette_bwd_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wsum,
                      g_sil, npix, g_pix);
+  return launch_status();
+}
+
+static inline bool depth_aligned(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+extern "C" int voge_depth_fwd(const float *weight, const float *len, const int64_t *valid_num, long npix, int K, int normalize,
+                              float background, float *depth, float *wsum, voge_stream_t stream) {
+  if (npix < 0 || K <= 0) return VOGE_ERR_BAD_ARG;
+  if (K > VOGE_MAX_K) return VOGE_ERR_K_TOO_LARGE;
+  if (npix == 0) return 0;
+  if (!weight || !len || !valid_num || !depth || !wsum) return VOGE_ERR_BAD_ARG;
+  const bool vec = (K & 3) == 0 && depth_aligned(weight, len);
+  const int LP = depth_lanes(vec ? K / 4 : K);
+  const long per_wg = 4L * (64 / LP);
+  const dim3 grid((unsigned)((npix + per_wg - 1) / per_wg));
+  if (vec)
+    hipLaunchKernelGGL(depth_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, weight, len, valid_num, npix, K, LP,
+                       normalize, background, depth, wsum);
+  else
+    hipLaunchKernelGGL(depth_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, weight, len, valid_num, npix, K, LP,
+                       normalize, background, depth, wsum);
+  return launch_status();
+}
+
+extern "C" int voge_depth_bwd(const float *weight, const float *len, const int64_t *valid_num, const float *depth,
+                              const float *wsum, const float *g_depth, long npix, int K, int normalize, float *g_weight,
+                              float *g_len, voge_stream_t stream) {
+  if (npix < 0 || K <= 0) return VOGE_ERR_BAD_ARG;
+  if (K > VOGE_MAX_K) return VOGE_ERR_K_TOO_LARGE;
+  if (npix == 0) return 0;
+  if (!weight || !len || !valid_num || !g_depth || !g_weight || !g_len || (normalize && (!depth || !wsum))) return VOGE_ERR_BAD_ARG;
+  const bool vec = (K & 3) == 0 && depth_aligned(weight, len, g_weight, g_len);
+  const int LP = depth_lanes(vec ? K / 4 : K);
+  const long per_wg = 4L * (64 / LP);
+  const dim3 grid((unsigned)((npix + per_wg - 1) / per_wg));
+  if (vec)
+    hipLaunchKernelGGL(depth_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, weight, len, valid_num, depth, wsum,
+                       g_depth, npix, K, LP, normalize, g_weight, g_len);
+  else
+    hipLaunchKernelGGL(depth_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, weight, len, valid_num, depth, wsum,
+                       g_depth, npix, K, LP, normalize, g_weight, g_len);
   return launch_status();
 }
 

@@ -955,12 +955,14 @@ def _lazy_fragment_bwd(lz, p1, weight, ln, g_weight, ad=(None, None), g_len=None
                            lz.cnt, lz.B, lz.N, (lz.p0, lz.p1), weight, ad[0], ln, ad[1], g_weight, g_len, lz.occ if occ is None else occ), None)
 
 
-def _frame_acc(lz, need):
+def _frame_acc(lz, need, per=None):
     """(round 6) Fragments of the camera-input trace: the accumulator of the coming backward, allocated by the forward whose launch
-    zeroes it on its way -- no fill launch in front of that backward (voge_frame_*_bwd_*).  None when that does not apply."""
+    zeroes it on its way -- no fill launch in front of that backward (voge_frame_*_bwd_*).  None when that does not apply.
+    per: bytes per Gaussian of an entry with a layout of its own (the depth form: 16, no colour term)."""
     if lz.frame and need and lz.K <= 128 and FRAME_DIRECT_BWD:
-        return torch.empty((lz.B * lz.N * (32 if lz.gen is None else (48 if lz.gen[0] == 1 else 64)),), dtype=torch.uint8,
-                           device=lz.sel_idx.device)
+        if per is None:
+            per = 32 if lz.gen is None else (48 if lz.gen[0] == 1 else 64)
+        return torch.empty((lz.B * lz.N * per,), dtype=torch.uint8, device=lz.sel_idx.device)
     return None
 
 
@@ -1204,6 +1206,79 @@ def composite_merge(lz, attr):
     with lz.grad():
         rgb, wsum, weight, valid, sil = _CompositeMerge.apply(attr, lz.p0, lz.p1, lz.sel_len, lz, lz.p2)
     return rgb, wsum, lz.through(weight), valid, sil
+
+
+class _CompositeDepth(torch.autograd.Function):
+    """aggregation + get_depth + the per-pixel weight sum + get_silhouette in ONE forward pass (voge_frame_depth_fwd_iso: the frame's
+    composite with the depth stage instead of a colour table): forward(p0, p1, sel_len, lz, normalize, background) -> depth,
+    weight sum, weight, valid_num, silhouette.  The backward is ONE fused launch (voge_frame_depth_bwd_iso: the two per-pixel
+    scalars of the depth's gradient are formed inside the kernel, the silhouette's gradient folds into one of them, then composite
+    + trace) on the accumulator the forward zeroed.  Scalar-sigma fragments of the frame path only (composite_depth)."""
+
+    @staticmethod
+    def forward(ctx, p0, p1, sel_len, lz, normalize, background, p2=None):
+        lib = _lib.load()
+        idx, K = lz.sel_idx, lz.K
+        dev = idx.device
+        depth = torch.empty(idx.shape[:-1], dtype=torch.float32, device=dev)
+        wsum, sil = torch.empty_like(depth), torch.empty_like(depth)
+        weight = torch.empty_like(sel_len)
+        valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=dev)
+        ctx.gbuf = acc = _frame_acc(lz, any(ctx.needs_input_grad[:2]), 16)
+        with _on(dev):
+            rc = lib.voge_frame_depth_fwd_iso(_p(idx), _p(lz.cnt), _p(sel_len), _p(lz.records), _p(lz.rays), lz.occ, int(normalize),
+                                              float(background), idx.numel() // K, K, _p(weight), _p(valid), _p(depth), _p(wsum), _p(sil),
+                                              _p(acc), 0 if acc is None else acc.numel(), _stream())
+        _lib.check(rc, "voge_frame_depth_fwd_iso")
+        weight.voge_act_dsd = (None, None)
+        ctx.save_for_backward(_dev(p1, torch.float32, "sigmas"), sel_len, weight, depth, wsum)
+        ctx.lz, ctx.normalize = lz, bool(normalize)
+        ctx.mark_non_differentiable(valid, wsum)
+        ctx.set_materialize_grads(False)
+        return depth, wsum, weight, valid, sil
+
+    @staticmethod
+    def backward(ctx, g_depth, _g_wsum, g_weight, _g_valid, g_sil):
+        p1, ln, weight, depth, wsum = ctx.saved_tensors
+        lz = ctx.lz
+        lz.check()
+        g0 = g1 = None
+        if g_depth is not None or g_sil is not None:
+            lib = _lib.load()
+            idx = lz.sel_idx
+            B, H, W, K = idx.shape
+            dev = idx.device
+            gd, gs_pix = None, 0
+            if g_depth is not None:
+                gd, gs_pix, _ = _grad_layout(g_depth, 1)
+            gs = None if g_sil is None else _dev(g_sil, torch.float32, "grad_silhouette")
+            acc, ctx.gbuf = ctx.gbuf, None      # (zeroed by the forward, good for ONE backward: a second one zeroes its own)
+            if acc is None:
+                acc = torch.zeros((lz.B * lz.N * 16,), dtype=torch.uint8, device=dev)
+            g0 = torch.empty(lz.p0.shape, dtype=torch.float32, device=dev)
+            g1 = torch.empty(lz.p1.shape, dtype=torch.float32, device=dev)
+            with _on(dev):
+                rc = lib.voge_frame_depth_bwd_iso(_p(lz.records), _p(p1), int(lz.shared), lz.sigma_mode, _p(lz.rays), _p(idx), _p(lz.cnt),
+                                                  _p(weight), _p(ln), _p(depth), _p(wsum), _p(gd), gs_pix, _p(gs), int(ctx.normalize),
+                                                  lz.occ, lz.B, lz.N, B * H, W, K, _p(acc), acc.numel(), _p(g0), _p(g1), _stream())
+            _lib.check(rc, "voge_frame_depth_bwd_iso")
+        if g_weight is not None:
+            h0, h1, _ = _lazy_fragment_bwd(lz, p1, weight, ln, g_weight)
+            g0, g1 = (h0, h1) if g0 is None else (g0 + h0, g1 + h1)
+        need = ctx.needs_input_grad
+        return (g0 if need[0] else None), (g1 if need[1] else None), None, None, None, None, None
+
+
+def composite_depth(lz, normalize, background):
+    """-> depth, weight sum, weight, valid_num, silhouette of deferred-composite fragments in one pass (_CompositeDepth); or None
+    when the one-pass form does not apply (anything but scalar sigmas on the frame path, K > 128, edited fragments)."""
+    if not (lz.frame and lz.gen is None) or lz.K > 128 or not lz.usable():
+        return None
+    if os.environ.get("VOGE_SHADE_THROUGH", "1") == "0":
+        return None
+    with lz.grad():
+        depth, wsum, weight, valid, sil = _CompositeDepth.apply(lz.p0, lz.p1, lz.sel_len, lz, normalize, background, lz.p2)
+    return depth, wsum, lz.through(weight), valid, sil
 
 
 def trace_lean(mode, p0, p1, origin, rays, cam_fwd, thr_act, n_assign, sigma_mode=0, occ=1.0):
@@ -1626,6 +1701,46 @@ class _Silhouette(torch.autograd.Function):
         return g_pix.unsqueeze(-1).expand(*wsum.shape, ctx.K)
 
 
+class _Depth(torch.autograd.Function):
+    """get_depth of composited fragments (extension; voge_depth_fwd / _bwd): forward(weight [.., K], hit_length [.., K], valid_num
+    [..], normalize, background) -> depth [..]: sum_{k<n} w_k len_k / sum_{k<n} w_k over the n = min(valid_num, K) live slots
+    (`background` where the sum of the weights is not positive), or the un-normalised sum.  The backward hands autograd the
+    gradients of the weights and of vert_hit_length, zero in the dead slots."""
+
+    @staticmethod
+    def forward(ctx, weight, hit_length, valid_num, normalize, background):
+        w = _dev(weight, torch.float32, "weight")
+        ln = _dev(hit_length, torch.float32, "vert_hit_length")
+        vn = _dev(valid_num, torch.int64, "valid_num")
+        lib = _lib.load()
+        if ln.shape != w.shape or vn.shape != w.shape[:-1]:
+            raise ValueError(f"get_depth: weight {tuple(w.shape)}, vert_hit_length {tuple(ln.shape)} and valid_num {tuple(vn.shape)} "
+                             "do not describe the same fragments")
+        K = w.shape[-1]
+        depth = torch.empty(w.shape[:-1], dtype=torch.float32, device=w.device)
+        wsum = torch.empty_like(depth)
+        with _on(w.device):
+            rc = lib.voge_depth_fwd(_p(w), _p(ln), _p(vn), w.numel() // max(K, 1), K, int(normalize), float(background), _p(depth),
+                                    _p(wsum), _stream())
+        _lib.check(rc, "voge_depth_fwd")
+        ctx.save_for_backward(w, ln, vn, depth, wsum)
+        ctx.normalize = bool(normalize)
+        return depth
+
+    @staticmethod
+    def backward(ctx, g_depth):
+        lib = _lib.load()
+        w, ln, vn, depth, wsum = ctx.saved_tensors
+        K = w.shape[-1]
+        gd = _dev(g_depth, torch.float32, "grad_depth")
+        g_w, g_len = torch.empty_like(w), torch.empty_like(w)
+        with _on(w.device):
+            rc = lib.voge_depth_bwd(_p(w), _p(ln), _p(vn), _p(depth), _p(wsum), _p(gd), w.numel() // max(K, 1), K, int(ctx.normalize),
+                                    _p(g_w), _p(g_len), _stream())
+        _lib.check(rc, "voge_depth_bwd")
+        return g_w, g_len, None, None, None
+
+
 class _PixelRays(torch.autograd.Function):
     """Ray bundle of VoGE/Renderer.py:124-130: (R [B,3,3], T [B,3], focal [B,2], pp [B,2]) ->
     unit world-space directions [B,h,W,3] of image rows row0..row0+h-1 and the camera centres [B,3]."""
@@ -1851,3 +1966,7 @@ def shade(attr, weight, idx, valid_num, bg, thr=-1.0):
 
 def silhouette(weight):
     return _Silhouette.apply(weight)
+
+
+def depth(weight, hit_length, valid_num, normalize=True, background=0.0):
+    return _Depth.apply(weight, hit_length, valid_num, bool(normalize), float(background))
