@@ -595,6 +595,27 @@ int voge_depth_bwd(const float *weight, const float *len, const int64_t *valid_n
                    float *g_len, voge_stream_t stream);
 
 /*
+ * View-dependent colours from spherical-harmonic coefficients (EXTENSION: the reference has no spherical-harmonic code).
+ * sh [N][M][C] with M in {1, 4, 9, 16} (maximum degree L = sqrt(M) - 1) and C in 1..4; verts [N][3] (shared_verts != 0: one set
+ * for every view) or [B][N][3]; centres [B][3], the camera centres.  For view b and Gaussian n, delta = v - c_b and
+ * d = delta / |delta| (d = 0 where |delta|^2 <= 1e-20: only the constant term survives):
+ *   pre = sum_{m < (degree+1)^2} Y_m(d) sh[n][m][:] + 0.5,   out [B*N][C], row b*N + n, = max(pre, 0) (clamp != 0) or pre,
+ * with 0 <= degree <= L the ACTIVE degree and Y_m the orthonormal real SH in the order and with the signs of
+ * voge_amd/Aggregation.py sh_colors (the convention trained Gaussian scenes store their coefficients in).  Replaces that torch
+ * expression -- a normalise, up to 16 polynomials, a contraction, an offset and a clamp -- by one launch.
+ * Backward: g_out [B*N][C] -> g_sh [N][M][C] (EVERY element written; zero above the active degree) and g_verts ([N][3] summed
+ * over the views when shared_verts, else [B][N][3]), through d d / d v = (I - d d^T) / |delta|; zero where pre <= 0 under the clamp
+ * and, for the vertices, where d = 0.  The direction and the clamp mask are recomputed from the inputs: nothing is saved by the
+ * forward.  One thread owns a Gaussian and walks the views in order -- no atomics, the same bits on every run.  Replaces
+ * autograd's backward of that expression.  No gradient for the centres.  B == 0 or N == 0: success, nothing is launched or
+ * written.  Where M * C is a multiple of 4, sh and g_sh must be 16-byte aligned (VOGE_ERR_BAD_ARG otherwise).
+ */
+int voge_sh_colors_fwd(const float *sh, const float *verts, const float *centres, int B, int N, int M, int C, int degree,
+                       int shared_verts, int clamp, float *out, voge_stream_t stream);
+int voge_sh_colors_bwd(const float *sh, const float *verts, const float *centres, const float *g_out, int B, int N, int M, int C,
+                       int degree, int shared_verts, int clamp, float *g_sh, float *g_verts, voge_stream_t stream);
+
+/*
  * Background blend backward: g_out [npix,C] -> g_rgb [npix,C] and the additive term
  * g_weight_add [npix,K] (d out / d weight through the silhouette; zero where thr > 0 or
  * where the silhouette is clamped).  Recomputes the clamps from rgb / weight / bg.

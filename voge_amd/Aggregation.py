@@ -93,3 +93,69 @@ def oriented_sigma(scales, quats):
     p = (scales[..., None, :] * R)[..., :, None, :] * R[..., None, :, :]      # [.., i, j, k] = (s_k R_ik) R_jk
     S = (p[..., 0] + p[..., 1]) + p[..., 2]
     return torch.triu(S) + torch.triu(S, 1).transpose(-1, -2)
+
+
+# The orthonormal real spherical harmonics of degree <= 3 as polynomials of a unit vector (x, y, z), in the order and with the
+# signs trained Gaussian scenes store their colour coefficients in.
+_SH_C0 = 0.28209479177387814
+_SH_C1 = 0.4886025119029199
+_SH_C2 = (1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+_SH_C3 = (0.5900435899266435, 2.890611442640554, 0.4570457994644658, 0.3731763325901154, 1.445305721320277)
+
+
+def _sh_basis(d, count):
+    """[..., 3] unit vectors -> the first `count` (1, 4, 9 or 16) basis values, a list of [...] tensors."""
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    Y = [torch.full_like(x, _SH_C0)]
+    if count > 1:
+        Y += [-_SH_C1 * y, _SH_C1 * z, -_SH_C1 * x]
+    if count > 4:
+        xx, yy, zz = x * x, y * y, z * z
+        a, b, c = _SH_C2
+        Y += [a * (x * y), -a * (y * z), b * (2 * zz - xx - yy), -a * (x * z), c * (xx - yy)]
+    if count > 9:
+        a, b, c, e, f = _SH_C3
+        q = 4 * zz - xx - yy
+        Y += [-a * (y * (3 * xx - yy)), b * (x * y * z), -c * (y * q), e * (z * (2 * zz - 3 * xx - 3 * yy)), -c * (x * q),
+              f * (z * (xx - yy)), -a * (x * (xx - 3 * yy))]
+    return Y
+
+
+def sh_degree(sh, degree=None):
+    """The active degree of sh [N, M, C] (M in {1, 4, 9, 16}: maximum degree L = sqrt(M) - 1), checked: `degree`, or L."""
+    if sh.dim() != 3 or sh.shape[1] not in (1, 4, 9, 16):
+        raise ValueError('sh[N, M, C] with M in (1, 4, 9, 16) expected, got shape: ' + str(tuple(sh.shape)))
+    L = (1, 4, 9, 16).index(sh.shape[1])
+    if degree is None:
+        return L
+    if int(degree) != degree or not 0 <= degree <= L:
+        raise ValueError(f'degree must be an integer in 0..{L} for sh of shape {tuple(sh.shape)}, got {degree!r}')
+    return int(degree)
+
+
+def sh_colors(sh, verts, cam_center, degree=None, clamp=True):
+    """View-dependent colours [B*N, C] (row b*N + n: what the fragments of a B-view render index) from spherical-harmonic
+    coefficients sh [N, M, C], M in {1, 4, 9, 16}; verts [N,3] or [B,N,3]; cam_center [B,3].  An extension: the reference has none.
+
+    For view b and Gaussian n: delta = v - c_b, d = delta / |delta| -- the direction from the camera to the Gaussian; where
+    |delta|^2 <= 1e-20, d = 0: only the constant term survives and verts gets no gradient --
+        pre[b,n,:] = sum_{m < (degree+1)^2} Y_m(d) sh[n,m,:] + 0.5,      out = relu(pre) if clamp else pre.
+    `degree` (default: the maximum, sqrt(M) - 1) is the ACTIVE degree: the coefficients above it are not read and get a zero
+    gradient (progressive training).  Y_m, the +0.5 and the clamp at 0 are the convention trained Gaussian scenes are stored in.
+
+    Differentiable torch on any device / dtype (sh, verts and cam_center all get autograd's gradient): the definition the kernel
+    (ops._ShColors, Renderer.sh_to_colors) is tested against, and the route for everything the kernel does not take."""
+    degree = sh_degree(sh, degree)
+    if cam_center.dim() != 2 or cam_center.shape[-1] != 3 or verts.shape[-1] != 3 or verts.dim() not in (2, 3):
+        raise ValueError('verts[N,3] or [B,N,3] and cam_center[B,3] expected, got ' + str(tuple(verts.shape)) + ' / ' + str(tuple(cam_center.shape)))
+    B, N = cam_center.shape[0], sh.shape[0]
+    if verts.shape[-2] != N or (verts.dim() == 3 and verts.shape[0] != B):
+        raise ValueError(f'verts {tuple(verts.shape)} do not match sh {tuple(sh.shape)} and cam_center {tuple(cam_center.shape)}')
+    delta = (verts if verts.dim() == 3 else verts[None]) - cam_center[:, None, :]
+    n2 = (delta * delta).sum(-1, keepdim=True)
+    ok = n2 > 1e-20
+    inv = torch.where(ok, torch.rsqrt(torch.where(ok, n2, torch.ones_like(n2))), torch.zeros_like(n2))
+    active = (degree + 1) ** 2
+    Y = torch.stack(_sh_basis(delta * inv, active), dim=-1)                      # [B, N, active]
+    pre = torch.einsum('bnm,nmc->bnc', Y, sh[:, :active]) + 0.5
+    return (torch.relu(pre) if clamp else pre).reshape(B * N, sh.shape[2])

@@ -1,7 +1,7 @@
 """Host-side mirror of VoGE/Renderer.py: GaussianRenderer (:87-150), GaussianRenderSettings
 (:53-84), Fragments (:13-50), interpolate_attr (:153), get_silhouette (:157-159),
 to_colored_background (:162-171), to_white_background (:174-176) -- same names, same argument
-meaning; get_depth is an extension.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
+meaning; get_depth and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
 tensors raises instead of falling back.
 """
 import math
@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .Aggregation import aggregation, expend_sigma, merge_final, oriented_sigma
+from .Aggregation import aggregation, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
 from . import RayTracing
 from .RayTracing import _view_axis
 from .cameras import camera_tensors, pixel_rays
@@ -387,6 +387,36 @@ def get_depth(fragments: Fragments, normalize: bool = True, background: float = 
             fragments._wsum = (fragments._shaped(out[1]), w, w._version, fragments._shaped(out[4]))
             return fragments._shaped(out[0])
     return ops.depth(fragments.vert_weight, fragments.vert_hit_length, fragments.valid_num, normalize, background)
+
+
+def sh_to_colors(sh: torch.Tensor, verts: torch.Tensor, cameras_or_centres, degree: Union[None, int] = None, clamp: bool = True):
+    """View-dependent colours (an extension: the reference has none) -> [B*N, C], row b*N + n: the attribute table the fragments
+    of a B-view render index, to hand to to_colored_background / to_white_background / interpolate_attr like any colours.
+
+    sh [N, M, C] holds the spherical-harmonic coefficients of each Gaussian's colour, M in {1, 4, 9, 16} (maximum degree
+    sqrt(M) - 1, 0..3); verts [N,3] or [B,N,3] the centres the renderer gets; cameras_or_centres a [B,3] tensor of camera centres
+    or a cameras object.  For view b and Gaussian n, with d the unit vector from the camera centre to the Gaussian,
+        colour = relu(sum_{m < (degree+1)^2} Y_m(d) sh[n,m,:] + 0.5)      (clamp=False: without the relu)
+    in the basis order, signs, offset and clamp trained Gaussian scenes are stored in (Aggregation.sh_colors spells Y_m out and IS
+    the definition).  `degree` (default: the maximum) is the active degree: higher coefficients are not read and get a zero
+    gradient, for progressive training.  The gradient is zero where the clamp is active.
+
+    fp32 tensors on ONE HIP device with 1 <= C <= 4 and camera centres that need no gradient take one HIP launch each way
+    (ops._ShColors: no atomics, the same bits on every run, nothing but the outputs allocated, so the step still captures into a
+    HIP graph -- with one exception: where M * C is a multiple of 4 the kernel loads a Gaussian's coefficients 16 bytes at a time,
+    and an `sh` that does not start on a 16-byte boundary, such as a view at an odd offset into a flat buffer, is copied first);
+    anything else -- other dtypes, tensors on the host or on different devices, C = 0 or C > 4, a camera centre that requires
+    grad -- returns
+    Aggregation.sh_colors(...): the same values with autograd's gradients, the camera centres' included.
+
+    A cameras object is asked for get_camera_center() on EVERY call -- a matrix inverse and an einsum, several launches: when the
+    cameras are fixed, compute the centres once and pass the tensor."""
+    centres = cameras_or_centres if torch.is_tensor(cameras_or_centres) else cameras_or_centres.get_camera_center()
+    degree = sh_degree(sh, degree)
+    if (sh.is_cuda and verts.device == centres.device == sh.device and sh.dtype == verts.dtype == centres.dtype == torch.float32
+            and 1 <= sh.shape[2] <= 4 and not centres.requires_grad):
+        return ops.sh_colors(sh, verts, centres, degree, clamp)
+    return sh_colors(sh, verts, centres, degree, clamp)
 
 
 _BG_CACHE = {}

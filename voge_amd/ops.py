@@ -1741,6 +1741,55 @@ class _Depth(torch.autograd.Function):
         return g_w, g_len, None, None, None
 
 
+def _aligned16(t_):
+    """t_ itself, or a copy whose first element sits on a 16-byte boundary (a slice taken in the middle of a row does not)."""
+    return t_ if t_.data_ptr() % 16 == 0 else t_.clone()
+
+
+class _ShColors(torch.autograd.Function):
+    """View-dependent colours (extension; voge_sh_colors_fwd / _bwd): forward(sh [N,M,C], verts [N,3] | [B,N,3], centres [B,3],
+    degree, clamp) -> [B*N, C], the values of Aggregation.sh_colors.  One launch each way on the current stream and no allocation
+    but the outputs -- except that an `sh` off the 16-byte boundary the kernels' vector loads need is copied (_aligned16); the backward
+    recomputes the directions and the clamp mask from the saved INPUTS and writes every element of g_sh and g_verts (no zero
+    fill, no atomics: the same bits on every run).  The centres get no gradient here -- Renderer.sh_to_colors sends a centre that
+    wants one to the torch definition."""
+
+    @staticmethod
+    def forward(ctx, sh, verts, centres, degree, clamp):
+        sh = _aligned16(_dev(sh, torch.float32, "sh"))
+        verts = _dev(verts, torch.float32, "verts")
+        centres = _dev(centres, torch.float32, "cam_center")
+        lib = _lib.load()
+        N, M, C = sh.shape
+        B = centres.shape[0]
+        if centres.shape != (B, 3) or tuple(verts.shape) not in ((N, 3), (B, N, 3)):
+            raise ValueError(f"sh_colors: sh {tuple(sh.shape)}, verts {tuple(verts.shape)} and cam_center {tuple(centres.shape)} do not "
+                             "describe the same Gaussians and views")
+        out = torch.empty((B * N, C), dtype=torch.float32, device=sh.device)
+        with _on(sh.device):
+            rc = lib.voge_sh_colors_fwd(_p(sh), _p(verts), _p(centres), B, N, M, C, degree, int(verts.dim() == 2), int(clamp), _p(out),
+                                        _stream())
+        _lib.check(rc, "voge_sh_colors_fwd")
+        ctx.save_for_backward(sh, verts, centres)
+        ctx.degree, ctx.clamp = degree, bool(clamp)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        sh, verts, centres = ctx.saved_tensors
+        N, M, C = sh.shape
+        B = centres.shape[0]
+        go = _dev(g_out, torch.float32, "grad_colors")
+        make = torch.zeros_like if B * N == 0 else torch.empty_like      # (nothing is launched for an empty batch)
+        g_sh, g_verts = make(sh), make(verts)
+        with _on(sh.device):
+            rc = lib.voge_sh_colors_bwd(_p(sh), _p(verts), _p(centres), _p(go), B, N, M, C, ctx.degree, int(verts.dim() == 2),
+                                        int(ctx.clamp), _p(g_sh), _p(g_verts), _stream())
+        _lib.check(rc, "voge_sh_colors_bwd")
+        return g_sh, g_verts, None, None, None
+
+
 class _PixelRays(torch.autograd.Function):
     """Ray bundle of VoGE/Renderer.py:124-130: (R [B,3,3], T [B,3], focal [B,2], pp [B,2]) ->
     unit world-space directions [B,h,W,3] of image rows row0..row0+h-1 and the camera centres [B,3]."""
@@ -1970,3 +2019,7 @@ def silhouette(weight):
 
 def depth(weight, hit_length, valid_num, normalize=True, background=0.0):
     return _Depth.apply(weight, hit_length, valid_num, bool(normalize), float(background))
+
+
+def sh_colors(sh, verts, centres, degree, clamp=True):
+    return _ShColors.apply(sh, verts, centres, degree, clamp)
