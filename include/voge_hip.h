@@ -616,6 +616,29 @@ int voge_sh_colors_bwd(const float *sh, const float *verts, const float *centres
                        int degree, int shared_verts, int clamp, float *g_sh, float *g_verts, voge_stream_t stream);
 
 /*
+ * Surface normals from a depth map (EXTENSION: the reference has neither depth nor normals).  depth [B][h][W] is the distance
+ * along each pixel's unit ray (voge_depth_fwd, voge_frame_depth_fwd_iso); R [B][3][3], focal [B][2], pp [B][2] the cameras of
+ * voge_rays_fwd (no T: the camera centre cancels in every difference); band row i is image row row0 + i.  The kernels make the
+ * rays themselves.  With valid = isfinite(depth) && depth > 0 and P = depth * ray, a neighbour is usable if it lies inside the
+ * band, is valid and (edge < 0: no test) |depth_nb - depth| <= edge * depth; D_x = P(j+1) - P(j-1), P(j+1) - P(j) or
+ * P(j) - P(j-1) by which of the two are usable, D_y likewise along i; c = D_x x D_y and
+ *   normals [B][h][W][3] = +-c / |c| with n . ray <= 0 (towards the camera) where the pixel is valid, both differences exist
+ *   and 0 < |c|^2 < inf;  (0, 0, 0) everywhere else.   view_space != 0: n_world @ R_b (row vectors, X_view = X_world @ R + T).
+ * Replaces voge_amd/Aggregation.py depth_normals on rays from voge_rays_fwd -- about 30 torch launches over [B,h,W,3]
+ * temporaries -- by one launch.
+ * Backward: g_normals [B][h][W][3] -> g_depth [B][h][W], EVERY element written (zero where the depth is not valid).  The
+ * gradient flows through P, the cross product and the normalisation; the choice of stencil, the edge test and the sign are
+ * constants.  A gather: pixel q's thread recomputes the stencils of the up to five outputs that read depth(q) and sums them in a
+ * fixed order -- no atomics, the same bits on every run; nothing is saved by the forward.  Replaces autograd's backward of that
+ * expression.  B, h or W == 0: success, nothing is launched or written.  row0 < 0, a NaN edge, B > 65535 or h > 262140:
+ * VOGE_ERR_BAD_ARG.
+ */
+int voge_depth_normals_fwd(const float *depth, const float *R, const float *focal, const float *pp, int B, int row0, int h, int W,
+                           float edge, int view_space, float *normals, voge_stream_t stream);
+int voge_depth_normals_bwd(const float *depth, const float *R, const float *focal, const float *pp, const float *g_normals, int B,
+                           int row0, int h, int W, float edge, int view_space, float *g_depth, voge_stream_t stream);
+
+/*
  * Background blend backward: g_out [npix,C] -> g_rgb [npix,C] and the additive term
  * g_weight_add [npix,K] (d out / d weight through the silhouette; zero where thr > 0 or
  * where the silhouette is clamped).  Recomputes the clamps from rgb / weight / bg.

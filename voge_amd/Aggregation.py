@@ -159,3 +159,71 @@ def sh_colors(sh, verts, cam_center, degree=None, clamp=True):
     Y = torch.stack(_sh_basis(delta * inv, active), dim=-1)                      # [B, N, active]
     pre = torch.einsum('bnm,nmc->bnc', Y, sh[:, :active]) + 0.5
     return (torch.relu(pre) if clamp else pre).reshape(B * N, sh.shape[2])
+
+
+def _shifted(x, dim, k):
+    """y[.., i, ..] = x[.., i + k, ..] along `dim` for k = +-1, zeros (False) where i + k falls outside."""
+    n = x.shape[dim]
+    if n == 0:
+        return x
+    pad = torch.zeros_like(x.narrow(dim, 0, 1))
+    return torch.cat([x.narrow(dim, 1, n - 1), pad], dim) if k > 0 else torch.cat([pad, x.narrow(dim, 0, n - 1)], dim)
+
+
+def _stencil_difference(P, d, valid, dim, edge):
+    """The finite difference of P [B,h,W,3] along `dim` (1: rows, 2: columns) by the rule of depth_normals -> (D, exists)."""
+    up, um = _shifted(valid, dim, 1), _shifted(valid, dim, -1)
+    if edge is not None:
+        up = up & ((_shifted(d, dim, 1) - d).abs() <= edge * d)
+        um = um & ((_shifted(d, dim, -1) - d).abs() <= edge * d)
+    Pp, Pm = _shifted(P, dim, 1), _shifted(P, dim, -1)
+    up3, um3 = up[..., None], um[..., None]
+    D = torch.where(up3 & um3, Pp - Pm, torch.where(up3, Pp - P, torch.where(um3, P - Pm, torch.zeros_like(P))))
+    return D, up | um
+
+
+def depth_normals(depth, rays, edge=None):
+    """Surface normals [B,h,W,3] of a depth map (an extension: the reference has neither): depth [B,h,W] is the distance along
+    each pixel's UNIT ray -- what Renderer.get_depth returns, not view-space z --, rays [B,h,W,3] the unit world-space directions
+    of the same pixels (cameras.pixel_rays).  The normal of the rendered surface from finite differences of the back-projected
+    points; the camera centre cancels in every difference and is not needed.
+
+        valid = isfinite(depth) & (depth > 0),      P = depth * ray
+        a neighbour (i, j +- 1) is USABLE if it lies inside [0, W), is valid and -- with an `edge`, a relative depth jump that
+            cuts the stencil at occlusion boundaries -- |depth_nb - depth| <= edge * depth
+        D_x = P(j+1) - P(j-1) if both are usable, P(j+1) - P(j) or P(j) - P(j-1) if one is, undefined if neither;
+        D_y the same along i inside [0, h) (rows outside the band do not exist)
+        c = D_x x D_y;  the pixel is DEFINED iff it is valid, both differences exist and 0 < |c|^2 < inf
+        n = c / |c|, negated where n . ray > 0 (the normal faces the camera: no handedness convention leaks out); (0, 0, 0)
+            at every pixel that is not defined.
+
+    The gradient flows through P, the cross product and the normalisation to `depth` (and to `rays`); the choice of stencil,
+    the edge test and the sign are constants.  A pixel that is not defined gives its upstream gradient to nothing, and a depth
+    that is not valid gets exactly zero; NaN and inf in such depths reach no output and no gradient (every masked quantity is
+    replaced BEFORE it is used: no sqrt(0), no 0/0 under a where).
+
+    fp32: the differences cancel, so the error is about 2^-23 * depth / pixel footprint -- 2e-6 to 5e-6 at focal lengths of 30
+    to 60 pixels, 3.3e-5 at 500, 1.2e-4 at 2000 and distance 6 (against fp64, on the same depth values).  That is the floor of
+    the problem in this number format: the kernels avoid it in their own arithmetic (normals.hip), nobody avoids it for the
+    rounding the fp32 depth values already carry.
+
+    Differentiable torch on any device / dtype: the definition the kernels (ops._DepthNormals, Renderer.get_normals) are tested
+    against, and the route for everything they do not take."""
+    if depth.dim() != 3 or tuple(rays.shape) != tuple(depth.shape) + (3,):
+        raise ValueError(f'depth[B,h,W] and rays[B,h,W,3] expected, got {tuple(depth.shape)} / {tuple(rays.shape)}')
+    if edge is not None:
+        edge = float(edge)
+        if not 0.0 <= edge < float('inf'):
+            raise ValueError(f'edge must be None or a finite relative depth jump >= 0, got {edge!r}')
+    valid = torch.isfinite(depth) & (depth > 0)
+    d = torch.where(valid, depth, torch.zeros_like(depth))
+    P = d[..., None] * rays
+    Dx, has_x = _stencil_difference(P, d.detach(), valid, 2, edge)
+    Dy, has_y = _stencil_difference(P, d.detach(), valid, 1, edge)
+    c = torch.cross(Dx, Dy, dim=-1)
+    c2 = (c * c).sum(-1).detach()
+    defined = valid & has_x & has_y & (c2 > 0) & torch.isfinite(c2)
+    c = torch.where(defined[..., None], c, torch.zeros_like(c))
+    n = c * torch.rsqrt(torch.where(defined, (c * c).sum(-1), torch.ones_like(c2)))[..., None]
+    away = (n.detach() * rays.detach()).sum(-1, keepdim=True) > 0
+    return torch.where(away, -n, n)

@@ -1,7 +1,7 @@
 """Host-side mirror of VoGE/Renderer.py: GaussianRenderer (:87-150), GaussianRenderSettings
 (:53-84), Fragments (:13-50), interpolate_attr (:153), get_silhouette (:157-159),
 to_colored_background (:162-171), to_white_background (:174-176) -- same names, same argument
-meaning; get_depth and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
+meaning; get_depth, get_normals and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
 tensors raises instead of falling back.
 """
 import math
@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .Aggregation import aggregation, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
+from .Aggregation import aggregation, depth_normals, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
 from . import RayTracing
 from .RayTracing import _view_axis
 from .cameras import camera_tensors, pixel_rays
@@ -387,6 +387,86 @@ def get_depth(fragments: Fragments, normalize: bool = True, background: float = 
             fragments._wsum = (fragments._shaped(out[1]), w, w._version, fragments._shaped(out[4]))
             return fragments._shaped(out[0])
     return ops.depth(fragments.vert_weight, fragments.vert_hit_length, fragments.valid_num, normalize, background)
+
+
+def get_normals(depth: torch.Tensor, cameras_or_rays, rows=None, edge: Union[None, float] = None, view_space: bool = False):
+    """Surface normals of a depth map (an extension: the reference has none) -> [B,h,W,3] for depth [B,h,W], [h,W,3] for [h,W].
+    `depth` is what get_depth returns: the distance along each pixel's UNIT ray from the camera centre, not view-space z (a
+    z-buffer has to be divided by rays . view_axis first).  The Gaussians themselves have no usable normal -- at a slot's hit point,
+    the density maximum along the ray, the density gradient is perpendicular to the ray by construction -- so this is the normal of
+    the RENDERED surface, from finite differences of the back-projected points P = depth * ray:
+
+        valid: isfinite(depth) and depth > 0.  A neighbour (i, j +- 1) is usable if it is inside the image, valid and, with
+        `edge` (a relative depth jump, e.g. 0.1, that cuts the stencil at occlusion boundaries), |depth_nb - depth| <= edge * depth.
+        D_x = P(j+1) - P(j-1) if both are usable, the one-sided difference if one is; D_y the same along the rows of the map;
+        n = +-normalise(D_x x D_y), the sign that faces the camera (n . ray <= 0); (0, 0, 0) where the pixel is not valid, a
+        difference does not exist or the cross product vanishes.
+
+    Aggregation.depth_normals spells the rules out and IS the definition.  The gradient reaches `depth` -- and through get_depth's
+    backward the Gaussians -- through P, the cross product and the normalisation; the choice of stencil, the edge test and the
+    sign are constants; a pixel without a normal passes no gradient on and a depth that is not valid gets exactly zero, NaN or
+    inf in it reaching nothing.  view_space=True returns n_world @ R (row vectors, X_view = X_world @ R + T).
+
+    fp32 floor: the differences cancel, so whatever rounding the depth values carry is amplified by depth / pixel footprint.  The
+    plain fp32 definition is off from fp64, on the same depth values, by about 2^-23 * depth / footprint: 2e-6 to 5e-6 at focal
+    lengths of 30 to 60 pixels, 3.3e-5 at 500, 1.2e-4 at 2000 and distance 6 (the bunny's camera).  The kernels difference the depth
+    and the ray separately and add no such error of their own (a few 1e-7 against fp64 at any focal length), but they cannot take
+    back the rounding an fp32 depth map ARRIVES with -- 2^-24 relative from get_depth, amplified the same way: at focal length 2000
+    a normal from an fp32 depth map is good to about 1e-4, whoever computes it.
+
+    cameras_or_rays is a cameras object (R, focal_length, principal_point; T is not needed) or a [B,h,W,3] tensor of unit rays:
+      * cameras with fp32 tensors on the depth's HIP device, none requiring grad, and an fp32 depth: one HIP launch each way
+        (ops._DepthNormals: the kernels make the rays themselves, the backward is a gather without atomics -- the same bits on
+        every run -- and nothing but the outputs is allocated, so the step still captures into a HIP graph).  rows=(r0, r1) has the
+        meaning of the renderer's rows=: the map holds image rows r0 .. r1-1, and r1 - r0 must be h.
+      * a camera that wants a gradient, or a depth of another dtype or device: cameras.pixel_rays(...) + the torch definition --
+        the same values, and autograd reaches the camera.
+      * a tensor of rays: the torch definition directly, on any device; world space only (view_space=True raises).
+    A distributed.Stripes band raises: stacked stripe rows are not image neighbours -- gather the depth (gather_stripes) first."""
+    if hasattr(rows, "stripe_h"):
+        raise ValueError("get_normals: the rows of a distributed.Stripes band are not image neighbours -- gather the depth map "
+                         "(distributed.gather_stripes) and take the normals of the whole frame")
+    if not torch.is_tensor(depth) or depth.dim() not in (2, 3):
+        raise ValueError("get_normals: depth[B,h,W] or [h,W] expected, got " + (str(tuple(depth.shape)) if torch.is_tensor(depth) else repr(depth)))
+    if edge is not None and not 0.0 <= float(edge) < math.inf:
+        raise ValueError(f"get_normals: edge must be None or a finite relative depth jump >= 0, got {edge!r}")
+    single = depth.dim() == 2
+    d = depth[None] if single else depth
+    B, h, W = d.shape
+    if torch.is_tensor(cameras_or_rays):
+        rays = cameras_or_rays
+        if view_space:
+            raise ValueError("get_normals: view_space=True needs the cameras (a tensor of rays carries no rotation)")
+        if rows is not None:
+            raise ValueError("get_normals: rows= goes with a cameras object; a tensor of rays already is the band's")
+        if single and rays.dim() == 3:
+            rays = rays[None]
+        if tuple(rays.shape) != (B, h, W, 3):
+            raise ValueError(f"get_normals: rays {tuple(cameras_or_rays.shape)} do not match depth {tuple(depth.shape)}")
+        out = depth_normals(d, rays, edge)
+        return out[0] if single else out
+    cameras = cameras_or_rays
+    r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+    if r0 < 0 or r1 - r0 != h:
+        raise ValueError(f"get_normals: rows=({r0}, {r1}) do not describe the {h} rows of depth {tuple(depth.shape)}")
+    views = max(cameras.R.reshape(-1, 3, 3).shape[0], 1)
+    if views not in (1, B):
+        raise ValueError(f"get_normals: {views} cameras for depth {tuple(depth.shape)}")
+    ct = camera_tensors(cameras, (r1, W), (r0, r1))
+    if ct is not None and d.is_cuda and d.dtype == torch.float32 and ct[0].device == d.device:
+        R, _, focal, pp = ct[:4]
+        if R.shape[0] != B:
+            R, focal, pp = R.expand(B, 3, 3), focal.expand(B, 2), pp.expand(B, 2)
+        out = ops.depth_normals(d, R, focal, pp, r0, edge, view_space)
+        return out[0] if single else out
+    rays = pixel_rays(cameras, (r1, W), rows=(r0, r1))[0]
+    if rays.shape[0] != B:
+        rays = rays.expand(B, h, W, 3)
+    out = depth_normals(d, rays.to(device=d.device, dtype=d.dtype), edge)
+    if view_space:
+        R = cameras.R.reshape(-1, 3, 3).to(device=d.device, dtype=d.dtype)
+        out = torch.einsum("bhwi,bij->bhwj", out, R.expand(B, 3, 3))
+    return out[0] if single else out
 
 
 def sh_to_colors(sh: torch.Tensor, verts: torch.Tensor, cameras_or_centres, degree: Union[None, int] = None, clamp: bool = True):

@@ -1790,6 +1790,48 @@ class _ShColors(torch.autograd.Function):
         return g_sh, g_verts, None, None, None
 
 
+class _DepthNormals(torch.autograd.Function):
+    """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
+    row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
+    image rows row0 .. row0+h-1 (times R when view_space).  The kernels make the rays from the camera; one launch each way on the
+    current stream and no allocation but the outputs.  The backward recomputes every stencil from the saved INPUTS (the forward
+    saves nothing of its own) as a gather: every element of g_depth is written, no zero fill, no atomics, the same bits on every
+    run.  The camera gets no gradient here -- Renderer.get_normals sends a camera that wants one to the torch definition."""
+
+    @staticmethod
+    def forward(ctx, depth, R, focal, pp, row0, edge, view_space):
+        depth = _dev(depth, torch.float32, "depth")
+        R, focal, pp = _dev(R, torch.float32, "R"), _dev(focal, torch.float32, "focal_length"), _dev(pp, torch.float32, "principal_point")
+        lib = _lib.load()
+        if depth.dim() != 3 or R.shape != (depth.shape[0], 3, 3) or focal.shape != (depth.shape[0], 2) or pp.shape != focal.shape:
+            raise ValueError(f"depth_normals: depth {tuple(depth.shape)}, R {tuple(R.shape)}, focal_length {tuple(focal.shape)} and "
+                             f"principal_point {tuple(pp.shape)} do not describe the same views")
+        B, h, W = depth.shape
+        edge = -1.0 if edge is None else float(edge)
+        out = torch.empty((B, h, W, 3), dtype=torch.float32, device=depth.device)
+        with _on(depth.device):
+            rc = lib.voge_depth_normals_fwd(_p(depth), _p(R), _p(focal), _p(pp), B, int(row0), h, W, edge, int(bool(view_space)), _p(out),
+                                            _stream())
+        _lib.check(rc, "voge_depth_normals_fwd")
+        ctx.save_for_backward(depth, R, focal, pp)
+        ctx.args = (int(row0), edge, int(bool(view_space)))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_normals):
+        lib = _lib.load()
+        depth, R, focal, pp = ctx.saved_tensors
+        B, h, W = depth.shape
+        row0, edge, view_space = ctx.args
+        gn = _dev(g_normals, torch.float32, "grad_normals")
+        g_depth = (torch.zeros_like if depth.numel() == 0 else torch.empty_like)(depth)      # (nothing is launched for an empty map)
+        with _on(depth.device):
+            rc = lib.voge_depth_normals_bwd(_p(depth), _p(R), _p(focal), _p(pp), _p(gn), B, row0, h, W, edge, view_space, _p(g_depth),
+                                            _stream())
+        _lib.check(rc, "voge_depth_normals_bwd")
+        return g_depth, None, None, None, None, None, None
+
+
 class _PixelRays(torch.autograd.Function):
     """Ray bundle of VoGE/Renderer.py:124-130: (R [B,3,3], T [B,3], focal [B,2], pp [B,2]) ->
     unit world-space directions [B,h,W,3] of image rows row0..row0+h-1 and the camera centres [B,3]."""
@@ -2023,3 +2065,7 @@ def depth(weight, hit_length, valid_num, normalize=True, background=0.0):
 
 def sh_colors(sh, verts, centres, degree, clamp=True):
     return _ShColors.apply(sh, verts, centres, degree, clamp)
+
+
+def depth_normals(depth, R, focal, pp, row0=0, edge=None, view_space=False):
+    return _DepthNormals.apply(depth, R, focal, pp, row0, edge, view_space)
