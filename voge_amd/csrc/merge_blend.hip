@@ -65,7 +65,9 @@ shade_fwd_kernel(const float *__restrict__ attr, int32_t *__restrict__ idx, cons
   const long base = pix0 * K;
   for (int c0 = 0; c0 < max(C, 1); c0 += 4) {
     const int nc = max(0, min(4, C - c0));
-    if (lane < kRun * 5) (&L.acc[0][0])[lane] = 0.0f;
+    // (the weight sum, column 4, is formed in the first pass only and read by the finalise step of every pass: later passes
+    //  clear the four channel columns alone)
+    if (lane < kRun * 5 && (c0 == 0 || lane % 5 != 4)) (&L.acc[0][0])[lane] = 0.0f;
     for (int it0 = 0; it0 < nit; it0 += kShadeU) {
       float w[kShadeU];
       int p[kShadeU], lx[kShadeU];
