@@ -595,6 +595,35 @@ int voge_depth_bwd(const float *weight, const float *len, const int64_t *valid_n
                    float *g_len, voge_stream_t stream);
 
 /*
+ * Depth-distortion regulariser of composited fragments (EXTENSION: the reference has none; the term of Mip-NeRF 360 and 2D
+ * Gaussian splatting that pulls a ray's mass onto one surface).  weight, len [npix][K], valid_num [npix] (int64); over the
+ * n = min(max(valid_num, 0), K) live slots of a pixel, with w = weight and t = len (the distance along the UNIT ray: no
+ * near / far mapping),
+ *   L = sum_i sum_j w_i w_j |t_i - t_j|;   dist [npix] = L (normalize == 0), or L / S^2 where S > 0 and 0 elsewhere
+ *   (normalize != 0: the distortion of the weights rescaled to sum to 1);   wsum [npix] = S = sum_k w_k.
+ * Slots k >= n never contribute.  Evaluated as a prefix scan: order the live slots by (t_k, k) -- ascending len, exact ties by
+ * slot position --, let u_k = t_k - t_first (t_first the smallest live len: the recentring is part of the numerics, the fp32
+ * closed form on t itself loses 2e-4 at t = 1000) and, over the slots before / after slot i in that order,
+ * W<_i = sum w_j, X<_i = sum w_j u_j, W>_i, X>_i likewise:
+ *   L = 2 sum_i w_i (u_i W<_i - X<_i),   dL/dw_i = 2 [u_i (W<_i - W>_i) - (X<_i - X>_i)],   dL/dt_i = 2 w_i (W<_i - W>_i).
+ * At an exact tie this is the POSITIONAL subgradient -- the earlier slot counts as nearer: tied i before j get -2 w_i w_j and
+ * +2 w_i w_j --, not torch's sign(0) = 0.  Fragments arrive in ascending (len, index) order, so the scan runs in slot order; a
+ * pixel whose live len are not non-decreasing (edited fragments, find_farest_k) is walked pairwise in the same launch, with the
+ * same definition.  The sums use a fixed association: the same bits on every run.
+ * Replaces the torch expression (w[..., :, None] * w[..., None, :] * (t[..., :, None] - t[..., None, :]).abs()).sum((-1, -2))
+ * on the live slots -- a [.., K, K] tensor -- or a sort + cumsum chain of about a dozen launches (Aggregation.distortion).
+ * Backward: with a = g_dist / S^2, b = -2 g_dist dist / S where S > 0 and a = b = 0 elsewhere (normalize; dist and wsum are the
+ * forward's), or a = g_dist, b = 0 (dist / wsum may then be NULL):  g_weight[k] = a dL/dw_k + b,  g_len[k] = a dL/dt_k for
+ * k < n and ZERO in the dead slots: every element is written, no fill, no atomics; the scan is recomputed from weight and len.
+ * Replaces autograd's backward of that expression.  K <= VOGE_MAX_K; npix == 0: success, nothing is launched.
+ */
+int voge_distortion_fwd(const float *weight, const float *len, const int64_t *valid_num, long npix, int K, int normalize,
+                        float *dist, float *wsum, voge_stream_t stream);
+int voge_distortion_bwd(const float *weight, const float *len, const int64_t *valid_num, const float *dist,
+                        const float *wsum, const float *g_dist, long npix, int K, int normalize, float *g_weight,
+                        float *g_len, voge_stream_t stream);
+
+/*
  * View-dependent colours from spherical-harmonic coefficients (EXTENSION: the reference has no spherical-harmonic code).
  * sh [N][M][C] with M in {1, 4, 9, 16} (maximum degree L = sqrt(M) - 1) and C in 1..4; verts [N][3] (shared_verts != 0: one set
  * for every view) or [B][N][3]; centres [B][3], the camera centres.  For view b and Gaussian n, delta = v - c_b and

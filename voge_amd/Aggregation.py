@@ -227,3 +227,48 @@ def depth_normals(depth, rays, edge=None):
     n = c * torch.rsqrt(torch.where(defined, (c * c).sum(-1), torch.ones_like(c2)))[..., None]
     away = (n.detach() * rays.detach()).sum(-1, keepdim=True) > 0
     return torch.where(away, -n, n)
+
+
+def distortion(weight, hit_length, valid_num, normalize=False):
+    """Depth-distortion regulariser [..] of composited fragments (an extension: the reference has none): weight, hit_length
+    [.., K], valid_num [..].  Over the n = min(max(valid_num, 0), K) live slots of a pixel, with w = weight and t = hit_length,
+
+        L = sum_i sum_j w_i w_j |t_i - t_j|
+
+    evaluated WITHOUT a [.., K, K] tensor: a stable sort of the live slots by t puts them in the total order (t_k, k) -- ascending
+    t, exact ties by slot position --, u_k = t_k - t_first recentres them on the smallest live t (L is translation invariant; in
+    fp32 the closed form on t itself loses 2e-4 at t = 1000, on u it holds 2e-7 at any offset) and, with the exclusive prefix
+    sums W<_i = sum_{j before i} w_j and X<_i = sum_{j before i} w_j u_j,
+
+        L = 2 sum_i w_i (u_i W<_i - X<_i).
+
+    Autograd through this form yields dL/dw_i = 2 [u_i (W<_i - W>_i) - (X<_i - X>_i)] and dL/dt_i = 2 w_i (W<_i - W>_i) (W>, X>:
+    the same sums over the slots after i) -- at an exact tie the POSITIONAL subgradient, the earlier slot counting as nearer: tied
+    i before j get -2 w_i w_j and +2 w_i w_j, not the sign(0) = 0 of the pairwise expression.  Dead slots get exactly zero.
+
+    normalize=False: L (0 where nothing is hit).  normalize=True: L / S^2 with S = sum_k w_k where S > 0 -- the distortion of the
+    weights rescaled to sum to 1 --, 0 with zero gradient elsewhere.
+
+    Differentiable torch on any device / dtype, O(K) memory a pixel: the definition the kernels (ops._Distortion,
+    Renderer.get_distortion) are tested against, and the route for everything they do not take."""
+    if hit_length.shape != weight.shape or valid_num.shape != weight.shape[:-1]:
+        raise ValueError(f'weight {tuple(weight.shape)}, hit_length {tuple(hit_length.shape)} and valid_num {tuple(valid_num.shape)} '
+                         'do not describe the same fragments')
+    K = weight.shape[-1]
+    live = torch.arange(K, device=weight.device) < valid_num.clamp(0, K)[..., None]
+    key = torch.where(live, hit_length.detach(), torch.full_like(hit_length, float('inf')))      # (dead slots sort last)
+    order = torch.sort(key, dim=-1, stable=True)[1]
+    w = torch.gather(torch.where(live, weight, torch.zeros_like(weight)), -1, order)
+    t = torch.gather(torch.where(live, hit_length, torch.zeros_like(hit_length)), -1, order)
+    live = torch.gather(live, -1, order)
+    u = torch.where(live, t - t[..., :1].detach(), torch.zeros_like(t))
+    x = w * u
+    zero = torch.zeros_like(w[..., :1])
+    w_before = torch.cat([zero, w[..., :-1]], -1).cumsum(-1)      # (exclusive prefix sums)
+    x_before = torch.cat([zero, x[..., :-1]], -1).cumsum(-1)
+    L = 2 * (w * (u * w_before - x_before)).sum(-1)
+    if not normalize:
+        return L
+    S = w.sum(-1)
+    hit = S > 0
+    return torch.where(hit, L / torch.where(hit, S * S, torch.ones_like(S)), torch.zeros_like(L))

@@ -1,7 +1,7 @@
 """Host-side mirror of VoGE/Renderer.py: GaussianRenderer (:87-150), GaussianRenderSettings
 (:53-84), Fragments (:13-50), interpolate_attr (:153), get_silhouette (:157-159),
 to_colored_background (:162-171), to_white_background (:174-176) -- same names, same argument
-meaning; get_depth, get_normals and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
+meaning; get_depth, get_distortion, get_normals and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
 tensors raises instead of falling back.
 """
 import math
@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .Aggregation import aggregation, depth_normals, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
+from .Aggregation import aggregation, depth_normals, distortion, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
 from . import RayTracing
 from .RayTracing import _view_axis
 from .cameras import camera_tensors, pixel_rays
@@ -387,6 +387,35 @@ def get_depth(fragments: Fragments, normalize: bool = True, background: float = 
             fragments._wsum = (fragments._shaped(out[1]), w, w._version, fragments._shaped(out[4]))
             return fragments._shaped(out[0])
     return ops.depth(fragments.vert_weight, fragments.vert_hit_length, fragments.valid_num, normalize, background)
+
+
+def get_distortion(fragments: Fragments, normalize: bool = False):
+    """Depth-distortion regulariser of the fragments (an extension: the reference has none) -> [..., H, W] fp32, the leading
+    dimensions of vert_index[..., 0]: the term of Mip-NeRF 360 and 2D Gaussian splatting that pulls a ray's mass onto one surface.
+    For a pixel with n = min(max(valid_num, 0), K) live slots, w = vert_weight and t = vert_hit_length,
+
+        L = sum_i sum_j w_i w_j |t_i - t_j|      over the live slots; slots k >= n never contribute, forward or backward.
+
+    normalize=False: L itself (0 where nothing is hit).  sum_k w_k is NOT bounded by 1 here (see get_depth), so L grows with the
+                     square of the mass on the ray.
+    normalize=True:  L / S^2 with S = sum_k w_k where S > 0 -- the distortion of the weights rescaled to sum to 1; elsewhere 0,
+                     with zero gradient.
+
+    It is evaluated as a prefix scan over the slots in the total order (t_k, k) -- ascending hit length, exact ties by slot position
+    -- on u_k = t_k - t_first, the lengths recentred on the nearest live slot (Aggregation.distortion spells it out and IS the
+    definition).  Tie rule: at an exact tie the gradient is the POSITIONAL subgradient, the earlier slot counting as nearer -- for
+    tied i before j, d/dt_i gets -2 w_i w_j and d/dt_j gets +2 w_i w_j --, not torch's sign(0) = 0.  t is the distance along the
+    UNIT pixel ray, as everywhere else here: there is no near / far mapping -- for the loss in [near, far] units multiply the
+    result by 1 / (far - near).  The sums use a fixed association: the same bits on every run.
+
+    fp32 fragments on a HIP device take one streaming launch each way (ops._Distortion), unsorted pixels (edited fragments,
+    find_farest_k) included; on fragments whose composite is still pending, reading the weights runs that composite first and the
+    gradient reaches the Gaussians through its backward.  Anything else -- host tensors, other dtypes -- returns
+    Aggregation.distortion(...): the same values, with autograd's gradients."""
+    w, ln, vn = fragments.vert_weight, fragments.vert_hit_length, fragments.valid_num
+    if w.is_cuda and ln.is_cuda and vn.is_cuda and w.dtype == ln.dtype == torch.float32:
+        return ops.distortion(w, ln, vn, normalize)
+    return distortion(w, ln, vn, normalize)
 
 
 def get_normals(depth: torch.Tensor, cameras_or_rays, rows=None, edge: Union[None, float] = None, view_space: bool = False):

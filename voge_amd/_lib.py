@@ -112,6 +112,8 @@ SIGNATURES = {
     "voge_silhouette_bwd": (_c_int, [_c_void_p] * 2 + [_c_long] + [_c_void_p] * 2),
     "voge_depth_fwd": (_c_int, [_c_void_p] * 3 + [_c_long, _c_int, _c_int, _c_float] + [_c_void_p] * 3),
     "voge_depth_bwd": (_c_int, [_c_void_p] * 6 + [_c_long, _c_int, _c_int] + [_c_void_p] * 3),
+    "voge_distortion_fwd": (_c_int, [_c_void_p] * 3 + [_c_long, _c_int, _c_int] + [_c_void_p] * 3),
+    "voge_distortion_bwd": (_c_int, [_c_void_p] * 6 + [_c_long, _c_int, _c_int] + [_c_void_p] * 3),
     "voge_sh_colors_fwd": (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [_c_void_p] * 2),
     "voge_sh_colors_bwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 7 + [_c_void_p] * 3),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),

@@ -1741,6 +1741,46 @@ class _Depth(torch.autograd.Function):
         return g_w, g_len, None, None, None
 
 
+class _Distortion(torch.autograd.Function):
+    """get_distortion of composited fragments (extension; voge_distortion_fwd / _bwd): forward(weight [.., K], hit_length [.., K],
+    valid_num [..], normalize) -> [..]: sum_i sum_j w_i w_j |t_i - t_j| over the n = min(max(valid_num, 0), K) live slots, or
+    that over (sum_k w_k)^2 (0 where the sum is not positive) -- the values of Aggregation.distortion.  One launch each way on the
+    current stream; the backward recomputes the prefix scan from the saved inputs and writes every element of both gradients,
+    zero in the dead slots (no zero fill, no atomics: the same bits on every run)."""
+
+    @staticmethod
+    def forward(ctx, weight, hit_length, valid_num, normalize):
+        w = _dev(weight, torch.float32, "weight")
+        ln = _dev(hit_length, torch.float32, "vert_hit_length")
+        vn = _dev(valid_num, torch.int64, "valid_num")
+        lib = _lib.load()
+        if ln.shape != w.shape or vn.shape != w.shape[:-1]:
+            raise ValueError(f"get_distortion: weight {tuple(w.shape)}, vert_hit_length {tuple(ln.shape)} and valid_num "
+                             f"{tuple(vn.shape)} do not describe the same fragments")
+        K = w.shape[-1]
+        dist = torch.empty(w.shape[:-1], dtype=torch.float32, device=w.device)
+        wsum = torch.empty_like(dist)
+        with _on(w.device):
+            rc = lib.voge_distortion_fwd(_p(w), _p(ln), _p(vn), w.numel() // max(K, 1), K, int(normalize), _p(dist), _p(wsum), _stream())
+        _lib.check(rc, "voge_distortion_fwd")
+        ctx.save_for_backward(w, ln, vn, dist, wsum)
+        ctx.normalize = bool(normalize)
+        return dist
+
+    @staticmethod
+    def backward(ctx, g_dist):
+        lib = _lib.load()
+        w, ln, vn, dist, wsum = ctx.saved_tensors
+        K = w.shape[-1]
+        gd = _dev(g_dist, torch.float32, "grad_distortion")
+        g_w, g_len = torch.empty_like(w), torch.empty_like(w)
+        with _on(w.device):
+            rc = lib.voge_distortion_bwd(_p(w), _p(ln), _p(vn), _p(dist), _p(wsum), _p(gd), w.numel() // max(K, 1), K,
+                                         int(ctx.normalize), _p(g_w), _p(g_len), _stream())
+        _lib.check(rc, "voge_distortion_bwd")
+        return g_w, g_len, None, None
+
+
 def _aligned16(t_):
     """t_ itself, or a copy whose first element sits on a 16-byte boundary (a slice taken in the middle of a row does not)."""
     return t_ if t_.data_ptr() % 16 == 0 else t_.clone()
@@ -2061,6 +2101,10 @@ def silhouette(weight):
 
 def depth(weight, hit_length, valid_num, normalize=True, background=0.0):
     return _Depth.apply(weight, hit_length, valid_num, bool(normalize), float(background))
+
+
+def distortion(weight, hit_length, valid_num, normalize=False):
+    return _Distortion.apply(weight, hit_length, valid_num, bool(normalize))
 
 
 def sh_colors(sh, verts, centres, degree, clamp=True):
