@@ -1,0 +1,127 @@
+"""The fused backward's accumulation table (voge_common.h: WaveDirTable -- a directory of 256 keys probed by double hashing
+over 96 dense value entries per wave, 512 keys in the kernel of scalar sigmas and three colour channels; fragment_bwd.hip) at the smallest shapes where it can go wrong: a 4x3 group with more
+distinct Gaussians than the table has entries (the straight-to-memory path), keys that all hash to one directory slot, the
+ordinary forms (K = 40, odd K, per-axis and full 3x3 sigmas), and the repeatability of the atomics.  Gradients are compared
+with the fp64 oracle chain at the tolerance the whole-frame tests of test_gpu_configs.py use (1e-4 of max(1, largest entry))."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import camera_np
+import test_gpu_configs as cfg
+from util import log_line
+
+pytestmark = pytest.mark.gpu
+
+ND, NEV, GW, GH = 512, 96, 4, 3      # fragment_bwd.hip: kFbNDFrame (the kernel these scenes run; 256 elsewhere), kFbNEV, kFbGW, kFbGH
+MUL = 2654435761
+
+
+def dir_slot(ids):
+    """the directory slot a Gaussian id starts its probe sequence at (wd_find2: the top 9 bits of id * 2654435761 for 512 keys;
+    ids that share it share the slot of a 256-key directory too)"""
+    return ((np.asarray(ids, np.uint64) * MUL) & 0xFFFFFFFF) >> 23
+
+
+def _radius_to_sigma(r):
+    return (1.0 / (r * r / (2 * np.log(1 / 0.6)))).astype(np.float32)
+
+
+def _scene(verts, sig, cols, H, W, K, focal, dist=3.0):
+    return dict(verts=verts, sigmas=sig, colors=cols, focal=focal, principal=(W / 2.0, H / 2.0), image_size=(H, W), dist=dist,
+                elev=10.0, azim=70.0, K=K)
+
+
+def _group_distinct(idx):
+    """distinct Gaussians of every 4x3 group of an [H, W, K] index array (-1: empty)"""
+    H, W, _ = idx.shape
+    out = []
+    for y0 in range(0, H, GH):
+        for x0 in range(0, W, GW):
+            g = idx[y0:y0 + GH, x0:x0 + GW].ravel()
+            out.append(len(np.unique(g[g >= 0])))
+    return np.array(out)
+
+
+def _grads_vs_oracle(label, sc, seed, min_same=0.9):
+    frag, img, gm, colors, (R, T) = cfg._render(sc)
+    ref = cfg._oracle_frame(sc, R, T)
+    idx = cfg.n(frag.vert_index)
+    same = (idx == np.where(ref["idx"] < 0, 0, ref["idx"])).all(-1) | (idx == ref["idx"]).all(-1)
+    assert same.mean() >= min_same, f"{label}: only {same.mean():.3f} of the pixels have the oracle's index list"
+    # (pixels whose member set differs from the oracle's leave the loss, as in test_gpu_configs.py: what remains is arithmetic)
+    g_img = np.random.default_rng(seed).normal(size=ref["image"].shape) * same[..., None]
+    (img * cfg.t(g_img)).sum().backward()
+    want = cfg._oracle_grads(sc, ref, g_img)
+    out = cfg._check_grads(label, (colors.grad, gm.verts.grad, gm.sigmas.grad), want, mult=1)
+    return ref, out
+
+
+def test_group_with_more_gaussians_than_table_entries(hip_lib):
+    """16 x 12 pixels, K = 128 (the largest list the two-slots-per-lane kernel takes), 4000 Gaussians two to three pixels wide in a
+    cube behind the image: a 4x3 group sees several hundred distinct ids, the table has 96 entries -- the rest goes straight
+    to memory, key by key and whole."""
+    H, W, K, N = 12, 16, 128, 4000
+    rng = np.random.default_rng(11)
+    verts = (rng.uniform(-1, 1, (N, 3)) * 0.8).astype(np.float32)
+    sig = _radius_to_sigma(rng.uniform(0.07, 0.11, N))
+    cols = rng.uniform(0, 1, (N, 3)).astype(np.float32)
+    sc = _scene(verts, sig, cols, H, W, K, focal=40.0, dist=4.0)
+    ref, _ = _grads_vs_oracle("table over capacity 16x12 K=128", sc, seed=1)
+    distinct = _group_distinct(ref["idx"][0])
+    log_line(f"[table] over capacity: distinct Gaussians per 4x3 group min {distinct.min()} max {distinct.max()} ({NEV} entries); "
+             f"hits per pixel max {(ref['idx'][0] >= 0).sum(-1).max()}")
+    assert distinct.max() > NEV, "no group exceeds the table's entries: the scene does not test the straight-to-memory path"
+    assert (ref["idx"][0] >= 0).sum(-1).max() > 64      # lists beyond one wave's 64 slots per pixel
+
+
+def test_keys_that_share_one_directory_slot(hip_lib):
+    """32 x 24, K = 40, 144 000 Gaussians of which only those whose id hashes to ONE directory slot stand in front of the camera
+    (about 280; the others lie far off to the side): every look-up of the frame starts at the same slot and walks its
+    double-hash sequence."""
+    H, W, K, N = 24, 32, 40, 144000
+    rng = np.random.default_rng(12)
+    ids = np.arange(N)
+    chosen = ids[dir_slot(ids) == 75]
+    assert 200 < len(chosen) < 400
+    verts = (rng.uniform(-1, 1, (N, 3)) * 0.5 + np.array([0.0, 60.0, 0.0])).astype(np.float32)      # out of view
+    verts[chosen] = rng.uniform(-0.6, 0.6, (len(chosen), 3)).astype(np.float32)
+    sig = _radius_to_sigma(rng.uniform(0.08, 0.16, N))
+    cols = rng.uniform(0, 1, (N, 3)).astype(np.float32)
+    sc = _scene(verts, sig, cols, H, W, K, focal=35.0)
+    ref, _ = _grads_vs_oracle("table colliding keys 32x24 K=40", sc, seed=2)
+    seen = np.unique(ref["idx"][ref["idx"] >= 0])
+    assert len(seen) > 100 and (dir_slot(seen) == 75).all(), "the frame must see the chosen Gaussians and only them"
+    distinct = _group_distinct(ref["idx"][0])
+    log_line(f"[table] colliding keys: {len(seen)} Gaussians in view, all in directory slot 75; distinct per group max {distinct.max()}")
+    assert distinct.max() > 16      # (more keys in one group than the probe limit: sequences must part after the first slot)
+
+
+@pytest.mark.parametrize("K,form", [(40, "scalar"), (25, "scalar"), (40, "diag"), (40, "full")])
+def test_ordinary_scenes(hip_lib, K, form):
+    """64 x 48, 3000 Gaussians: K = 40, K = 25 (odd: the slot-by-slot loads), (N,3) per-axis and [N,3,3] sigmas."""
+    from voge_amd import scenes
+    H, W, N = 48, 64, 3000
+    verts, sig, cols = scenes.random_gaussians(N, seed=5, anisotropic={"scalar": False, "diag": "diag", "full": True}[form],
+                                               r_lo=0.04, r_hi=0.11)
+    sc = _scene(verts, sig, cols, H, W, K, focal=70.0)
+    ref, _ = _grads_vs_oracle(f"table ordinary 64x48 K={K} {form}", sc, seed=3)
+    assert (ref["idx"] >= 0).sum(-1).max() == K and _group_distinct(ref["idx"][0]).max() > 20
+
+
+def test_two_backwards_agree_within_the_atomics_noise(hip_lib):
+    """The table's sums per Gaussian and wave are bit-identical from run to run; only the order of the waves' global atomics
+    differs.  bench.py bounds that at 1e-4 of the largest entry (measured 2e-6)."""
+    from voge_amd import scenes
+    verts, sig, cols = scenes.random_gaussians(3000, seed=5, r_lo=0.04, r_hi=0.11)
+    sc = _scene(verts, sig, cols, 48, 64, 40, focal=70.0)
+    g_img = np.random.default_rng(4).normal(size=(1, 48, 64, 3))
+    runs = []
+    for _ in range(2):
+        frag, img, gm, colors, _ = cfg._render(sc)
+        (img * cfg.t(g_img)).sum().backward()
+        runs.append([cfg.n(x).astype(np.float64) for x in (colors.grad, gm.verts.grad, gm.sigmas.grad)])
+    for name, a, b in zip(("colors", "verts", "sigmas"), *runs):
+        d = np.abs(a - b).max() / np.abs(a).max()
+        log_line(f"[table] repeatability {name}: {d:.2e} of the largest entry (bound 1e-4)")
+        assert np.abs(a).max() > 0 and d <= 1e-4

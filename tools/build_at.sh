@@ -9,6 +9,6 @@ rm -rf "$SRC"; mkdir -p "$SRC" "$ROOT/build/variants"
 git -C "$ROOT" archive "$C" voge_amd/csrc include | tar -x -C "$SRC"
 cd "$SRC/voge_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wno-unused-function \
-  -I"$SRC/include" -I. "$@" -shared -o "$ROOT/build/variants/$NAME.so" trace_fwd.hip trace_bwd.hip composite.hip merge_blend.hip rays.hip extras.hip fragment_bwd.hip
+  -I"$SRC/include" -I. "$@" -shared -o "$ROOT/build/variants/$NAME.so" *.hip
 rm -rf "$SRC"
 ls -la "$ROOT/build/variants/$NAME.so"

@@ -25,7 +25,24 @@ namespace voge {
 #ifndef VOGE_FB_NE
 #define VOGE_FB_NE 128
 #endif
-constexpr int kFbNE = VOGE_FB_NE;  // table entries per wave
+constexpr int kFbNE = VOGE_FB_NE;  // table entries per wave (four slots per lane: WaveTable, one array of keys and values)
+// Two slots per lane: WaveDirTable (voge_common.h) -- a directory of kFbND keys probed by double hashing over kFbNEV dense value
+// entries.  A 4x3 group holds 45 distinct Gaussians on average and 81 at most at cfg3, 71 at most at cfg4 (the whole frames:
+// tools/table_probe_sim.py --gpu, profiles/r13_fb_table.txt); a group with more takes the straight-to-memory path for the
+// keys that come late.  96 entries + 256 keys keep every instantiation's LDS at or under what the 128-slot table took (as many
+// workgroups per CU by LDS as before, or more).  The frame's own kernel -- scalar sigmas, three colour channels through the
+// shade stage -- takes 512 keys: 1.5-2 us faster at cfg3 (2.0 loop iterations per round instead of 2.5), 9552 bytes, 17
+// workgroups per CU by LDS where its registers allow 16.
+#ifndef VOGE_FB_ND
+#define VOGE_FB_ND 256
+#endif
+#ifndef VOGE_FB_ND_FRAME
+#define VOGE_FB_ND_FRAME 512
+#endif
+#ifndef VOGE_FB_NEV
+#define VOGE_FB_NEV 96
+#endif
+constexpr int kFbND = VOGE_FB_ND, kFbNDFrame = VOGE_FB_ND_FRAME, kFbNEV = VOGE_FB_NEV;
 // A wave's group of pixels: GW x GH (<= 64 pixels; lane g of the wave holds pixel (g % GW, g / GW)'s hit count).  The
 // lanes are handed out by those counts (composite_core.h, "Lane packing by hit count"): ceil(count / 2) lanes per
 // pixel, as many consecutive pixels per round as fit the wave.
@@ -53,16 +70,15 @@ __device__ unsigned long long g_fb_wall[kFbTimesWaves][2];       // its first an
 #define FB_TOUT() do {} while (0)
 #endif
 
-template <int NV4, int NS>
+template <int NV4, int NS, int ND>
 struct FragBwdLds {
   // key = Gaussian index; values: (g_mu, g_a), (w g_rgb, -) for A = a I [NV4 = 2];
   //                               (g_mu, g_A[0]), g_A[1..4], g_A[5..8], (w g_rgb, -) for a full 3x3 A [NV4 = 4];
   //                               without the colour term (SRC = 1): NV4 = 1 | 3
   static constexpr int kRows = NS * 64 + 4 * kFbG;      // a round's padded rows: 64 lanes' slots + two sentinel pairs per pixel
-  WaveTable<kFbNE, NV4> tab;
+  std::conditional_t<NS == 2, WaveDirTable<ND, kFbNEV, NV4>, WaveTable<kFbNE, NV4>> tab;
   float len[kRows], sp[kRows], E[kRows], u[kRows];
   float r[kRows];                 // row sums of the composite backward, accumulated by the column walks (compn_bwd_wave)
-  unsigned spare[kFbG];           // (not read: it held the round's window radii; kept, so the LDS size and occupancy stay as measured)
 };
 
 #ifndef VOGE_FB_ABL
@@ -114,7 +130,8 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
   // less, and the kernel went from 107 to 137 us.  An entry's eight sums are ONE 32-byte atomic request here and three requests
   // into three arrays there; the kernel's tail is bound by those requests.  acc stays; the forward zeroes it on its way.)
   auto sum_add = [&](const int key, const int c, const float v) { unsafeAtomicAdd(acc + NACC * (size_t)key + c, v); };
-  __shared__ __attribute__((aligned(16))) FragBwdLds<NV4, NS> L;
+  constexpr int ND = (SRC == 0 && ISO && C == 3) ? kFbNDFrame : kFbND;      // directory keys (NS == 2)
+  __shared__ __attribute__((aligned(16))) FragBwdLds<NV4, NS, ND> L;
   float *const Llen = L.len, *const Lsp = L.sp, *const LE = L.E, *const Lu = L.u, *const LR = L.r;
   const int lane = threadIdx.x;
   FB_T0();
@@ -131,7 +148,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
   const int need = (lead_g + NS - 1) / NS;
   const int incl = wave_incl_scan(need, lane);
   if (__builtin_amdgcn_readlane(incl, 63) == 0) return;     // nothing was hit in these pixels
-  wt_clear(L.tab, lane);
+  if constexpr (NS == 2) wd_clear(L.tab, lane); else wt_clear(L.tab, lane);
   int pc = 0, off = 0;
   while (pc < kFbG) {
     PackLane pk;
@@ -389,7 +406,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
     }
     const float dn2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
     const float idn = __builtin_amdgcn_rcpf(dn2);
-    // (two slots per lane: both slots' terms first, then ONE table pass for both -- wt_find2, wt_add2_by_group)
+    // (two slots per lane: both slots' terms first, then ONE table pass for both -- wd_find2, wt_add2_by_group)
     constexpr bool PAIR = NS == 2;
     float4 valp[PAIR ? 2 : 1][NV4];
     bool gop[2] = {false, false};
@@ -484,6 +501,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
         gop[a] = go;
         continue;
       }
+      if constexpr (!PAIR) {
       if (!__any(go)) continue;     // uniform
       FB_TICK(3);
 #if VOGE_FB_ABL & 1       // (timing experiment: no table, nothing accumulated)
@@ -517,11 +535,15 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
         }
       }
       FB_TICK(4);
+      }
     }
-    if (PAIR && __any(gop[0] | gop[1])) {
+    if constexpr (PAIR) if (__any(gop[0] | gop[1])) {
       FB_TICK(3);
+#if VOGE_FB_ABL & 1       // (timing experiment: no table, nothing accumulated)
+      if (gop[0] && gop[1] && valp[0][0].x == 1.2345f && valp[PAIR ? 1 : 0][NV4 - 1].y == 3.21f) acc[id[0]] = valp[0][NV4 - 1].w + valp[PAIR ? 1 : 0][0].x;
+#else
       int slot0, slot1;
-      wt_find2(L.tab, id[0], gop[0], id[NS - 1], gop[1], slot0, slot1);
+      wd_find2(L.tab, id[0], gop[0], id[NS - 1], gop[1], lane, slot0, slot1);
       wt_add2_by_group(L.tab, slot0, valp[0], gop[0] && slot0 >= 0, slot1, valp[PAIR ? 1 : 0], gop[1] && slot1 >= 0, pk.ord);
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
@@ -535,6 +557,7 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
           }
         }
       }
+#endif
       FB_TICK(4);
     }
   }
@@ -543,11 +566,16 @@ fragment_bwd_kernel(const float4 *__restrict__ rec, const float *__restrict__ ra
     constexpr int EPI = 64 / NACC;      // entries per iteration (12 sums: five entries, four idle lanes)
     const int e = lane / NACC, c = lane - e * NACC;
     const float *vals = reinterpret_cast<const float *>(L.tab.vals);
-    const int n = wt_compact(L.tab, lane);
-    const lds_vint *list = lds_volatile(L.tab.owner);
-    for (int i = e; i < n && e < EPI; i += EPI) {
-      const int s = list[i];
-      sum_add(L.tab.keys[s], c, vals[s * NACC + c]);
+    if constexpr (NS == 2) {      // the entries are dense: 0 .. n - 1, each with its key
+      const int n = wd_count(L.tab);
+      for (int i = e; i < n && e < EPI; i += EPI) sum_add(L.tab.ekey[i], c, vals[i * NACC + c]);
+    } else {
+      const int n = wt_compact(L.tab, lane);
+      const lds_vint *list = lds_volatile(L.tab.owner);
+      for (int i = e; i < n && e < EPI; i += EPI) {
+        const int s = list[i];
+        sum_add(L.tab.keys[s], c, vals[s * NACC + c]);
+      }
     }
   }
   FB_TICK(5);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "voge_hip.h"
 
@@ -959,29 +960,6 @@ __device__ __forceinline__ int wt_find(WaveTable<NE, NV4> &t, const int key, con
   return slot;
 }
 
-// The same for TWO keys per lane in one probing loop: both compare-and-swaps of a step are in flight together, and the loop
-// lasts as long as the longer of a lane's two probe sequences instead of their sum.  Must be called by the whole wave.
-template <int NE, int NV4>
-__device__ __forceinline__ void wt_find2(WaveTable<NE, NV4> &t, const int key0, const bool want0, const int key1, const bool want1,
-                                         int &slot0, int &slot1) {
-  unsigned h0 = ((unsigned)key0 * 2654435761u) >> (32 - __builtin_ctz(NE));
-  unsigned h1 = ((unsigned)key1 * 2654435761u) >> (32 - __builtin_ctz(NE));
-  slot0 = slot1 = -1;
-  bool p0 = want0, p1 = want1;
-#pragma unroll 1
-  for (int pr = 0; pr < kWtProbe && __any(p0 | p1); ++pr) {
-    int old0 = -2, old1 = -2;
-    if (p0) old0 = atomicCAS(&t.keys[h0], -1, key0);
-    if (p1) old1 = atomicCAS(&t.keys[h1], -1, key1);
-    if (p0) {
-      if (old0 == -1 || old0 == key0) { slot0 = (int)h0; p0 = false; } else h0 = (h0 + 1) & (NE - 1);
-    }
-    if (p1) {
-      if (old1 == -1 || old1 == key1) { slot1 = (int)h1; p1 = false; } else h1 = (h1 + 1) & (NE - 1);
-    }
-  }
-}
-
 // vals[slot] += v for every lane with `on` (slot >= 0).  Must be called by the whole wave.
 template <int NE, int NV4>
 __device__ __forceinline__ void wt_add(WaveTable<NE, NV4> &t, const int slot, const float4 (&v)[NV4],
@@ -1009,35 +987,120 @@ __device__ __forceinline__ void wt_add(WaveTable<NE, NV4> &t, const int slot, co
 // one after the other -- `ord` = the lane's pixel ordinal in the round, 0 .. n - 1 -- and inside a step every lane reads,
 // adds and writes its two entries with no owner word written, read back and compared.  The fused backward's rounds hold 3-4
 // pixels and its elections took 3.4 rounds: as many steps, each a third cheaper.  Must be called by the whole wave.
-template <int NE, int NV4>
-__device__ __forceinline__ void wt_add2_by_group(WaveTable<NE, NV4> &t, const int slot0, const float4 (&v0)[NV4], const bool on0,
+// (Tab: a WaveTable or a WaveDirTable below -- only its vals are touched; slot = the entry's index in vals.)
+template <class Tab, int NV4>
+__device__ __forceinline__ void wt_add2_by_group(Tab &t, const int slot0, const float4 (&v0)[NV4], const bool on0,
                                                  const int slot1, const float4 (&v1)[NV4], const bool on1, const int ord) {
   bool pend = on0 | on1;
+  // (a lane's two entries are different ones -- two Gaussians of one pixel -- so both are read before either is written: one LDS
+  //  round trip per step, not two.  An entry that is off reads entry 0 and writes nothing.)
+  float4 *const d0 = t.vals + (on0 ? slot0 : 0) * NV4, *const d1 = t.vals + (on1 ? slot1 : 0) * NV4;
 #pragma unroll 1
   for (int g = 0; __any(pend); ++g) {
     if (pend && ord == g) {
-      if (on0) {
-        float4 *dst = t.vals + slot0 * NV4;
+      float4 x0[NV4], x1[NV4];
 #pragma unroll
-        for (int q = 0; q < NV4; ++q) {
-          float4 x = dst[q];
-          x.x += v0[q].x; x.y += v0[q].y; x.z += v0[q].z; x.w += v0[q].w;
-          dst[q] = x;
-        }
+      for (int q = 0; q < NV4; ++q) { x0[q] = d0[q]; x1[q] = d1[q]; }
+#pragma unroll
+      for (int q = 0; q < NV4; ++q) {
+        x0[q].x += v0[q].x; x0[q].y += v0[q].y; x0[q].z += v0[q].z; x0[q].w += v0[q].w;
+        x1[q].x += v1[q].x; x1[q].y += v1[q].y; x1[q].z += v1[q].z; x1[q].w += v1[q].w;
+      }
+      if (on0) {
+#pragma unroll
+        for (int q = 0; q < NV4; ++q) d0[q] = x0[q];
       }
       if (on1) {
-        float4 *dst = t.vals + slot1 * NV4;
 #pragma unroll
-        for (int q = 0; q < NV4; ++q) {
-          float4 x = dst[q];
-          x.x += v1[q].x; x.y += v1[q].y; x.z += v1[q].z; x.w += v1[q].w;
-          dst[q] = x;
-        }
+        for (int q = 0; q < NV4; ++q) d1[q] = x1[q];
       }
       pend = false;
     }
     wave_lds_sync();      // (the next pixel's reads come after this pixel's writes in the wave's LDS queue)
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// The same table with the key DIRECTORY apart from the VALUES: ND directory slots (a power of two) over NE entries, so the
+// directory's load factor is chosen for the probing loop (short sequences) and the entry count for the LDS the values take.
+//   * a key claims a directory slot with the LDS compare-and-swap of wt_find, probing by DOUBLE HASHING: the step is odd and
+//     comes from other bits of the same product, so a sequence visits every slot and two keys that meet in one slot part at
+//     the next (linear probing over 128 slots: 5.0 loop iterations per round of the fused backward at cfg3; this over 256:
+//     2.6 -- tools/table_probe_sim.py);
+//   * entries are handed out densely: the lanes that claimed a slot in this call take n, n + 1, ... by a ballot prefix over
+//     the table's count n, write the index beside the slot (a byte) and the key beside the entry; after one
+//     wave_lds_sync every lane reads the indices of its two keys in one round trip;
+//   * the flush walks entries 0 .. min(n, NE) - 1 (ekey, vals): no owner array, no compaction pass;
+//   * a key that comes when the NE entries are used up keeps its directory slot with index kWdNone, and a key whose probes
+//     run out gets none: either way the caller adds that key's sums straight to memory, whole, now and in later rounds.
+// ------------------------------------------------------------------------------------------
+constexpr unsigned kWdNone = 0xFFu;
+template <int ND, int NE, int NV4>
+struct WaveDirTable {
+  static_assert((ND & (ND - 1)) == 0 && ND >= 4 && ND <= 65536 && NE < (int)kWdNone, "directory: a power of two; entry indices are bytes");
+  float4 vals[NE * NV4];
+  int keys[ND];               // directory: the slot's key, -1 = free
+  int ekey[NE];               // entry -> key
+  unsigned char eidx[ND];     // directory slot -> entry (written by the claiming lane before anyone reads it: never cleared)
+  int n;                      // entries handed out so far (it may pass NE).  In LDS, not in a scalar register that would be live
+                              // across the caller's whole round: the fused backward has none to spare (tests/test_isa_cpu.py)
+};
+
+template <int ND, int NE, int NV4>
+__device__ __forceinline__ void wd_clear(WaveDirTable<ND, NE, NV4> &t, const int lane) {
+  for (int i = lane; i < ND; i += VOGE_WAVE) t.keys[i] = -1;
+  for (int i = lane; i < NE * NV4; i += VOGE_WAVE) t.vals[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (lane == 0) t.n = 0;
+}
+// entries in use (for the flush; call behind a wave_lds_sync that follows the last wd_find2 -- it ends with one)
+template <int ND, int NE, int NV4>
+__device__ __forceinline__ int wd_count(const WaveDirTable<ND, NE, NV4> &t) { return min(t.n, NE); }
+
+// Entries of TWO keys per lane in one probing loop -- both compare-and-swaps of a step are in flight together, and the loop lasts as
+// long as the longer of a lane's two probe sequences instead of their sum (e0 / e1: index into vals in units of NV4 float4s, or -1: this key goes straight to memory).
+// Must be called by the whole wave, and a wave_lds_sync must lie between wd_clear and the first call.
+template <int ND, int NE, int NV4>
+__device__ __forceinline__ void wd_find2(WaveDirTable<ND, NE, NV4> &t, const int key0, const bool want0, const int key1, const bool want1,
+                                         const int lane, int &e0, int &e1) {
+  constexpr int B = __builtin_ctz(ND);
+  constexpr unsigned kFound = 1u << 30, kClaimed = 1u << 31;      // flags kept in the slot number's upper bits: no lane mask per flag
+  const unsigned m0 = (unsigned)key0 * 2654435761u, m1 = (unsigned)key1 * 2654435761u;
+  unsigned h0 = m0 >> (32 - B), h1 = m1 >> (32 - B);
+  const unsigned s0 = ((m0 >> (32 - 2 * B)) & (ND - 1)) | 1u, s1 = ((m1 >> (32 - 2 * B)) & (ND - 1)) | 1u;
+  bool p0 = want0, p1 = want1;
+  const int n = t.n;      // (asked for ahead of the loop: it is back by the time the claims are counted)
+#pragma unroll 1
+  for (int pr = 0; pr < kWtProbe && __any(p0 | p1); ++pr) {
+    int old0 = -2, old1 = -2;      // (a lane that is not pending: neither -1 nor its key, keys being >= 0)
+    if (p0) old0 = atomicCAS(&t.keys[h0], -1, key0);
+    if (p1) old1 = atomicCAS(&t.keys[h1], -1, key1);
+    const bool hit0 = old0 == -1 || old0 == key0, hit1 = old1 == -1 || old1 == key1;
+    h0 = hit0 ? (h0 | (old0 == -1 ? (kFound | kClaimed) : kFound)) : (p0 ? ((h0 + s0) & (ND - 1)) : h0);
+    h1 = hit1 ? (h1 | (old1 == -1 ? (kFound | kClaimed) : kFound)) : (p1 ? ((h1 + s1) & (ND - 1)) : h1);
+    p0 = p0 && !hit0;
+    p1 = p1 && !hit1;
+  }
+  const bool c0 = (h0 & kClaimed) != 0, c1 = (h1 & kClaimed) != 0, f0 = (h0 & kFound) != 0, f1 = (h1 & kFound) != 0;
+  h0 &= ND - 1; h1 &= ND - 1;
+  const unsigned long long b0 = __ballot(c0), b1 = __ballot(c1);
+  if (b0 | b1) {      // (uniform) new keys: dense indices by a ballot prefix, published beside the slots
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int n0 = __popcll(b0);
+    const int i0 = n + __popcll(b0 & below), i1 = n + n0 + __popcll(b1 & below);
+    if (c0) {
+      t.eidx[h0] = (unsigned char)(i0 < NE ? (unsigned)i0 : kWdNone);
+      if (i0 < NE) t.ekey[i0] = key0;
+    }
+    if (c1) {
+      t.eidx[h1] = (unsigned char)(i1 < NE ? (unsigned)i1 : kWdNone);
+      if (i1 < NE) t.ekey[i1] = key1;
+    }
+    if (lane == 0) t.n = n + n0 + __popcll(b1);
+    wave_lds_sync();
+  }
+  const unsigned x0 = f0 ? (unsigned)t.eidx[h0] : kWdNone, x1 = f1 ? (unsigned)t.eidx[h1] : kWdNone;
+  e0 = x0 == kWdNone ? -1 : (int)x0;
+  e1 = x1 == kWdNone ? -1 : (int)x1;
 }
 
 // Compact the occupied slots into t.owner[0..n) (the election array is free once accumulation
