@@ -21,8 +21,9 @@
 //     h(|x|) = erfc(|x|)/2, and  Phi = 1 - h in front, h behind.  The "1" parts are prefix /
 //     suffix sums, the h parts die out beyond |len_m - len_k| >= 4 / s (h < 8e-9), so every row
 //     walks a WINDOW away from the diagonal and stops.
-//   * h(x) = 2^Q(x'), x' = x sqrt(log2 e), Q a degree-6 polynomial (|err| <= 1.5e-7 absolute on
-//     [0, 5]): one transcendental per evaluation, no reciprocal, no select.
+//   * h(x) = 2^Q(x'), x' = x sqrt(log2 e), Q a degree-5 polynomial (|err| <= 6.0e-7 absolute on
+//     [0, 5], falling to 0 beyond: no range clamp): one transcendental per evaluation, no
+//     reciprocal, no select, no min (composite_core.h).
 //   * Two list entries per trip: (len, s, E) live in separate LDS arrays, ds_read2_b32 returns
 //     neighbours as a register pair and the arithmetic is packed fp32 (v_pk_fma_f32 ...).
 //   * Pads of sentinel entries (E = 0, len = -/+ 3e38) on both sides of every pixel's row: no

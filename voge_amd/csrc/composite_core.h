@@ -26,38 +26,56 @@ constexpr float kRsqrtPi = 0.5641895835477563f;
 #endif
 constexpr float kSat = VOGE_KSAT;                // erfc(3.5)/2 = 3.7e-7, below the fp32 rounding of S ~ O(1..K)
 constexpr float kCs = 1.2011224087864498f;       // sqrt(log2 e): x' = x * kCs, exp(-x^2) = 2^(-x'^2)
-constexpr float kXcap = 5.0f * kCs;              // the fit's range; h(5) = 7.7e-13
 constexpr float kBig = 3.0e38f;
 
 // log2(erfc(x)/2) as a polynomial in x' = x sqrt(log2 e) on [0, 5 sqrt(log2 e)], weighted minimax
-// on the absolute error of 2^Q (tools/fit_erfc.py).  Degree 6: |err| <= 1.5e-7 (the accuracy of
-// Abramowitz-Stegun 7.1.26); degree 8 gives 5.2e-8 and h(0) = 1/2 exactly for two more packed FMAs
-// per pair of entries (tools/fit_erfc.py fits degrees 6 to 8).
-constexpr float kQ0 = -9.999997020e-01f, kQ1 = -1.355341077e+00f, kQ2 = -6.364040971e-01f,
-                kQ3 = -8.642258495e-02f, kQ4 = 1.487037074e-02f, kQ5 = -1.475012978e-03f,
-                kQ6 = 4.851150516e-05f;
+// on the absolute error of 2^Q (tools/fit_erfc.py).  Degree 5: |err| <= 6.0e-7 in the fp32 Horner
+// evaluation (degree 6: 1.5e-7, degree 8: 5.2e-8; DESIGN.md §8 has the table).  The leading coefficient
+// is NEGATIVE, so Q keeps falling past the fitted range: 2^Q is finite and non-increasing for every
+// fp32 x' >= 5 sqrt(log2 e), at most 3.6e-13 there, and exactly 0 at +inf (kQ5 * inf = -inf, and
+// -inf * x' + c stays -inf: no inf - inf can arise for x' >= 0).  So h_pair needs NO clamp of x' --
+// the even degrees' positive leading coefficient made 2^Q diverge out there and cost two v_min_f32
+// and a sixth packed FMA per pair.  Every caller of h_pair passes x' >= 0 and never a NaN: the
+// sorted walks and diagonal blocks by sortedness (a NaN len marks the pixel unsorted), sentinel
+// rows of +/-kBig give a huge finite x' or +inf, dead columns x' = 0 (tests/test_erfc_fit_cpu.py).
+constexpr float kQ0 = -1.000001669e+00f, kQ1 = -1.355278134e+00f, kQ2 = -6.367735267e-01f,
+                kQ3 = -8.563093096e-02f, kQ4 = 1.412141882e-02f, kQ5 = -1.158451778e-03f;
 
 __device__ __forceinline__ v2f pk_fma(const v2f a, const v2f b, const v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f splat(const float x) { return (v2f){x, x}; }
 
-// h(x') = erfc(x'/kCs)/2 for x' >= 0 (capped at kXcap), two at a time
-__device__ __forceinline__ v2f h_pair(v2f xp) {
-  xp.x = fminf(xp.x, kXcap);
-  xp.y = fminf(xp.y, kXcap);
-  v2f q = pk_fma(splat(kQ6), xp, splat(kQ5));
-  q = pk_fma(q, xp, splat(kQ4));
+// h(x') = erfc(x'/kCs)/2 for any x' in [0, +inf], two at a time: five packed FMAs and two exp2
+__device__ __forceinline__ v2f h_pair(const v2f xp) {
+  v2f q = pk_fma(splat(kQ5), xp, splat(kQ4));
   q = pk_fma(q, xp, splat(kQ3));
   q = pk_fma(q, xp, splat(kQ2));
   q = pk_fma(q, xp, splat(kQ1));
   q = pk_fma(q, xp, splat(kQ0));
   return (v2f){__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
 }
+// The cold paths' evaluator (an unsorted list's full K x K scans): one value, and any input at all -- fminf
+// turns a NaN into the cap, so a NaN len gives h(5) = 7.7e-13 as it always has.  These paths are not
+// instruction bound; they keep the clamped degree-6 fit (|err| <= 1.5e-7, positive leading coefficient)
+// they have had since the walks were written, bit for bit.
+constexpr float kC0 = -9.999997020e-01f, kC1 = -1.355341077e+00f, kC2 = -6.364040971e-01f,
+                kC3 = -8.642258495e-02f, kC4 = 1.487037074e-02f, kC5 = -1.475012978e-03f,
+                kC6 = 4.851150516e-05f;
+constexpr float kColdCap = 5.0f * kCs;           // that fit's range
+__device__ __forceinline__ float h_one(const float xp) {
+  const float x = fminf(xp, kColdCap);
+  float q = fmaf(kC6, x, kC5);
+  q = fmaf(q, x, kC4);
+  q = fmaf(q, x, kC3);
+  q = fmaf(q, x, kC2);
+  q = fmaf(q, x, kC1);
+  q = fmaf(q, x, kC0);
+  return __builtin_amdgcn_exp2f(q);
+}
 // 2^(-x'^2) = exp(-x^2), two at a time
 __device__ __forceinline__ v2f gauss_pair(const v2f xp) {
   const v2f q = -(xp * xp);
   return (v2f){__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
 }
-__device__ __forceinline__ float h_one(const float xp) { return h_pair(splat(xp)).x; }
 // entries (e, e+1), e even: one 8-byte LDS read
 __device__ __forceinline__ v2f ld2(const float *a, const int e) { return *reinterpret_cast<const v2f *>(a + e); }
 __device__ __forceinline__ v2f abs2(const v2f v) { return (v2f){fabsf(v.x), fabsf(v.y)}; }
