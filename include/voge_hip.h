@@ -520,6 +520,10 @@ int voge_fragment_bwd(const float *mus, const float *isigmas, const float *rays,
  * cnt: NULL, or [npix] int32 = the trace forward's out_cnt for the same lists (slots k >= cnt are
  * its sentinels): valid_num = cnt, idx may be NULL and is not read, slots beyond cnt are not
  * loaded at all and workgroups whose pixels are all empty only write zeros.
+ * Alignment: with K % 4 == 0 the kernel moves 16 bytes per access and act, len, dsd and weight must start on a 16-byte
+ * boundary; with K % 4 == 2, 8 bytes and an 8-byte boundary; odd K goes slot by slot and takes any float pointer.  A pointer
+ * off its boundary is refused with VOGE_ERR_BAD_ARG before anything is launched (row r of a [rows, K] array keeps the boundary
+ * of row 0).
  */
 int voge_composite_fwd(const int32_t *idx, const int32_t *cnt, const float *act, const float *len,
                        const float *dsd, float occ, long npix, int K, float *weight,
@@ -531,6 +535,9 @@ int voge_composite_fwd(const int32_t *idx, const int32_t *cnt, const float *act,
  * output for the same inputs (saves the backward recomputing it); NULL -> recomputed.
  * cnt (NULL allowed) = the trace forward's out_cnt, as in voge_composite_fwd: slots k >= cnt are
  * the trace's sentinels and are not loaded; workgroups whose pixels are all empty write zeros.
+ * Alignment: with weight given and K even the kernel moves 8 bytes per access: act, len, dsd, weight, g_weight, g_act, g_len
+ * and g_dsd must start on an 8-byte boundary, else VOGE_ERR_BAD_ARG and nothing is launched.  Odd K, and weight == NULL
+ * (one slot per lane), take any float pointer.
  */
 int voge_composite_bwd(const float *act, const float *len, const float *dsd, const float *weight,
                        const int32_t *cnt, const float *g_weight, float occ, long npix, int K, float *g_act,

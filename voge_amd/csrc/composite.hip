@@ -1067,6 +1067,14 @@ static int launch_composite(int mode, const int32_t *idx, const float *act, cons
 #define VOGE_COMP_NS_BWD 2     // the backward is evaluation-bound, not LDS-bound: 4 slots only cost registers
 #endif
     const int NS = ((mode == 0 ? VOGE_COMP_NS : VOGE_COMP_NS_BWD) == 4 && (K & 3) == 0) ? 4 : 2;
+    // whole groups (K % NS == 0): the kernel reads and writes 4 NS bytes at a time, so every array it touches that way has to
+    // start on that boundary (include/voge_hip.h).  The forward from the records (voge_composite_fwd_iso) is fed the fragments'
+    // own tensors, like the other one-pass entries, and is not looked at here.
+    if (K % NS == 0 && rec == nullptr) {
+      const void *const wide[] = {act, len, dsd, w_in, g_weight, o0, o1, o2};
+      for (const void *ptr : wide)
+        if (reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)(4 * NS - 1)) return VOGE_ERR_BAD_ARG;
+    }
     const int LPn = compn_lanes(K, NS);
     // the barrier-free one-wave-per-pixel form wherever a pixel's lanes fit one wave -- measured (cfg3, one-wave workgroups):
     // backward 101 -> 87 us, forward 52 -> 50 us (the forward lost 7 us in this form while it still ran as 256-thread workgroups)

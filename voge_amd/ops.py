@@ -290,10 +290,20 @@ def _trace_bwd(mode, p0, p1, origin, shared, sigma_mode, rays, idx, cnt, g_len, 
     return g0, g1, g_ray
 
 
+def _comp_aligned(t_, K):
+    """t_ itself, or a copy on the boundary of the composite kernels' accesses: 16 bytes for K % 4 == 0, 8 for other even K (a
+    contiguous view into a larger buffer may start anywhere; odd K goes slot by slot).  voge_composite_fwd / _bwd refuse the rest."""
+    if t_ is None or t_.data_ptr() % (16 if K % 4 == 0 else (8 if K % 2 == 0 else 4)) == 0:
+        return t_
+    return t_.clone()
+
+
 def _composite_bwd(act, ln, dsd, weight, cnt, g_weight, occ):
     """voge_composite_bwd: the gradient of the weights -> (g_act, g_len, g_dsd)."""
     K = act.shape[-1]
-    gw = _dev(g_weight, torch.float32, "grad_weight")
+    gw = _comp_aligned(_dev(g_weight, torch.float32, "grad_weight"), K)
+    if weight is not None:      # (recomputed weights: the one-slot kernel, no wide access)
+        act, ln, dsd, weight = (_comp_aligned(x, K) for x in (act, ln, dsd, weight))
     g_act, g_len, g_dsd = torch.empty_like(act), torch.empty_like(act), torch.empty_like(act)
     with _on(act.device):
         rc = _lib.load().voge_composite_bwd(_p(act), _p(ln), _p(dsd), _p(weight), _p(cnt), _p(gw), occ, act.numel() // max(K, 1), K,
@@ -1439,6 +1449,7 @@ class _Composite(torch.autograd.Function):
         dsd = _dev(sel_dsd, torch.float32, "sel_dsd")
         K = idx.shape[-1]
         npix = idx.numel() // max(K, 1)
+        act, ln, dsd = (_comp_aligned(x, K) for x in (act, ln, dsd))
         weight = torch.empty_like(act)
         valid = torch.empty(idx.shape[:-1], dtype=torch.int64, device=idx.device)
         with _on(idx.device):
