@@ -55,7 +55,7 @@ NO_EMPTY_WG = {("bwd_recomputed", 1), ("bwd_recomputed", 2), ("bwd_recomputed", 
 def route(K, which):
     """What launch_composite picks from K alone.  which: fwd | bwd_given | bwd_recomputed | fwd_iso (voge_composite_fwd_iso: the forward's
     choice, from the records) | onepass (composite_shade_fwd_impl, voge_frame_depth_fwd_iso: four slots whatever K is)."""
-    if which == "bwd_recomputed":      # composite_kernel<1>: one slot per lane, 256 threads
+    if which == "bwd_recomputed":      # composite_recompute_bwd_kernel: one slot per lane, 256 threads
         return dict(NS=1, wide=False, wave=False, lanes=K, ppw=256 // K, idle=256 - (256 // K) * K)
     NS = 4 if which == "onepass" or (which in ("fwd", "fwd_iso") and K % 4 == 0) else 2
     lanes = -(-K // NS)

@@ -42,9 +42,7 @@ struct CompLds {
 // dynamic LDS: CompLds, then the padded per-pixel arrays len / sp / E (/ u in the backward),
 // `rows` floats each
 __host__ __device__ inline int comp_rows(const int K) { return ((kCompThreads / K) * comp_row_stride(K) + 3) & ~3; }   // sized for the largest workgroup
-__host__ __device__ inline size_t comp_lds_bytes(const int K, const bool bwd) {
-  return sizeof(CompLds) + sizeof(float) * (size_t)comp_rows(K) * (bwd ? 4 : 3);
-}
+__host__ __device__ inline size_t comp_lds_bytes(const int K) { return sizeof(CompLds) + sizeof(float) * (size_t)comp_rows(K) * 4; }
 
 // (the wave form keeps no per-workgroup state: no CompLds block in front of the arrays)
 __host__ __device__ inline size_t compn_lds_bytes(const int K, const int NS, const bool bwd, const int threads, const bool wave) {
@@ -52,28 +50,22 @@ __host__ __device__ inline size_t compn_lds_bytes(const int K, const int NS, con
   return (wave ? 0 : sizeof(CompLds)) + sizeof(float) * (size_t)compn_rows(K, NS, threads, wave) * (bwd ? 5 : 3) + (wave ? 64 * sizeof(unsigned) : 0);      // (backward: + u, + the row sums of compn_bwd_wave)
 }
 
-
-
-// MODE 0: forward.  1: backward, weights recomputed (S_m again).  2: backward with the forward's
-// weights given: the row pass only needs r_m, i.e. exp(-x^2) but no erfc.
-template <int MODE>
+// The backward with the weights recomputed (S_m again), one slot per lane: voge_composite_bwd without the forward's weights.
+// (The three unnamed arguments are where the removed forward / given-weights modes had idx, w_in and valid_num.  Nothing reads
+// them; they stay because dropping them moves every kernel-argument load, and this kernel's body is held to the parent's.)
 __global__ void __launch_bounds__(kCompThreads)
-composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
-                 const float *__restrict__ len, const float *__restrict__ dsd,
-                 const float *__restrict__ w_in, const float *__restrict__ g_weight, const int32_t *__restrict__ cnt_in,
-                 const float occ, const long npix, const int K,
-                 const int ppw, float *__restrict__ out0 /* weight | g_act */,
-                 float *__restrict__ out1 /* g_len */, float *__restrict__ out2 /* g_dsd */,
-                 int64_t *__restrict__ valid_num) {
-  constexpr bool BWD = MODE != 0;
-  constexpr bool HAVE_W = MODE == 2;
+composite_recompute_bwd_kernel(const int32_t *, const float *__restrict__ act, const float *__restrict__ len,
+                               const float *__restrict__ dsd, const float *, const float *__restrict__ g_weight,
+                               const int32_t *__restrict__ cnt_in, const float occ, const long npix, const int K, const int ppw,
+                               float *__restrict__ out0 /* g_act */, float *__restrict__ out1 /* g_len */,
+                               float *__restrict__ out2 /* g_dsd */, int64_t *) {
   extern __shared__ __attribute__((aligned(16))) unsigned char comp_smem[];
   CompLds &L = *reinterpret_cast<CompLds *>(comp_smem);
   const int rows = comp_rows(K);
   float *const Llen = reinterpret_cast<float *>(comp_smem + sizeof(CompLds));
   float *const Lsp = Llen + rows;
   float *const LE = Lsp + rows;
-  float *const Lu = LE + rows;   // backward only
+  float *const Lu = LE + rows;
   const int tid = threadIdx.x;
   // tid / K without the integer-division sequence (exact for tid < 2^20)
   const int p = __float2int_rz(((float)tid + 0.5f) * __builtin_amdgcn_rcpf((float)K)), k = tid - p * K;
@@ -92,61 +84,40 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
   if (cnt_in != nullptr) {
     lead = active ? min(K, max(0, cnt_in[pix])) : 0;
     if (!__syncthreads_or(lead > 0)) {
-      if (active) {
-        out0[f] = 0.0f;
-        if (BWD) { out1[f] = 0.0f; out2[f] = 0.0f; }
-        else if (k == 0) valid_num[pix] = 0;
-      }
+      if (active) { out0[f] = 0.0f; out1[f] = 0.0f; out2[f] = 0.0f; }
       return;
     }
   }
-  if (tid < ppw) { L.unsorted[tid] = 0; L.rmaxi[tid] = 0; L.cnt[tid] = 0; }
-  float lm = VOGE_SENT_LEN, sm = 1e-5f, em = 0.f, gw = 0.f, wgiven = 0.f;   // what a sentinel slot evaluates to
-  int id = -1;
+  if (tid < ppw) { L.unsorted[tid] = 0; L.rmaxi[tid] = 0; L.cnt[tid] = 0; }      // (cnt: the workgroup form's forward counts there; zeroed here as ever)
+  float lm = VOGE_SENT_LEN, sm = 1e-5f, em = 0.f, gw = 0.f;   // what a sentinel slot evaluates to
   if (active && k < lead) {
     em = FAST_EXP(-act[f]);
     lm = len[f];
     sm = FAST_SQRT(dsd[f] + 1e-10f);
-    if (BWD) gw = g_weight[f]; else if (cnt_in == nullptr) id = idx[f];
-    if (HAVE_W) wgiven = w_in[f];
+    gw = g_weight[f];
   }
-  if (in_wg) {
-    Llen[bi] = lm; Lsp[bi] = sm * kCs; LE[bi] = HAVE_W ? em * (sm * kCs) : em;
-    if (BWD) Lu[bi] = 0.0f;
-  }
+  if (in_wg) { Llen[bi] = lm; Lsp[bi] = sm * kCs; LE[bi] = em; Lu[bi] = 0.0f; }
   // sentinels: one aligned pair in front of the row, one (K odd: three entries) behind it.  Every
   // window loop stops at the first sentinel it meets (len = -/+ 3e38, and the tests are written so
   // that a NaN also stops them), so nothing beyond is ever read.
   if (in_wg && k < 3) {
     const int r0 = p * RS;
     for (int q = k; q < 3; q += K) {     // (K < 3: a thread writes more than one)
-      if (q < PAD) { Llen[r0 + q] = -kBig; Lsp[r0 + q] = 1.0f; LE[r0 + q] = 0.0f; if (BWD) Lu[r0 + q] = 0.0f; }
+      if (q < PAD) { Llen[r0 + q] = -kBig; Lsp[r0 + q] = 1.0f; LE[r0 + q] = 0.0f; Lu[r0 + q] = 0.0f; }
       const int eb = r0 + PAD + K + q;
-      if (eb < r0 + RS) { Llen[eb] = kBig; Lsp[eb] = 1.0f; LE[eb] = 0.0f; if (BWD) Lu[eb] = 0.0f; }
+      if (eb < r0 + RS) { Llen[eb] = kBig; Lsp[eb] = 1.0f; LE[eb] = 0.0f; Lu[eb] = 0.0f; }
     }
   }
   __syncthreads();
   if (active && k > 0 && !(Llen[bi - 1] <= lm)) L.unsorted[p] = 1;
-  // Per-pixel reductions.  The workgroup scan below is LDS-issue bound, so as little as possible
-  // rides on it: the assigned-slot count is a ballot + popcount per wave merged by one LDS atomic
-  // per (wave, pixel) run; the window radius (largest 3.5/s) shares the scan's 64-bit elements
-  // when there is a scan (an 8-byte LDS access costs the same issue slots as a 4-byte one), and is
-  // a segmented wave max + one atomic per run when there is none (backward with given weights).
-  // Max and integer add are order independent: no determinism is lost.
-  const int lane = tid & 63;
-  const bool head = in_wg && (lane == 0 || k == 0);
-  if (!BWD && cnt_in == nullptr) {
-    const unsigned long long m = __ballot(id >= 0);
-    const int lo = max(0, lane - k), hi = min(63, lane + (K - 1 - k));     // this pixel's lanes in the wave
-    const unsigned long long seg = ((hi - lo == 63) ? ~0ull : ((1ull << (hi - lo + 1)) - 1ull) << lo);
-    if (head) atomicAdd(&L.cnt[p], __popcll(m & seg));
-  }
-  float mx = (em != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm) : 0.0f;
+  // The workgroup scan below is LDS-issue bound, so the window radius (largest 3.5/s) shares the
+  // scan's 64-bit elements (an 8-byte LDS access costs the same issue slots as a 4-byte one).
+  const float mx = (em != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm) : 0.0f;
   // Inclusive prefix sum of E within each pixel: ping-pong Hillis-Steele scan over the workgroup.
   // Its association is a function of the slot index only, so a pixel's result does not depend on
   // where it sits in the workgroup (row bands reproduce the whole frame bit for bit).
-  float pre_incl = em;
-  if (!HAVE_W) {
+  float pre_incl;
+  {
     v2f x = {em, mx};
     int par = 0;
     for (int o = 1; o < K; o <<= 1) {
@@ -161,17 +132,9 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
     }
     pre_incl = x.x;
     if (in_wg && k == K - 1) L.rmaxi[p] = __float_as_int(x.y);
-  } else {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {     // lane + o holds slot k + o of the same pixel iff k + o < K
-      const float y = __shfl_down(mx, o, 64);
-      if (lane + o < 64 && k + o < K) mx = fmaxf(mx, y);
-    }
-    if (head) atomicMax(&L.rmaxi[p], __float_as_int(mx));     // mx >= 0: float order == int order
   }
   __syncthreads();
   const float rwin_all = in_wg ? __int_as_float(L.rmaxi[p]) : 0.0f;
-  const int cnt_all = (!BWD && in_wg) ? (cnt_in != nullptr ? (active ? cnt_in[pix] : 0) : L.cnt[p]) : 0;
   const bool sorted = active && (L.unsorted[p] == 0);
   const float rwin = sorted ? rwin_all : 0.0f;   // 0: the windowed loops do nothing
 
@@ -187,28 +150,26 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
     {   // diagonal pair: entry d0 is in front of (or is) this slot; d0+1 is this slot (odd) or behind
       const v2f s2 = ld2(Lsp, d0), E2 = ld2(LE, d0);
       const v2f xp = abs2(lm2 - ld2(Llen, d0)) * s2;
-      if (!HAVE_W) {
-        const v2f eh = E2 * h_pair(xp);
-        accF = (v2f){eh.x, odd ? eh.y : 0.0f};
-        accB = (v2f){0.0f, odd ? 0.0f : eh.y};
-      }
-      if (BWD) accR = (HAVE_W ? E2 : E2 * s2) * gauss_pair(xp);
+      const v2f eh = E2 * h_pair(xp);
+      accF = (v2f){eh.x, odd ? eh.y : 0.0f};
+      accB = (v2f){0.0f, odd ? 0.0f : eh.y};
+      accR = (E2 * s2) * gauss_pair(xp);
     }
     for (int e = d0 - 2;; e -= 2) {      // pairs in front, nearest first
       const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
       const v2f d = lm2 - l2;
       if (!(d.y < rwin)) break;
       const v2f xp = d * s2;
-      if (!HAVE_W) accF = pk_fma(E2, h_pair(xp), accF);
-      if (BWD) accR = pk_fma(HAVE_W ? E2 : E2 * s2, gauss_pair(xp), accR);
+      accF = pk_fma(E2, h_pair(xp), accF);
+      accR = pk_fma(E2 * s2, gauss_pair(xp), accR);
     }
     for (int e = d0 + 2;; e += 2) {      // pairs behind
       const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
       const v2f d = l2 - lm2;
       if (!(d.x < rwin)) break;
       const v2f xp = d * s2;
-      if (!HAVE_W) accB = pk_fma(E2, h_pair(xp), accB);
-      if (BWD) accR = pk_fma(HAVE_W ? E2 : E2 * s2, gauss_pair(xp), accR);
+      accB = pk_fma(E2, h_pair(xp), accB);
+      accR = pk_fma(E2 * s2, gauss_pair(xp), accR);
     }
     sum = (pre_incl - (accF.x + accF.y)) + (accB.x + accB.y);
     rterm = (accR.x + accR.y) * (kRsqrtPi / kCs);
@@ -218,24 +179,13 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
       const float Ej = LE[e];
       if (Ej == 0.0f) continue;
       const float xp = (lm - Llen[e]) * Lsp[e];
-      if (!HAVE_W) {
-        const float h = h_one(fabsf(xp));
-        sum = fmaf(Ej, xp >= 0.0f ? 1.0f - h : h, sum);
-      }
-      if (BWD) {
-        const float xc = fminf(fabsf(xp), 16.0f);
-        rterm = fmaf(HAVE_W ? Ej : Ej * Lsp[e], __builtin_amdgcn_exp2f(-xc * xc) * (kRsqrtPi / kCs), rterm);
-      }
+      const float h = h_one(fabsf(xp));
+      sum = fmaf(Ej, xp >= 0.0f ? 1.0f - h : h, sum);
+      const float xc = fminf(fabsf(xp), 16.0f);
+      rterm = fmaf(Ej * Lsp[e], __builtin_amdgcn_exp2f(-xc * xc) * (kRsqrtPi / kCs), rterm);
     }
   }
-  const float w = HAVE_W ? wgiven : ((em != 0.0f) ? FAST_EXP(-occ * sum) * em * kInvNorm : 0.0f);
-  if (!BWD) {
-    if (active) {
-      out0[f] = w;
-      if (k == 0) valid_num[pix] = cnt_all;
-    }
-    return;
-  }
+  const float w = (em != 0.0f) ? FAST_EXP(-occ * sum) * em * kInvNorm : 0.0f;
   const float um = gw * w;
   if (in_wg) Lu[bi] = um;
   float suf_incl;
@@ -324,7 +274,6 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
   }
 }
 
-
 // ------------------------------------------------------------------------------------------
 // NS (2 or 4) consecutive slots per lane (forward, and backward with the forward's weights).
 // A lane owns the aligned group of slots [NS q, NS q + NS) of its pixel, so every pair of list
@@ -345,9 +294,10 @@ composite_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
 // shade kernel would read again (idx and weight: 8 bytes per slot) is never read.
 struct CompShade {
   const float *colors, *bg;
-  float thr;
-  long Nattr;
-  float *rgb, *img, *wsum;
+  union { float thr; float depth_bg; };           // silhouette threshold | (depth stage) the background depth
+  union { long Nattr; long normalize; };          // rows of the colour table | (depth stage) depth = sum w len / sum w, not the plain sum
+  union { float *rgb; float *depth; };            // [npix][SC] | (depth stage) [npix]
+  float *img, *wsum;
   int32_t *idx_fix;
   // (round 6) zero_n4 float4s this launch sets to zero on its way: the accumulator of the frame's backward
   // (voge_frame_shade_fwd_iso's bwd_acc) -- no fill launch in front of that backward.  The first ceil(zero_n4 / 64) workgroups
@@ -356,9 +306,9 @@ struct CompShade {
   float4 *zero_p = nullptr;
   long zero_n4 = 0;
   float *sil = nullptr;      // (round 6) NULL | [npix]: get_silhouette = min(sum_k w_k, 1) (Renderer.py:157-159), written with the sum
-  // SC = -1, the DEPTH stage (voge_frame_depth_fwd_iso) reuses the fields instead of growing the struct, which every shade
-  // instantiation pays for in kernel-argument registers: rgb = depth [npix], Nattr = the normalize flag, thr = the background
-  // depth; colors, bg, img and idx_fix are not touched (get_depth does not rewrite the index list).
+  // SC = -1, the DEPTH stage (voge_frame_depth_fwd_iso) shares three fields (the unions above) instead of growing the struct,
+  // which every shade instantiation pays for in kernel-argument registers; colors, bg, img and idx_fix are not touched
+  // (get_depth does not rewrite the index list).
 };
 // SC = -1 (forward from the records, wave form): the DEPTH stage instead -- depth = sum_k w_k len_k / sum_k w_k over the live
 // slots (or the un-normalised sum), one more partial sum through the shade stage's reduction; no colour table, no index rewrite.
@@ -378,13 +328,13 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
                   const CompShade sh = CompShade{}) {
   static_assert(SC == 0 || (MODE == 0 && WAVE && SC <= 4 && SC >= -1), "the shade stage rides in the wave-form forward only");
   constexpr bool BWD = MODE != 0;
-  if (SC != 0 && (long)blockIdx.x * blockDim.x < sh.zero_n4) {      // (uniform; the launch covers zero_n4: composite_shade_fwd_impl)
+  if (SC != 0 && (long)blockIdx.x * blockDim.x < sh.zero_n4) {      // (uniform; the launch covers zero_n4: comp_zero_rider)
     const long zi = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (zi < sh.zero_n4) sh.zero_p[zi] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   constexpr int NP = NS / 2;       // own aligned pairs
   extern __shared__ __attribute__((aligned(16))) unsigned char comp_smem[];
-  CompLds &L = *reinterpret_cast<CompLds *>(comp_smem);      // (workgroup form only)
+  CompLds &L = *reinterpret_cast<CompLds *>(comp_smem);      // (workgroup form only: its flags are set up before the forms part)
   const int rows = compn_rows(K, NS, (int)blockDim.x, WAVE);
   float *const Llen = reinterpret_cast<float *>(comp_smem + (WAVE ? 0 : sizeof(CompLds)));
   float *const Lsp = Llen + rows;
@@ -395,7 +345,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
   const int LP = compn_lanes(K, NS);
   int p, q;
   bool in_wg;
-  if (WAVE) {
+  if constexpr (WAVE) {
     const int pw = 64 / LP;                       // pixels per wave
     const int pl = __float2int_rz(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)LP));
     q = lane - pl * LP;
@@ -428,9 +378,9 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
       if (active) {
 #pragma unroll
         for (int a = 0; a < NS; ++a)
-          if (has[a]) { out0[f + a] = 0.0f; if (BWD) { out1[f + a] = 0.0f; out2[f + a] = 0.0f; } if (SC > 0) sh.idx_fix[f + a] = 0; }
+          if (has[a]) { out0[f + a] = 0.0f; if constexpr (BWD) { out1[f + a] = 0.0f; out2[f + a] = 0.0f; } if constexpr (SC > 0) sh.idx_fix[f + a] = 0; }
         if (!BWD && q == 0) valid_num[pix] = 0;
-        if (SC > 0 && q == 0) {      // nothing was hit: the background
+        if constexpr (SC > 0) if (q == 0) {      // nothing was hit: the background
           sh.wsum[pix] = 0.0f;
           if (sh.sil != nullptr) sh.sil[pix] = 0.0f;
 #pragma unroll
@@ -439,10 +389,10 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
             if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(sh.bg[c], 1.0f);
           }
         }
-        if (SC < 0 && q == 0) {      // nothing was hit: the background depth (normalised) or an empty sum
+        if constexpr (SC < 0) if (q == 0) {      // nothing was hit: the background depth (normalised) or an empty sum
           sh.wsum[pix] = 0.0f;
           if (sh.sil != nullptr) sh.sil[pix] = 0.0f;
-          sh.rgb[pix] = sh.Nattr != 0 ? sh.thr : 0.0f;
+          sh.depth[pix] = sh.normalize != 0 ? sh.depth_bg : 0.0f;
         }
       }
       return;
@@ -470,11 +420,11 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
           iv[a] = 0; lv[a] = 0.0f;
           if (k0 + a < lead) { iv[a] = idx[f + a]; lv[a] = len[f + a]; }
         }
-      } else if (NS == 4) {
+      } else if constexpr (NS == 4) {
         const int4 i4 = at_bytes<int4>(idx, fb);
         const float4 l4 = at_bytes<float4>(len, fb);
-        iv[0] = i4.x; iv[1] = i4.y; iv[NS - 2] = i4.z; iv[NS - 1] = i4.w;
-        lv[0] = l4.x; lv[1] = l4.y; lv[NS - 2] = l4.z; lv[NS - 1] = l4.w;
+        iv[0] = i4.x; iv[1] = i4.y; iv[2] = i4.z; iv[3] = i4.w;
+        lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
       } else {
         const int2 i2 = at_bytes<int2>(idx, fb);
         const v2f l2 = at_bytes<v2f>(len, fb);
@@ -487,7 +437,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
 #pragma unroll
         for (int r = 0; r < NR; ++r)
           rc[a][r] = at_bytes<float4>(rec, (uint32_t)max(iv[a], 0) * (16u * NR) + 16u * r);      // (a slot beyond the count: record 0, selected out below -- no exec-mask region per slot)
-      if (SC > 0) {
+      if constexpr (SC > 0) {
 #pragma unroll
         for (int a = 0; a < NS; ++a) ivk[a] = (k0 + a < lead) ? iv[a] : -1;
       }
@@ -496,11 +446,11 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
         if (GEN && !(k0 + a < lead)) continue;
         {
           PairOut o;
-          if (GEN == 2) {
+          if constexpr (GEN == 2) {
             const float4 r0 = rc[a][0], r1 = rc[a][NR - 1];
             o = pair_eval_diag(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, d.x, d.y, d.z);
             if (out1 != nullptr) { out1[f + a] = o.act; out2[f + a] = o.dsd; }
-          } else if (GEN) {
+          } else if constexpr (GEN != 0) {
             const float4 r0 = rc[a][0], r1 = rc[a][GEN == 1 ? 1 : 0], r2 = rc[a][GEN == 1 ? 2 : 0];
             const float A[9] = {r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
             o = pair_eval(r0.x, r0.y, r0.z, make_eval(r0.x, r0.y, r0.z, A), d.x, d.y, d.z, d.x * d.x, d.y * d.y, d.z * d.z,
@@ -519,22 +469,22 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
   } else if (active) {
     if (vec && k0 + NS <= lead) {        // the whole group is live: one wide access per array
       float av[NS], lv[NS], dv[NS];
-      if (NS == 4) {
+      if constexpr (NS == 4) {
         const float4 a4 = at_bytes<float4>(act, fb), l4 = at_bytes<float4>(len, fb),
                      d4 = at_bytes<float4>(dsd, fb);
-        av[0] = a4.x; av[1] = a4.y; av[NS - 2] = a4.z; av[NS - 1] = a4.w;
-        lv[0] = l4.x; lv[1] = l4.y; lv[NS - 2] = l4.z; lv[NS - 1] = l4.w;
-        dv[0] = d4.x; dv[1] = d4.y; dv[NS - 2] = d4.z; dv[NS - 1] = d4.w;
-        if (BWD) {
+        av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
+        lv[0] = l4.x; lv[1] = l4.y; lv[2] = l4.z; lv[3] = l4.w;
+        dv[0] = d4.x; dv[1] = d4.y; dv[2] = d4.z; dv[3] = d4.w;
+        if constexpr (BWD) {
           const float4 g4 = at_bytes<float4>(g_weight, fb), w4 = at_bytes<float4>(w_in, fb);
-          gw[0] = g4.x; gw[1] = g4.y; gw[NS - 2] = g4.z; gw[NS - 1] = g4.w;
-          wg[0] = w4.x; wg[1] = w4.y; wg[NS - 2] = w4.z; wg[NS - 1] = w4.w;
+          gw[0] = g4.x; gw[1] = g4.y; gw[2] = g4.z; gw[3] = g4.w;
+          wg[0] = w4.x; wg[1] = w4.y; wg[2] = w4.z; wg[3] = w4.w;
         }
       } else {
         const v2f a2 = at_bytes<v2f>(act, fb), l2 = at_bytes<v2f>(len, fb),
                   d2 = at_bytes<v2f>(dsd, fb);
         av[0] = a2.x; av[1] = a2.y; lv[0] = l2.x; lv[1] = l2.y; dv[0] = d2.x; dv[1] = d2.y;
-        if (BWD) {
+        if constexpr (BWD) {
           const v2f g2 = at_bytes<v2f>(g_weight, fb), w2 = at_bytes<v2f>(w_in, fb);
           gw[0] = g2.x; gw[1] = g2.y; wg[0] = w2.x; wg[1] = w2.y;
         }
@@ -595,88 +545,118 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
     wave_cnt = c;
     if (!WAVE && head) atomicAdd(&L.cnt[p], c);
   }
-  if (BWD && WAVE) {
-    // backward, wave form: shared with the fused fragment backward (composite_core.h, fragment_bwd.hip)
-    float um[NS], ga[NS], gl[NS], gd[NS];
+  if constexpr (WAVE) {
+    // ---- ONE-WAVE FORM: compn_lanes(K, NS) <= 64, i.e. K <= 128 with two slots per lane (every backward; the forward when
+    // K % 4 != 0) and K <= 256 -- every K the entries accept -- with four (launch_composite's plan).  No barrier from here on.
+    if constexpr (BWD) {
+      // backward, wave form: shared with the fused fragment backward (composite_core.h, fragment_bwd.hip)
+      float um[NS], ga[NS], gl[NS], gd[NS];
 #pragma unroll
-    for (int a = 0; a < NS; ++a) um[a] = gw[a] * wg[a];
-    compn_bwd_wave<NS>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, occ, ga,
-                       gl, gd, LR);
-    if (active) {
-      if (vec && NS == 4) {
-        at_bytes_w<float4>(out0, fb) = make_float4(ga[0], ga[1], ga[NS - 2], ga[NS - 1]);
-        at_bytes_w<float4>(out1, fb) = make_float4(gl[0], gl[1], gl[NS - 2], gl[NS - 1]);
-        at_bytes_w<float4>(out2, fb) = make_float4(gd[0], gd[1], gd[NS - 2], gd[NS - 1]);
-      } else if (vec) {
-        at_bytes_w<v2f>(out0, fb) = (v2f){ga[0], ga[1]};
-        at_bytes_w<v2f>(out1, fb) = (v2f){gl[0], gl[1]};
-        at_bytes_w<v2f>(out2, fb) = (v2f){gd[0], gd[1]};
-      } else {
+      for (int a = 0; a < NS; ++a) um[a] = gw[a] * wg[a];
+      compn_bwd_wave<NS>(lm, sm, em, um, Llen, Lsp, LE, Lu, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, occ, ga,
+                         gl, gd, LR);
+      if (active) {
+        if (vec && NS == 4) {
+          at_bytes_w<float4>(out0, fb) = make_float4(ga[0], ga[1], ga[NS - 2], ga[NS - 1]);
+          at_bytes_w<float4>(out1, fb) = make_float4(gl[0], gl[1], gl[NS - 2], gl[NS - 1]);
+          at_bytes_w<float4>(out2, fb) = make_float4(gd[0], gd[1], gd[NS - 2], gd[NS - 1]);
+        } else if (vec) {
+          at_bytes_w<v2f>(out0, fb) = (v2f){ga[0], ga[1]};
+          at_bytes_w<v2f>(out1, fb) = (v2f){gl[0], gl[1]};
+          at_bytes_w<v2f>(out2, fb) = (v2f){gd[0], gd[1]};
+        } else {
 #pragma unroll
-        for (int a = 0; a < NS; ++a) if (has[a]) { out0[f + a] = ga[a]; out1[f + a] = gl[a]; out2[f + a] = gd[a]; }
-      }
-    }
-    return;
-  }
-  if (!BWD && WAVE) {
-    // forward, wave form: the row pass shared with round 3's fused sweep epilogue (composite_core.h)
-    float w[NS];
-    compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo, occ, w);
-    if (active) {
-      if (vec && NS == 4) at_bytes_w<float4>(out0, fb) = make_float4(w[0], w[1], w[NS - 2], w[NS - 1]);
-      else if (vec) at_bytes_w<v2f>(out0, fb) = (v2f){w[0], w[1]};
-      else {
-#pragma unroll
-        for (int a = 0; a < NS; ++a) if (has[a]) out0[f + a] = w[a];
-      }
-      if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)wave_cnt;
-    }
-    if (SC > 0) {
-      // ---- shade: sum_k w_k colour[idx_k] and sum_k w_k over the pixel's lanes; blend over the background ----
-      float part[(SC > 0 ? SC : 0) + 1];
-#pragma unroll
-      for (int c = 0; c <= SC; ++c) part[c] = 0.0f;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const int p2 = ivk[a];
-        if (SC == 3 || SC == 4) {
-          // (no exec-mask region per slot: a slot that contributes nothing reads colour row 0 and multiplies a zero; the
-          //  row is selected to zero first, so a non-finite colour there cannot leak)
-          const bool on = p2 >= 0 && p2 < sh.Nattr && w[a] != 0.0f;
-          const uint32_t o = (uint32_t)(on ? p2 : 0) * (uint32_t)(4 * SC);      // (bytes; Nattr * SC < 2^30: host)
-          if (SC == 3) {
-            const float3 v = at_bytes<float3>(sh.colors, o);
-            part[0] = fmaf(w[a], on ? v.x : 0.0f, part[0]); part[1] = fmaf(w[a], on ? v.y : 0.0f, part[1]);
-            part[2] = fmaf(w[a], on ? v.z : 0.0f, part[2]);
-          } else {
-            const float4 v = at_bytes<float4>(sh.colors, o);
-            part[0] = fmaf(w[a], on ? v.x : 0.0f, part[0]); part[1] = fmaf(w[a], on ? v.y : 0.0f, part[1]);
-            part[2] = fmaf(w[a], on ? v.z : 0.0f, part[2]); part[SC - 1] = fmaf(w[a], on ? v.w : 0.0f, part[SC - 1]);
-          }
-        } else if (p2 >= 0 && p2 < sh.Nattr && w[a] != 0.0f) {
-          const uint32_t o = (uint32_t)p2 * (uint32_t)(4 * SC);
-          {
-#pragma unroll
-            for (int c = 0; c < SC; ++c) part[c] = fmaf(w[a], at_bytes<float>(sh.colors, o + 4u * c), part[c]);
-          }
+          for (int a = 0; a < NS; ++a) if (has[a]) { out0[f + a] = ga[a]; out1[f + a] = gl[a]; out2[f + a] = gd[a]; }
         }
-        part[SC] += w[a];
       }
-      if (SC == 3 && LP >= 3 && blockDim.x == 64) {      // (uniform; one-wave workgroups: the scratch below is the wave's OWN rows -- in a
-                                                          //  workgroup of several waves another wave may still be walking them)
-        // Three colour sums and sum w over the pixel's lanes.  Round 6: through LDS -- every lane leaves its four partial sums in the
-        // (now idle) row arrays, the pixel's lanes 0 .. 2 each add up ONE colour's column and the weights' column in lane order:
-        // two dependent LDS round trips instead of the four of a shuffle tree (which were 5 us of this kernel; a tree with fewer
-        // shuffles but five dependent steps gained nothing).  A fixed association per pixel, as before.
-        float *const A0 = const_cast<float *>(Llen), *const A1 = const_cast<float *>(Lsp), *const A2 = const_cast<float *>(LE);
-        wave_lds_sync();      // (the walks' reads of these rows are over)
-        constexpr int T_ = 64;      // (rows >= 128 for every K with LP >= 3: compn_rows)
-        A0[tid] = part[0]; A1[tid] = part[1]; A2[tid] = part[2]; A0[T_ + tid] = part[3];
-        wave_lds_sync();
-        float xs = 0.0f, ws = 0.0f;
-        if (in_wg && q < 3) {
-          const float *const col = (q == 0 ? A0 : (q == 1 ? A1 : A2)) + (tid - q), *const wc = A0 + T_ + (tid - q);
-          for (int j = 0; j < LP; ++j) { xs += col[j]; ws += wc[j]; }
+    } else {
+      // forward, wave form: the row pass shared with round 3's fused sweep epilogue (composite_core.h)
+      float w[NS];
+      compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo, occ, w);
+      if (active) {
+        if (vec && NS == 4) at_bytes_w<float4>(out0, fb) = make_float4(w[0], w[1], w[NS - 2], w[NS - 1]);
+        else if (vec) at_bytes_w<v2f>(out0, fb) = (v2f){w[0], w[1]};
+        else {
+#pragma unroll
+          for (int a = 0; a < NS; ++a) if (has[a]) out0[f + a] = w[a];
+        }
+        if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)wave_cnt;
+      }
+      if constexpr (SC > 0) {
+        // ---- shade: sum_k w_k colour[idx_k] and sum_k w_k over the pixel's lanes; blend over the background ----
+        float part[(SC > 0 ? SC : 0) + 1];
+#pragma unroll
+        for (int c = 0; c <= SC; ++c) part[c] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < NS; ++a) {
+          const int p2 = ivk[a];
+          if (SC == 3 || SC == 4) {
+            // (no exec-mask region per slot: a slot that contributes nothing reads colour row 0 and multiplies a zero; the
+            //  row is selected to zero first, so a non-finite colour there cannot leak)
+            const bool on = p2 >= 0 && p2 < sh.Nattr && w[a] != 0.0f;
+            const uint32_t o = (uint32_t)(on ? p2 : 0) * (uint32_t)(4 * SC);      // (bytes; Nattr * SC < 2^30: host)
+            if (SC == 3) {
+              const float3 v = at_bytes<float3>(sh.colors, o);
+              part[0] = fmaf(w[a], on ? v.x : 0.0f, part[0]); part[1] = fmaf(w[a], on ? v.y : 0.0f, part[1]);
+              part[2] = fmaf(w[a], on ? v.z : 0.0f, part[2]);
+            } else {
+              const float4 v = at_bytes<float4>(sh.colors, o);
+              part[0] = fmaf(w[a], on ? v.x : 0.0f, part[0]); part[1] = fmaf(w[a], on ? v.y : 0.0f, part[1]);
+              part[2] = fmaf(w[a], on ? v.z : 0.0f, part[2]); part[SC - 1] = fmaf(w[a], on ? v.w : 0.0f, part[SC - 1]);
+            }
+          } else if (p2 >= 0 && p2 < sh.Nattr && w[a] != 0.0f) {
+            const uint32_t o = (uint32_t)p2 * (uint32_t)(4 * SC);
+            {
+#pragma unroll
+              for (int c = 0; c < SC; ++c) part[c] = fmaf(w[a], at_bytes<float>(sh.colors, o + 4u * c), part[c]);
+            }
+          }
+          part[SC] += w[a];
+        }
+        if (SC == 3 && LP >= 3 && blockDim.x == 64) {      // (uniform; one-wave workgroups: the scratch below is the wave's OWN rows -- in a
+                                                            //  workgroup of several waves another wave may still be walking them)
+          // Three colour sums and sum w over the pixel's lanes.  Round 6: through LDS -- every lane leaves its four partial sums in the
+          // (now idle) row arrays, the pixel's lanes 0 .. 2 each add up ONE colour's column and the weights' column in lane order:
+          // two dependent LDS round trips instead of the four of a shuffle tree (which were 5 us of this kernel; a tree with fewer
+          // shuffles but five dependent steps gained nothing).  A fixed association per pixel, as before.
+          float *const A0 = const_cast<float *>(Llen), *const A1 = const_cast<float *>(Lsp), *const A2 = const_cast<float *>(LE);
+          wave_lds_sync();      // (the walks' reads of these rows are over)
+          constexpr int T_ = 64;      // (rows >= 128 for every K with LP >= 3: compn_rows)
+          A0[tid] = part[0]; A1[tid] = part[1]; A2[tid] = part[2]; A0[T_ + tid] = part[3];
+          wave_lds_sync();
+          float xs = 0.0f, ws = 0.0f;
+          if (in_wg && q < 3) {
+            const float *const col = (q == 0 ? A0 : (q == 1 ? A1 : A2)) + (tid - q), *const wc = A0 + T_ + (tid - q);
+            for (int j = 0; j < LP; ++j) { xs += col[j]; ws += wc[j]; }
+          }
+          if (active) {
+            // merge_final rewrites empty slots of the index list in place, -1 -> 0 (Aggregation.py:131)
+            if (k0 + NS > lead) {
+#pragma unroll
+              for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) sh.idx_fix[f + a] = 0;
+            }
+            if (q < 3) {
+              float sil = fminf(ws, 1.0f);
+              if (sh.thr > 0.0f) sil = sil > sh.thr ? 1.0f : 0.0f;
+              sh.rgb[pix * SC + q] = xs;
+              if (sh.img != nullptr) sh.img[pix * SC + q] = fminf(fmaf(1.0f - sil, sh.bg[q], xs), 1.0f);
+              if (q == 0) {
+                sh.wsum[pix] = ws;
+                if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+              }
+            }
+          }
+          return;
+        }
+        // the pixel's lanes are consecutive in the wave: sum towards its first lane (a fixed association per pixel)
+#pragma unroll
+        for (int c = 0; c <= SC; ++c) {
+          float x = part[c];
+          for (int o = 1; o < LP; o <<= 1) {
+            const float y = __shfl_down(x, o, 64);
+            if (q + o < LP && in_wg) x += y;
+          }
+          part[c] = x;
         }
         if (active) {
           // merge_final rewrites empty slots of the index list in place, -1 -> 0 (Aggregation.py:131)
@@ -684,363 +664,314 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
 #pragma unroll
             for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) sh.idx_fix[f + a] = 0;
           }
-          if (q < 3) {
+          if (q == 0) {
+            const float ws = part[SC];
             float sil = fminf(ws, 1.0f);
             if (sh.thr > 0.0f) sil = sil > sh.thr ? 1.0f : 0.0f;
-            sh.rgb[pix * SC + q] = xs;
-            if (sh.img != nullptr) sh.img[pix * SC + q] = fminf(fmaf(1.0f - sil, sh.bg[q], xs), 1.0f);
-            if (q == 0) {
-              sh.wsum[pix] = ws;
-              if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+            sh.wsum[pix] = ws;
+            if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+#pragma unroll
+            for (int c = 0; c < SC; ++c) {
+              sh.rgb[pix * SC + c] = part[c];
+              if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(fmaf(1.0f - sil, sh.bg[c], part[c]), 1.0f);
             }
           }
         }
-        return;
       }
-      // the pixel's lanes are consecutive in the wave: sum towards its first lane (a fixed association per pixel)
+      if constexpr (SC < 0) {
+        // ---- depth: sum_k w_k len_k and sum_k w_k over the pixel's LIVE slots (the lane holds both factors), summed towards
+        // the pixel's first lane like the shade stage's sums: a fixed association per pixel ----
+        float part[2] = {0.0f, 0.0f};
 #pragma unroll
-      for (int c = 0; c <= SC; ++c) {
-        float x = part[c];
-        for (int o = 1; o < LP; o <<= 1) {
-          const float y = __shfl_down(x, o, 64);
-          if (q + o < LP && in_wg) x += y;
+        for (int a = 0; a < NS; ++a) {
+          const bool on = k0 + a < lead;
+          part[0] = fmaf(on ? w[a] : 0.0f, on ? lm[a] : 0.0f, part[0]);
+          part[1] += on ? w[a] : 0.0f;
         }
-        part[c] = x;
-      }
-      if (active) {
-        // merge_final rewrites empty slots of the index list in place, -1 -> 0 (Aggregation.py:131)
-        if (k0 + NS > lead) {
 #pragma unroll
-          for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) sh.idx_fix[f + a] = 0;
+        for (int c = 0; c < 2; ++c) {
+          float x = part[c];
+          for (int o = 1; o < LP; o <<= 1) {
+            const float y = __shfl_down(x, o, 64);
+            if (q + o < LP && in_wg) x += y;
+          }
+          part[c] = x;
         }
-        if (q == 0) {
-          const float ws = part[SC];
-          float sil = fminf(ws, 1.0f);
-          if (sh.thr > 0.0f) sil = sil > sh.thr ? 1.0f : 0.0f;
+        if (active && q == 0) {
+          const float ws = part[1];
           sh.wsum[pix] = ws;
           if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+          sh.depth[pix] = sh.normalize != 0 ? (ws > 0.0f ? part[0] / ws : sh.depth_bg) : part[0];
+        }
+      }
+    }
+  } else {
+    // ---- WORKGROUP FORM: compn_lanes(K, NS) > 64, which only two slots per lane reach: 128 < K <= 256 in the backward, and in the
+    // forward when K % 4 != 0 as well (launch_composite's plan).  A pixel's lanes span waves: scans and flags go through LDS
+    // (CompLds) between barriers.
+    float mx = 0.0f, esum = 0.0f;
 #pragma unroll
-          for (int c = 0; c < SC; ++c) {
-            sh.rgb[pix * SC + c] = part[c];
-            if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(fmaf(1.0f - sil, sh.bg[c], part[c]), 1.0f);
+    for (int a = 0; a < NS; ++a) {
+      mx = fmaxf(mx, (em[a] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[a]) : 0.0f);
+      esum += em[a];
+    }
+    // Exclusive prefix (over the lanes of the pixel) of the per-lane sums of E, Hillis-Steele with the
+    // window radius riding along; the association is a function of the lane's index in the pixel only.
+    float ex = 0.0f;   // sum of E over the slots in front of this lane's group
+    if constexpr (!BWD) {
+      v2f x = {esum, mx};
+      L.scan[0][tid] = x;
+      __syncthreads();
+      const v2f y = (q > 0 && in_wg) ? L.scan[0][tid - 1] : splat(0.0f);
+      x = (v2f){y.x, fmaxf(mx, y.y)};      // exclusive sum so far, inclusive max so far
+      int par = 1;
+      for (int o = 1; o < LP; o <<= 1) {
+        L.scan[par][tid] = x;
+        __syncthreads();
+        if (q >= o && in_wg) {
+          const v2f z = L.scan[par][tid - o];
+          x.x += z.x;                        // (z.x = 0 for the pixel's first lane)
+          x.y = fmaxf(x.y, z.y);
+        }
+        par ^= 1;
+      }
+      ex = x.x;
+      if (in_wg && q == LP - 1) L.rmaxi[p] = __float_as_int(x.y);
+    } else {      // (the weights are given: no prefix of E, only the radius -- a segmented wave max + one LDS atomic per (wave, pixel) run)
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const float y = __shfl_down(mx, o, 64);
+        if (lane + o < 64 && q + o < LP) mx = fmaxf(mx, y);
+      }
+      if (head) atomicMax(&L.rmaxi[p], __float_as_int(mx));     // mx >= 0: float order == int order
+    }
+    __syncthreads();
+    const float rwin_all = in_wg ? __int_as_float(L.rmaxi[p]) : 0.0f;
+    const bool sorted = active && (L.unsorted[in_wg ? p : 0] == 0);
+    const float rwin = sorted ? rwin_all : 0.0f;
+    bool any_e = false;
+#pragma unroll
+    for (int a = 0; a < NS; ++a) any_e = any_e || (em[a] != 0.0f);
+    const float h0 = __builtin_amdgcn_exp2f(kQ0);      // h(0), exactly what h_pair(0) returns
+
+    // ---- rows = the lane's own slots -------------------------------------------------------------
+    float S[NS], rterm[NS];
+#pragma unroll
+    for (int a = 0; a < NS; ++a) { S[a] = 0.0f; rterm[a] = 0.0f; }
+    if (any_e && sorted) {
+      v2f accF[NS], accB[NS], accR[NS];
+#pragma unroll
+      for (int a = 0; a < NS; ++a) { accF[a] = splat(0.0f); accB[a] = splat(0.0f); accR[a] = splat(0.0f); }
+      // diagonal block (registers): for rows a < b, column b is behind row a and column a in front of row b
+#pragma unroll
+      for (int a = 0; a < NS; ++a) {
+        if (!BWD) accF[a].x = em[a] * h0; else accR[a].x = Es[a];         // self
+#pragma unroll
+        for (int b2 = a + 1; b2 < NS; ++b2) {
+          const float gap = lm[b2] - lm[a];
+          const v2f xp = (v2f){gap * sp[b2], gap * sp[a]};                 // (row a, col b), (row b, col a)
+          if (!BWD) {
+            const v2f h = h_pair(xp);
+            accB[a].y = fmaf(em[b2], h.x, accB[a].y);
+            accF[b2].y = fmaf(em[a], h.y, accF[b2].y);
+          } else {
+            const v2f g = gauss_pair(xp);
+            accR[a].y = fmaf(Es[b2], g.x, accR[a].y);
+            accR[b2].y = fmaf(Es[a], g.y, accR[b2].y);
+          }
+        }
+      }
+      float lmB = lm[0];                 // the last live row decides how far back to walk
+#pragma unroll
+      for (int a = 1; a < NS; ++a) lmB = (em[a] != 0.0f) ? lm[a] : lmB;
+      for (int e = d0 - 2;; e -= 2) {      // column pairs in front of every own row; row 0 is the nearest
+        const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
+        if (!(lm[0] - l2.y < rwin)) break;
+#pragma unroll
+        for (int a = 0; a < NS; ++a) {
+          const v2f xa = (splat(lm[a]) - l2) * s2;
+          if (!BWD) accF[a] = pk_fma(E2, h_pair(xa), accF[a]); else accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
+        }
+      }
+      for (int e = d0 + NS;; e += 2) {     // column pairs behind every own row
+        const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
+        if (!(l2.x - lmB < rwin)) break;
+#pragma unroll
+        for (int a = 0; a < NS; ++a) {
+          const v2f xa = (l2 - splat(lm[a])) * s2;
+          if (!BWD) accB[a] = pk_fma(E2, h_pair(xa), accB[a]); else accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
+        }
+      }
+      float pre = ex;
+#pragma unroll
+      for (int a = 0; a < NS; ++a) {
+        pre += em[a];                                                     // inclusive prefix sum of E
+        if (!BWD) S[a] = (pre - (accF[a].x + accF[a].y)) + (accB[a].x + accB[a].y);
+        else rterm[a] = (accR[a].x + accR[a].y) * (kRsqrtPi / kCs);
+      }
+    } else if (any_e && active) {          // unsorted list: every column, signs from the data
+      const int r0 = d0 - k0;
+      for (int j = 0; j < K; ++j) {
+        const float Ej = LE[r0 + j];
+        if (Ej == 0.0f) continue;
+        const float lj = Llen[r0 + j], sj = Lsp[r0 + j];
+#pragma unroll
+        for (int a = 0; a < NS; ++a) {
+          const float xp = (lm[a] - lj) * sj;
+          if (!BWD) {
+            const float h = h_one(fabsf(xp));
+            S[a] = fmaf(Ej, xp >= 0.0f ? 1.0f - h : h, S[a]);
+          } else {
+            const float xc = fminf(fabsf(xp), 16.0f);
+            rterm[a] = fmaf(Ej * (kRsqrtPi / kCs), __builtin_amdgcn_exp2f(-xc * xc), rterm[a]);
           }
         }
       }
     }
-    if (SC < 0) {
-      // ---- depth: sum_k w_k len_k and sum_k w_k over the pixel's LIVE slots (the lane holds both factors), summed towards
-      // the pixel's first lane like the shade stage's sums: a fixed association per pixel ----
-      float part[2] = {0.0f, 0.0f};
+    if constexpr (!BWD) {
+      float w[NS];
 #pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const bool on = k0 + a < lead;
-        part[0] = fmaf(on ? w[a] : 0.0f, on ? lm[a] : 0.0f, part[0]);
-        part[1] += on ? w[a] : 0.0f;
+      for (int a = 0; a < NS; ++a) w[a] = (em[a] != 0.0f) ? FAST_EXP(-occ * S[a]) * em[a] * kInvNorm : 0.0f;
+      if (active) {
+        if (vec && NS == 4) at_bytes_w<float4>(out0, fb) = make_float4(w[0], w[1], w[NS - 2], w[NS - 1]);
+        else if (vec) at_bytes_w<v2f>(out0, fb) = (v2f){w[0], w[1]};
+        else {
+#pragma unroll
+          for (int a = 0; a < NS; ++a) if (has[a]) out0[f + a] = w[a];
+        }
+        if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)L.cnt[p];
       }
+    } else {
+      // ---- backward: u = g_w * w, suffix sums, then the lane's own columns --------------------------
+      float um[NS], usum = 0.0f;
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        float x = part[c];
+      for (int a = 0; a < NS; ++a) { um[a] = gw[a] * wg[a]; usum += um[a]; }
+      if (in_wg) {
+#pragma unroll
+        for (int h2 = 0; h2 < NP; ++h2) *reinterpret_cast<v2f *>(Lu + d0 + 2 * h2) = (v2f){um[2 * h2], um[2 * h2 + 1]};
+      }
+      float sx = 0.0f;   // sum of u over the slots behind this lane's group
+      {
+        float(*sf)[kCompThreads] = reinterpret_cast<float(*)[kCompThreads]>(L.scan);
+        sf[0][tid] = usum;
+        __syncthreads();
+        float x = (q + 1 < LP && in_wg) ? sf[0][tid + 1] : 0.0f;
+        int par = 1;
         for (int o = 1; o < LP; o <<= 1) {
-          const float y = __shfl_down(x, o, 64);
-          if (q + o < LP && in_wg) x += y;
+          sf[par][tid] = x;
+          __syncthreads();
+          if (q + o < LP && in_wg) x += sf[par][tid + o];      // (0 for the pixel's last lane)
+          par ^= 1;
         }
-        part[c] = x;
+        sx = x;
       }
-      if (active && q == 0) {
-        const float ws = part[1];
-        sh.wsum[pix] = ws;
-        if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
-        sh.rgb[pix] = sh.Nattr != 0 ? (ws > 0.0f ? part[0] / ws : sh.thr) : part[0];
-      }
-    }
-    return;
-  }
-  float mx = 0.0f, esum = 0.0f;
-#pragma unroll
-  for (int a = 0; a < NS; ++a) {
-    mx = fmaxf(mx, (em[a] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[a]) : 0.0f);
-    esum += em[a];
-  }
-  // Exclusive prefix (over the lanes of the pixel) of the per-lane sums of E, Hillis-Steele with the
-  // window radius riding along; the association is a function of the lane's index in the pixel only.
-  float ex = 0.0f;   // sum of E over the slots in front of this lane's group
-  float wave_rmax = 0.0f;
-  if (!BWD && WAVE) {            // the same Hillis-Steele steps on wave shuffles (same association)
-    v2f x = {esum, mx};
-    const v2f y = (v2f){__shfl_up(x.x, 1, 64), __shfl_up(x.y, 1, 64)};
-    x = (q > 0 && in_wg) ? (v2f){y.x, fmaxf(mx, y.y)} : (v2f){0.0f, mx};
-    for (int o = 1; o < LP; o <<= 1) {
-      const v2f z = (v2f){__shfl_up(x.x, o, 64), __shfl_up(x.y, o, 64)};
-      if (q >= o && in_wg) {
-        x.x += z.x;
-        x.y = fmaxf(x.y, z.y);
-      }
-    }
-    ex = x.x;
-    wave_rmax = __shfl(x.y, min(63, seg_lo + LP - 1), 64);      // the pixel's last lane holds the maximum
-  } else if (!BWD) {
-    v2f x = {esum, mx};
-    L.scan[0][tid] = x;
-    __syncthreads();
-    const v2f y = (q > 0 && in_wg) ? L.scan[0][tid - 1] : splat(0.0f);
-    x = (v2f){y.x, fmaxf(mx, y.y)};      // exclusive sum so far, inclusive max so far
-    int par = 1;
-    for (int o = 1; o < LP; o <<= 1) {
-      L.scan[par][tid] = x;
       __syncthreads();
-      if (q >= o && in_wg) {
-        const v2f z = L.scan[par][tid - o];
-        x.x += z.x;                        // (z.x = 0 for the pixel's first lane)
-        x.y = fmaxf(x.y, z.y);
-      }
-      par ^= 1;
-    }
-    ex = x.x;
-    if (in_wg && q == LP - 1) L.rmaxi[p] = __float_as_int(x.y);
-  } else {
+      float ga[NS], gl[NS], gd[NS];
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float y = __shfl_down(mx, o, 64);
-      if (lane + o < 64 && q + o < LP) mx = fmaxf(mx, y);
-    }
-    if (WAVE) wave_rmax = __shfl(mx, seg_lo, 64);                // the pixel's first lane holds the maximum
-    else if (head) atomicMax(&L.rmaxi[p], __float_as_int(mx));
-  }
-  if (!WAVE) __syncthreads();
-  const float rwin_all = WAVE ? (in_wg ? wave_rmax : 0.0f) : (in_wg ? __int_as_float(L.rmaxi[p]) : 0.0f);
-  const bool sorted = active && (WAVE ? !wave_unsorted : (L.unsorted[in_wg ? p : 0] == 0));
-  const float rwin = sorted ? rwin_all : 0.0f;
-  bool any_e = false;
+      for (int a = 0; a < NS; ++a) { ga[a] = 0.0f; gl[a] = 0.0f; gd[a] = 0.0f; }
+      if (any_e && active) {
+        float cPhi[NS], cphi[NS], cphil[NS];
+        if (sorted) {
+          float rj[NS];
+          v2f aH[NS], aP[NS], aL[NS], bH[NS], bP[NS], bL[NS];   // per own column: rows behind (a*) / in front (b*)
 #pragma unroll
-  for (int a = 0; a < NS; ++a) any_e = any_e || (em[a] != 0.0f);
-  const float h0 = __builtin_amdgcn_exp2f(kQ0);      // h(0), exactly what h_pair(0) returns
-
-  // ---- rows = the lane's own slots -------------------------------------------------------------
-  float S[NS], rterm[NS];
+          for (int b2 = 0; b2 < NS; ++b2) {
+            rj[b2] = (em[b2] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[b2]) : 0.0f;   // an empty column needs no rows
+            aH[b2] = (v2f){um[b2] * h0, 0.0f}; aP[b2] = (v2f){um[b2], 0.0f}; aL[b2] = splat(0.0f);   // self
+            bH[b2] = splat(0.0f); bP[b2] = splat(0.0f); bL[b2] = splat(0.0f);
+          }
+          // diagonal block: for own slots a < b, row b is behind column a and row a in front of column b
 #pragma unroll
-  for (int a = 0; a < NS; ++a) { S[a] = 0.0f; rterm[a] = 0.0f; }
-  if (any_e && sorted) {
-    v2f accF[NS], accB[NS], accR[NS];
+          for (int a = 0; a < NS; ++a) {
 #pragma unroll
-    for (int a = 0; a < NS; ++a) { accF[a] = splat(0.0f); accB[a] = splat(0.0f); accR[a] = splat(0.0f); }
-    // diagonal block (registers): for rows a < b, column b is behind row a and column a in front of row b
+            for (int b2 = a + 1; b2 < NS; ++b2) {
+              const float gap = lm[b2] - lm[a];
+              const v2f xp = (v2f){gap * sp[a], gap * sp[b2]};      // (row b, col a), (row a, col b)
+              const v2f g = gauss_pair(xp), h = h_pair(xp);
+              aH[a].y = fmaf(um[b2], h.x, aH[a].y); aP[a].y = fmaf(um[b2], g.x, aP[a].y); aL[a].y = fmaf(um[b2] * g.x, gap, aL[a].y);
+              bH[b2].y = fmaf(um[a], h.y, bH[b2].y); bP[b2].y = fmaf(um[a], g.y, bP[b2].y); bL[b2].y = fmaf(um[a] * g.y, gap, bL[b2].y);
+            }
+          }
+          for (int e = d0 + NS;; e += 2) {     // row pairs behind every own column
+            const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
+            bool need = false;
 #pragma unroll
-    for (int a = 0; a < NS; ++a) {
-      if (!BWD) accF[a].x = em[a] * h0; else accR[a].x = Es[a];         // self
+            for (int b2 = 0; b2 < NS; ++b2) need = need || (l2.x - lm[b2] < rj[b2]);
+            if (!need) break;
 #pragma unroll
-      for (int b2 = a + 1; b2 < NS; ++b2) {
-        const float gap = lm[b2] - lm[a];
-        const v2f xp = (v2f){gap * sp[b2], gap * sp[a]};                 // (row a, col b), (row b, col a)
-        if (!BWD) {
-          const v2f h = h_pair(xp);
-          accB[a].y = fmaf(em[b2], h.x, accB[a].y);
-          accF[b2].y = fmaf(em[a], h.y, accF[b2].y);
+            for (int b2 = 0; b2 < NS; ++b2) {
+              const v2f d = l2 - splat(lm[b2]);
+              const v2f xp = d * splat(sp[b2]);
+              const v2f y = u2 * gauss_pair(xp);
+              aH[b2] = pk_fma(u2, h_pair(xp), aH[b2]); aP[b2] = aP[b2] + y; aL[b2] = pk_fma(y, d, aL[b2]);
+            }
+          }
+          for (int e = d0 - 2;; e -= 2) {      // row pairs in front of every own column
+            const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
+            bool need = false;
+#pragma unroll
+            for (int b2 = 0; b2 < NS; ++b2) need = need || (lm[b2] - l2.y < rj[b2]);
+            if (!need) break;
+#pragma unroll
+            for (int b2 = 0; b2 < NS; ++b2) {
+              const v2f d = splat(lm[b2]) - l2;
+              const v2f xp = d * splat(sp[b2]);
+              const v2f y = u2 * gauss_pair(xp);
+              bH[b2] = pk_fma(u2, h_pair(xp), bH[b2]); bP[b2] = bP[b2] + y; bL[b2] = pk_fma(y, d, bL[b2]);
+            }
+          }
+          float suf = sx;
+#pragma unroll
+          for (int b2 = NS - 1; b2 >= 0; --b2) {
+            suf += um[b2];                                                   // inclusive suffix sum of u
+            cPhi[b2] = (suf - (aH[b2].x + aH[b2].y)) + (bH[b2].x + bH[b2].y);
+            cphi[b2] = ((aP[b2].x + aP[b2].y) + (bP[b2].x + bP[b2].y)) * kRsqrtPi;
+            cphil[b2] = ((aL[b2].x + aL[b2].y) - (bL[b2].x + bL[b2].y)) * kRsqrtPi;
+          }
         } else {
-          const v2f g = gauss_pair(xp);
-          accR[a].y = fmaf(Es[b2], g.x, accR[a].y);
-          accR[b2].y = fmaf(Es[a], g.y, accR[b2].y);
+#pragma unroll
+          for (int b2 = 0; b2 < NS; ++b2) { cPhi[b2] = 0.0f; cphi[b2] = 0.0f; cphil[b2] = 0.0f; }
+          const int r0 = d0 - k0;
+          for (int m = 0; m < K; ++m) {
+            const float ur = Lu[r0 + m];
+            if (ur == 0.0f) continue;
+            const float lr = Llen[r0 + m];
+#pragma unroll
+            for (int b2 = 0; b2 < NS; ++b2) {
+              const float dl = lr - lm[b2];
+              const float xp = dl * sp[b2];
+              const float h = h_one(fabsf(xp));
+              const float xc = fminf(fabsf(xp), 16.0f);
+              const float ph = ur * (__builtin_amdgcn_exp2f(-xc * xc) * kRsqrtPi);
+              cPhi[b2] = fmaf(ur, xp >= 0.0f ? 1.0f - h : h, cPhi[b2]);
+              cphi[b2] += ph;
+              cphil[b2] = fmaf(ph, dl, cphil[b2]);
+            }
+          }
+        }
+#pragma unroll
+        for (int b2 = 0; b2 < NS; ++b2) {
+          if (em[b2] != 0.0f) {
+            ga[b2] = fmaf(occ * em[b2], cPhi[b2], -um[b2]);
+            gl[b2] = -occ * (um[b2] * rterm[b2] - em[b2] * sm[b2] * cphi[b2]);
+            gd[b2] = -occ * em[b2] * (0.5f * __builtin_amdgcn_rcpf(sm[b2])) * cphil[b2];
+          }
         }
       }
-    }
-    float lmB = lm[0];                 // the last live row decides how far back to walk
-#pragma unroll
-    for (int a = 1; a < NS; ++a) lmB = (em[a] != 0.0f) ? lm[a] : lmB;
-    for (int e = d0 - 2;; e -= 2) {      // column pairs in front of every own row; row 0 is the nearest
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(lm[0] - l2.y < rwin)) break;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (splat(lm[a]) - l2) * s2;
-        if (!BWD) accF[a] = pk_fma(E2, h_pair(xa), accF[a]); else accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
-      }
-    }
-    for (int e = d0 + NS;; e += 2) {     // column pairs behind every own row
-      const v2f l2 = ld2(Llen, e), s2 = ld2(Lsp, e), E2 = ld2(LE, e);
-      if (!(l2.x - lmB < rwin)) break;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const v2f xa = (l2 - splat(lm[a])) * s2;
-        if (!BWD) accB[a] = pk_fma(E2, h_pair(xa), accB[a]); else accR[a] = pk_fma(E2, gauss_pair(xa), accR[a]);
-      }
-    }
-    float pre = ex;
-#pragma unroll
-    for (int a = 0; a < NS; ++a) {
-      pre += em[a];                                                     // inclusive prefix sum of E
-      if (!BWD) S[a] = (pre - (accF[a].x + accF[a].y)) + (accB[a].x + accB[a].y);
-      else rterm[a] = (accR[a].x + accR[a].y) * (kRsqrtPi / kCs);
-    }
-  } else if (any_e && active) {          // unsorted list: every column, signs from the data
-    const int r0 = d0 - k0;
-    for (int j = 0; j < K; ++j) {
-      const float Ej = LE[r0 + j];
-      if (Ej == 0.0f) continue;
-      const float lj = Llen[r0 + j], sj = Lsp[r0 + j];
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        const float xp = (lm[a] - lj) * sj;
-        if (!BWD) {
-          const float h = h_one(fabsf(xp));
-          S[a] = fmaf(Ej, xp >= 0.0f ? 1.0f - h : h, S[a]);
+      if (active) {
+        if (vec && NS == 4) {
+          at_bytes_w<float4>(out0, fb) = make_float4(ga[0], ga[1], ga[NS - 2], ga[NS - 1]);
+          at_bytes_w<float4>(out1, fb) = make_float4(gl[0], gl[1], gl[NS - 2], gl[NS - 1]);
+          at_bytes_w<float4>(out2, fb) = make_float4(gd[0], gd[1], gd[NS - 2], gd[NS - 1]);
+        } else if (vec) {
+          at_bytes_w<v2f>(out0, fb) = (v2f){ga[0], ga[1]};
+          at_bytes_w<v2f>(out1, fb) = (v2f){gl[0], gl[1]};
+          at_bytes_w<v2f>(out2, fb) = (v2f){gd[0], gd[1]};
         } else {
-          const float xc = fminf(fabsf(xp), 16.0f);
-          rterm[a] = fmaf(Ej * (kRsqrtPi / kCs), __builtin_amdgcn_exp2f(-xc * xc), rterm[a]);
+#pragma unroll
+          for (int a = 0; a < NS; ++a) if (has[a]) { out0[f + a] = ga[a]; out1[f + a] = gl[a]; out2[f + a] = gd[a]; }
         }
-      }
     }
-  }
-  if (!BWD) {
-    float w[NS];
-#pragma unroll
-    for (int a = 0; a < NS; ++a) w[a] = (em[a] != 0.0f) ? FAST_EXP(-occ * S[a]) * em[a] * kInvNorm : 0.0f;
-    if (active) {
-      if (vec && NS == 4) at_bytes_w<float4>(out0, fb) = make_float4(w[0], w[1], w[NS - 2], w[NS - 1]);
-      else if (vec) at_bytes_w<v2f>(out0, fb) = (v2f){w[0], w[1]};
-      else {
-#pragma unroll
-        for (int a = 0; a < NS; ++a) if (has[a]) out0[f + a] = w[a];
-      }
-      if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)(WAVE ? wave_cnt : L.cnt[p]);
-    }
-    return;
-  }
-  // ---- backward: u = g_w * w, suffix sums, then the lane's own columns --------------------------
-  float um[NS], usum = 0.0f;
-#pragma unroll
-  for (int a = 0; a < NS; ++a) { um[a] = gw[a] * wg[a]; usum += um[a]; }
-  if (in_wg) {
-#pragma unroll
-    for (int h2 = 0; h2 < NP; ++h2) *reinterpret_cast<v2f *>(Lu + d0 + 2 * h2) = (v2f){um[2 * h2], um[2 * h2 + 1]};
-  }
-  float sx = 0.0f;   // sum of u over the slots behind this lane's group
-  if (WAVE) {
-    const float y = __shfl_down(usum, 1, 64);
-    float x = (q + 1 < LP && in_wg) ? y : 0.0f;
-    for (int o = 1; o < LP; o <<= 1) {
-      const float z = __shfl_down(x, o, 64);
-      if (q + o < LP && in_wg) x += z;
-    }
-    sx = x;
-    wave_lds_sync();
-  } else {
-    float(*sf)[kCompThreads] = reinterpret_cast<float(*)[kCompThreads]>(L.scan);
-    sf[0][tid] = usum;
-    __syncthreads();
-    float x = (q + 1 < LP && in_wg) ? sf[0][tid + 1] : 0.0f;
-    int par = 1;
-    for (int o = 1; o < LP; o <<= 1) {
-      sf[par][tid] = x;
-      __syncthreads();
-      if (q + o < LP && in_wg) x += sf[par][tid + o];      // (0 for the pixel's last lane)
-      par ^= 1;
-    }
-    sx = x;
-  }
-  if (!WAVE) __syncthreads();
-  float ga[NS], gl[NS], gd[NS];
-#pragma unroll
-  for (int a = 0; a < NS; ++a) { ga[a] = 0.0f; gl[a] = 0.0f; gd[a] = 0.0f; }
-  if (any_e && active) {
-    float cPhi[NS], cphi[NS], cphil[NS];
-    if (sorted) {
-      float rj[NS];
-      v2f aH[NS], aP[NS], aL[NS], bH[NS], bP[NS], bL[NS];   // per own column: rows behind (a*) / in front (b*)
-#pragma unroll
-      for (int b2 = 0; b2 < NS; ++b2) {
-        rj[b2] = (em[b2] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[b2]) : 0.0f;   // an empty column needs no rows
-        aH[b2] = (v2f){um[b2] * h0, 0.0f}; aP[b2] = (v2f){um[b2], 0.0f}; aL[b2] = splat(0.0f);   // self
-        bH[b2] = splat(0.0f); bP[b2] = splat(0.0f); bL[b2] = splat(0.0f);
-      }
-      // diagonal block: for own slots a < b, row b is behind column a and row a in front of column b
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-#pragma unroll
-        for (int b2 = a + 1; b2 < NS; ++b2) {
-          const float gap = lm[b2] - lm[a];
-          const v2f xp = (v2f){gap * sp[a], gap * sp[b2]};      // (row b, col a), (row a, col b)
-          const v2f g = gauss_pair(xp), h = h_pair(xp);
-          aH[a].y = fmaf(um[b2], h.x, aH[a].y); aP[a].y = fmaf(um[b2], g.x, aP[a].y); aL[a].y = fmaf(um[b2] * g.x, gap, aL[a].y);
-          bH[b2].y = fmaf(um[a], h.y, bH[b2].y); bP[b2].y = fmaf(um[a], g.y, bP[b2].y); bL[b2].y = fmaf(um[a] * g.y, gap, bL[b2].y);
-        }
-      }
-      for (int e = d0 + NS;; e += 2) {     // row pairs behind every own column
-        const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
-        bool need = false;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) need = need || (l2.x - lm[b2] < rj[b2]);
-        if (!need) break;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) {
-          const v2f d = l2 - splat(lm[b2]);
-          const v2f xp = d * splat(sp[b2]);
-          const v2f y = u2 * gauss_pair(xp);
-          aH[b2] = pk_fma(u2, h_pair(xp), aH[b2]); aP[b2] = aP[b2] + y; aL[b2] = pk_fma(y, d, aL[b2]);
-        }
-      }
-      for (int e = d0 - 2;; e -= 2) {      // row pairs in front of every own column
-        const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
-        bool need = false;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) need = need || (lm[b2] - l2.y < rj[b2]);
-        if (!need) break;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) {
-          const v2f d = splat(lm[b2]) - l2;
-          const v2f xp = d * splat(sp[b2]);
-          const v2f y = u2 * gauss_pair(xp);
-          bH[b2] = pk_fma(u2, h_pair(xp), bH[b2]); bP[b2] = bP[b2] + y; bL[b2] = pk_fma(y, d, bL[b2]);
-        }
-      }
-      float suf = sx;
-#pragma unroll
-      for (int b2 = NS - 1; b2 >= 0; --b2) {
-        suf += um[b2];                                                   // inclusive suffix sum of u
-        cPhi[b2] = (suf - (aH[b2].x + aH[b2].y)) + (bH[b2].x + bH[b2].y);
-        cphi[b2] = ((aP[b2].x + aP[b2].y) + (bP[b2].x + bP[b2].y)) * kRsqrtPi;
-        cphil[b2] = ((aL[b2].x + aL[b2].y) - (bL[b2].x + bL[b2].y)) * kRsqrtPi;
-      }
-    } else {
-#pragma unroll
-      for (int b2 = 0; b2 < NS; ++b2) { cPhi[b2] = 0.0f; cphi[b2] = 0.0f; cphil[b2] = 0.0f; }
-      const int r0 = d0 - k0;
-      for (int m = 0; m < K; ++m) {
-        const float ur = Lu[r0 + m];
-        if (ur == 0.0f) continue;
-        const float lr = Llen[r0 + m];
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) {
-          const float dl = lr - lm[b2];
-          const float xp = dl * sp[b2];
-          const float h = h_one(fabsf(xp));
-          const float xc = fminf(fabsf(xp), 16.0f);
-          const float ph = ur * (__builtin_amdgcn_exp2f(-xc * xc) * kRsqrtPi);
-          cPhi[b2] = fmaf(ur, xp >= 0.0f ? 1.0f - h : h, cPhi[b2]);
-          cphi[b2] += ph;
-          cphil[b2] = fmaf(ph, dl, cphil[b2]);
-        }
-      }
-    }
-#pragma unroll
-    for (int b2 = 0; b2 < NS; ++b2) {
-      if (em[b2] != 0.0f) {
-        ga[b2] = fmaf(occ * em[b2], cPhi[b2], -um[b2]);
-        gl[b2] = -occ * (um[b2] * rterm[b2] - em[b2] * sm[b2] * cphi[b2]);
-        gd[b2] = -occ * em[b2] * (0.5f * __builtin_amdgcn_rcpf(sm[b2])) * cphil[b2];
-      }
-    }
-  }
-  if (active) {
-    if (vec && NS == 4) {
-      at_bytes_w<float4>(out0, fb) = make_float4(ga[0], ga[1], ga[NS - 2], ga[NS - 1]);
-      at_bytes_w<float4>(out1, fb) = make_float4(gl[0], gl[1], gl[NS - 2], gl[NS - 1]);
-      at_bytes_w<float4>(out2, fb) = make_float4(gd[0], gd[1], gd[NS - 2], gd[NS - 1]);
-    } else if (vec) {
-      at_bytes_w<v2f>(out0, fb) = (v2f){ga[0], ga[1]};
-      at_bytes_w<v2f>(out1, fb) = (v2f){gl[0], gl[1]};
-      at_bytes_w<v2f>(out2, fb) = (v2f){gd[0], gd[1]};
-    } else {
-#pragma unroll
-      for (int a = 0; a < NS; ++a) if (has[a]) { out0[f + a] = ga[a]; out1[f + a] = gl[a]; out2[f + a] = gd[a]; }
     }
   }
 }
@@ -1049,70 +980,101 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
 
 using namespace voge;
 
-static int launch_composite(int mode, const int32_t *idx, const float *act, const float *len, const float *dsd,
-                            const float *w_in, const float *g_weight, const int32_t *cnt_in, float occ, long npix, int K, float *o0, float *o1,
-                            float *o2, int64_t *valid_num, voge_stream_t stream, const float *rec = nullptr,
-                            const float *rays = nullptr) {
 #ifndef VOGE_COMP_T
 #define VOGE_COMP_T 256
 #endif
-  // workgroup size: the smallest multiple of 64 that is >= VOGE_COMP_T and holds one pixel
-  const int threads = (K <= VOGE_COMP_T) ? VOGE_COMP_T : kCompThreads;
-  hipStream_t st = (hipStream_t)stream;
 #ifndef VOGE_COMP_NS
 #define VOGE_COMP_NS 4
 #endif
-  if (mode != 1) {   // NS slots per lane: 4 when the lists are whole groups of 4, else 2
 #ifndef VOGE_COMP_NS_BWD
 #define VOGE_COMP_NS_BWD 2     // the backward is evaluation-bound, not LDS-bound: 4 slots only cost registers
 #endif
-    const int NS = ((mode == 0 ? VOGE_COMP_NS : VOGE_COMP_NS_BWD) == 4 && (K & 3) == 0) ? 4 : 2;
-    // whole groups (K % NS == 0): the kernel reads and writes 4 NS bytes at a time, so every array it touches that way has to
-    // start on that boundary (include/voge_hip.h).  The forward from the records (voge_composite_fwd_iso) is fed the fragments'
-    // own tensors, like the other one-pass entries, and is not looked at here.
-    if (K % NS == 0 && rec == nullptr) {
-      const void *const wide[] = {act, len, dsd, w_in, g_weight, o0, o1, o2};
-      for (const void *ptr : wide)
-        if (reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)(4 * NS - 1)) return VOGE_ERR_BAD_ARG;
-    }
-    const int LPn = compn_lanes(K, NS);
-    // the barrier-free one-wave-per-pixel form wherever a pixel's lanes fit one wave -- measured (cfg3, one-wave workgroups):
-    // backward 101 -> 87 us, forward 52 -> 50 us (the forward lost 7 us in this form while it still ran as 256-thread workgroups)
-    const bool wavem = LPn <= 64;
 #ifndef VOGE_COMP_WAVE_T
 #define VOGE_COMP_WAVE_T 64     // waves of the barrier-free form never talk to each other: one-wave workgroups schedule finest
                                 // (cfg3 backward: 256 / 128 / 64 threads -> 92.2 / 89.1 / 86.7 us)
 #endif
-    const int tn = wavem ? VOGE_COMP_WAVE_T : kCompThreads;
-    const int ppwn = compn_pixels(K, NS, tn, wavem);
-    const dim3 gridn((unsigned)((npix + ppwn - 1) / ppwn)), blockn(tn);
-    const size_t ldsn = compn_lds_bytes(K, NS, mode != 0, tn, wavem);
-    const bool small = (double)npix * K < (double)(1l << 30);      // every byte offset fits 32 bits
-#define VOGE_LAUNCH_COMPN(M, N, WV)                                                                                     \
-    do {                                                                                                                \
-      if (small)                                                                                                        \
-        hipLaunchKernelGGL((compositen_kernel<M, N, WV, uint32_t>), gridn, blockn, ldsn, st, idx, act, len, dsd, w_in, g_weight,    \
-                           cnt_in, occ, npix, K, ppwn, o0, o1, o2, valid_num, reinterpret_cast<const float4 *>(rec), rays); \
-      else                                                                                                              \
-        hipLaunchKernelGGL((compositen_kernel<M, N, WV, size_t>), gridn, blockn, ldsn, st, idx, act, len, dsd, w_in, g_weight,      \
-                           cnt_in, occ, npix, K, ppwn, o0, o1, o2, valid_num, reinterpret_cast<const float4 *>(rec), rays); \
-    } while (0)
-    if (wavem) {
-      if (mode == 2) { if (NS == 4) VOGE_LAUNCH_COMPN(2, 4, true); else VOGE_LAUNCH_COMPN(2, 2, true); }
-      else { if (NS == 4) VOGE_LAUNCH_COMPN(0, 4, true); else VOGE_LAUNCH_COMPN(0, 2, true); }
-    } else {
-      if (mode == 2) { if (NS == 4) VOGE_LAUNCH_COMPN(2, 4, false); else VOGE_LAUNCH_COMPN(2, 2, false); }
-      else { if (NS == 4) VOGE_LAUNCH_COMPN(0, 4, false); else VOGE_LAUNCH_COMPN(0, 2, false); }
-    }
-#undef VOGE_LAUNCH_COMPN
+
+// How compositen_kernel is launched for (K, npix).  mode 0: forward, 2: backward with the forward's weights.  onepass: the
+// forward from the records with a shade / depth stage -- four slots per lane for every K (a last group may be short).
+struct CompPlan {
+  int NS, lanes, threads, ppw;
+  bool wave, small;
+  dim3 grid;
+  size_t lds;
+};
+static CompPlan comp_plan(const int K, const long npix, const int mode, const bool onepass) {
+  CompPlan P;
+  // NS slots per lane: 4 when the lists are whole groups of 4, else 2
+  P.NS = (onepass || ((mode == 0 ? VOGE_COMP_NS : VOGE_COMP_NS_BWD) == 4 && (K & 3) == 0)) ? 4 : 2;
+  P.lanes = compn_lanes(K, P.NS);
+  // the barrier-free one-wave-per-pixel form wherever a pixel's lanes fit one wave -- measured (cfg3, one-wave workgroups):
+  // backward 101 -> 87 us, forward 52 -> 50 us (the forward lost 7 us in this form while it still ran as 256-thread workgroups)
+  P.wave = P.lanes <= 64;      // (four slots per lane: every K <= VOGE_MAX_K)
+  P.threads = P.wave ? VOGE_COMP_WAVE_T : kCompThreads;
+  P.ppw = compn_pixels(K, P.NS, P.threads, P.wave);
+  P.grid = dim3((unsigned)((npix + P.ppw - 1) / P.ppw));
+  P.lds = compn_lds_bytes(K, P.NS, mode != 0, P.threads, P.wave);
+  P.small = (double)npix * K < (double)(1l << 30);      // every byte offset fits 32 bits
+  return P;
+}
+
+// compositen_kernel's arguments between the plan's and the shade stage's
+struct CompArgs {
+  const int32_t *idx;
+  const float *act, *len, *dsd, *w_in, *g_weight;
+  const int32_t *cnt;
+  float occ;
+  long npix;
+  int K;
+  float *o0, *o1, *o2;
+  int64_t *valid_num;
+  const float *rec, *rays;
+};
+template <int MODE, int NS, bool WAVE, int SC = 0, int GEN = 0>
+static void launch_compn(const CompPlan &P, const CompArgs &A, const CompShade &sh, hipStream_t st) {
+  const float4 *rec = reinterpret_cast<const float4 *>(A.rec);
+  if (P.small)
+    hipLaunchKernelGGL((compositen_kernel<MODE, NS, WAVE, uint32_t, SC, GEN>), P.grid, dim3(P.threads), P.lds, st, A.idx, A.act, A.len,
+                       A.dsd, A.w_in, A.g_weight, A.cnt, A.occ, A.npix, A.K, P.ppw, A.o0, A.o1, A.o2, A.valid_num, rec, A.rays, sh);
+  else
+    hipLaunchKernelGGL((compositen_kernel<MODE, NS, WAVE, size_t, SC, GEN>), P.grid, dim3(P.threads), P.lds, st, A.idx, A.act, A.len,
+                       A.dsd, A.w_in, A.g_weight, A.cnt, A.occ, A.npix, A.K, P.ppw, A.o0, A.o1, A.o2, A.valid_num, rec, A.rays, sh);
+}
+
+static int launch_composite(int mode, const int32_t *idx, const float *act, const float *len, const float *dsd,
+                            const float *w_in, const float *g_weight, const int32_t *cnt_in, float occ, long npix, int K, float *o0, float *o1,
+                            float *o2, int64_t *valid_num, voge_stream_t stream, const float *rec = nullptr,
+                            const float *rays = nullptr) {
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == 1) {   // the one-slot kernel; workgroup size: the smallest multiple of 64 that is >= VOGE_COMP_T and holds one pixel
+    const int threads = (K <= VOGE_COMP_T) ? VOGE_COMP_T : kCompThreads;
+    const int ppw = threads / K;
+    const dim3 grid((unsigned)((npix + ppw - 1) / ppw)), block(threads);
+    hipLaunchKernelGGL(composite_recompute_bwd_kernel, grid, block, comp_lds_bytes(K), st, nullptr, act, len, dsd, nullptr, g_weight,
+                       cnt_in, occ, npix, K, ppw, o0, o1, o2, nullptr);
     return launch_status();
   }
-  // mode 1: the one-slot kernel
-  const int ppw = threads / K;
-  const dim3 grid((unsigned)((npix + ppw - 1) / ppw)), block(threads);
-  const size_t lds = comp_lds_bytes(K, true);
-  hipLaunchKernelGGL(composite_kernel<1>, grid, block, lds, st, idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, ppw, o0,
-                     o1, o2, valid_num);
+  const CompPlan P = comp_plan(K, npix, mode, false);
+  // whole groups (K % NS == 0): the kernel reads and writes 4 NS bytes at a time, so every array it touches that way has to
+  // start on that boundary (include/voge_hip.h).  The forward from the records (voge_composite_fwd_iso) is fed the fragments'
+  // own tensors, like the other one-pass entries, and is not looked at here.
+  if (K % P.NS == 0 && rec == nullptr) {
+    const void *const wide[] = {act, len, dsd, w_in, g_weight, o0, o1, o2};
+    for (const void *ptr : wide)
+      if (reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)(4 * P.NS - 1)) return VOGE_ERR_BAD_ARG;
+  }
+  const CompArgs A{idx, act, len, dsd, w_in, g_weight, cnt_in, occ, npix, K, o0, o1, o2, valid_num, rec, rays};
+  const CompShade sh{};
+  switch ((mode == 2 ? 4 : 0) | (P.NS == 4 ? 2 : 0) | (P.wave ? 1 : 0)) {      // <MODE, NS, WAVE>
+    case 0: launch_compn<0, 2, false>(P, A, sh, st); break;
+    case 1: launch_compn<0, 2, true>(P, A, sh, st); break;
+    case 2: launch_compn<0, 4, false>(P, A, sh, st); break;
+    case 3: launch_compn<0, 4, true>(P, A, sh, st); break;
+    case 4: launch_compn<2, 2, false>(P, A, sh, st); break;
+    case 5: launch_compn<2, 2, true>(P, A, sh, st); break;
+    case 6: launch_compn<2, 4, false>(P, A, sh, st); break;
+    default: launch_compn<2, 4, true>(P, A, sh, st); break;
+  }
   return launch_status();
 }
 
@@ -1139,7 +1101,18 @@ extern "C" int voge_composite_fwd_iso(const int32_t *idx, const int32_t *cnt, co
                           stream, records, rays);
 }
 
-// Composite forward (from the records) with the shade stage in the same pass: weights, valid_num AND the image.
+// The accumulator of the frame's backward is zeroed by the forward's launch on its way (CompShade::zero_p): no fill launch in
+// front of that backward.  More to zero than the launch has threads (once in a blue moon): a fill of its own instead.
+static hipError_t comp_zero_rider(CompShade &sh, const CompPlan &P, void *zero_p, const size_t zero_bytes, hipStream_t st) {
+  if (zero_bytes == 0) return hipSuccess;
+  const long n4 = (long)(zero_bytes / 16);
+  if ((long)P.grid.x * P.threads < n4) return voge_fill_async(zero_p, 0, zero_bytes, st);
+  sh.zero_p = reinterpret_cast<float4 *>(zero_p);
+  sh.zero_n4 = n4;
+  return hipSuccess;
+}
+
+// Composite forward (from the records) with the shade (C = 3, 4) or depth (C = -1) stage in the same pass: weights, valid_num AND the image.
 // gen: the records are the general path's packed (mu, A) (voge_trace_lean_fwd) instead of (mu, a).  C = 0: no shade stage.
 static int composite_shade_fwd_impl(const int gen /* 0: (mu, a) records; 1: packed (mu, A); 2: compact per-axis */, int32_t *idx, const int32_t *cnt, const float *len, const float *records,
                                     const float *rays, float occ, const float *colors, const float *bg, float thr,
@@ -1149,7 +1122,7 @@ static int composite_shade_fwd_impl(const int gen /* 0: (mu, a) records; 1: pack
   if ((act_out == nullptr) != (dsd_out == nullptr)) return VOGE_ERR_BAD_ARG;
   if (zero_bytes > 0 && (!zero_p || C == 0 || (zero_bytes & 15) || (reinterpret_cast<uintptr_t>(zero_p) & 15))) return VOGE_ERR_BAD_ARG;
   if (npix < 0 || K <= 0 || Nattr < 0) return VOGE_ERR_BAD_ARG;
-  if (K > VOGE_MAX_K || (C != 0 && C != 3 && C != 4)) return VOGE_ERR_K_TOO_LARGE;      // four slots per lane (any K: a last group may be short); RGB / RGBA
+  if (K > VOGE_MAX_K || (C != 0 && C != 3 && C != 4 && C != -1)) return VOGE_ERR_K_TOO_LARGE;      // four slots per lane (any K: a last group may be short); RGB / RGBA
   if (npix == 0) return 0;
   // (img == NULL: merge_final + the weight sum only -- interpolate_attr and get_silhouette, no background; bg unused)
   if (!idx || !cnt || !len || !records || !rays || !weight || !valid_num) return VOGE_ERR_BAD_ARG;
@@ -1160,37 +1133,26 @@ static int composite_shade_fwd_impl(const int gen /* 0: (mu, a) records; 1: pack
   //  dereferences nothing of its own)
   if (C > 0 && Nattr == 0) colors = rgb;
   if (Nattr * (C > 0 ? C : 1) >= (1l << 30)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the colour gathers
-  constexpr int NS = 4;
-  const int tn = VOGE_COMP_WAVE_T;
-  const int ppwn = compn_pixels(K, NS, tn, true);
-  const dim3 gridn((unsigned)((npix + ppwn - 1) / ppwn)), blockn(tn);
-  const size_t ldsn = compn_lds_bytes(K, NS, false, tn, true);
-  const bool small = (double)npix * K < (double)(1l << 30);
-  CompShade sh{colors, bg, thr, Nattr, rgb, img, wsum, idx};
-  sh.sil = C > 0 ? sil : nullptr;
-  if (zero_bytes > 0) {
-    sh.zero_p = reinterpret_cast<float4 *>(zero_p); sh.zero_n4 = (long)(zero_bytes / 16);
-    if ((long)gridn.x * tn < sh.zero_n4) {      // (more to zero than the launch has threads: a fill of its own, once in a blue moon)
-      const hipError_t e = voge_fill_async(zero_p, 0, zero_bytes, (hipStream_t)stream);
-      if (e != hipSuccess) return (int)e;
-      sh.zero_p = nullptr; sh.zero_n4 = 0;
-    }
-  }
+  const CompPlan P = comp_plan(K, npix, 0, true);
+  CompShade sh{colors, bg, {thr}, {Nattr}, {rgb}, img, wsum, C < 0 ? nullptr : idx};      // (C = -1: depth_bg, normalize, depth)
+  sh.sil = C != 0 ? sil : nullptr;
+  const hipError_t e = comp_zero_rider(sh, P, zero_p, zero_bytes, (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const CompArgs A{idx, nullptr, len, nullptr, nullptr, nullptr, cnt, occ, npix, K, weight, act_out, dsd_out, valid_num, records, rays};
   hipStream_t st = (hipStream_t)stream;
-  const float4 *rec = reinterpret_cast<const float4 *>(records);
-#define VOGE_LAUNCH_CS(OT, CC, GG)                                                                                           \
-  hipLaunchKernelGGL((compositen_kernel<0, NS, true, OT, CC, GG>), gridn, blockn, ldsn, st, idx, nullptr, len, nullptr, nullptr, nullptr, \
-                     cnt, occ, npix, K, ppwn, weight, act_out, dsd_out, valid_num, rec, rays, sh)
-#define VOGE_LAUNCH_CS2(CC, GG) do { if (small) VOGE_LAUNCH_CS(uint32_t, CC, GG); else VOGE_LAUNCH_CS(size_t, CC, GG); } while (0)
-  if (gen == 2) {
-    if (C == 3) VOGE_LAUNCH_CS2(3, 2); else if (C == 4) VOGE_LAUNCH_CS2(4, 2); else VOGE_LAUNCH_CS2(0, 2);
-  } else if (gen) {
-    if (C == 3) VOGE_LAUNCH_CS2(3, 1); else if (C == 4) VOGE_LAUNCH_CS2(4, 1); else VOGE_LAUNCH_CS2(0, 1);
-  } else {
-    if (C == 3) VOGE_LAUNCH_CS2(3, 0); else if (C == 4) VOGE_LAUNCH_CS2(4, 0); else VOGE_LAUNCH_CS2(0, 0);
+  switch (10 * gen + C) {      // <forward, four slots, wave form, SC, GEN>
+    case -1: launch_compn<0, 4, true, -1, 0>(P, A, sh, st); break;
+    case 0: launch_compn<0, 4, true, 0, 0>(P, A, sh, st); break;
+    case 3: launch_compn<0, 4, true, 3, 0>(P, A, sh, st); break;
+    case 4: launch_compn<0, 4, true, 4, 0>(P, A, sh, st); break;
+    case 10: launch_compn<0, 4, true, 0, 1>(P, A, sh, st); break;
+    case 13: launch_compn<0, 4, true, 3, 1>(P, A, sh, st); break;
+    case 14: launch_compn<0, 4, true, 4, 1>(P, A, sh, st); break;
+    case 20: launch_compn<0, 4, true, 0, 2>(P, A, sh, st); break;
+    case 23: launch_compn<0, 4, true, 3, 2>(P, A, sh, st); break;
+    case 24: launch_compn<0, 4, true, 4, 2>(P, A, sh, st); break;
+    default: return VOGE_ERR_BAD_ARG;      // (the depth stage exists for the (mu, a) records only)
   }
-#undef VOGE_LAUNCH_CS2
-#undef VOGE_LAUNCH_CS
   return launch_status();
 }
 
@@ -1231,29 +1193,11 @@ extern "C" int voge_frame_depth_fwd_iso(const int32_t *idx, const int32_t *cnt, 
   if (bwd_acc_bytes > 0 && ((bwd_acc_bytes & 15) || (reinterpret_cast<uintptr_t>(bwd_acc) & 15))) return VOGE_ERR_BAD_ARG;
   if (npix == 0) return bwd_acc_bytes ? (int)voge_fill_async(bwd_acc, 0, bwd_acc_bytes, (hipStream_t)stream) : 0;      // (no launch to ride on)
   if (!idx || !cnt || !len || !records || !rays || !weight || !valid_num || !depth || !wsum) return VOGE_ERR_BAD_ARG;
-  constexpr int NS = 4;
-  const int tn = VOGE_COMP_WAVE_T;
-  const int ppwn = compn_pixels(K, NS, tn, true);
-  const dim3 gridn((unsigned)((npix + ppwn - 1) / ppwn)), blockn(tn);
-  const size_t ldsn = compn_lds_bytes(K, NS, false, tn, true);
-  CompShade sh{nullptr, nullptr, background, normalize ? 1L : 0L, depth, nullptr, wsum, nullptr};
-  sh.sil = sil;
-  if (bwd_acc_bytes > 0) {
-    sh.zero_p = reinterpret_cast<float4 *>(bwd_acc); sh.zero_n4 = (long)(bwd_acc_bytes / 16);
-    if ((long)gridn.x * tn < sh.zero_n4) {      // (more to zero than the launch has threads: a fill of its own)
-      const hipError_t e = voge_fill_async(bwd_acc, 0, bwd_acc_bytes, (hipStream_t)stream);
-      if (e != hipSuccess) return (int)e;
-      sh.zero_p = nullptr; sh.zero_n4 = 0;
-    }
-  }
-  const float4 *rec = reinterpret_cast<const float4 *>(records);
-  if ((double)npix * K < (double)(1l << 30))
-    hipLaunchKernelGGL((compositen_kernel<0, NS, true, uint32_t, -1, 0>), gridn, blockn, ldsn, (hipStream_t)stream, idx, nullptr, len,
-                       nullptr, nullptr, nullptr, cnt, occ, npix, K, ppwn, weight, nullptr, nullptr, valid_num, rec, rays, sh);
-  else
-    hipLaunchKernelGGL((compositen_kernel<0, NS, true, size_t, -1, 0>), gridn, blockn, ldsn, (hipStream_t)stream, idx, nullptr, len,
-                       nullptr, nullptr, nullptr, cnt, occ, npix, K, ppwn, weight, nullptr, nullptr, valid_num, rec, rays, sh);
-  return launch_status();
+  // (C = -1: rgb = the depth image, Nattr = the normalize flag, thr = the background depth -- CompShade's unions; the stage
+  //  does not write the index list)
+  return composite_shade_fwd_impl(0, const_cast<int32_t *>(idx), cnt, len, records, rays, occ, nullptr, nullptr, background, npix, K, -1,
+                                  normalize ? 1L : 0L, weight, valid_num, depth, nullptr, wsum, stream, nullptr, nullptr, bwd_acc,
+                                  bwd_acc_bytes, sil);
 }
 
 // ... and for the general forms (records = the packed (mu, A) of voge_frame_trace_fwd_gen / voge_trace_lean_fwd; act / dsd kept
