@@ -76,8 +76,10 @@ int voge_trace_pool_usage(const void *workspace, size_t workspace_bytes, int B, 
 
 /*
  * (Not part of this ABI: `voge_debug_sweep_variant(int)` exists in -DVOGE_AB builds only -- voge_amd/libvoge_hip_ab.so, a
- * test artefact that also carries round 3's scalar-sigma sweep for the bit-for-bit comparison in
- * tests/test_gpu_configs.py::test_rebuilt_sweep_equals_round_3_sweep_bit_for_bit.  The product library is stateless.)
+ * test artefact that also carries round 3's sweep (csrc/sweep_r3.h: scalar-sigma and general forms) for the bit-for-bit
+ * comparisons in tests/test_gpu_configs.py, test_rebuilt_sweep_equals_round_3_sweep_bit_for_bit and
+ * test_general_sweep_equals_round_3_general_sweep_bit_for_bit.  The product library is stateless and has no voge_debug_* symbol;
+ * -DVOGE_SWEEP_TIMES / -DVOGE_BIN_TIMES timing builds (tools/) add voge_debug_sweep_times / voge_debug_bin_*.)
  */
 
 /*

@@ -22,7 +22,7 @@ import collections
 dur = collections.defaultdict(list); gap = collections.defaultdict(list); chain = []
 for i, r in enumerate(rows):
     n = short(r["Kernel_Name"])
-    if not any(k in n for k in ("binA", "binB", "trace_fwd_kernel", "sweep_iso")):
+    if not any(k in n for k in ("binA", "binB", "trace_fwd_kernel", "sweep_r3_kernel", "sweep_iso")):
         continue
     s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
     dur[n].append((e - s) / 1e3)

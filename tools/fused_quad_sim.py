@@ -1,6 +1,6 @@
 """What would a fused binB + sweep kernel (one workgroup per 16x16-px quad -- bin phase, then its four tiles swept
 by its four waves) take?  Measured per-workgroup durations of today's two kernels on the same frame (debug build with both timers:
-tools/tune_variants.sh bst:"-DVOGE_BIN_TIMES -DVOGE_SWEEP_STATS"), then a list-scheduling simulation of the fused launch: a quad's
+tools/tune_variants.sh bst:"-DVOGE_BIN_TIMES -DVOGE_SWEEP_TIMES"), then a list-scheduling simulation of the fused launch: a quad's
 workgroup lasts (its binB workgroup's duration) + (its slowest tile's duration) and holds one of `slots` residency slots -- the
 sweep's top-K lists are 17.7 KB of LDS per tile, 71 KB per quad: two quads per CU, 512 slots.  Optimistic: nothing is charged for
 sharing a CU, for the lost heaviest-first tile order inside a quad, or for finding the order.

@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """Is every kernel's machine code body the same at two commits?  (No GPU needed: hipcc emits gfx950 assembly.)
 
-usage: tools/isa_identity.py [-v] [parent-commit, default HEAD] [old=new ...]      (head = the working tree)
+usage: tools/isa_identity.py [-v] [--flags=-DX,-DY] [parent-commit, default HEAD] [old=new ...]      (head = the working tree)
 
 Compiles every unit of voge_amd/csrc/Makefile's SRCS, of both trees, with the product flags to assembly, cuts out every function
 whose label starts with `_ZN4voge`, replaces the function-numbered labels `.LBB<n>_<m>` by `.LBB_<m>` -- a new instantiation in
 front renumbers them -- and compares the bodies line by line, matched by symbol name.  `old=new` (substrings of the mangled
-names) pairs a kernel that was renamed: its own symbol is normalised inside the body too.
+names) pairs a kernel that was renamed: its own symbol is normalised inside the body too.  `--flags=` appends compile flags
+(comma-separated) to both sides: `--flags=-DVOGE_AB` compares the A/B library's units.
 
 Prints one line per unit (`N kernels, all IDENTICAL`; -v: one line per kernel), always the register counts of the six named
 kernels below (the five of tests/test_isa_cpu.py and the wave-form composite + shade the cfg3 frame launches), every differing
@@ -22,6 +23,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+EXTRA = []      # --flags=
 NAMED = ["fragment_bwd_kernelILi0ELi3ELi2EjLb1ELb1ELb0E", "fragment_bwd_kernelILi0ELi4ELi2EjLb1ELb1ELb0E",
          "fragment_bwd_kernelILi1ELi0ELi2EjLb1ELb1ELb0E", "fragment_bwd_kernelILi0ELi3ELi2EjLb0ELb1ELb1E",
          "fragment_bwd_kernelILi0ELi3ELi2EjLb0ELb0ELb0E",
@@ -36,7 +38,7 @@ def units(tree):
 def asm(tree, unit, out):
     csrc = os.path.join(tree, "voge_amd", "csrc")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
-                           "-I" + os.path.join(tree, "include"), "-I" + csrc, "-S", "--offload-device-only", "-o", out,
+                           "-I" + os.path.join(tree, "include"), "-I" + csrc] + EXTRA + ["-S", "--offload-device-only", "-o", out,
                            os.path.join(csrc, unit + ".hip")], stderr=subprocess.DEVNULL)
     return open(out).read()
 
@@ -94,8 +96,9 @@ def compare(unit, par, head, renames, verbose):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "-v"]
-    verbose = len(args) != len(sys.argv) - 1
+    args = [a for a in sys.argv[1:] if a != "-v" and not a.startswith("--flags=")]
+    verbose = "-v" in sys.argv[1:]
+    EXTRA.extend(f for a in sys.argv[1:] if a.startswith("--flags=") for f in a[len("--flags="):].split(",") if f)
     renames = [tuple(a.split("=", 1)) for a in args if "=" in a]
     commits = [a for a in args if "=" not in a]
     parent = commits[0] if commits else "HEAD"

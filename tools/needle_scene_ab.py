@@ -45,7 +45,7 @@ ab = ctx.__enter__()
 ab.voge_debug_sweep_variant.restype, ab.voge_debug_sweep_variant.argtypes = ctypes.c_int, [ctypes.c_int]
 try:
     assert ab.voge_debug_sweep_variant(1) == 0
-    b = timed("round 3's general sweep (trace_fwd_kernel<1, false>, A/B build)")
+    b = timed("round 3's general sweep (sweep_r3_kernel<false>, A/B build)")
 finally:
     ab.voge_debug_sweep_variant(0)
     ctx.__exit__()

@@ -15,4 +15,4 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU" "SQ_INSTS_SALU
 done
 python tools/pmc_summary.py $OUT/sq_1 $OUT/sq_2 $OUT/sq_3 $OUT/sq_4 > $OUT/${TAG}_pmc_sq_counters.txt
 rm -rf $OUT/sq_1 $OUT/sq_2 $OUT/sq_3 $OUT/sq_4
-grep -A17 "trace_fwd_kernel" $OUT/${TAG}_pmc_sq_counters.txt | head -20
+grep -A17 "trace_fwd_kernel\|sweep_r3_kernel" $OUT/${TAG}_pmc_sq_counters.txt | head -20

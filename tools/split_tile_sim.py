@@ -1,5 +1,5 @@
 """What would splitting the sweep's heaviest tiles over two waves buy?  Per-tile durations from the sweep's timers (debug build:
-tools/tune_variants.sh bst:"-DVOGE_BIN_TIMES -DVOGE_SWEEP_STATS"), list-scheduled heaviest-first on the 2 304 one-wave slots of today's
+tools/tune_variants.sh bst:"-DVOGE_BIN_TIMES -DVOGE_SWEEP_TIMES"), list-scheduled heaviest-first on the 2 304 one-wave slots of today's
 kernel; a tile longer than T becomes two jobs of (share x duration + merge) each.  The shares are the model's assumption: a half walks
 `share` of the whole tile's depth (0.5 = a perfect shared exit bound; 1.0 = each half walks as deep as the whole, no gain).
 usage (GPU box): VOGE_HIP_LIB=build/variants/bst.so [FULL=1] python tools/split_tile_sim.py"""

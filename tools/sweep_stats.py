@@ -1,4 +1,5 @@
-"""Counters of the forward sweep (debug build: tools/tune_variants.sh stats:"-DVOGE_SWEEP_STATS").
+"""Per-tile timestamps of the forward sweep, sweep_iso_kernel (timing build: tools/tune_variants.sh stats:"-DVOGE_SWEEP_TIMES";
+SLOW=1 with "-DVOGE_SWEEP_TIMES -DVOGE_SWEEP_SLOW": the list insertions as well).
 usage on the GPU box: VOGE_HIP_LIB=build/variants/stats.so python tools/sweep_stats.py [config]"""
 import ctypes
 import sys
@@ -23,8 +24,6 @@ settings = GaussianRenderSettings(image_size=(H, W), max_assign=K, thr_activatio
                                   max_point_per_bin=-1)
 renderer = GaussianRenderer(cams, settings).to(dev)
 lib = _lib.load()
-out = (ctypes.c_ulonglong * 16)()
-ctypes.CDLL(_lib.LIB_PATH).voge_debug_sweep_stats(out)
 FULL = bool(os.environ.get("FULL"))      # FULL=1: the stand-alone trace entry point (idx, len, act, dsd) instead of the renderer's
 if FULL:
     import math
@@ -43,20 +42,12 @@ with torch.no_grad():
     for _ in range(3):
         frag = run()
     torch.cuda.synchronize()
-    ctypes.CDLL(_lib.LIB_PATH).voge_debug_sweep_stats(out)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     frag = run()
     e1.record()
 torch.cuda.synchronize()
 print('renderer forward (events) us', e0.elapsed_time(e1) * 1000)
-ctypes.CDLL(_lib.LIB_PATH).voge_debug_sweep_stats(out)
-names = ["waves", "staged(per WG)", "evaluated(per wave sum)", "trips", "slow_entries", "slow_shift_steps(wave max sum)",
-         "hits(lane sum)", "list_len(per WG sum)", "list_consumed", "batches"]
-v = list(out)
-for n, x in zip(names, v):
-    print(f"{n:36s} {x:14d}   per wave {x / max(v[0], 1):10.1f}")
-print("rays", H * W, "hits per ray", v[6] / (H * W), "evals per ray (wave evals)", v[2] * 64 / (H * W))
 
 import numpy as np
 nwg = ((W + 7) // 8) * ((H + 7) // 8)

@@ -570,7 +570,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
         }
       }
     } else {
-      // forward, wave form: the row pass shared with round 3's fused sweep epilogue (composite_core.h)
+      // forward, wave form: the row pass (composite_core.h)
       float w[NS];
       compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, active, active && !wave_unsorted, seg_lo, occ, w);
       if (active) {

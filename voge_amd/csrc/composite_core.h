@@ -1,8 +1,7 @@
 // Shared pieces of the depth-ordered compositing (VoGE/Aggregation.py:30-107): constants, the erfc / Gaussian
 // evaluators, the LDS row layout, and the forward row pass of the lane-owns-NS-slots form.  Used by composite.hip
-// (voge_composite_fwd / _bwd) and by the fused epilogue of round 3's sweep in trace_fwd.hip (-DVOGE_AB builds; measured
-// and not used: HISTORY.md §5): ONE implementation, so fragments composited inside the sweep are bit-identical to the
-// stand-alone kernel's.
+// (voge_composite_fwd / _bwd) and fragment_bwd.hip; sweep_iso.h takes pk_fma and splat from here.  (Round 3's sweep once
+// composited inside its epilogue through this header -- measured and not used, HISTORY.md §5; that epilogue is gone.)
 #pragma once
 #include "voge_common.h"
 

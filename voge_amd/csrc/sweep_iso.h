@@ -1,5 +1,5 @@
 // Round 4: the scalar-sigma sweep, rebuilt around what round 3's per-tile timers and a VALU / LDS issue micro-benchmark
-// (tools/valu_bench.hip, profiles/r4_valu_bench.txt) said about the old kernel (trace_fwd_kernel<1, true>):
+// (tools/valu_bench.hip, profiles/r4_valu_bench.txt) said about the old kernel (then trace_fwd_kernel<1, true>; what is left of it: sweep_r3.h, the A/B build's oracle):
 //   * a tile spends two thirds of its life in the consume loop, ~160 ns per candidate at 1.75 waves per SIMD: ~27 VALU +
 //     ~14 SALU + 3 LDS instructions, of which the 64-bit (ord(len) << 32 | id) keys cost the most (key building, two 64-bit
 //     compares at ~2x the price of a float compare, register pairs through every select);
@@ -30,8 +30,8 @@ struct Sweep2Stage {
   };
   int pos[64 + kS2Pad];      // the staged entries' handles: Gaussian id, or position in the tile's stream (see h_is_id)
 };
-__host__ __device__ inline size_t sweep2_len_bytes(const int K) { return (sizeof(float) * (size_t)(K + 1) * kS2TP + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t sweep2_pos_bytes(const int K) { return (sizeof(uint16_t) * (size_t)(K + 1) * kS2TQ + 15) & ~(size_t)15; }
+__host__ __device__ constexpr size_t sweep2_len_bytes(const int K) { return (sizeof(float) * (size_t)(K + 1) * kS2TP + 15) & ~(size_t)15; }
+__host__ __device__ constexpr size_t sweep2_pos_bytes(const int K) { return (sizeof(uint16_t) * (size_t)(K + 1) * kS2TQ + 15) & ~(size_t)15; }
 // GEN (full 3x3 forms, round 5): the staged chunk's eleven further coefficients of pair_eval_gen's record -- s11, s22, s01, s02,
 // s12, b (3), k (3); s00 sits in Sweep2Stage::a, where an isotropic candidate keeps its a -- SoA like the rest.  e[0][i]
 // (s11) is NaN for a staged ISOTROPIC candidate (and for the padding): that is how the consume loop tells the two apart.
@@ -40,7 +40,7 @@ struct Sweep2Gen {
 };
 // gen: 0 scalar sigmas, 1 general forms (eleven coefficient arrays), 2 a launch of per-axis forms only (five: s11, s22, b)
 constexpr int kS2DiagRows = 5;
-__host__ __device__ inline size_t sweep2_lds_bytes(const int K, const int gen = 0) {
+__host__ __device__ constexpr size_t sweep2_lds_bytes(const int K, const int gen = 0) {
   return sweep2_len_bytes(K) + sweep2_pos_bytes(K) + sizeof(Sweep2Stage) +
          (gen == 1 ? sizeof(Sweep2Gen) : (gen == 2 ? sizeof(float) * kS2DiagRows * (64 + kS2Pad) : 0));
 }

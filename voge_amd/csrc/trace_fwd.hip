@@ -227,816 +227,13 @@ iso_prep_kernel(const float *__restrict__ mus, const float *__restrict__ isg, co
   ms[(size_t)b * N + g] = make_float4(c.x, c.y, c.z, a);
 }
 
-// ------------------------------------------------------------------------------------------
-// sweep.  One workgroup = WAVES waves = a TW x TH pixel tile (each wave an 8x8 sub-tile, one
-// ray per lane).  Its candidate stream is the sorted list of its super-tile (or, if that bin
-// overflowed, every Gaussian of the batch element), read in chunks of T:
-//   fill   : thread i gathers the cull record of stream entry base+i and tests it against the
-//            workgroup's bounding cone; survivors are compacted IN ORDER into LDS together with
-//            their eval record and len bound;
-//   consume: each wave re-tests the survivors against its own 8x8 cone, 64 at a time (one per
-//            lane, ballot), then for every remaining candidate all 64 lanes evaluate their ray
-//            against it (record broadcast from LDS) and insert into their LDS top-K list.
-//   exit   : once every lane of a wave holds K hits and the next candidate's len bound exceeds
-//            the wave's largest kept len, nothing later in the (sorted) stream can enter.
-// Both culls and the exit test are conservative, so the result equals the brute-force sweep.
-// The epilogue re-maps lanes to (pixel, slot) so that all four outputs are written as
-// contiguous runs of TW*K floats.
-// ------------------------------------------------------------------------------------------
-#ifdef VOGE_SWEEP_STATS
-#define VOGE_SWEEP_TIMES 1
-#endif
-#ifdef VOGE_SWEEP_TIMES
-__device__ unsigned long long g_sweep_stats[16];
+#ifdef VOGE_SWEEP_TIMES      // timing builds only (tools/sweep_stats.py): sweep_iso_kernel's per-tile stamps, read by voge_debug_sweep_times
 __device__ unsigned long long g_sweep_times[8192 * 8];   // per WG: start, after cones, fill sum, consume sum, loop end, end, evals, smid
 #endif
-#ifndef VOGE_TRIP
-#define VOGE_TRIP 4
-#endif
-constexpr int kTrip = VOGE_TRIP;   // candidates evaluated per trip of the sweep's inner loop
 
 }  // namespace voge
 #include "sweep_iso.h"      // round 4's scalar-sigma sweep (sweep_iso_kernel)
 namespace voge {
-
-template <int T, bool ISO>
-struct TraceLds {
-  // layout inside dynamic LDS, after the [K][T+1] key array.  ISO (the scalar-sigma entry point: every
-  // candidate is isotropic) stages no full records; with the K = 40 key array that is 22.9 KB per
-  // single-wave workgroup -- seven of them per CU instead of six.
-  float4 cull[T > 64 ? T : 1];   // (mu, reach): the per-wave re-test of multi-wave tiles only
-  float4 ms[T];         // (mu, s00 | NaN): all an isotropic evaluation needs
-  float4 ev[ISO ? 1 : T * 3];    // full eval record, staged for anisotropic candidates only
-  int32_t id[T];        // candidate ids of the staged chunk; per-ray hit counts during the epilogue
-  float lb[T];
-  float red[(T / 64) * 8];
-  int wcnt[2][4];
-  int done;
-};
-
-template <int WAVES, bool ISO>
-__global__ void __launch_bounds__(64 * WAVES)
-trace_fwd_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ evr,
-                 const float4 *__restrict__ ms, const float *__restrict__ rays, const int *__restrict__ bin_count,
-                 const int32_t *__restrict__ bin_id, const float *__restrict__ bin_lb,
-                 const int *__restrict__ tl_count, const int32_t *__restrict__ tl_id,
-                 const float *__restrict__ tl_lb, const int32_t *__restrict__ pool_id, const float *__restrict__ pool_lb,
-                 const int *__restrict__ tl_off, const int2 *__restrict__ order, const int tiles_per_img,
-                 const int nstx, const int nst,
-                 const int N, const int H,
-                 const int W, const int K, const float thr_act, int32_t *__restrict__ out_idx,
-                 float *__restrict__ out_len, float *__restrict__ out_act, float *__restrict__ out_dsd,
-                 int32_t *__restrict__ out_cnt, const float occ, float *__restrict__ out_weight,
-                 int64_t *__restrict__ out_valid) {
-  constexpr int T = 64 * WAVES;
-  constexpr int TP = T + 1;   // key row stride: the transposed epilogue read stays conflict-light
-  constexpr int TW = (WAVES >= 2) ? 16 : 8;
-  constexpr int TH = (WAVES == 4) ? 16 : 8;
-  constexpr int kCap = T;     // one chunk of the candidate stream is staged at a time
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint64_t *keys = reinterpret_cast<uint64_t *>(smem_raw);
-  TraceLds<T, ISO> &L = *reinterpret_cast<TraceLds<T, ISO> *>(smem_raw + ((sizeof(uint64_t) * (size_t)(K + 1) * TP + 15) & ~(size_t)15));
-
-#ifdef VOGE_SWEEP_TIMES
-  const unsigned long long ts0 = wall_clock64();
-  unsigned long long ts_fill = 0, ts_cons = 0;
-#endif
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles_x = (W + TW - 1) / TW;
-  // Heavy tiles first: workgroup i takes slot i % 16 of the super-tile with launch rank i / 16 (binB: super-tiles by
-  // descending candidate count, inside them quad by quad, a quad's tiles by descending list length).  The sweep lasts as long as its longest
-  // tile, so that one must not start late; everything shorter fills in behind it.
-  const int2 slot = order[blockIdx.x];               // (tile [| kPoolFlag], length of its list | -1 = overflowed)
-  if (slot.x < 0 || slot.y == 0) return;             // outside the image | nothing can hit it: binB wrote its outputs
-  const bool pooled = (slot.x & kPoolFlag) != 0;     // a long list (binB's long path): it lives in the pool
-  const int lin = slot.x & ~kPoolFlag;
-  const int b = lin / tiles_per_img, bx = lin - b * tiles_per_img;
-  const int tx = bx % tiles_x, ty = bx / tiles_x;
-  const int px = tx * TW + (wave & 1) * 8 * (TW == 16) + (lane & 7);
-  const int py = ty * TH + (wave >> 1) * 8 + (lane >> 3);
-  const bool valid = (px < W) && (py < H);
-  const int cpx = min(px, W - 1), cpy = min(py, H - 1);
-  const size_t ray_id = ((size_t)b * H + cpy) * W + cpx;
-  const float dx = rays[3 * ray_id + 0], dy = rays[3 * ray_id + 1], dz = rays[3 * ray_id + 2];
-  const float qxx = dx * dx, qyy = dy * dy, qzz = dz * dz, qxy = dx * dy, qxz = dx * dz, qyz = dy * dz;
-  if (tid == 0) L.done = 0;
-
-  // ---- bounding cones (wave, then workgroup) ---------------------------------------------
-  const RayDir u = ray_dir(dx, dy, dz);
-  const bool wave_dirs_ok = __all(u.ok);
-  const bool unit_rays = __all(!u.ok || u.unit);
-  const float wsx = wave_sum_dpp(u.ok ? u.ux : 0.f), wsy = wave_sum_dpp(u.ok ? u.uy : 0.f), wsz = wave_sum_dpp(u.ok ? u.uz : 0.f);
-  Cone wcone, gcone;
-  {
-    const float n = sqrtf(fmaf(wsz, wsz, fmaf(wsy, wsy, wsx * wsx)));
-    const float ax = wsx / n, ay = wsy / n, az = wsz / n;
-    float smax = 0.f, cmin = 1.f;
-    cone_partial(u, ax, ay, az, smax, cmin);
-    wcone = cone_finish(ax, ay, az, n, wave_max(smax), wave_min(cmin), wave_dirs_ok);
-    gcone = wcone;
-  }
-  if (WAVES > 1) {
-    if (lane == 0) {
-      L.red[wave * 8 + 0] = wsx; L.red[wave * 8 + 1] = wsy; L.red[wave * 8 + 2] = wsz;
-      L.red[wave * 8 + 3] = wave_dirs_ok ? 1.f : 0.f;
-    }
-    __syncthreads();
-    float gx = 0, gy = 0, gz = 0; bool gok = true;
-    for (int w = 0; w < WAVES; ++w) {
-      gx += L.red[w * 8 + 0]; gy += L.red[w * 8 + 1]; gz += L.red[w * 8 + 2];
-      gok = gok && (L.red[w * 8 + 3] != 0.f);
-    }
-    const float n = sqrtf(fmaf(gz, gz, fmaf(gy, gy, gx * gx)));
-    const float ax = gx / n, ay = gy / n, az = gz / n;
-    float smax = 0.f, cmin = 1.f;
-    cone_partial(u, ax, ay, az, smax, cmin);
-    smax = wave_max(smax); cmin = wave_min(cmin);
-    if (lane == 0) { L.red[wave * 8 + 4] = smax; L.red[wave * 8 + 5] = cmin; }
-    __syncthreads();
-    for (int w = 0; w < WAVES; ++w) { smax = fmaxf(smax, L.red[w * 8 + 4]); cmin = fminf(cmin, L.red[w * 8 + 5]); }
-    gcone = cone_finish(ax, ay, az, n, smax, cmin, gok);
-  } else {
-    __syncthreads();
-  }
-
-#ifdef VOGE_SWEEP_TIMES
-  const unsigned long long ts1 = wall_clock64();
-#endif
-  // ---- candidate stream of this tile -----------------------------------------------------
-  // tile list (bin2) -> super-tile list (bin) -> every Gaussian of the batch element
-  const int tile = lin;
-  // (fallback of an overflowed tile list: the ordered list of the tile's 16x16-pixel quad, which binB then spilled)
-  const int bin = (b * nst + ((ty * TH) / kST) * nstx + (tx * TW) / kST) * 4 + (((ty * TH) / kQuad) & 1) * 2 + (((tx * TW) / kQuad) & 1);
-  const int tc = slot.y;
-  const int bc = (tc >= 0) ? tc : ((bin_count != nullptr) ? bin_count[bin] : -1);
-  const bool binned = bc >= 0;
-  const int src_n = binned ? bc : N;
-  const size_t list_at = pooled ? (size_t)tl_off[tile] : (size_t)tile * kTileCap;
-  const int32_t *src_id = (tc >= 0) ? (pooled ? pool_id : tl_id) + list_at : (binned ? bin_id + (size_t)bin * kQCap : nullptr);
-  const float *src_lb = (tc >= 0) ? (pooled ? pool_lb : tl_lb) + list_at : (binned ? bin_lb + (size_t)bin * kQCap : nullptr);
-  const float4 *cullb = cull + (size_t)b * N;
-  const float4 *evrb = evr + (size_t)b * N * 3;
-  const float4 cull_none = make_float4(0.f, 0.f, 0.f, -1.f);
-  auto load_id = [&](int g) { return (g < src_n) ? (binned ? src_id[g] : g) : -1; };
-  auto load_lb = [&](int g) { return (binned && g < src_n) ? src_lb[g] : -INFINITY; };
-  auto load_rec = [&](int id) { return (id >= 0) ? cullb[id] : cull_none; };
-  const float4 *msb = ms + (size_t)b * N;
-  auto load_ms = [&](int id) { return (id >= 0) ? msb[id] : cull_none; };
-  // the tile's own list was already filtered with this tile's cone (bin2): no second test
-  const bool prefiltered = (WAVES == 1) && (tc >= 0);
-
-  uint64_t *mykeys = keys + tid;
-  int cnt = 0;
-  uint64_t worst = valid ? ((uint64_t)f2ord(VOGE_SENT_LEN) << 32) : 0ull, tail = 0ull;
-  bool wdone = false, reported = false;
-#ifdef VOGE_SWEEP_STATS
-  unsigned st_staged = 0, st_eval = 0, st_trips = 0, st_slow = 0, st_shift = 0, st_hits = 0, st_batches = 0;
-#endif
-
-  int base = 0, par = 0;
-  // two-deep software pipeline: ids two chunks ahead, cull / ms records one chunk ahead
-  int id0 = load_id(tid);
-  float lb0 = load_lb(tid);
-  float4 c0r = prefiltered ? cull_none : load_rec(id0);
-  float4 m0r = load_ms(id0);
-  int id1 = load_id(T + tid);
-  float lb1 = load_lb(T + tid);
-  bool tile_gen = false;      // an anisotropic candidate was staged at some point (workgroup-uniform)
-  while (base < src_n) {
-    int nbuf = 0;
-    bool chunk_iso = true;   // every staged candidate of this buffer is isotropic (wave-uniform)
-    bool chunk_gen = !ISO;   // ... or every one is anisotropic
-#ifdef VOGE_SWEEP_TIMES
-    const unsigned long long tsa = wall_clock64();
-#endif
-    while (base < src_n && nbuf + T <= kCap) {
-      const int id = id0;
-      const float lbv = lb0;
-      const float4 c = c0r;
-      const float4 mrec = m0r;
-      id0 = id1; lb0 = lb1;
-      c0r = prefiltered ? cull_none : load_rec(id0);
-      m0r = load_ms(id0);
-      id1 = load_id(base + 2 * T + tid);
-      lb1 = load_lb(base + 2 * T + tid);
-      const bool keep = prefiltered ? (id >= 0) : cone_keep(c, gcone);
-      const unsigned long long m = __ballot(keep);
-      if (!ISO) {
-        chunk_iso = chunk_iso && __all(!keep || (mrec.w == mrec.w));
-        chunk_gen = chunk_gen && __all(!keep || !(mrec.w == mrec.w));
-      }
-      if (lane == 0) L.wcnt[par][wave] = __popcll(m);
-      __syncthreads();
-      int off = nbuf, tot = 0;
-#pragma unroll
-      for (int w = 0; w < WAVES; ++w) {
-        const int cw = L.wcnt[par][w];
-        if (w < wave) off += cw;
-        tot += cw;
-      }
-      if (keep) {
-        const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
-        if (WAVES > 1) L.cull[slot] = c;
-        L.ms[slot] = mrec;
-        L.id[slot] = id;
-        L.lb[slot] = lbv;
-        if (!ISO && !(mrec.w == mrec.w)) {   // anisotropic: the full record (dependent gather, not prefetched)
-          L.ev[slot * 3 + 0] = evrb[(size_t)id * 3 + 0];
-          L.ev[slot * 3 + 1] = evrb[(size_t)id * 3 + 1];
-          L.ev[slot * 3 + 2] = evrb[(size_t)id * 3 + 2];
-        }
-      }
-      nbuf += tot;
-      base += T;
-      par ^= 1;
-    }
-#ifdef VOGE_SWEEP_STATS
-    st_staged += nbuf;
-#endif
-    tile_gen = tile_gen || !chunk_iso;
-    __syncthreads();
-#ifdef VOGE_SWEEP_TIMES
-    const unsigned long long tsb = wall_clock64();
-    ts_fill += tsb - tsa;
-#endif
-    // consume
-    if (!wdone) {
-      for (int c0 = 0; c0 < nbuf && !wdone; c0 += 64) {
-        const int i = c0 + lane;
-        bool keep = false;
-        if (i < nbuf) keep = (WAVES == 1) ? true : cone_keep(L.cull[i], wcone);
-        unsigned long long m = __ballot(keep);
-        // Exit test, once per 64-candidate batch.  The bound is refreshed here only: a stale
-        // (larger) bound merely delays the exit, because a lane's worst key only ever decreases.
-        // The list bounds are monotone, so "first candidate past the bound" cuts the batch.
-        bool last_batch = false;
-        if (binned && unit_rays && __all(!valid || cnt == K)) {
-          const float wmax = wave_max(valid ? ord2f((uint32_t)(worst >> 32)) : -INFINITY);
-          const unsigned long long ex = __ballot(i < nbuf && L.lb[i] > wmax);
-          if (ex) {
-            m &= (1ull << __builtin_ctzll(ex)) - 1ull;
-            last_batch = true;
-          }
-        }
-        // (gid = the candidate's global id, read from L.id by the caller: the fast loops fetch the ids of a
-        // trip together with its records, so no LDS latency sits between two commits)
-        auto commit = [&](const PairOut &o, const int gid, const bool on) {
-          const uint64_t key = ((uint64_t)f2ord(o.len) << 32) | (uint32_t)gid;
-          // (rays outside the image start with worst = 0, the others with the key of len = 1e10: `key < worst`
-          // also says "a ray of the image" and "len below the sentinel")
-          const bool take = on & (o.act < thr_act) & (key < worst);
-#ifdef VOGE_SWEEP_STATS
-          {
-            const bool app = take && (cnt < K) && (key >= tail);
-            const bool slow = take && !app;
-            st_hits += __popcll(__ballot(take));
-            if (__any(slow)) {
-              ++st_slow;
-              int steps = 0;
-              if (slow) { int pos = min(cnt, K - 1); while (pos > 0 && mykeys[(pos - 1) * TP] > key) { --pos; ++steps; } }
-              st_shift += (unsigned)wave_max((float)steps);
-            }
-          }
-#endif
-          topk_commit<!ISO>(mykeys, TP, K, cnt, worst, tail, key, take);
-        };
-#ifdef VOGE_SWEEP_STATS
-        st_eval += __popcll(m); ++st_batches;
-#endif
-        if (WAVES == 1 && chunk_iso) {
-          // Single-wave tile, all-isotropic chunk (the common case): the surviving candidates are
-          // the contiguous range [c0, c0 + n) -- no bit scanning, no per-candidate isotropy test.
-          const int s_end = c0 + __popcll(m);
-          for (int s0 = c0; s0 < s_end; s0 += kTrip) {
-#ifdef VOGE_SWEEP_STATS
-            ++st_trips;
-#endif
-            float4 cc[kTrip];
-            int gid[kTrip];
-            PairOut o[kTrip];
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) {
-              cc[q] = L.ms[min(s0 + q, s_end - 1)];
-              gid[q] = L.id[min(s0 + q, s_end - 1)] + b * N;
-            }
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q)
-              o[q] = pair_eval_iso(cc[q].x, cc[q].y, cc[q].z, cc[q].w, dx, dy, dz, qxx, qyy, qzz);
-            // The evaluations must finish as one block of four interleaved chains: without this
-            // the compiler sinks each one behind its own commit's predicate and the wave (alone on
-            // its SIMD) runs four dependent chains back to back.
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) asm volatile("" : "+v"(o[q].len), "+v"(o[q].act));
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) commit(o[q], gid[q], s0 + q < s_end);
-          }
-          m = 0ull;
-        } else if (!ISO && WAVES == 1 && chunk_gen) {
-          // the same contiguous-range loop for an all-anisotropic chunk (full records from LDS)
-          const int s_end = c0 + __popcll(m);
-          for (int s0 = c0; s0 < s_end; s0 += kTrip) {
-#ifdef VOGE_SWEEP_STATS
-            ++st_trips;
-#endif
-            PairOut o[kTrip];
-            int gid[kTrip];
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) {
-              const int sidx = min(s0 + q, s_end - 1);
-              const float4 cc = L.ms[sidx];
-              gid[q] = L.id[sidx] + b * N;
-              o[q] = pair_eval_gen(cc.x, cc.y, cc.z, unpack_eval(L.ev[sidx * 3], L.ev[sidx * 3 + 1], L.ev[sidx * 3 + 2]), dx, dy,
-                                   dz, qxx, qyy, qzz, qxy, qxz, qyz);
-            }
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) asm volatile("" : "+v"(o[q].len), "+v"(o[q].act));
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) commit(o[q], gid[q], s0 + q < s_end);
-          }
-          m = 0ull;
-        }
-        while (m) {
-#ifdef VOGE_SWEEP_STATS
-          ++st_trips;
-#endif
-          // four candidates per trip: their evaluations are independent instruction streams
-          int sq[kTrip];
-          int nt = 0;
-#pragma unroll
-          for (int q = 0; q < kTrip; ++q) {
-            sq[q] = c0 + (m ? __builtin_ctzll(m) : 0);
-            if (m) { ++nt; m &= m - 1ull; }
-          }
-          // The four evaluations form ONE straight-line block (the isotropic / general choice is
-          // made per batch, on scalar registers), so the scheduler interleaves their chains.
-          PairOut o[kTrip];
-          float4 cc[kTrip], e0[kTrip];
-          int gid[kTrip];
-          bool iso = true, any_iso = false;
-          bool fiso[kTrip];
-#pragma unroll
-          for (int q = 0; q < kTrip; ++q) {
-            cc[q] = L.ms[sq[q]];
-            gid[q] = L.id[sq[q]] + b * N;
-            const bool f = fiso[q] = (__builtin_amdgcn_readfirstlane(__float_as_uint(cc[q].w)) & 0x7fffffffu) <= 0x7f800000u;
-            iso = iso && f;
-            any_iso = any_iso || f;
-          }
-          if (ISO || iso) {
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q)
-              o[q] = pair_eval_iso(cc[q].x, cc[q].y, cc[q].z, cc[q].w, dx, dy, dz, qxx, qyy, qzz);
-          } else {
-            float4 e1[kTrip], e2[kTrip];
-#pragma unroll
-            for (int q = 0; q < kTrip; ++q) {
-              e0[q] = L.ev[sq[q] * 3]; e1[q] = L.ev[sq[q] * 3 + 1]; e2[q] = L.ev[sq[q] * 3 + 2];
-            }
-            if (!any_iso) {
-#pragma unroll
-              for (int q = 0; q < kTrip; ++q)
-                o[q] = pair_eval_gen(cc[q].x, cc[q].y, cc[q].z, unpack_eval(e0[q], e1[q], e2[q]), dx, dy, dz, qxx, qyy,
-                                     qzz, qxy, qxz, qyz);
-            } else {  // mixed batch: per-candidate dispatch (same arithmetic, just not interleaved)
-#pragma unroll
-              for (int q = 0; q < kTrip; ++q) {
-                if (fiso[q])   // uniform: the flag came through readfirstlane
-                  o[q] = pair_eval_iso(cc[q].x, cc[q].y, cc[q].z, cc[q].w, dx, dy, dz, qxx, qyy, qzz);
-                else
-                  o[q] = pair_eval_gen(cc[q].x, cc[q].y, cc[q].z, unpack_eval(e0[q], e1[q], e2[q]), dx, dy, dz, qxx, qyy,
-                                       qzz, qxy, qxz, qyz);
-              }
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < kTrip; ++q) commit(o[q], gid[q], q < nt);
-        }
-        if (last_batch) wdone = true;
-      }
-    }
-#ifdef VOGE_SWEEP_TIMES
-    ts_cons += wall_clock64() - tsb;
-#endif
-    if (wdone && !reported) {
-      reported = true;
-      if (lane == 0) atomicAdd(&L.done, 1);
-    }
-    __syncthreads();
-    if (L.done == WAVES) break;
-  }
-
-#ifdef VOGE_SWEEP_TIMES
-  const unsigned long long ts2 = wall_clock64();
-#endif
-#ifdef VOGE_SWEEP_STATS
-  if (lane == 0) {
-    atomicAdd(&g_sweep_stats[0], 1ull);
-    atomicAdd(&g_sweep_stats[1], (unsigned long long)(wave == 0 ? st_staged : 0));
-    atomicAdd(&g_sweep_stats[2], (unsigned long long)st_eval);
-    atomicAdd(&g_sweep_stats[3], (unsigned long long)st_trips);
-    atomicAdd(&g_sweep_stats[4], (unsigned long long)st_slow);
-    atomicAdd(&g_sweep_stats[5], (unsigned long long)st_shift);
-    atomicAdd(&g_sweep_stats[6], (unsigned long long)st_hits);
-    atomicAdd(&g_sweep_stats[7], (unsigned long long)(wave == 0 ? src_n : 0));
-    atomicAdd(&g_sweep_stats[8], (unsigned long long)(wave == 0 ? min(base, src_n) : 0));
-    atomicAdd(&g_sweep_stats[9], (unsigned long long)st_batches);
-  }
-#endif
-  // ---- epilogue: lanes re-mapped to (pixel, slot); act / dsd recomputed with pair_eval ------
-  __syncthreads();            // every wave is done with the staged ids: the array now holds the hit counts
-  L.id[tid] = cnt;
-#ifdef VOGE_SWEEP_TIMES
-  const int cnt_dbg = (int)__popcll(__ballot(cnt > 0));   // rays of the tile with at least one hit
-#endif
-  if (out_cnt != nullptr && valid) out_cnt[((size_t)b * H + py) * W + px] = cnt;
-  __syncthreads();
-  const int tw = min(TW, W - tx * TW);
-  const int row_items = tw * K;
-  auto slot_value = [&](const int r, const int x, const int s, const size_t pix, int32_t &oi, float &ol, float &oa,
-                        float &od) {
-    const int owner = ((x >> 3) + (TW / 8) * (r >> 3)) * 64 + (x & 7) + 8 * (r & 7);
-    oi = -1; ol = VOGE_SENT_LEN; oa = VOGE_SENT_ACT; od = 0.0f;
-    if (s < L.id[owner]) {
-      const uint64_t key = keys[(size_t)s * TP + owner];
-      oi = (int32_t)(uint32_t)key;
-      const float *ry = rays + pix * 3;
-      const float ex = ry[0], ey = ry[1], ez = ry[2];
-      const float4 cc = ms[oi];      // (centre, a | NaN): an isotropic Gaussian needs nothing else
-      PairOut o;
-      if (ISO || cc.w == cc.w) {
-        o = pair_eval_iso(cc.x, cc.y, cc.z, cc.w, ex, ey, ez, ex * ex, ey * ey, ez * ez);
-      } else {
-        const EvalRec e = unpack_eval(evr[(size_t)oi * 3 + 0], evr[(size_t)oi * 3 + 1], evr[(size_t)oi * 3 + 2]);
-        o = pair_eval(cc.x, cc.y, cc.z, e, ex, ey, ez, ex * ex, ey * ey, ez * ez, ex * ey, ex * ez, ey * ez);
-      }
-      ol = ord2f((uint32_t)(key >> 32));
-      oa = o.act;
-      od = o.dsd;
-    }
-  };
-  const bool vec4 = ((K & 3) == 0);   // rows of K floats stay 16-byte aligned: 16-byte stores
-  if (WAVES == 1 && out_weight != nullptr) {
-    // ---- fused epilogue: fragments AND their composite weights (VoGE/Aggregation.py:82-107).  The depth-ordered
-    // list of every ray is in LDS right now; instead of writing (idx, len, act, dsd) and letting a second kernel read
-    // them back (126 MB at cfg3) the wave composites here: a lane owns four consecutive slots of a pixel, 64 / (K/4)
-    // pixels per round, the row pass is the stand-alone kernel's (composite_core.h: bit-identical weights).  The
-    // keys, the (mu, a) gathers and the ray of round r + 1 are requested before round r is computed.  (host: K % 4 == 0)
-    constexpr int NS = 4;
-    const int LP = K >> 2, pw = 64 / LP;
-    const int rows = compn_rows(K, NS, 64, true);
-    float *const Llen = reinterpret_cast<float *>(smem_raw + ((sizeof(uint64_t) * (size_t)(K + 1) * TP + 15) & ~(size_t)15) + ((sizeof(TraceLds<T, ISO>) + 15) & ~(size_t)15));
-    float *const Lsp = Llen + rows, *const LE = Lsp + rows;
-    const int RS = compn_stride(K, NS);
-    const int pl = __float2int_rz(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)LP)), q = lane - pl * LP;
-    const bool in_wg = pl < pw;
-    const int k0 = NS * q, seg_lo = lane - q;
-    const int d0 = (in_wg ? pl : 0) * RS + 2 + (in_wg ? k0 : 0);
-    if (in_wg && q < 2) {      // the sentinel pairs in front of and behind every pixel's row: written once
-      const int r0 = pl * RS;
-      for (int t2 = q; t2 < 2; t2 += LP) {
-        Llen[r0 + t2] = -kBig; Lsp[r0 + t2] = 1.0f; LE[r0 + t2] = 0.0f;
-        const int eb = r0 + RS - 2 + t2;
-        Llen[eb] = kBig; Lsp[eb] = 1.0f; LE[eb] = 0.0f;
-      }
-    }
-    const int th = min(TH, H - ty * TH);
-    struct Req {
-      uint64_t key[NS];
-      float4 rec[NS];
-      float ex, ey, ez;
-      int nv, cntp;
-      bool on;
-      size_t pix;
-    };
-    auto request = [&](const int round, Req &r) {
-      const int pixl = round * pw + pl;                  // pixel of the tile: x = pixl & 7, row = pixl >> 3
-      r.on = in_wg && pixl < 64 && (pixl & 7) < tw && (pixl >> 3) < th;
-      r.pix = ((size_t)b * H + ty * TH + (pixl >> 3)) * W + (size_t)tx * TW + (pixl & 7);
-      r.cntp = r.on ? L.id[pixl & 63] : 0;
-      r.nv = max(0, min(NS, r.cntp - k0));
-      r.ex = r.ey = r.ez = 0.0f;
-#pragma unroll
-      for (int a = 0; a < NS; ++a) r.key[a] = (a < r.nv) ? keys[(size_t)(k0 + a) * TP + (pixl & 63)] : 0ull;
-      if (r.nv > 0) { r.ex = rays[r.pix * 3]; r.ey = rays[r.pix * 3 + 1]; r.ez = rays[r.pix * 3 + 2]; }
-#pragma unroll
-      for (int a = 0; a < NS; ++a) r.rec[a] = (a < r.nv) ? ms[(uint32_t)r.key[a]] : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    const int nround = (64 + pw - 1) / pw;
-    Req cur, nxt;
-    request(0, cur);
-    for (int round = 0; round < nround; ++round) {
-      if (round + 1 < nround) request(round + 1, nxt);
-      int32_t oi[NS];
-      float ol[NS], oa[NS], od[NS], lm[NS], sm[NS], em[NS];
-      const float qxx = cur.ex * cur.ex, qyy = cur.ey * cur.ey, qzz = cur.ez * cur.ez;
-      bool gen_any = false;
-      if (!ISO) {
-#pragma unroll
-        for (int a = 0; a < NS; ++a) gen_any = gen_any || ((a < cur.nv) && !(cur.rec[a].w == cur.rec[a].w));
-        gen_any = __any(gen_any);
-      }
-      float4 g0[NS], g1[NS], g2[NS];
-      if (!ISO && gen_any) {      // anisotropic entries (w = NaN): their full records, all in flight together
-#pragma unroll
-        for (int a = 0; a < NS; ++a) {
-          g0[a] = g1[a] = g2[a] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if ((a < cur.nv) && !(cur.rec[a].w == cur.rec[a].w)) {
-            const size_t eo = (size_t)(uint32_t)cur.key[a] * 3;
-            g0[a] = evr[eo]; g1[a] = evr[eo + 1]; g2[a] = evr[eo + 2];
-          }
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < NS; ++a) {
-        oi[a] = -1; ol[a] = VOGE_SENT_LEN; oa[a] = VOGE_SENT_ACT; od[a] = 0.0f;
-        lm[a] = VOGE_SENT_LEN; sm[a] = 1e-5f; em[a] = 0.0f;      // what the stand-alone kernel takes an empty slot for
-        if (a < cur.nv) {
-          oi[a] = (int32_t)(uint32_t)cur.key[a];
-          ol[a] = ord2f((uint32_t)(cur.key[a] >> 32));
-          PairOut o;
-          if (ISO || cur.rec[a].w == cur.rec[a].w) {
-            o = pair_eval_iso_at(cur.rec[a].x, cur.rec[a].y, cur.rec[a].z, cur.rec[a].w, ol[a], cur.ex, cur.ey, cur.ez,
-                                 (qxx + qyy) + qzz);     // len is in the key: no second division
-          } else {
-            const EvalRec e = unpack_eval(g0[a], g1[a], g2[a]);
-            o = pair_eval(cur.rec[a].x, cur.rec[a].y, cur.rec[a].z, e, cur.ex, cur.ey, cur.ez, qxx, qyy, qzz, cur.ex * cur.ey,
-                          cur.ex * cur.ez, cur.ey * cur.ez);
-          }
-          oa[a] = o.act; od[a] = o.dsd;
-          lm[a] = ol[a]; em[a] = FAST_EXP(-oa[a]); sm[a] = FAST_SQRT(od[a] + 1e-10f);
-        }
-      }
-      if (in_wg) {
-#pragma unroll
-        for (int h2 = 0; h2 < NS / 2; ++h2) {
-          const int a = 2 * h2;
-          *reinterpret_cast<v2f *>(Llen + d0 + a) = (v2f){lm[a], lm[a + 1]};
-          *reinterpret_cast<v2f *>(Lsp + d0 + a) = (v2f){sm[a] * kCs, sm[a + 1] * kCs};
-          *reinterpret_cast<v2f *>(LE + d0 + a) = (v2f){em[a], em[a + 1]};
-        }
-      }
-      wave_lds_sync();
-      float wgt[NS];
-      compn_fwd_rows<NS>(lm, sm, em, Llen, Lsp, LE, d0, k0, K, q, LP, LP, in_wg, cur.on, true, seg_lo, occ, wgt);
-      wave_lds_sync();      // the rows are rewritten by the next round
-      if (cur.on) {
-        const size_t ob = cur.pix * K + k0;
-        st16i<true>(out_idx + ob, oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<true>(out_len + ob, ol[0], ol[1], ol[2], ol[3]);
-        st16f<true>(out_act + ob, oa[0], oa[1], oa[2], oa[3]);
-        st16f<true>(out_dsd + ob, od[0], od[1], od[2], od[3]);
-        *reinterpret_cast<float4 *>(out_weight + ob) = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
-        if (q == 0 && out_valid != nullptr) out_valid[cur.pix] = (int64_t)cur.cntp;
-      }
-      cur = nxt;
-    }
-  } else if (vec4) {
-    // All rows of the tile as one item space; an item = 4 consecutive slots of one pixel.  kEpiU
-    // items per thread go through the stages together -- LDS keys, then one 16-byte gather per
-    // slot (isotropic Gaussians need nothing more), then arithmetic and the 16-byte stores -- so
-    // a thread has up to 4 * kEpiU gathers in flight instead of one dependent chain per slot.
-#ifndef VOGE_EPI_U
-#define VOGE_EPI_U 4
-#endif
-    constexpr int kEpiU = VOGE_EPI_U;
-    const int th = min(TH, H - ty * TH);
-    const int ipr = row_items >> 2;
-    const int nitem = th * ipr;
-    const float inv_ipr = 1.0f / (float)ipr, invK = 1.0f / (float)K;
-    // Tiles that staged anisotropic candidates: centre and full record (4 gathers per slot) are issued
-    // together for kEpiG items -- one round trip per round instead of "centre, then 3 more per slot".
-    // (pair_eval dispatches on the record, so an isotropic entry in such a tile is still exact.)
-    constexpr int kEpiG = 2;
-    const bool want_ad = out_act != nullptr;
-    for (int it0 = tid; tile_gen && want_ad && it0 < nitem; it0 += T * kEpiG) {
-      uint64_t key[kEpiG][4];
-      float4 rc[kEpiG][4], g0[kEpiG][4], g1[kEpiG][4], g2[kEpiG][4];
-      float ex[kEpiG], ey[kEpiG], ez[kEpiG];
-      size_t ob[kEpiG];
-      int nv[kEpiG];
-#pragma unroll
-      for (int u = 0; u < kEpiG; ++u) {
-        const int it = it0 + u * T;
-        nv[u] = -1;
-        ob[u] = 0;
-        ex[u] = ey[u] = ez[u] = 0.0f;
-        if (it < nitem) {
-          const int r = __float2int_rz(((float)it + 0.5f) * inv_ipr);
-          const int j = (it - r * ipr) * 4;
-          const int x = __float2int_rz(((float)j + 0.5f) * invK);
-          const int sl = j - x * K;
-          const int owner = ((x >> 3) + (TW / 8) * (r >> 3)) * 64 + (x & 7) + 8 * (r & 7);
-          const size_t pix = ((size_t)b * H + ty * TH + r) * W + (size_t)tx * TW + x;
-          ob[u] = pix * K + sl;
-          nv[u] = max(0, min(4, L.id[owner] - sl));
-#pragma unroll
-          for (int q = 0; q < 4; ++q) key[u][q] = (q < nv[u]) ? keys[(size_t)(sl + q) * TP + owner] : 0ull;
-          if (nv[u] > 0) { ex[u] = rays[pix * 3]; ey[u] = rays[pix * 3 + 1]; ez[u] = rays[pix * 3 + 2]; }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kEpiG; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          rc[u][q] = g0[u][q] = g1[u][q] = g2[u][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (q < nv[u]) {
-            const size_t gi = (uint32_t)key[u][q];
-            rc[u][q] = ms[gi]; g0[u][q] = evr[gi * 3]; g1[u][q] = evr[gi * 3 + 1]; g2[u][q] = evr[gi * 3 + 2];
-          }
-        }
-#pragma unroll
-      for (int u = 0; u < kEpiG; ++u) {
-        if (nv[u] < 0) continue;
-        int32_t oi[4];
-        float ol[4], oa[4], od[4];
-        const float qxx = ex[u] * ex[u], qyy = ey[u] * ey[u], qzz = ez[u] * ez[u];
-        const float qxy = ex[u] * ey[u], qxz = ex[u] * ez[u], qyz = ey[u] * ez[u];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          oi[q] = -1; ol[q] = VOGE_SENT_LEN; oa[q] = VOGE_SENT_ACT; od[q] = 0.0f;
-          if (q < nv[u]) {
-            oi[q] = (int32_t)(uint32_t)key[u][q];
-            ol[q] = ord2f((uint32_t)(key[u][q] >> 32));
-            const PairOut o = pair_eval(rc[u][q].x, rc[u][q].y, rc[u][q].z, unpack_eval(g0[u][q], g1[u][q], g2[u][q]),
-                                        ex[u], ey[u], ez[u], qxx, qyy, qzz, qxy, qxz, qyz);
-            oa[q] = o.act;
-            od[q] = o.dsd;
-          }
-        }
-        st16i<true>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<true>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
-        st16f<true>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
-        st16f<true>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
-      }
-    }
-    // Fragment mode without act / dsd (out_act == NULL; voge_fragments_fwd_iso*): index and len are the key itself --
-    // no gather, no ray, no arithmetic; the composite kernel behind the sweep derives act / dsd from the same
-    // records with the same operations (composite.hip), at its own, much higher residency.
-    for (int it0 = tid; !want_ad && it0 < nitem; it0 += T * kEpiU) {
-#pragma unroll
-      for (int u = 0; u < kEpiU; ++u) {
-        const int it = it0 + u * T;
-        if (it >= nitem) break;
-        const int r = __float2int_rz(((float)it + 0.5f) * inv_ipr);
-        const int j = (it - r * ipr) * 4;
-        const int x = __float2int_rz(((float)j + 0.5f) * invK);
-        const int sl = j - x * K;
-        const int owner = ((x >> 3) + (TW / 8) * (r >> 3)) * 64 + (x & 7) + 8 * (r & 7);
-        const size_t pix = ((size_t)b * H + ty * TH + r) * W + (size_t)tx * TW + x;
-        const int nv = max(0, min(4, L.id[owner] - sl));
-        int32_t oi[4];
-        float ol[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint64_t key = (q < nv) ? keys[(size_t)(sl + q) * TP + owner] : 0ull;
-          oi[q] = (q < nv) ? (int32_t)(uint32_t)key : -1;
-          ol[q] = (q < nv) ? ord2f((uint32_t)(key >> 32)) : VOGE_SENT_LEN;
-        }
-        *reinterpret_cast<int4 *>(out_idx + pix * K + sl) = make_int4(oi[0], oi[1], oi[2], oi[3]);
-        *reinterpret_cast<float4 *>(out_len + pix * K + sl) = make_float4(ol[0], ol[1], ol[2], ol[3]);
-      }
-    }
-    for (int it0 = tid; !tile_gen && want_ad && it0 < nitem; it0 += T * kEpiU) {
-      uint64_t key[kEpiU][4];
-      float4 rec[kEpiU][4];
-      float ex[kEpiU], ey[kEpiU], ez[kEpiU];
-      size_t ob[kEpiU];
-      int nv[kEpiU];
-#pragma unroll
-      for (int u = 0; u < kEpiU; ++u) {
-        const int it = it0 + u * T;
-        nv[u] = -1;
-        ob[u] = 0;
-        ex[u] = ey[u] = ez[u] = 0.0f;
-        if (it < nitem) {
-          const int r = __float2int_rz(((float)it + 0.5f) * inv_ipr);
-          const int j = (it - r * ipr) * 4;
-          const int x = __float2int_rz(((float)j + 0.5f) * invK);
-          const int sl = j - x * K;
-          const int owner = ((x >> 3) + (TW / 8) * (r >> 3)) * 64 + (x & 7) + 8 * (r & 7);
-          const size_t pix = ((size_t)b * H + ty * TH + r) * W + (size_t)tx * TW + x;
-          ob[u] = pix * K + sl;
-          nv[u] = max(0, min(4, L.id[owner] - sl));
-#pragma unroll
-          for (int q = 0; q < 4; ++q) key[u][q] = (q < nv[u]) ? keys[(size_t)(sl + q) * TP + owner] : 0ull;
-          if (nv[u] > 0) { ex[u] = rays[pix * 3]; ey[u] = rays[pix * 3 + 1]; ez[u] = rays[pix * 3 + 2]; }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kEpiU; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          rec[u][q] = (q < nv[u]) ? ms[(uint32_t)key[u][q]] : make_float4(0.f, 0.f, 0.f, 0.f);
-      // anisotropic entries (w = NaN) need their full record: 3 more gathers each.  They are issued for
-      // all four slots of an item before any is used (12 in flight per lane instead of 3).
-      bool gen_any = false;
-#pragma unroll
-      for (int u = 0; u < kEpiU; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gen_any = gen_any || ((q < nv[u]) && !(rec[u][q].w == rec[u][q].w));
-      gen_any = __any(gen_any);
-#pragma unroll
-      for (int u = 0; u < kEpiU; ++u) {
-        if (nv[u] < 0) continue;
-        int32_t oi[4];
-        float ol[4], oa[4], od[4];
-        const float qxx = ex[u] * ex[u], qyy = ey[u] * ey[u], qzz = ez[u] * ez[u];
-        float4 g0[4], g1[4], g2[4];
-        if (gen_any) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            g0[q] = g1[q] = g2[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((q < nv[u]) && !(rec[u][q].w == rec[u][q].w)) {
-              const size_t eo = (size_t)(uint32_t)key[u][q] * 3;
-              g0[q] = evr[eo]; g1[q] = evr[eo + 1]; g2[q] = evr[eo + 2];
-            }
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          oi[q] = -1; ol[q] = VOGE_SENT_LEN; oa[q] = VOGE_SENT_ACT; od[q] = 0.0f;
-          if (q < nv[u]) {
-            oi[q] = (int32_t)(uint32_t)key[u][q];
-            ol[q] = ord2f((uint32_t)(key[u][q] >> 32));
-            PairOut o;
-            if (rec[u][q].w == rec[u][q].w) {
-              o = pair_eval_iso_at(rec[u][q].x, rec[u][q].y, rec[u][q].z, rec[u][q].w, ol[q], ex[u], ey[u], ez[u],
-                                   (qxx + qyy) + qzz);     // len is in the key: no second division
-            } else {
-              const EvalRec e = unpack_eval(g0[q], g1[q], g2[q]);
-              o = pair_eval(rec[u][q].x, rec[u][q].y, rec[u][q].z, e, ex[u], ey[u], ez[u], qxx, qyy, qzz, ex[u] * ey[u],
-                            ex[u] * ez[u], ey[u] * ez[u]);
-            }
-            oa[q] = o.act;
-            od[q] = o.dsd;
-          }
-        }
-        st16i<true>(out_idx + ob[u], oi[0], oi[1], oi[2], oi[3]);      // (write-once, 16 B per slot: non-temporal, voge_common.h)
-        st16f<true>(out_len + ob[u], ol[0], ol[1], ol[2], ol[3]);
-        st16f<true>(out_act + ob[u], oa[0], oa[1], oa[2], oa[3]);
-        st16f<true>(out_dsd + ob[u], od[0], od[1], od[2], od[3]);
-      }
-    }
-  }
-  if (!vec4 && out_weight == nullptr && out_act == nullptr) {
-    // K not a multiple of four, fragments without act / dsd (ShapeFitting's max_assign = 25): index and len are the keys
-    // themselves -- every slot of the tile is one independent LDS read and two 4-byte stores, no gather, no arithmetic
-    const int th = min(TH, H - ty * TH);
-    const float inv_ri = 1.0f / (float)row_items;
-    for (int it = tid; it < th * row_items; it += T) {
-      const int r = __float2int_rz(((float)it + 0.5f) * inv_ri);
-      const int j = it - r * row_items;
-      const int x = j / K, sl = j - x * K;
-      const int owner = ((x >> 3) + (TW / 8) * (r >> 3)) * 64 + (x & 7) + 8 * (r & 7);
-      const bool in = sl < L.id[owner];
-      const uint64_t key = in ? keys[(size_t)sl * TP + owner] : 0ull;
-      const size_t o = (((size_t)b * H + ty * TH + r) * W + (size_t)tx * TW) * K + j;
-      out_idx[o] = in ? (int32_t)(uint32_t)key : -1;
-      out_len[o] = in ? ord2f((uint32_t)(key >> 32)) : VOGE_SENT_LEN;
-    }
-  }
-  if (!vec4 && out_weight == nullptr && out_act != nullptr) {
-    // K not a multiple of four, act / dsd wanted: one slot per lane and trip over the whole tile (rows x pixels x slots
-    // flattened, so a wave makes th * tw * K / 64 trips instead of th * ceil(tw * K / 64)), four trips in flight
-    const int th = min(TH, H - ty * TH);
-    const float inv_ri = 1.0f / (float)row_items;
-    const int nit = th * row_items;
-    for (int it0 = tid; it0 < nit; it0 += 4 * T) {
-      int32_t oi[4];
-      float ol[4], oa[4], od[4];
-      size_t oo[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int it = it0 + u * T;
-        oo[u] = 0; oi[u] = -1; ol[u] = VOGE_SENT_LEN; oa[u] = VOGE_SENT_ACT; od[u] = 0.0f;
-        if (it < nit) {
-          const int r = __float2int_rz(((float)it + 0.5f) * inv_ri);
-          const int j = it - r * row_items;
-          const int x = j / K, sl = j - x * K;
-          const size_t pix = ((size_t)b * H + ty * TH + r) * W + (size_t)tx * TW + x;
-          slot_value(r, x, sl, pix, oi[u], ol[u], oa[u], od[u]);
-          oo[u] = pix * K + sl;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (it0 + u * T < nit) { out_idx[oo[u]] = oi[u]; out_len[oo[u]] = ol[u]; out_act[oo[u]] = oa[u]; out_dsd[oo[u]] = od[u]; }
-      }
-    }
-  }
-#ifdef VOGE_SWEEP_TIMES
-  if (tid == 0 && b == 0 && bx < 8192) {
-    unsigned long long *o = g_sweep_times + 8 * (size_t)bx;
-    o[0] = ts0; o[1] = ts1; o[2] = ts_fill; o[3] = ts_cons; o[4] = ts2; o[5] = wall_clock64();
-#ifdef VOGE_SWEEP_STATS
-    o[6] = st_eval;
-#else
-    o[6] = (unsigned long long)cnt_dbg;
-#endif
-    o[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-  }
-#endif
-}
 
 // ------------------------------------------------------------------------------------------
 // explicit candidate lists (the reference's bin_points tensor): one ray per lane, each lane
@@ -1187,28 +384,26 @@ static size_t trace_ws_layout(int B, int N, int H, int W, void *base, TraceWs *w
   return off;
 }
 
-// -DVOGE_AB builds only (libvoge_hip_ab.so, never the product library): a process-wide switch between sweep_iso_kernel (0)
-// and round 3's scalar-sigma sweep, trace_fwd_kernel<1, true> (1) -- for A/B timing and the bit-for-bit comparison in
-// tests/test_gpu_configs.py (voge_debug_sweep_variant).  The product library has neither the switch nor the old kernel.
+}  // namespace voge
 #ifdef VOGE_AB
-static std::atomic<int> g_sweep_variant{0};
+#include "sweep_r3.h"      // round 3's sweep and the switch to it: the A/B library's bit-for-bit oracle, never in the product
+#else
+namespace voge { constexpr bool ab_round3_selected() { return false; } }
 #endif
+namespace voge {
+
 // binB + the sweep (one wave = one 8x8-pixel tile per workgroup)
 template <bool ISO>
 static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *rays, int B, int N, int H, int W, int K,
-                        float thr_act, int32_t *idx, float *len, float *act, float *dsd, int32_t *cnt, float occ,
-                        hipStream_t st, const CamView &cam, const bool diag = false) {
+                        float thr_act, int32_t *idx, float *len, float *act, float *dsd, int32_t *cnt, hipStream_t st,
+                        const CamView &cam, const bool diag = false) {
   constexpr int T = 64;
   // (diag: every general form of the launch is a per-axis one -- the frame path's gen_kind 1 -- sweep_iso_kernel<2>)
   const int gen = ISO ? 0 : (diag ? 2 : 1);
   const auto sweep = ISO ? sweep_iso_kernel<0> : (diag ? sweep_iso_kernel<2> : sweep_iso_kernel<1>);
   // sweep_iso_kernel (sweep_iso.h: float-compare commits, 6-byte list entries) -- <0> for scalar sigmas (round 4), <1> / <2>
   // for the general forms (round 5)
-#ifdef VOGE_AB
-  const bool v2 = g_sweep_variant.load(std::memory_order_relaxed) != 1;
-#else
-  constexpr bool v2 = true;
-#endif
+  const bool v2 = !ab_round3_selected();      // (always true in the product library: sweep_r3.h)
   const size_t lds2 = sweep2_lds_bytes(K, gen);
   {
     static DynLdsCache cache2[2];      // (one per kernel of this instantiation)
@@ -1217,14 +412,6 @@ static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *ra
       if (rc) return rc;
     }
   }
-#ifdef VOGE_AB
-  const size_t lds = ((sizeof(uint64_t) * (size_t)(K + 1) * (T + 1) + 15) & ~(size_t)15) + ((sizeof(TraceLds<T, ISO>) + 15) & ~(size_t)15);
-  if (!v2) {
-    static DynLdsCache cache;
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(trace_fwd_kernel<1, ISO>), lds, cache);
-    if (rc) return rc;
-  }
-#endif
   hipLaunchKernelGGL(binB_kernel<!ISO>, dim3(ws.nstx * ws.nsty * 4, B), dim3(kQT), 0, st, ws.cull, ws.ell, ws.seg_count, ws.seg_id, ws.seg_rec,
                      cones, N, H, W, ws.nstx, ws.nsty, ws.nbin, ws.q_count, ws.q_id, ws.q_lb, ws.tl_count, ws.tl_id, ws.tl_lb,
                      ws.order, ws.pool_top, ws.pool_cap, ws.pool_id, ws.pool_lb, ws.tl_off, ws.seg_ext, ws.ext_id, K,
@@ -1234,20 +421,13 @@ static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *ra
     int rc = launch_status();
     if (rc) return rc;
   }
-  const int2 *order = ws.order;
   dim3 grid(ws.nbin * kTilesPerBin);     // one workgroup per tile slot of every super-tile (slots outside the image exit)
-  if (v2) {
-    hipLaunchKernelGGL(sweep, grid, dim3(T), lds2, st, ws.cull, ws.ms, ws.evr, rays, ws.q_count, ws.q_id, ws.q_lb, ws.tl_id,
-                       ws.tl_lb, ws.pool_id, ws.pool_lb, ws.tl_off, order, ((W + 7) / 8) * ((H + 7) / 8), ws.nstx, ws.nstx * ws.nsty, N, H, W, K,
-                       thr_act, idx, len, act, dsd, cnt, cam);
-    return launch_status();
-  }
 #ifdef VOGE_AB
-  if (cam.R != nullptr) return VOGE_ERR_BAD_ARG;      // (round 3's sweeps read the bundle)
-  hipLaunchKernelGGL((trace_fwd_kernel<1, ISO>), grid, dim3(T), lds, st, ws.cull, ws.evr, ws.ms, rays, ws.q_count, ws.q_id, ws.q_lb,
-                     ws.tl_count, ws.tl_id, ws.tl_lb, ws.pool_id, ws.pool_lb, ws.tl_off, order, ((W + 7) / 8) * ((H + 7) / 8), ws.nstx,
-                     ws.nstx * ws.nsty, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, nullptr, nullptr);
+  if (!v2) return launch_sweep_r3<ISO>(ws, rays, grid, N, H, W, K, thr_act, idx, len, act, dsd, cnt, st, cam);
 #endif
+  hipLaunchKernelGGL(sweep, grid, dim3(T), lds2, st, ws.cull, ws.ms, ws.evr, rays, ws.q_count, ws.q_id, ws.q_lb, ws.tl_id,
+                     ws.tl_lb, ws.pool_id, ws.pool_lb, ws.tl_off, ws.order, ((W + 7) / 8) * ((H + 7) / 8), ws.nstx, ws.nstx * ws.nsty, N, H, W, K,
+                     thr_act, idx, len, act, dsd, cnt, cam);
   return launch_status();
 }
 
@@ -1255,15 +435,6 @@ static int launch_trace(const TraceWs &ws, const ConeRec *cones, const float *ra
 
 using namespace voge;
 
-#ifdef VOGE_SWEEP_TIMES
-// debug builds only (tools/sweep_stats.py): read and clear the sweep counters
-extern "C" int voge_debug_sweep_stats(unsigned long long *out16) {
-  hipError_t e = hipMemcpyFromSymbol(out16, HIP_SYMBOL(voge::g_sweep_stats), sizeof(unsigned long long) * 16);
-  if (e != hipSuccess) return (int)e;
-  unsigned long long z[16] = {0};
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(voge::g_sweep_stats), z, sizeof(z));
-}
-#endif
 #ifdef VOGE_SWEEP_TIMES
 extern "C" int voge_debug_sweep_times(unsigned long long *out, int n_wg) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(voge::g_sweep_times), sizeof(unsigned long long) * 8 * (size_t)n_wg);
@@ -1280,13 +451,6 @@ extern "C" int voge_debug_bin_times(unsigned long long *out, int which, int n_wg
 }
 #endif
 
-#ifdef VOGE_AB
-extern "C" int voge_debug_sweep_variant(int variant) {
-  if (variant < 0 || variant > 1) return VOGE_ERR_BAD_ARG;
-  voge::g_sweep_variant.store(variant, std::memory_order_relaxed);
-  return 0;
-}
-#endif
 
 // Round 5: the scratch is sized for a CHUNK of the batch, not for all of it (it used to be B x 165 MB at 512^2, B x 774 MB at
 // 1024^2: 6.2 GB for eight 1024^2 views).  Views are independent in every stage, so the entry points walk a batch in
@@ -1386,8 +550,9 @@ static int trace_topk_fwd_impl(const int iso_in, const IsoView view, const float
   if (N > 0 && (!mus || !isigmas)) return VOGE_ERR_BAD_ARG;
   // (one view's scratch is the least that works; voge_trace_workspace_bytes(B, ...) is what to allocate)
   if (workspace_bytes < trace_ws_bytes(1, N, H, W)) return VOGE_ERR_WORKSPACE;
-  // the top-K lists of one 8x8 tile must fit the CU's LDS: validated before anything is enqueued
-  if (sizeof(uint64_t) * (size_t)(K + 1) * 65 + 16 + sizeof(TraceLds<64, false>) > 160 * 1024) return VOGE_ERR_K_TOO_LARGE;
+  // the top-K lists of one 8x8 tile fit the CU's LDS at every K the check above lets through
+  static_assert(sweep2_lds_bytes(VOGE_MAX_K, 0) <= 160 * 1024 && sweep2_lds_bytes(VOGE_MAX_K, 1) <= 160 * 1024 &&
+                sweep2_lds_bytes(VOGE_MAX_K, 2) <= 160 * 1024, "sweep_iso_kernel's LDS at VOGE_MAX_K");
   // ---- the batch in chunks of as many views as the scratch holds (all of them, when it was sized for that): every array the
   // caller sees is offset to the chunk's first view, the chunk runs as a batch of its own, and the indices it wrote -- local
   // to that first view -- are moved up by b0 N afterwards (one pass over idx, chunks behind the first only)
@@ -1484,13 +649,13 @@ static int trace_chunk_fwd(const int iso_in, const IsoView view, const float *mu
   // One wave (an 8x8 pixel tile) per sweep workgroup.  Residency is set by the LDS top-K lists (~7 waves per CU at
   // K = 40), and independent single-wave workgroups measured 4-10 % faster than 16x8 / 16x16 tiles in round 1.
   // Fragments wanted as well (weight != NULL): the stand-alone composite kernel runs behind the sweep.  Compositing
-  // inside the sweep's epilogue was built and measured (same bits; HISTORY.md §5, trace_fwd_kernel): the sweep holds ~1.5 waves per
+  // inside the sweep's epilogue was built and measured (same bits; HISTORY.md §5, in round 3's sweep): the sweep holds ~1.5 waves per
   // SIMD (its top-K lists fill the LDS), so the composite's row walks run latency-bound there -- sweep 64 -> 142 us at
   // cfg3 against 52 us for the kernel it would replace, which does the same instructions at eight waves per SIMD and
   // reads its 126 MB mostly from the Infinity Cache.
   int rc;
-  if (iso_in) rc = launch_trace<true>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, st, cam);
-  else rc = launch_trace<false>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, occ, st, cam, view.gen_kind == 1);
+  if (iso_in) rc = launch_trace<true>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, st, cam);
+  else rc = launch_trace<false>(ws, cones, rays, B, N, H, W, K, thr_act, idx, len, act, dsd, cnt, st, cam, view.gen_kind == 1);
   if (rc || weight == nullptr) return rc;
   if (act == nullptr)
     return voge_composite_fwd_iso(idx, cnt, len, reinterpret_cast<const float *>(ws.ms), cam.R != nullptr ? cam.rays_out : rays, occ,
