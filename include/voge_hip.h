@@ -654,6 +654,34 @@ int voge_sh_colors_bwd(const float *sh, const float *verts, const float *centres
                        int degree, int shared_verts, int clamp, float *g_sh, float *g_verts, voge_stream_t stream);
 
 /*
+ * Per-view normals of oriented Gaussians (EXTENSION: the reference has neither oriented Gaussians nor normals).  scales [N][3] and
+ * quats [N][4] (w, x, y, z; not necessarily unit) when shared_orient != 0 -- one set for every view -- or [B][N][3] / [B][N][4];
+ * verts [N][3] (shared_verts != 0) or [B][N][3]; centres [B][3], the camera centres.  R = the rotation of q / |q|, the identity
+ * for a quaternion whose squared norm as fp32 computes it is not a positive finite number (voge_frame_trace_fwd_ori's rule).
+ * The oriented Gaussian S = R diag(s) R^T stands for a flat surface element; its normal is the thinnest axis, a COLUMN of R:
+ *   k* = 0; for j = 1, 2 in that order: k* = j if s_j > s_k* (inverse_sigma == 0: A = 2 S, a larger s is a thinner extent) or
+ *   s_j < s_k* (inverse_sigma != 0: A = R diag(2 / s) R^T) -- an exact tie keeps the lowest index, a NaN never wins, a NaN in
+ *   s_0 stays chosen;   n0 = R[:][k*];
+ *   for view b, delta = v - c_b and t = n0 . delta:   out [B*N][3], row b*N + n, = -n0 where t > 0 and n0 otherwise,
+ * the side that faces the camera (n . delta <= 0); t == 0, delta == 0 and a NaN t keep n0.  Replaces
+ * voge_amd/Aggregation.py gaussian_normals -- a normalise, the [16,9] product map, an argmax, a gather, a dot product per view
+ * and a select -- by one launch.
+ * Backward: g_out [B*N][3] -> g_quats ([N][4] summed over the views in a fixed order when shared_orient, else [B][N][4]), EVERY
+ * element written: g_n0 = sum_b sign_b g_out[b*N + n] in fp64, through d R[:][k*] / d qh in fp64 and
+ * g_q = (g_qh - qh (qh . g_qh)) / |q| -- orthogonal to q; zero for a quaternion without a usable norm.  The axis and the signs
+ * are recomputed from the inputs (nothing is saved by the forward) and are constants of the gradient; scales, verts and centres
+ * get none.  No atomics, the same bits on every run.  Replaces autograd's backward of that expression.  quats and g_quats are
+ * read and written 16 bytes at a time where both start on a 16-byte boundary, element by element otherwise.  B == 0 or N == 0:
+ * success, nothing is launched or written.  A negative size, a null pointer with work to do, or B * N * 3 beyond an int:
+ * VOGE_ERR_BAD_ARG before any HIP call.
+ */
+int voge_gauss_normals_fwd(const float *scales, const float *quats, const float *verts, const float *centres, int B, int N,
+                           int shared_orient, int shared_verts, int inverse_sigma, float *out, voge_stream_t stream);
+int voge_gauss_normals_bwd(const float *scales, const float *quats, const float *verts, const float *centres, const float *g_out,
+                           int B, int N, int shared_orient, int shared_verts, int inverse_sigma, float *g_quats,
+                           voge_stream_t stream);
+
+/*
  * Surface normals from a depth map (EXTENSION: the reference has neither depth nor normals).  depth [B][h][W] is the distance
  * along each pixel's unit ray (voge_depth_fwd, voge_frame_depth_fwd_iso); R [B][3][3], focal [B][2], pp [B][2] the cameras of
  * voge_rays_fwd (no T: the camera centre cancels in every difference); band row i is image row row0 + i.  The kernels make the

@@ -95,6 +95,52 @@ def oriented_sigma(scales, quats):
     return torch.triu(S) + torch.triu(S, 1).transpose(-1, -2)
 
 
+def gaussian_normals_shapes(scales, quats, verts, cam_center):
+    """(B, N) of gaussian_normals' arguments, checked: scales [N,3] | [B,N,3], quats [N,4] | [B,N,4] with the same leading
+    dimensions, verts [N,3] | [B,N,3], cam_center [B,3]."""
+    if (scales.dim() not in (2, 3) or scales.shape[-1] != 3 or quats.shape[-1:] != (4,) or quats.shape[:-1] != scales.shape[:-1]):
+        raise ValueError('scales[N,3] or [B,N,3] and quats[N,4] or [B,N,4] with the same leading dims expected, got '
+                         + str(tuple(scales.shape)) + ' / ' + str(tuple(quats.shape)))
+    if cam_center.dim() != 2 or cam_center.shape[-1] != 3 or verts.shape[-1:] != (3,) or verts.dim() not in (2, 3):
+        raise ValueError('verts[N,3] or [B,N,3] and cam_center[B,3] expected, got ' + str(tuple(verts.shape)) + ' / ' + str(tuple(cam_center.shape)))
+    B, N = cam_center.shape[0], scales.shape[-2]
+    if verts.shape[-2] != N or (verts.dim() == 3 and verts.shape[0] != B) or (scales.dim() == 3 and scales.shape[0] != B):
+        raise ValueError(f'verts {tuple(verts.shape)} do not match scales {tuple(scales.shape)} and cam_center {tuple(cam_center.shape)}')
+    return B, N
+
+
+def gaussian_normals(scales, quats, verts, cam_center, inverse_sigma=False):
+    """Per-view normals [B*N, 3] (row b*N + n: what the fragments of a B-view render index) of oriented Gaussians: scales [N,3]
+    or [B,N,3]; quats [N,4] or [B,N,4] (w, x, y, z; not necessarily unit; the leading dimensions of scales); verts [N,3] or
+    [B,N,3]; cam_center [B,3].  An extension: the reference has none.
+
+    The oriented Gaussian S = R diag(s) R^T, R = quaternion_to_matrix(quats), stands for a flat surface element, and its normal
+    is its thinnest axis -- a COLUMN of R, the axes of S being the columns of R.  S stands where a `sigmas` would: with
+    inverse_sigma=False the trace uses A = 2 S, so a LARGER s_k is a thinner extent; with inverse_sigma=True it uses
+    A = R diag(2 / s) R^T, so a SMALLER s_k is thinner.  The axis k*: start at k = 0; for j = 1, 2 in that order take j if
+    s_j > s_k (inverse_sigma=False) or s_j < s_k (True) -- exact ties keep the lowest index, a NaN never wins, a NaN in s_0 stays
+    chosen.  n0 = R[:, k*].  For view b, delta = v - c_b and t = n0 . delta: the output is -n0 where t > 0 and n0 otherwise, the
+    side get_normals picks (n . delta <= 0: towards the camera); t == 0, delta == 0 and a NaN t keep n0.
+
+    Only quats get a gradient: through the chosen column of R, orthogonal to quats, summed over the views when the quaternions
+    are shared, zero for a quaternion without a usable norm (the identity rotation).  The axis and the sign are constants, so
+    scales, verts and cam_center get none (no graph edge).  Differentiable torch on any device / dtype: the definition the kernel
+    (ops._GaussNormals, Renderer.gaussian_normals) is tested against, and the route for everything the kernel does not take."""
+    B, N = gaussian_normals_shapes(scales, quats, verts, cam_center)
+    R = quaternion_to_matrix(quats)                                              # [.., N, 3, 3]
+    sc = scales.detach()
+    s0, s1, s2 = sc[..., 0], sc[..., 1], sc[..., 2]
+    better = torch.lt if inverse_sigma else torch.gt
+    take1 = better(s1, s0)
+    take2 = better(s2, torch.where(take1, s1, s0))
+    k = torch.where(take2, torch.full_like(take1, 2, dtype=torch.long), take1.long())
+    n0 = torch.gather(R, -1, k[..., None, None].expand(k.shape + (3, 1))).squeeze(-1)      # [.., N, 3]: column k* of R
+    n0 = n0 if n0.dim() == 3 else n0[None]
+    delta = ((verts if verts.dim() == 3 else verts[None]) - cam_center[:, None, :]).detach()
+    t = (n0.detach() * delta).sum(-1, keepdim=True)                              # [B, N, 1]
+    return torch.where(t > 0, -n0, n0).reshape(B * N, 3)
+
+
 # The orthonormal real spherical harmonics of degree <= 3 as polynomials of a unit vector (x, y, z), in the order and with the
 # signs trained Gaussian scenes store their colour coefficients in.
 _SH_C0 = 0.28209479177387814

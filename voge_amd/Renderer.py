@@ -1,7 +1,7 @@
 """Host-side mirror of VoGE/Renderer.py: GaussianRenderer (:87-150), GaussianRenderSettings
 (:53-84), Fragments (:13-50), interpolate_attr (:153), get_silhouette (:157-159),
 to_colored_background (:162-171), to_white_background (:174-176) -- same names, same argument
-meaning; get_depth, get_distortion, get_normals and sh_to_colors are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
+meaning; get_depth, get_distortion, get_normals, sh_to_colors, gaussian_normals and get_rendered_normals are extensions.  Every stage behind these calls is a HIP kernel (voge_amd.ops); a renderer on CPU
 tensors raises instead of falling back.
 """
 import math
@@ -12,7 +12,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .Aggregation import aggregation, depth_normals, distortion, expend_sigma, merge_final, oriented_sigma, sh_colors, sh_degree
+from .Aggregation import (aggregation, depth_normals, distortion, expend_sigma, gaussian_normals as _gaussian_normals_def,
+                          gaussian_normals_shapes, merge_final, oriented_sigma, sh_colors, sh_degree)
 from . import RayTracing
 from .RayTracing import _view_axis
 from .cameras import camera_tensors, pixel_rays
@@ -526,6 +527,60 @@ def sh_to_colors(sh: torch.Tensor, verts: torch.Tensor, cameras_or_centres, degr
             and 1 <= sh.shape[2] <= 4 and not centres.requires_grad):
         return ops.sh_colors(sh, verts, centres, degree, clamp)
     return sh_colors(sh, verts, centres, degree, clamp)
+
+
+def gaussian_normals(scales: torch.Tensor, quats: torch.Tensor, verts: torch.Tensor, cameras_or_centres, inverse_sigma: bool = False):
+    """Per-view normals of oriented Gaussians (an extension: the reference has none) -> [B*N, 3], row b*N + n: the attribute table
+    the fragments of a B-view render index, to hand to get_rendered_normals / interpolate_attr like any attributes.
+
+    scales [N,3] or [B,N,3] and quats [N,4] or [B,N,4] (w, x, y, z; not necessarily unit) are what OrientedGaussianMeshes holds,
+    verts [N,3] or [B,N,3] the centres the renderer gets; cameras_or_centres a [B,3] tensor of camera centres or a cameras object;
+    inverse_sigma the renderer's setting.  An oriented, flattened Gaussian stands for a surface element whose normal is its
+    THINNEST axis: the column k* of R = quaternion_to_matrix(quats) with the largest scale (inverse_sigma=False: A = 2 S, a larger
+    s is a thinner extent) or the smallest (inverse_sigma=True: A = R diag(2 / s) R^T), exact ties keeping the lowest index; for
+    view b the result is that column with the sign that faces the camera, n . (v - c_b) <= 0 -- the side get_normals picks
+    (Aggregation.gaussian_normals spells the rules out and IS the definition).  Only quats get a gradient, through the chosen
+    column, orthogonal to quats and summed over the views when the quaternions are shared; the axis and the sign are constants, so
+    scales, verts and the camera centres get none, whether they require grad or not.
+
+    fp32 tensors on ONE HIP device take one HIP launch each way (ops._GaussNormals: no atomics, the same bits on every run, nothing
+    but the outputs allocated, so the step still captures into a HIP graph); anything else -- other dtypes, tensors on the host
+    or on different devices -- returns Aggregation.gaussian_normals(...): the same values with autograd's gradient.
+
+    A cameras object is asked for get_camera_center() on EVERY call -- a matrix inverse and an einsum, several launches: when the
+    cameras are fixed, compute the centres once and pass the tensor."""
+    centres = cameras_or_centres if torch.is_tensor(cameras_or_centres) else cameras_or_centres.get_camera_center()
+    gaussian_normals_shapes(scales, quats, verts, centres)
+    if (quats.is_cuda and scales.device == verts.device == centres.device == quats.device
+            and scales.dtype == quats.dtype == verts.dtype == centres.dtype == torch.float32):
+        return ops.gauss_normals(scales, quats, verts, centres, inverse_sigma)
+    return _gaussian_normals_def(scales, quats, verts, centres, inverse_sigma)
+
+
+def get_rendered_normals(fragments: Fragments, normals_table: torch.Tensor, normalize: bool = True):
+    """Rendered normal map sum_k w_k n_k of the fragments (an extension: the reference has none) -> [..., H, W, 3]:
+    M = interpolate_attr(fragments, normals_table) with normals_table [B*N, 3] from gaussian_normals -- on the frame path the
+    merge runs inside the composite's own pass, like any attribute table.  normalize=True returns M / |M| where |M| > 0 and
+    (0, 0, 0) elsewhere (nothing hit, or the weighted normals cancel); such a pixel passes no gradient on.  A thin torch
+    composition: no kernel of its own.  Fragments on the host (hand-made ones) are merged by the same sum in torch.
+
+    The normal-consistency term of 2D Gaussian splatting compares it with the normal of the rendered depth:
+        n_hat = get_rendered_normals(fragments, gaussian_normals(scales, quats, verts, centres))
+        n_depth = get_normals(get_depth(fragments), cameras)
+        both = (n_hat != 0).any(-1) & (n_depth != 0).any(-1)
+        loss = (1 - (n_hat * n_depth).sum(-1))[both].mean()
+    -- 1 - (n_hat . n_depth) on the pixels where both are non-zero; both face the camera, so the term is 0 where they agree."""
+    if fragments.vert_index.is_cuda:      # (vert_index: reading vert_weight would run a pending composite)
+        M = interpolate_attr(fragments, normals_table)
+    else:
+        w, idx, K = fragments.vert_weight, fragments.vert_index, fragments.vert_weight.shape[-1]
+        live = torch.arange(K, device=w.device) < fragments.valid_num[..., None]
+        M = (normals_table[idx.clamp(min=0).long()] * (w * live)[..., None]).sum(-2)
+    if not normalize:
+        return M
+    n2 = (M * M).sum(-1, keepdim=True)
+    ok = n2 > 0
+    return torch.where(ok, M / torch.sqrt(torch.where(ok, n2, torch.ones_like(n2))), torch.zeros_like(M))
 
 
 _BG_CACHE = {}

@@ -116,6 +116,8 @@ SIGNATURES = {
     "voge_distortion_bwd": (_c_int, [_c_void_p] * 6 + [_c_long, _c_int, _c_int] + [_c_void_p] * 3),
     "voge_sh_colors_fwd": (_c_int, [_c_void_p] * 3 + [_c_int] * 7 + [_c_void_p] * 2),
     "voge_sh_colors_bwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 7 + [_c_void_p] * 3),
+    "voge_gauss_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 5 + [_c_void_p] * 2),
+    "voge_gauss_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 2),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

@@ -1841,6 +1841,50 @@ class _ShColors(torch.autograd.Function):
         return g_sh, g_verts, None, None, None
 
 
+class _GaussNormals(torch.autograd.Function):
+    """Per-view normals of oriented Gaussians (extension; voge_gauss_normals_fwd / _bwd): forward(scales [N,3] | [B,N,3], quats
+    [N,4] | [B,N,4], verts [N,3] | [B,N,3], centres [B,3], inverse_sigma) -> [B*N, 3], the values of Aggregation.gaussian_normals.
+    One launch each way on the current stream and no allocation but the outputs (a quats off the 16-byte boundary, such as a view
+    at an odd offset into a flat buffer, is read element by element by the kernels: no copy); the backward recomputes the axis
+    and the signs from the saved INPUTS and writes every element of g_quats (no zero fill, no atomics: the same bits on every run).
+    Only quats get a gradient: the axis and the sign are constants, so scales, verts and centres have none by definition."""
+
+    @staticmethod
+    def forward(ctx, scales, quats, verts, centres, inverse_sigma):
+        scales = _dev(scales, torch.float32, "scales")
+        quats = _dev(quats, torch.float32, "quats")
+        verts = _dev(verts, torch.float32, "verts")
+        centres = _dev(centres, torch.float32, "cam_center")
+        lib = _lib.load()
+        B, N = centres.shape[0], scales.shape[-2] if scales.dim() >= 2 else -1
+        if (centres.shape != (B, 3) or tuple(scales.shape) not in ((N, 3), (B, N, 3)) or tuple(quats.shape) != tuple(scales.shape[:-1]) + (4,)
+                or tuple(verts.shape) not in ((N, 3), (B, N, 3))):
+            raise ValueError(f"gauss_normals: scales {tuple(scales.shape)}, quats {tuple(quats.shape)}, verts {tuple(verts.shape)} and "
+                             f"cam_center {tuple(centres.shape)} do not describe the same Gaussians and views")
+        out = torch.empty((B * N, 3), dtype=torch.float32, device=quats.device)
+        ctx.flags = (int(scales.dim() == 2), int(verts.dim() == 2), int(bool(inverse_sigma)))
+        with _on(quats.device):
+            rc = lib.voge_gauss_normals_fwd(_p(scales), _p(quats), _p(verts), _p(centres), B, N, *ctx.flags, _p(out), _stream())
+        _lib.check(rc, "voge_gauss_normals_fwd")
+        ctx.save_for_backward(scales, quats, verts, centres)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        lib = _lib.load()
+        scales, quats, verts, centres = ctx.saved_tensors
+        B, N = centres.shape[0], scales.shape[-2]
+        go = _dev(g_out, torch.float32, "grad_normals")
+        g_quats = (torch.zeros_like if B * N == 0 else torch.empty_like)(quats)      # (nothing is launched for an empty batch)
+        with _on(quats.device):
+            rc = lib.voge_gauss_normals_bwd(_p(scales), _p(quats), _p(verts), _p(centres), _p(go), B, N, *ctx.flags, _p(g_quats),
+                                            _stream())
+        _lib.check(rc, "voge_gauss_normals_bwd")
+        return None, g_quats, None, None, None
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
@@ -2120,6 +2164,10 @@ def distortion(weight, hit_length, valid_num, normalize=False):
 
 def sh_colors(sh, verts, centres, degree, clamp=True):
     return _ShColors.apply(sh, verts, centres, degree, clamp)
+
+
+def gauss_normals(scales, quats, verts, centres, inverse_sigma=False):
+    return _GaussNormals.apply(scales, quats, verts, centres, inverse_sigma)
 
 
 def depth_normals(depth, R, focal, pp, row0=0, edge=None, view_space=False):
