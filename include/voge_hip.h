@@ -876,6 +876,34 @@ int voge_find_nearest_k_bwd(const int32_t *idx, const float *g_len, const float 
 int voge_scatter_max(const float *weight, const int32_t *idx, long n, long Nv, float *out,
                      voge_stream_t stream);
 
+/*
+ * Exact k nearest neighbours of every point of a cloud among the cloud's points (EXTENSION.  The reference's only neighbour
+ * search is the chunked cdist + topk over all N^2 pairs of naive_point_cloud_converter, Converters.py:98-122; 3D Gaussian
+ * splatting ships a second module, simple-knn, for this step).
+ * points [N,3]; d2(i, j) = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j, ..., each operation one IEEE fp32 operation.  Row i of
+ * idx / d2 [N,k] holds the k lexicographically smallest (d2, j) pairs, ascending, j == i left out unless include_self; a row
+ * with fewer candidates is padded with idx -1, d2 +inf.  1 <= k <= 32.  The search runs over a uniform grid of gx x gy x gz cubic
+ * cells of edge `cell` whose corner is (lo_x, lo_y, lo_z): each axis in [1, 1024], gx gy gz <= max(8 N, 2^15), and the grid must
+ * cover the cloud's bounding box (g_a > extent_a / cell) -- the result does not depend on which such grid it is, nor on the run.
+ * workspace: voge_knn_workspace_bytes(N, gx, gy, gz) bytes on a 16-byte boundary (0: N or the grid is out of range).
+ * Six small launches and the search on `stream`.
+ */
+size_t voge_knn_workspace_bytes(long N, int gx, int gy, int gz);
+int voge_knn_points(const float *points, long N, int k, int include_self, float lo_x, float lo_y, float lo_z, float cell,
+                    int gx, int gy, int gz, int32_t *idx, float *d2, void *workspace, size_t workspace_bytes,
+                    voge_stream_t stream);
+
+/*
+ * Local PCA frames of a point cloud (EXTENSION; feeds the oriented Gaussians from the neighbourhoods the converter of
+ * Converters.py:98-122 only takes a mean distance from).  Row i of idx [N,k] (1 <= k <= 32) lists neighbours of point i; entries
+ * outside [0, N) are skipped.  Mean and covariance C of the listed points in two passes, eigenvalues eig [N,3] ascending,
+ * n = eigenvector of the smallest, t1 = of the largest, quats [N,4] = the rotation [t1, n x t1, n] as (w, x, y, z), unit, w >= 0.
+ * n's sign: n . (toward - p_i) >= 0 with toward [3] (toward_per_point == 0) or [N,3]; toward == NULL: n's component of largest
+ * magnitude is positive (the lowest index on a tie).  Fewer than three listed points, or eig1 <= 2^-18 eig2: the identity.
+ */
+int voge_knn_frames(const float *points, const int32_t *idx, long N, int k, const float *toward, int toward_per_point,
+                    float *quats, float *eig, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,183 @@ def naive_point_cloud_converter(points, percentage=0.5, n_nearest=4, thr_max=2, 
     return (pts.numpy(), isigma.numpy(), None) if to_np else (pts, isigma, None)
 
 
+KNN_MAX_K = 32
+
+
+def _on_hip(t):
+    return t.is_cuda and t.dtype == torch.float32
+
+
+def knn_points(points, k, include_self=False, cell_size=None, return_grid=False):
+    """Exact k nearest neighbours of every point among the points of its own cloud -> (idx [N,k] int32, d2 [N,k] fp32); an
+    extension (the reference searches only inside naive_point_cloud_converter, Converters.py:98-122, over all N^2 pairs).
+
+    d2(i, j) = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j, dy, dz, every operation a single fp32 operation.  Row i holds the k
+    lexicographically smallest (d2, j) over all j, ascending, without j = i unless include_self: an exact tie keeps the lower
+    index, a duplicate of point i at another index is a neighbour at distance 0.  A row with fewer than k candidates is padded
+    with idx -1 and d2 +inf.  1 <= k <= 32; non-finite coordinates raise ValueError; coordinates whose d2 overflows fp32 are out
+    of contract.
+
+    This torch form (rows of the N x N matrix in chunks, +inf on the diagonal when the point itself is left out, a stable sort)
+    is the definition, and what host tensors and other dtypes (cast to fp32) get.  fp32 points on a HIP device go to the grid
+    search of ops.knn_points, which returns the same bits whatever grid it uses; cell_size asks it for a cell edge of that size
+    instead of the default (about 2 N cells over the bounding box), and return_grid=True appends the grid (cell, gx, gy, gz)
+    that ran, or would run, to the result."""
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("knn_points: points must be a [N,3] tensor")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn_points: k must be in 1 .. {KNN_MAX_K}, got {k}")
+    from .. import ops
+    if _on_hip(points):
+        idx, d2, grid = ops.knn_points(points, k, include_self, cell_size)
+        return (idx, d2, grid) if return_grid else (idx, d2)
+    pts = points.detach().to(torch.float32)
+    N = pts.shape[0]
+    if not bool(torch.isfinite(pts).all()):
+        raise ValueError("knn_points: points hold non-finite coordinates")
+    idx = torch.full((N, k), -1, dtype=torch.int32, device=pts.device)
+    d2 = torch.full((N, k), float("inf"), dtype=torch.float32, device=pts.device)
+    have = min(k, N if include_self else N - 1)
+    if have > 0:
+        x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+        chunk = max(1, (1 << 24) // N)
+        for s in range(0, N, chunk):
+            e = min(s + chunk, N)
+            dx, dy, dz = x[s:e, None] - x[None, :], y[s:e, None] - y[None, :], z[s:e, None] - z[None, :]
+            d = (dx * dx + dy * dy) + dz * dz
+            if not include_self:
+                d[torch.arange(e - s), torch.arange(s, e)] = float("inf")
+            val, order = torch.sort(d, dim=1, stable=True)
+            d2[s:e, :have] = val[:, :have]
+            idx[s:e, :have] = order[:, :have].to(torch.int32)
+    if return_grid:
+        grid = (1.0, 1, 1, 1)
+        if N > 0:
+            grid = ops.knn_grid(pts.amin(0).tolist(), pts.amax(0).tolist(), N, cell_size)
+        return idx, d2, grid
+    return idx, d2
+
+
+def _rotation_to_quaternion(R):
+    """[n,3,3] rotations -> [n,4] unit quaternions (w, x, y, z) with w >= 0, in R's dtype (the branch on the largest of the
+    trace and the diagonal entries, so that no branch divides by a small number)."""
+    m = [[R[:, i, j] for j in range(3)] for i in range(3)]
+    tr = m[0][0] + m[1][1] + m[2][2]
+    one = torch.ones_like(tr)
+    s0 = 2 * torch.sqrt(torch.clamp(tr + 1, min=1e-30))
+    s1 = 2 * torch.sqrt(torch.clamp(one + m[0][0] - m[1][1] - m[2][2], min=1e-30))
+    s2 = 2 * torch.sqrt(torch.clamp(one + m[1][1] - m[0][0] - m[2][2], min=1e-30))
+    s3 = 2 * torch.sqrt(torch.clamp(one + m[2][2] - m[0][0] - m[1][1], min=1e-30))
+    q0 = torch.stack((0.25 * s0, (m[2][1] - m[1][2]) / s0, (m[0][2] - m[2][0]) / s0, (m[1][0] - m[0][1]) / s0), -1)
+    q1 = torch.stack(((m[2][1] - m[1][2]) / s1, 0.25 * s1, (m[0][1] + m[1][0]) / s1, (m[0][2] + m[2][0]) / s1), -1)
+    q2 = torch.stack(((m[0][2] - m[2][0]) / s2, (m[0][1] + m[1][0]) / s2, 0.25 * s2, (m[1][2] + m[2][1]) / s2), -1)
+    q3 = torch.stack(((m[1][0] - m[0][1]) / s3, (m[0][2] + m[2][0]) / s3, (m[1][2] + m[2][1]) / s3, 0.25 * s3), -1)
+    b0 = (tr > 0)[:, None]
+    b1 = ((m[0][0] > m[1][1]) & (m[0][0] > m[2][2]))[:, None]
+    b2 = (m[1][1] > m[2][2])[:, None]
+    q = torch.where(b0, q0, torch.where(b1, q1, torch.where(b2, q2, q3)))
+    q = q / q.norm(dim=-1, keepdim=True)
+    return torch.where(q[:, :1] < 0, -q, q)
+
+
+FRAME_DEGENERATE = 64.0 * 2.0 ** -24      # eig1 <= this x eig2: an fp32 covariance of <= 32 terms cannot tell eig1 from zero
+
+
+def point_cloud_frames(points, idx, toward=None):
+    """Local PCA frames of a point cloud -> (quats [N,4] (w, x, y, z), unit, w >= 0; eig [N,3], ascending); an extension.
+
+    Row i uses the valid entries of idx[i] (0 <= idx < N; make the rows with knn_points(..., include_self=True)): their mean m,
+    C = sum (p - m)(p - m)^T / n in two passes, eigenvalues eig0 <= eig1 <= eig2, n = the eigenvector of eig0, t1 = that of eig2,
+    t2 = n x t1, R = [t1 t2 n] (columns), a right-handed rotation whose third axis is the surface normal.  n's sign: with
+    toward ([3] or [N,3], a sensor position) n . (toward - p_i) >= 0; otherwise n's component of largest magnitude is positive
+    (the lowest index on a tie).  A row with n < 3, or with eig1 <= 64 * 2^-24 * eig2 (the neighbours lie on a line), is
+    degenerate and gets the identity quaternion; eig is reported all the same.
+
+    This torch form works in fp64 (torch.linalg.eigh) and returns points' dtype: it is the definition, and what host tensors
+    and other dtypes get.  fp32 points on a HIP device go to the kernel (ops.knn_frames: fp32, a fixed number of Jacobi sweeps)."""
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("point_cloud_frames: points must be a [N,3] tensor")
+    N = points.shape[0]
+    if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[0] != N:
+        raise ValueError("point_cloud_frames: idx must be a [N,k] tensor")
+    if toward is not None:
+        toward = torch.as_tensor(toward, device=points.device)
+        if tuple(toward.shape) not in ((3,), (N, 3)):
+            raise ValueError("point_cloud_frames: toward must be [3] or [N,3]")
+    if _on_hip(points) and 1 <= idx.shape[1] <= KNN_MAX_K:
+        from .. import ops
+        return ops.knn_frames(points, idx.to(points.device), None if toward is None else toward.to(torch.float32))
+    out_dtype = points.dtype if points.dtype in (torch.float32, torch.float64) else torch.float32
+    p = points.detach().to(torch.float64)
+    idx = idx.to(points.device).long()
+    valid = (idx >= 0) & (idx < N)
+    nb = p[torch.where(valid, idx, torch.zeros_like(idx))]                      # [N,k,3]
+    w = valid.to(torch.float64)[..., None]
+    n = valid.sum(1)
+    nn = n.clamp(min=1).to(torch.float64)[:, None]
+    mean = (nb * w).sum(1) / nn
+    diff = (nb - mean[:, None, :]) * w
+    C = diff.transpose(1, 2) @ diff / nn[..., None]
+    lam, vec = torch.linalg.eigh(C)
+    normal, t1 = vec[:, :, 0], vec[:, :, 2]
+    if toward is not None:
+        flip = (normal * (toward.to(torch.float64) - p)).sum(-1) < 0
+    else:
+        a = normal.abs()
+        best = normal[:, 0]
+        take1 = a[:, 1] > a[:, 0]
+        best = torch.where(take1, normal[:, 1], best)
+        best = torch.where(a[:, 2] > torch.where(take1, a[:, 1], a[:, 0]), normal[:, 2], best)
+        flip = best < 0
+    normal = torch.where(flip[:, None], -normal, normal)
+    t2 = torch.cross(normal, t1, dim=-1)
+    quats = _rotation_to_quaternion(torch.stack((t1, t2, normal), dim=-1))
+    degenerate = (n < 3) | (lam[:, 1] <= FRAME_DEGENERATE * lam[:, 2]) | ~torch.isfinite(quats).all(-1)
+    identity = torch.zeros_like(quats)
+    identity[:, 0] = 1
+    quats = torch.where(degenerate[:, None], identity, quats)
+    return quats.to(out_dtype), lam.to(out_dtype)
+
+
+def point_cloud_converter(points, percentage=0.5, n_nearest=4, thr_max=2, oriented=False, n_frame=16, flatten=4.0, toward=None):
+    """Gaussians from a raw point cloud by exact neighbour search; an extension on the formula of the reference's
+    naive_point_cloud_converter (Converters.py:98-122), which stays as it is.
+
+    Isotropic: (verts, isigma [N], None).  d = sqrt(d2) of knn_points(points, n_nearest, include_self=True) -- the reference's
+    topk keeps the zero self-distance too --, L = mean(min(d, mean(d) * thr_max)) over the row's valid entries and
+    isigma = 1 / (L^2 / (4 ln(1 / percentage)) + 1e-8).
+
+    oriented=True: (verts, scales [N,3], quats [N,4]) for OrientedGaussianMeshes.  quats are point_cloud_frames' over the
+    n_frame nearest (the point included; toward orients the normals), scales = isigma * (1, 1, flatten): the third axis of R(q)
+    is the PCA normal, flatten > 1 times thinner in the inverse_sigma=False sense, so Aggregation.gaussian_normals picks exactly
+    that axis.  A degenerate frame gets (isigma, isigma, isigma) with the identity, as normal_mesh_converter's auto_fix does.
+
+    Tensors in, tensors out, on the device of `points` (a HIP device takes the kernels); a numpy cloud gives numpy back."""
+    to_np = not torch.is_tensor(points)
+    pts = torch.as_tensor(points)
+    if pts.dtype != torch.float32:
+        pts = pts.to(torch.float32)
+    N = pts.shape[0]
+    with torch.no_grad():
+        idx, d2 = knn_points(pts, n_nearest, include_self=True)
+        valid = idx >= 0
+        cnt = valid.sum(1).clamp(min=1).to(torch.float32)
+        d = torch.where(valid, torch.sqrt(d2), torch.zeros_like(d2))
+        mean = d.sum(1) / cnt
+        capped = torch.where(valid, torch.min(d, (mean * thr_max)[:, None]), torch.zeros_like(d))
+        length = capped.sum(1) / cnt
+        isigma = 1 / (length ** 2 / (4 * np.log(1 / percentage)) + 1e-8)
+        if not oriented:
+            return (pts.numpy(), isigma.numpy(), None) if to_np else (pts, isigma, None)
+        fidx, _ = knn_points(pts, n_frame, include_self=True)
+        quats, eig = point_cloud_frames(pts, fidx, toward)
+        degenerate = (((fidx >= 0) & (fidx < N)).sum(1) < 3) | (eig[:, 1] <= FRAME_DEGENERATE * eig[:, 2])
+        axes = torch.tensor([1.0, 1.0, float(flatten)], dtype=torch.float32, device=pts.device)
+        scales = isigma[:, None] * torch.where(degenerate[:, None], torch.ones_like(axes), axes)
+    return (pts.numpy(), scales.numpy(), quats.numpy()) if to_np else (pts, scales, quats)
+
+
 def to_gaussian_meshes(converter, **kwargs):
     """converter(verts, faces, **kwargs) -> GaussianMeshes factory taking (verts, faces) tensors; the
     PyTorch3D-free counterpart of pytorch3d2gaussian (Converters.py:176-194)."""

@@ -118,6 +118,10 @@ SIGNATURES = {
     "voge_sh_colors_bwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 7 + [_c_void_p] * 3),
     "voge_gauss_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 5 + [_c_void_p] * 2),
     "voge_gauss_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_void_p] * 2),
+    "voge_knn_workspace_bytes": (_c_size_t, [_c_long] + [_c_int] * 3),
+    "voge_knn_points": (_c_int, [_c_void_p, _c_long, _c_int, _c_int] + [_c_float] * 4 + [_c_int] * 3 + [_c_void_p] * 3
+                        + [_c_size_t, _c_void_p]),
+    "voge_knn_frames": (_c_int, [_c_void_p, _c_void_p, _c_long, _c_int, _c_void_p, _c_int] + [_c_void_p] * 3),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

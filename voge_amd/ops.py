@@ -4,7 +4,9 @@ torch is used here for device memory, streams and autograd bookkeeping only; eve
 computation on the path is a HIP kernel in libvoge_hip.so.  Ownership follows SURVEY.md §8b:
 the caller (these Functions) allocates every output; the library never allocates.
 """
+import math
 import os
+import struct
 
 import torch
 
@@ -1883,6 +1885,87 @@ class _GaussNormals(torch.autograd.Function):
                                             _stream())
         _lib.check(rc, "voge_gauss_normals_bwd")
         return None, g_quats, None, None, None
+
+
+def knn_grid(lo, hi, n, cell_size=None):
+    """The uniform grid voge_knn_points searches: (cell, gx, gy, gz) for a cloud of n points whose bounding box is lo .. hi
+    (three floats each).  Default: about 2 n cubic cells over the box, cell = (volume / 2n)^(1/3) -- over the axes that have an
+    extent when some have none (a planar cloud: 2 n square cells), 1 when none has; cell_size asks for a cell of its own.  Either
+    way g_a = floor(extent_a / cell) + 1 >= 1, and the cell is enlarged until every g_a <= 1024 and gx gy gz <= max(8 n, 2^15).
+    The cell is an fp32 value: the kernels get exactly the number the counts were made from."""
+    ext = [max(float(h) - float(l), 0.0) for l, h in zip(lo, hi)]
+    if cell_size is None:
+        pos = [e for e in ext if e > 0.0]
+        cell = 1.0
+        if pos:
+            vol = 1.0
+            for e in pos:
+                vol *= e
+            cell = (vol / (2.0 * max(n, 1))) ** (1.0 / len(pos))
+    else:
+        cell = float(cell_size)
+        if not (cell > 0.0 and cell < 3.0e38):
+            raise ValueError(f"knn_points: cell_size must be a positive finite fp32 number, got {cell_size}")
+    cap = max(8 * n, 1 << 15)
+    cell = max(cell, max(ext) / 1023.0, 1e-30)
+    while True:
+        cell = struct.unpack("f", struct.pack("f", cell))[0]
+        g = [int(e / cell) + 1 for e in ext]
+        cells = g[0] * g[1] * g[2]
+        if max(g) <= 1024 and cells <= cap:
+            return cell, g[0], g[1], g[2]
+        cell *= max(1.05, (cells / cap) ** (1.0 / 3.0))      # (every round grows the cell: at the latest a one-cell grid ends it)
+
+
+def knn_points(points, k, include_self=False, cell_size=None):
+    """Exact k nearest neighbours inside a cloud (extension; voge_knn_points): points [N,3] on a HIP device -> (idx [N,k] int32,
+    d2 [N,k] fp32, (cell, gx, gy, gz)), the values of Converters.knn_points bit for bit, whatever the grid.  The bounding box
+    comes from torch.aminmax and is read on the host (one synchronisation: a converter runs once per cloud, and not under graph
+    capture); the scratch is the stream's cached workspace.  A points tensor that is not fp32, contiguous and on a 16-byte
+    boundary is copied.  Non-finite coordinates raise ValueError."""
+    pts = _aligned16(_dev(points, torch.float32, "points"))
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"knn_points: points [N,3] expected, got {tuple(pts.shape)}")
+    lib = _lib.load()
+    N, k = pts.shape[0], int(k)
+    idx = torch.empty((N, k), dtype=torch.int32, device=pts.device)
+    d2 = torch.empty((N, k), dtype=torch.float32, device=pts.device)
+    if N == 0:
+        return idx, d2, (1.0, 1, 1, 1)
+    box = torch.cat(torch.aminmax(pts, dim=0)).tolist()
+    if not all(math.isfinite(v) for v in box):
+        raise ValueError("knn_points: points hold non-finite coordinates")
+    cell, gx, gy, gz = knn_grid(box[:3], box[3:], N, cell_size)
+    with _on(pts.device):
+        nbytes = lib.voge_knn_workspace_bytes(N, gx, gy, gz)
+        ws = _workspace(pts.device, nbytes)
+        rc = lib.voge_knn_points(_p(pts), N, k, int(bool(include_self)), box[0], box[1], box[2], cell, gx, gy, gz, _p(idx), _p(d2),
+                                 _p(ws), nbytes, _stream())
+    _lib.check(rc, "voge_knn_points")
+    return idx, d2, (cell, gx, gy, gz)
+
+
+def knn_frames(points, idx, toward=None):
+    """Local PCA frames (extension; voge_knn_frames): points [N,3], idx [N,k] on a HIP device, toward None | [3] | [N,3] ->
+    (quats [N,4], eig [N,3]) fp32, one launch on the current stream; Converters.point_cloud_frames is the definition."""
+    pts = _dev(points, torch.float32, "points")
+    idx = _dev(idx, torch.int32, "idx")
+    N = pts.shape[0]
+    if pts.dim() != 2 or pts.shape[1] != 3 or idx.dim() != 2 or idx.shape[0] != N:
+        raise ValueError(f"knn_frames: points [N,3] and idx [N,k] expected, got {tuple(pts.shape)} / {tuple(idx.shape)}")
+    per_point = 0
+    if toward is not None:
+        toward = _dev(toward, torch.float32, "toward")
+        if tuple(toward.shape) not in ((3,), (N, 3)):
+            raise ValueError(f"knn_frames: toward [3] or [N,3] expected, got {tuple(toward.shape)}")
+        per_point = int(toward.dim() == 2)
+    lib = _lib.load()
+    quats = torch.empty((N, 4), dtype=torch.float32, device=pts.device)
+    eig = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
+    with _on(pts.device):
+        rc = lib.voge_knn_frames(_p(pts), _p(idx), N, idx.shape[1], _p(toward), per_point, _p(quats), _p(eig), _stream())
+    _lib.check(rc, "voge_knn_frames")
+    return quats, eig
 
 
 class _DepthNormals(torch.autograd.Function):
