@@ -6,8 +6,9 @@ dist 2.7, f = 126, 128 x 128; :125-133), an ico-sphere of level 4 (2562 vertices
 `naive_vertices_converter` and only its vertices trainable (`gradianted_args=[True, False, False]`, :239),
 a per-vertex colour parameter initialised to 0.5 (:242), `max_assign=25, max_point_per_bin=-1` (:226),
 5 random views per iteration (:231), SGD lr 0.8 momentum 0.9 (:245), loss = silhouette MSE, plus rgb MSE
-from iteration 400 on (:247,:276-277); the edge / normal / laplacian entries of the reference's loss table
-are never filled in its loop (:255-280) and are left out.
+from iteration 400 on (:247,:276-277).  The edge / normal / laplacian entries of the reference's loss table
+(weights 1.0 / 0 / 0.1) are never filled in its loop (:255-280); here they are off by default and --regularise adds them
+(VoGE.Losses.mesh_regularisers over the sphere's faces: one autograd node, HIP kernels) with the table's weights.
 
 What differs, and why: the reference renders its TARGET images with PyTorch3D's mesh rasteriser from
 data/cow.obj (:110-182); neither is available here, so the targets are rendered by this renderer from a
@@ -15,7 +16,8 @@ ground-truth Gaussian set (a bumpy, coloured closed surface).  There are therefo
 match; the run is pinned by the loss going down (tests/test_gpu_parity.py::test_shape_fitting_loop_converges)
 and by the gradient checks of the kernels it uses.
 
-usage: python demo/ShapeFitting.py [--iters 2000] [--level 4] [--size 128] [--save DIR]"""
+usage: python demo/ShapeFitting.py [--iters 2000] [--level 4] [--size 128] [--save DIR]
+                                   [--regularise [--w-edge 1.0] [--w-laplacian 0.1] [--w-normal 0.0]]"""
 import argparse
 import os
 import sys
@@ -26,6 +28,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from VoGE.Converter import Converters                                                  # noqa: E402
+from VoGE.Losses import MeshTopology, mesh_regularisers                                # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_silhouette, interpolate_attr  # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
 
@@ -75,6 +78,18 @@ def make_views(num_views, dist, device):
     return look_at_view_transform(dist=dist, elev=elev, azim=azim, device=device)
 
 
+REGULARISER_WEIGHTS = {"edge": 1.0, "laplacian": 0.1, "normal": 0.0}      # the reference's loss table (ShapeFitting.py:247)
+
+
+def regulariser_loss(verts, regularisers):
+    """sum_k w_k term_k of the mesh regularisers: regularisers = {"topo": MeshTopology, "edge": w, "laplacian": w, "normal": w}
+    (a missing weight is the table's); a term whose weight is 0 is not computed."""
+    w = {k: float(regularisers.get(k, REGULARISER_WEIGHTS[k])) for k in REGULARISER_WEIGHTS}
+    on = tuple(k for k in w if w[k] != 0.0)
+    terms = dict(zip(REGULARISER_WEIGHTS, mesh_regularisers(verts, regularisers["topo"], terms=on)))
+    return sum(w[k] * terms[k] for k in on)
+
+
 def gauss_renderer(render, gmesh, R, T, color):
     """[H, W, 4] = interpolated colour + silhouette (ShapeFitting.py:219-222)."""
     frag = render(gmesh, R=R, T=T)
@@ -87,11 +102,14 @@ class BatchedIteration:
     optimizer step are each ONE launch chain over B views instead of B chains, and -- with `graph=True` -- the whole
     iteration is captured once into a HIP graph and replayed (the views of an iteration are gathered ON THE DEVICE
     from the stacked cameras / targets by an index tensor, so nothing about an iteration depends on the host).
-    The mean over a [B,H,W(,3)] batch equals the reference's sum over views of per-view means / B."""
+    The mean over a [B,H,W(,3)] batch equals the reference's sum over views of per-view means / B.
+    regularisers (see regulariser_loss; default None: nothing is added) puts the weighted mesh regularisers of gsrc.verts
+    into the loss, inside the same graph."""
 
     def __init__(self, render, gsrc, vert_color, optimizer, R_all, T_all, target_rgb, target_silhouette, views_per_iter,
-                 graph=False):
+                 graph=False, regularisers=None):
         self.render, self.gsrc, self.vert_color, self.optimizer = render, gsrc, vert_color, optimizer
+        self.regularisers = regularisers
         self.R_all, self.T_all = R_all.contiguous(), T_all.contiguous()
         self.tgt_rgb, self.tgt_sil = torch.stack(list(target_rgb)), torch.stack(list(target_silhouette))
         dev, B = self.R_all.device, views_per_iter
@@ -131,7 +149,10 @@ class BatchedIteration:
         sil = get_silhouette(frag)
         l_sil = ((sil - self.tgt_sil.index_select(0, self.sel)) ** 2).mean()
         l_rgb = ((rgb - self.tgt_rgb.index_select(0, self.sel)) ** 2).mean()
-        (l_sil + self.w_rgb * l_rgb).backward()
+        loss = l_sil + self.w_rgb * l_rgb
+        if self.regularisers is not None:
+            loss = loss + regulariser_loss(self.gsrc.verts, self.regularisers)
+        loss.backward()
         self.optimizer.step()
         self.losses.copy_(torch.stack((l_sil.detach(), l_rgb.detach())))
 
@@ -149,10 +170,12 @@ class BatchedIteration:
 
 
 def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assign=25, rgb_on=400, seed=0,
-        device="cuda:0", log_every=100, save=None, quiet=False, per_view=False, graph=False, timed_from=0):
+        device="cuda:0", log_every=100, save=None, quiet=False, per_view=False, graph=False, timed_from=0, regularise=None):
     """Runs the optimisation; returns {"silhouette": [...], "rgb": [...], "sec_per_iter": s}.
     per_view=True renders the views of an iteration one at a time, as the reference's loop is written (:258-259);
-    the default renders them as one batch (BatchedIteration; graph=True replays the iteration as a HIP graph)."""
+    the default renders them as one batch (BatchedIteration; graph=True replays the iteration as a HIP graph).
+    regularise: None, or the weights {"edge": w, "laplacian": w, "normal": w} of the mesh regularisers over the sphere's faces
+    (a missing one is REGULARISER_WEIGHTS')."""
     device = torch.device(device)
     rng = np.random.RandomState(seed)
     focal, pp = 126.0 * size / 128.0, (size / 2.0, size / 2.0)
@@ -179,10 +202,11 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
         torch.from_numpy(sv), torch.from_numpy(sf), device=device, gradianted_args=[True, False, False])
     vert_color = torch.nn.Parameter(torch.ones((gsrc.verts.shape[0], 3), device=device) * 0.5, requires_grad=True)
     optimizer = torch.optim.SGD(list(gsrc.grad_parameters()) + [vert_color], lr=0.8, momentum=0.9)
+    regularisers = None if regularise is None else dict(regularise, topo=MeshTopology(faces=sf, num_verts=sv.shape[0], device=device))
     weights = {"rgb": 0.0, "silhouette": 1.0}
     history = {"rgb": [], "silhouette": []}
     step = None if per_view else BatchedIteration(render, gsrc, vert_color, optimizer, R, T, target_rgb, target_silhouette,
-                                                  views_per_iter, graph=graph)
+                                                  views_per_iter, graph=graph, regularisers=regularisers)
     trace = torch.zeros((iters, 2), device=device)                     # losses stay on the device: no per-iteration sync
 
     # the views of every iteration, drawn up front and kept on the device: an iteration then needs nothing from the host
@@ -208,6 +232,8 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
                 loss["silhouette"] = loss["silhouette"] + ((pred[..., 3] - target_silhouette[j]) ** 2).mean() / views_per_iter
                 loss["rgb"] = loss["rgb"] + ((pred[..., :3] - target_rgb[j]) ** 2).mean() / views_per_iter
             total = sum(loss[k] * weights[k] for k in weights)
+            if regularisers is not None:
+                total = total + regulariser_loss(gsrc.verts, regularisers)
             total.backward()
             optimizer.step()
             trace[i].copy_(torch.stack((loss["silhouette"].detach(), loss["rgb"].detach())))
@@ -240,8 +266,14 @@ if __name__ == "__main__":
     ap.add_argument("--save", default=None)
     ap.add_argument("--per-view", action="store_true", help="one renderer call per view, as the reference's loop is written")
     ap.add_argument("--graph", action="store_true", help="replay the batched iteration as a HIP graph")
+    ap.add_argument("--regularise", action="store_true", help="add the mesh regularisers (edge, laplacian, normal) to the loss")
+    ap.add_argument("--w-edge", type=float, default=REGULARISER_WEIGHTS["edge"])
+    ap.add_argument("--w-laplacian", type=float, default=REGULARISER_WEIGHTS["laplacian"])
+    ap.add_argument("--w-normal", type=float, default=REGULARISER_WEIGHTS["normal"])
     a = ap.parse_args()
-    h = fit(iters=a.iters, level=a.level, size=a.size, rgb_on=a.rgb_on, save=a.save, per_view=a.per_view, graph=a.graph)
+    reg = {"edge": a.w_edge, "laplacian": a.w_laplacian, "normal": a.w_normal} if a.regularise else None
+    h = fit(iters=a.iters, level=a.level, size=a.size, rgb_on=a.rgb_on, save=a.save, per_view=a.per_view, graph=a.graph,
+            regularise=reg)
     n = max(1, len(h["silhouette"]) // 20)
     print(f"silhouette loss {np.mean(h['silhouette'][:n]):.5f} -> {np.mean(h['silhouette'][-n:]):.5f}; "
           f"rgb loss {np.mean(h['rgb'][:n]):.5f} -> {np.mean(h['rgb'][-n:]):.5f}; "

@@ -904,6 +904,39 @@ int voge_knn_points(const float *points, long N, int k, int include_self, float 
 int voge_knn_frames(const float *points, const int32_t *idx, long N, int k, const float *toward, int toward_per_point,
                     float *quats, float *eig, voge_stream_t stream);
 
+/*
+ * Mesh regularisers (EXTENSION: the reference imports mesh_edge_loss, mesh_laplacian_smoothing and mesh_normal_consistency from
+ * PyTorch3D).  verts [B][V][3]; ONE topology for the B meshes, as int32 tables in the order of voge_amd/Losses.py MeshTopology:
+ * edges [E][2] (i < j), nbr_off [V+1] / nbr [2E] (CSR adjacency), pairs [P][4] = (v0, v1, a, b) -- two faces on the edge
+ * (v0, v1) with the opposite vertices a and b --, inc_off [V+1] / inc [4P] (per vertex the entries pair * 4 + role it has).
+ * Every index must be in range: the tables are trusted (MeshTopology validates them on the host).  terms: bit 0 edge, bit 1
+ * laplacian, bit 2 normal; a term that is off costs nothing, is 0 and takes no gradient.  out [3] = (edge, laplacian, normal):
+ *   edge      = (1 / BE) sum (|v_i - v_j| - target_length)^2            a zero length counts target_length^2, no gradient
+ *   laplacian = (1 / BV) sum |L_i|, L_i = (1 / d_i) sum_j (v_j - v_i)   uniform weights; L_i == 0 or d_i == 0: no gradient
+ *   normal    = (1 / BP) sum (1 - cos(n0, n1)), n0 = (v1 - v0) x (a - v0), n1 = -(v1 - v0) x (b - v0)
+ *                                                                       a pair with a zero-area face counts 1, no gradient
+ * and 0 where E, or P, is 0.  Replaces voge_amd/Aggregation.py mesh_edge_term / mesh_laplacian_term / mesh_normal_term (gathers,
+ * an index_add_ with float atomics, norms, a cosine: dozens of launches) by two launches: one over the E + V + P items of every
+ * mesh that leaves three partial sums a workgroup in `workspace` (>= voge_mesh_reg_workspace_bytes(B, V, E, P) bytes), and one
+ * workgroup that adds them in fp64 in an order that depends on the shapes alone.  lap_dir [B][V][3] (written when the laplacian
+ * is on) = L_i / (|L_i| d_i), saved for the backward.  The terms difference positions before anything else, so a translation
+ * of the mesh changes nothing but the roundings of the inputs; the edge term is evaluated in fp32, the laplacian and the pairs
+ * in fp64 from the fp32 positions (a sliver face or a small |L_i| would amplify the rounding of an fp32 difference).
+ * Backward: g_verts [B][V][3], EVERY element written by one launch, one thread a vertex: a gather through nbr (edge terms and
+ * -d_i dir_i + sum_j dir_j) and through inc (the pair's gradient recomputed for the vertex's role), sums in fp64.  g_edge, g_lap,
+ * g_normal point at ONE float each on the device, the gradients of the three outputs (null: 0).  Neither way uses an atomic:
+ * the same bits on every run.  B == 0 or V == 0: success, nothing is launched or written.  A negative size, a terms bit above 2,
+ * a null pointer with work to do, an edges / pairs off its row's alignment (8 / 16 bytes), B * V * 3 beyond an int, E >= 2^30 or
+ * P >= 2^29: VOGE_ERR_BAD_ARG; a workspace too small: VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+size_t voge_mesh_reg_workspace_bytes(int B, int V, int E, int P);
+int voge_mesh_reg_fwd(const float *verts, const int32_t *edges, const int32_t *nbr_off, const int32_t *nbr, const int32_t *pairs,
+                      int B, int V, int E, int P, int terms, float target_length, float *lap_dir, void *workspace,
+                      size_t workspace_bytes, float *out, voge_stream_t stream);
+int voge_mesh_reg_bwd(const float *verts, const int32_t *nbr_off, const int32_t *nbr, const int32_t *pairs, const int32_t *inc_off,
+                      const int32_t *inc, const float *lap_dir, const float *g_edge, const float *g_lap, const float *g_normal,
+                      int B, int V, int E, int P, int terms, float target_length, float *g_verts, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,173 @@
+"""Mesh regularisers for shape fitting (an extension: the reference's demo/ShapeFitting.py imports mesh_edge_loss,
+mesh_laplacian_smoothing and mesh_normal_consistency from PyTorch3D, which is not available here).
+
+A MeshTopology is built ONCE on the host from the faces (or from a plain edge list) and holds int32 tables on the device;
+mesh_regularisers evaluates the three terms of a vertex set over it as ONE autograd node.  The terms are defined in torch in
+Aggregation.mesh_edge_term / mesh_laplacian_term / mesh_normal_term; fp32 vertices on the HIP device that holds the tables take
+the kernels of voge_amd/csrc/mesh_reg.hip (ops._MeshReg: two launches forward, one backward, no atomics, the same bits on every
+run), everything else -- host tensors, other dtypes, vertices on another device than the tables -- takes the definitions.
+The cotangent ("cot", "cotcurv") Laplacians of PyTorch3D and a normal term on per-vertex normals are out of scope."""
+import numpy as np
+import torch
+
+from . import Aggregation, ops
+
+TERMS = ("edge", "laplacian", "normal")      # bit k of the kernels' mask
+
+
+def _index_array(x, width, name):
+    """x as an int64 numpy array [n, width]; ValueError for anything that is not an integer table of that width."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.size == 0:
+        x = np.zeros((0, width), np.int64)
+    if x.ndim != 2 or x.shape[1] != width or not np.issubdtype(x.dtype, np.integer):
+        raise ValueError(f"MeshTopology: {name} must be an integer array [n,{width}], got {x.dtype} {tuple(x.shape)}")
+    return x.astype(np.int64)
+
+
+def _csr(owner, n):
+    """offsets [n+1] of a sorted owner array"""
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(owner, minlength=n), out=off[1:])
+    return off
+
+
+class MeshTopology:
+    """The connectivity the mesh regularisers need, built once on the host with numpy (never per step).
+
+    MeshTopology(faces=[F,3]) takes a triangle mesh, MeshTopology(edges=[E,2]) a plain graph -- e.g. the symmetrised
+    Converters.knn_points neighbours of a point cloud --, which has no face pairs: its normal term is 0.  num_verts defaults to
+    the largest index + 1; a vertex nothing uses is allowed (degree 0).  ValueError: an index out of range, a face (or an edge)
+    that names a vertex twice, both faces and edges given, or neither.
+
+    The tables are int32 tensors on `device` (default: the host) in this fixed order:
+      edges   [E,2]   the unique undirected pairs i < j, sorted lexicographically;
+      nbr_off [V+1], nbr [2E]   the adjacency as CSR: nbr[nbr_off[i] : nbr_off[i+1]] are i's neighbours, ascending;
+      pairs   [P,4] = (v0, v1, a, b)   one row for every pair of faces that share the edge (v0, v1), v0 < v1; a and b are the
+              opposite vertices of the first and the second face.  An edge with m faces gives m (m - 1) / 2 rows, a boundary edge
+              none.  Rows are sorted by (edge, first face index, second face index);
+      inc_off [V+1], inc [4P]   per vertex the entries pair * 4 + role (role = the column of `pairs` that names it), ascending.
+    num_verts, num_edges, num_pairs and max_degree are Python ints; .to(device) gives the same tables on another device."""
+
+    _TABLES = ("edges", "nbr_off", "nbr", "pairs", "inc_off", "inc")
+
+    def __init__(self, faces=None, num_verts=None, edges=None, device=None):
+        if (faces is None) == (edges is None):
+            raise ValueError("MeshTopology: give faces or edges, not both and not neither")
+        given = _index_array(faces, 3, "faces") if faces is not None else _index_array(edges, 2, "edges")
+        V = int(given.max()) + 1 if num_verts is None and given.size else int(num_verts or 0)
+        if V < 0 or V > 2 ** 31 - 1 or (given.size and (given.min() < 0 or given.max() >= V)):
+            raise ValueError(f"MeshTopology: indices must lie in [0, {V})")
+        s = np.sort(given, axis=1)
+        if (s[:, 1:] == s[:, :-1]).any():
+            raise ValueError(f"MeshTopology: {'a face' if faces is not None else 'an edge'} names a vertex twice")
+
+        if faces is not None:
+            F = given.shape[0]
+            # the three edges of every face with the vertex opposite: (lo, hi, opposite, face)
+            corner = np.concatenate([given[:, [0, 1, 2]], given[:, [1, 2, 0]], given[:, [2, 0, 1]]])
+            lo, hi = np.minimum(corner[:, 0], corner[:, 1]), np.maximum(corner[:, 0], corner[:, 1])
+            opp, face = corner[:, 2], np.tile(np.arange(F), 3)
+            und = np.stack([lo, hi], 1)
+        else:
+            und = s
+        key, edge_of = np.unique(und[:, 0] * V + und[:, 1], return_inverse=True)      # (lexicographic: lo * V + hi, below 2^62)
+        uniq = np.stack([key // max(V, 1), key % max(V, 1)], 1)
+        E = uniq.shape[0]
+
+        owner = np.concatenate([uniq[:, 0], uniq[:, 1]])
+        other = np.concatenate([uniq[:, 1], uniq[:, 0]])
+        order = np.lexsort((other, owner))
+        nbr, nbr_off = other[order], _csr(owner[order], V)
+
+        pairs = np.zeros((0, 4), np.int64)
+        if faces is not None and E:
+            edge_of = edge_of.reshape(-1)
+            order = np.lexsort((face, edge_of))                       # the faces of every edge, by face index
+            e_s, f_s, o_s = edge_of[order], face[order], opp[order]
+            count = np.bincount(e_s, minlength=E)
+            start = _csr(e_s, E)[:-1]
+            rows = []
+            for m in np.unique(count[count >= 2]):
+                first, second = np.triu_indices(int(m), 1)
+                base = start[count == m][:, None]
+                i0, i1 = (base + first[None, :]).ravel(), (base + second[None, :]).ravel()
+                rows.append(np.stack([e_s[i0], f_s[i0], f_s[i1], o_s[i0], o_s[i1]], 1))
+            if rows:
+                r = np.concatenate(rows)
+                r = r[np.lexsort((r[:, 2], r[:, 1], r[:, 0]))]
+                pairs = np.concatenate([uniq[r[:, 0]], r[:, 3:5]], 1)
+        P = pairs.shape[0]
+        if E > 2 ** 30 - 1 or P > 2 ** 29 - 1:
+            raise ValueError("MeshTopology: too many edges or face pairs for the int32 tables")
+        vert = pairs.ravel()
+        inc = np.argsort(vert, kind="stable")                         # entry = pair * 4 + role, ascending inside a vertex
+        inc_off = _csr(vert, V)
+
+        self.num_verts, self.num_edges, self.num_pairs = V, E, P
+        self.max_degree = int((nbr_off[1:] - nbr_off[:-1]).max()) if V else 0
+        self._host = {"edges": uniq.reshape(E, 2), "nbr_off": nbr_off, "nbr": nbr, "pairs": pairs, "inc_off": inc_off, "inc": inc}
+        self._place(torch.device("cpu" if device is None else device))
+
+    def _place(self, device):
+        for name in self._TABLES:
+            setattr(self, name, torch.from_numpy(np.ascontiguousarray(self._host[name], dtype=np.int32)).to(device))
+        self.device = self.edges.device
+
+    def to(self, device):
+        """The same topology with its tables on `device` (self when they are there already)."""
+        device = torch.device(device)
+        if device == self.edges.device:
+            return self
+        other = object.__new__(MeshTopology)
+        other.num_verts, other.num_edges, other.num_pairs, other.max_degree = self.num_verts, self.num_edges, self.num_pairs, self.max_degree
+        other._host = self._host
+        other._place(device)
+        return other
+
+
+def _terms_mask(terms):
+    if isinstance(terms, str):
+        terms = (terms,)
+    mask = 0
+    for t in terms:
+        if t not in TERMS:
+            raise ValueError(f"mesh_regularisers: unknown term {t!r} (one of {TERMS})")
+        mask |= 1 << TERMS.index(t)
+    return mask
+
+
+def mesh_regularisers(verts, topo, target_length=0.0, terms=TERMS):
+    """(edge, laplacian, normal) of verts [V,3] | [B,V,3] over a MeshTopology, as 0-dim tensors; for a batch each term is the
+    mean over the B meshes, which share the topology.  A term that is not in `terms` is not computed, is returned as an exact 0
+    and passes no gradient.  Definitions: Aggregation.mesh_edge_term (target_length is a Python float), mesh_laplacian_term
+    (uniform weights; PyTorch3D's "cot" and "cotcurv" are out of scope) and mesh_normal_term.  Only verts get a gradient.
+    fp32 verts on the HIP device of the tables: ONE autograd node (ops._MeshReg), no double backward; otherwise the definitions,
+    with the tables moved to the vertices' device."""
+    mask = _terms_mask(terms)
+    if verts.dim() not in (2, 3) or tuple(verts.shape[-2:]) != (topo.num_verts, 3):
+        raise ValueError(f"mesh_regularisers: verts [{topo.num_verts},3] or [B,{topo.num_verts},3] expected, got {tuple(verts.shape)}")
+    if verts.is_cuda and verts.dtype == torch.float32 and topo.edges.device == verts.device:
+        return ops.mesh_reg(verts, topo, float(target_length), mask)
+    t = topo.to(verts.device)
+    zero = verts.new_zeros(())
+    return (Aggregation.mesh_edge_term(verts, t.edges, float(target_length)) if mask & 1 else zero,
+            Aggregation.mesh_laplacian_term(verts, t.nbr_off, t.nbr) if mask & 2 else zero,
+            Aggregation.mesh_normal_term(verts, t.pairs) if mask & 4 else zero)
+
+
+def mesh_edge_loss(verts, topo, target_length=0.0):
+    """(1 / E) sum_e (|v_i - v_j| - target_length)^2: mesh_regularisers with the edge term alone."""
+    return mesh_regularisers(verts, topo, target_length, ("edge",))[0]
+
+
+def mesh_laplacian_smoothing(verts, topo):
+    """(1 / V) sum_i |L_i| with uniform weights: mesh_regularisers with the laplacian term alone ("cot" / "cotcurv": out of scope)."""
+    return mesh_regularisers(verts, topo, 0.0, ("laplacian",))[1]
+
+
+def mesh_normal_consistency(verts, topo):
+    """(1 / P) sum (1 - cos) over the pairs of faces that share an edge: mesh_regularisers with the normal term alone."""
+    return mesh_regularisers(verts, topo, 0.0, ("normal",))[2]

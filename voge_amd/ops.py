@@ -1887,6 +1887,59 @@ class _GaussNormals(torch.autograd.Function):
         return None, g_quats, None, None, None
 
 
+class _MeshReg(torch.autograd.Function):
+    """Mesh regularisers (extension; voge_mesh_reg_fwd / _bwd): forward(verts [V,3] | [B,V,3], topo, target_length, terms) ->
+    (edge, laplacian, normal), three 0-dim views of ONE [3] buffer, the values of Aggregation.mesh_edge_term /
+    mesh_laplacian_term / mesh_normal_term over the tables of a Losses.MeshTopology on the same device.  terms: bit 0 edge,
+    bit 1 laplacian, bit 2 normal; a term that is off is not computed, is an exact 0 and takes no gradient.  Two launches forward
+    (the items of every mesh, then one workgroup that adds the partial sums in a fixed order), one backward; the partial sums
+    live in the stream's cached workspace, the forward saves L_i / (|L_i| d_i) [B,V,3] when the laplacian is on, and the backward
+    reads the three upstream gradients on the device and writes every element of g_verts (no zero fill, no atomics: the same
+    bits on every run).  Only verts get a gradient; no double backward."""
+
+    @staticmethod
+    def forward(ctx, verts, topo, target_length, terms):
+        v = _dev(verts, torch.float32, "verts")
+        lib = _lib.load()
+        V, E, P = topo.num_verts, topo.num_edges, topo.num_pairs
+        if tuple(v.shape[-2:]) != (V, 3) or v.dim() not in (2, 3):
+            raise ValueError(f"mesh_regularisers: verts [{V},3] or [B,{V},3] expected, got {tuple(v.shape)}")
+        if topo.edges.device != v.device:
+            raise _lib.VogeHipError(f"mesh_regularisers: verts on {v.device}, the topology on {topo.edges.device}")
+        B = v.shape[0] if v.dim() == 3 else 1
+        out = (torch.zeros if B * V == 0 else torch.empty)((3,), dtype=torch.float32, device=v.device)      # (nothing is launched for an empty batch)
+        lap_dir = torch.empty_like(v) if terms & 2 else None
+        with _on(v.device):
+            nbytes = lib.voge_mesh_reg_workspace_bytes(B, V, E, P)
+            ws = _workspace(v.device, nbytes)
+            rc = lib.voge_mesh_reg_fwd(_p(v), _p(topo.edges), _p(topo.nbr_off), _p(topo.nbr), _p(topo.pairs), B, V, E, P, terms,
+                                       target_length, _p(lap_dir), _p(ws), nbytes, _p(out), _stream())
+        _lib.check(rc, "voge_mesh_reg_fwd")
+        ctx.save_for_backward(v, lap_dir)
+        ctx.topo, ctx.target_length, ctx.terms = topo, target_length, terms
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_edge, g_lap, g_normal):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        lib = _lib.load()
+        v, lap_dir = ctx.saved_tensors
+        topo = ctx.topo
+        V = topo.num_verts
+        B = v.shape[0] if v.dim() == 3 else 1
+        g = [None if t_ is None else _dev(t_, torch.float32, "grad_term") for t_ in (g_edge, g_lap, g_normal)]
+        g_verts = (torch.zeros_like if B * V == 0 else torch.empty_like)(v)
+        with _on(v.device):
+            rc = lib.voge_mesh_reg_bwd(_p(v), _p(topo.nbr_off), _p(topo.nbr), _p(topo.pairs), _p(topo.inc_off), _p(topo.inc),
+                                       _p(lap_dir), _p(g[0]), _p(g[1]), _p(g[2]), B, V, topo.num_edges, topo.num_pairs, ctx.terms,
+                                       ctx.target_length, _p(g_verts), _stream())
+        _lib.check(rc, "voge_mesh_reg_bwd")
+        return g_verts, None, None, None
+
+
 def knn_grid(lo, hi, n, cell_size=None):
     """The uniform grid voge_knn_points searches: (cell, gx, gy, gz) for a cloud of n points whose bounding box is lo .. hi
     (three floats each).  Default: about 2 n cubic cells over the box, cell = (volume / 2n)^(1/3) -- over the axes that have an
@@ -2251,6 +2304,10 @@ def sh_colors(sh, verts, centres, degree, clamp=True):
 
 def gauss_normals(scales, quats, verts, centres, inverse_sigma=False):
     return _GaussNormals.apply(scales, quats, verts, centres, inverse_sigma)
+
+
+def mesh_reg(verts, topo, target_length=0.0, terms=7):
+    return _MeshReg.apply(verts, topo, float(target_length), int(terms))
 
 
 def depth_normals(depth, R, focal, pp, row0=0, edge=None, view_space=False):
