@@ -9,6 +9,8 @@ a per-vertex colour parameter initialised to 0.5 (:242), `max_assign=25, max_poi
 from iteration 400 on (:247,:276-277).  The edge / normal / laplacian entries of the reference's loss table
 (weights 1.0 / 0 / 0.1) are never filled in its loop (:255-280); here they are off by default and --regularise adds them
 (VoGE.Losses.mesh_regularisers over the sphere's faces: one autograd node, HIP kernels) with the table's weights.
+--w-chamfer W (default 0: nothing is computed) adds W * chamfer_distance(vertices, ground-truth vertices), the 3-D supervision a
+fit has when target points exist; it runs inside the captured iteration.
 
 What differs, and why: the reference renders its TARGET images with PyTorch3D's mesh rasteriser from
 data/cow.obj (:110-182); neither is available here, so the targets are rendered by this renderer from a
@@ -17,7 +19,7 @@ match; the run is pinned by the loss going down (tests/test_gpu_parity.py::test_
 and by the gradient checks of the kernels it uses.
 
 usage: python demo/ShapeFitting.py [--iters 2000] [--level 4] [--size 128] [--save DIR]
-                                   [--regularise [--w-edge 1.0] [--w-laplacian 0.1] [--w-normal 0.0]]"""
+                                   [--regularise [--w-edge 1.0] [--w-laplacian 0.1] [--w-normal 0.0]] [--w-chamfer 0.0]"""
 import argparse
 import os
 import sys
@@ -28,7 +30,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from VoGE.Converter import Converters                                                  # noqa: E402
-from VoGE.Losses import MeshTopology, mesh_regularisers                                # noqa: E402
+from VoGE.Losses import MeshTopology, chamfer_distance, mesh_regularisers              # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_silhouette, interpolate_attr  # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
 
@@ -104,12 +106,13 @@ class BatchedIteration:
     from the stacked cameras / targets by an index tensor, so nothing about an iteration depends on the host).
     The mean over a [B,H,W(,3)] batch equals the reference's sum over views of per-view means / B.
     regularisers (see regulariser_loss; default None: nothing is added) puts the weighted mesh regularisers of gsrc.verts
-    into the loss, inside the same graph."""
+    into the loss, inside the same graph; chamfer = (weight, target points [M,3]) (default None) adds
+    weight * chamfer_distance(gsrc.verts, target points) the same way."""
 
     def __init__(self, render, gsrc, vert_color, optimizer, R_all, T_all, target_rgb, target_silhouette, views_per_iter,
-                 graph=False, regularisers=None):
+                 graph=False, regularisers=None, chamfer=None):
         self.render, self.gsrc, self.vert_color, self.optimizer = render, gsrc, vert_color, optimizer
-        self.regularisers = regularisers
+        self.regularisers, self.chamfer = regularisers, chamfer
         self.R_all, self.T_all = R_all.contiguous(), T_all.contiguous()
         self.tgt_rgb, self.tgt_sil = torch.stack(list(target_rgb)), torch.stack(list(target_silhouette))
         dev, B = self.R_all.device, views_per_iter
@@ -152,6 +155,8 @@ class BatchedIteration:
         loss = l_sil + self.w_rgb * l_rgb
         if self.regularisers is not None:
             loss = loss + regulariser_loss(self.gsrc.verts, self.regularisers)
+        if self.chamfer is not None:
+            loss = loss + self.chamfer[0] * chamfer_distance(self.gsrc.verts, self.chamfer[1])[0]
         loss.backward()
         self.optimizer.step()
         self.losses.copy_(torch.stack((l_sil.detach(), l_rgb.detach())))
@@ -170,12 +175,14 @@ class BatchedIteration:
 
 
 def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assign=25, rgb_on=400, seed=0,
-        device="cuda:0", log_every=100, save=None, quiet=False, per_view=False, graph=False, timed_from=0, regularise=None):
+        device="cuda:0", log_every=100, save=None, quiet=False, per_view=False, graph=False, timed_from=0, regularise=None,
+        w_chamfer=0.0):
     """Runs the optimisation; returns {"silhouette": [...], "rgb": [...], "sec_per_iter": s}.
     per_view=True renders the views of an iteration one at a time, as the reference's loop is written (:258-259);
     the default renders them as one batch (BatchedIteration; graph=True replays the iteration as a HIP graph).
     regularise: None, or the weights {"edge": w, "laplacian": w, "normal": w} of the mesh regularisers over the sphere's faces
-    (a missing one is REGULARISER_WEIGHTS')."""
+    (a missing one is REGULARISER_WEIGHTS').  w_chamfer: the weight of chamfer_distance(vertices, ground-truth vertices); 0 (the
+    default) computes nothing."""
     device = torch.device(device)
     rng = np.random.RandomState(seed)
     focal, pp = 126.0 * size / 128.0, (size / 2.0, size / 2.0)
@@ -203,10 +210,11 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
     vert_color = torch.nn.Parameter(torch.ones((gsrc.verts.shape[0], 3), device=device) * 0.5, requires_grad=True)
     optimizer = torch.optim.SGD(list(gsrc.grad_parameters()) + [vert_color], lr=0.8, momentum=0.9)
     regularisers = None if regularise is None else dict(regularise, topo=MeshTopology(faces=sf, num_verts=sv.shape[0], device=device))
+    chamfer = None if not w_chamfer else (float(w_chamfer), torch.from_numpy(gv).to(device))
     weights = {"rgb": 0.0, "silhouette": 1.0}
     history = {"rgb": [], "silhouette": []}
     step = None if per_view else BatchedIteration(render, gsrc, vert_color, optimizer, R, T, target_rgb, target_silhouette,
-                                                  views_per_iter, graph=graph, regularisers=regularisers)
+                                                  views_per_iter, graph=graph, regularisers=regularisers, chamfer=chamfer)
     trace = torch.zeros((iters, 2), device=device)                     # losses stay on the device: no per-iteration sync
 
     # the views of every iteration, drawn up front and kept on the device: an iteration then needs nothing from the host
@@ -234,6 +242,8 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
             total = sum(loss[k] * weights[k] for k in weights)
             if regularisers is not None:
                 total = total + regulariser_loss(gsrc.verts, regularisers)
+            if chamfer is not None:
+                total = total + chamfer[0] * chamfer_distance(gsrc.verts, chamfer[1])[0]
             total.backward()
             optimizer.step()
             trace[i].copy_(torch.stack((loss["silhouette"].detach(), loss["rgb"].detach())))
@@ -270,10 +280,11 @@ if __name__ == "__main__":
     ap.add_argument("--w-edge", type=float, default=REGULARISER_WEIGHTS["edge"])
     ap.add_argument("--w-laplacian", type=float, default=REGULARISER_WEIGHTS["laplacian"])
     ap.add_argument("--w-normal", type=float, default=REGULARISER_WEIGHTS["normal"])
+    ap.add_argument("--w-chamfer", type=float, default=0.0, help="weight of the chamfer distance to the ground-truth vertices (0: off)")
     a = ap.parse_args()
     reg = {"edge": a.w_edge, "laplacian": a.w_laplacian, "normal": a.w_normal} if a.regularise else None
     h = fit(iters=a.iters, level=a.level, size=a.size, rgb_on=a.rgb_on, save=a.save, per_view=a.per_view, graph=a.graph,
-            regularise=reg)
+            regularise=reg, w_chamfer=a.w_chamfer)
     n = max(1, len(h["silhouette"]) // 20)
     print(f"silhouette loss {np.mean(h['silhouette'][:n]):.5f} -> {np.mean(h['silhouette'][-n:]):.5f}; "
           f"rgb loss {np.mean(h['rgb'][:n]):.5f} -> {np.mean(h['rgb'][-n:]):.5f}; "

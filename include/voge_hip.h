@@ -937,6 +937,50 @@ int voge_mesh_reg_bwd(const float *verts, const int32_t *nbr_off, const int32_t 
                       const int32_t *inc, const float *lap_dir, const float *g_edge, const float *g_lap, const float *g_normal,
                       int B, int V, int E, int P, int terms, float target_length, float *g_verts, voge_stream_t stream);
 
+/*
+ * The nearest point of a cloud for every query (EXTENSION.  Replaces the cdist + min over all Nq Np pairs that PyTorch3D's
+ * chamfer_distance, which the reference's demo/ShapeFitting.py imports, stands for; voge_knn_points searches inside ONE cloud).
+ * queries [Nq,3], points [Np,3]; d2(q, p) = (dx*dx + dy*dy) + dz*dz, each operation one IEEE fp32 operation.  idx [Nq] / d2 [Nq]:
+ * the lexicographically smallest (d2, index) over the points -- an exact tie keeps the lower index.  route 0: chosen by Nq Np,
+ * 1: brute force (the points tiled through LDS, one launch), 2: a uniform grid over the union of both clouds, chosen ON THE DEVICE
+ * (bounding box, the grid rule of voge_knn_points' wrapper, both clouds binned, a ring search with knn's stopping rule at k = 1:
+ * eleven small launches and the search); both return the same bits, and neither reads anything back on the host, so the call may
+ * be captured into a graph.  cell_size > 0 asks the grid route for a cell of that edge (enlarged until the grid fits its caps),
+ * 0: about 2 max(Nq, Np) cells.  workspace: voge_chamfer_workspace_bytes(Nq, Np) bytes on a 16-byte boundary (0: a size below 1
+ * or above 2^28 - 1); its first 32 bytes hold the grid that ran (lo[3], cell, 1 / cell as floats, gx, gy, gz as ints) after a
+ * grid-route call.  Non-finite coordinates: indices in range or -1, values out of contract.
+ * Nq == 0: success, nothing is launched.  Np < 1, a negative or too large size, an unknown route, a cell_size that is negative or
+ * not finite, a null pointer, a workspace that is null or off the 16-byte boundary: VOGE_ERR_BAD_ARG; a workspace too small:
+ * VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+size_t voge_chamfer_workspace_bytes(long Nx, long Ny);
+int voge_nearest_points(const float *queries, long Nq, const float *points, long Np, int route, float cell_size, int32_t *idx,
+                        float *d2, void *workspace, size_t workspace_bytes, voge_stream_t stream);
+
+/*
+ * Chamfer distance between two clouds x [Nx,3] and y [Ny,3] (EXTENSION: the reference's demo/ShapeFitting.py imports
+ * chamfer_distance from PyTorch3D).  Replaces voge_amd/Aggregation.py chamfer_term (rows of the Nx x Ny matrix in chunks):
+ *   loss[0] = (1 / Nx) sum_i min_j d2(x_i, y_j) + (1 / Ny) sum_j min_i d2(y_j, x_i)
+ * flags bit 0: the sums without their divisors ("sum"); bit 1: the first sum alone (single_directional; nn_y is not touched).
+ * nn_x [Nx] / nn_y [Ny] int32: the nearest indices, the values of voge_nearest_points (route as there), saved for the backward;
+ * meta [4] int32: meta[0] = s, the scale exponent of the backward's fixed-point sums, chosen on the device from the largest d2 and
+ * max(Nx, Ny).  Every d2 is fp32; the sums are fp64 -- one partial per 1024 queries, added by ONE workgroup in an order that depends
+ * on the shapes alone -- and the loss is rounded to fp32 once.  The same bits on every run; no host read-back: capturable.
+ * Backward: g_x [Nx,3], g_y [Ny,3], EVERY element written, from g_loss (ONE float on the device):
+ *   g_x[i] = g (2 / Nx) (x_i - y_nn(i)) + g (2 / Ny) sum_{j: nn(j) = i} (x_i - y_j), g_y likewise;
+ * three launches: a zero fill of the [Nx + Ny][3] int64 accumulators in the workspace, a scatter that adds every fp32 difference,
+ * scaled by 2^s and rounded to an integer, with 64-bit INTEGER atomics (exact: the sum does not depend on the order; a list of m
+ * points is off by at most m 2^-s / 2 per component), and a finish that adds the gather term in fp64 and rounds once.  An index
+ * outside its cloud is skipped.  No float atomics.  workspace: voge_chamfer_workspace_bytes(Nx, Ny) serves both calls.
+ * Nx < 1 or Ny < 1, a size above 2^28 - 1, an unknown route or flag, a null pointer (nn_y may be null with flags bit 1), a workspace
+ * that is null or off the 16-byte boundary: VOGE_ERR_BAD_ARG; a workspace too small: VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+int voge_chamfer_fwd(const float *x, long Nx, const float *y, long Ny, int route, int flags, float *loss, int32_t *nn_x,
+                     int32_t *nn_y, int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream);
+int voge_chamfer_bwd(const float *x, long Nx, const float *y, long Ny, const int32_t *nn_x, const int32_t *nn_y,
+                     const int32_t *meta, const float *g_loss, int flags, float *g_x, float *g_y, void *workspace,
+                     size_t workspace_bytes, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -384,3 +384,49 @@ def mesh_normal_term(verts, pairs):
     one = torch.ones_like(l0)
     cos = (torch.where(ok[..., None], n0, torch.zeros_like(n0)) * n1).sum(-1) / torch.where(ok, l0 * l1, one)
     return (1 - cos).mean()
+
+
+def nearest_rows(queries, points):
+    """For every row of queries [Nq,3] the lexicographically smallest (d2, index) over points [Np,3] (Np >= 1) -> (idx [Nq] int64,
+    d2 [Nq]), in the tensors' own dtype and not differentiable: d2 = (dx*dx + dy*dy) + dz*dz, each a single operation of that
+    dtype, rows of the Nq x Np matrix in chunks, an exact tie keeps the LOWER index (the minimum over the indices that attain the
+    row's minimum: no reliance on which of several equal entries torch.min reports)."""
+    q, p = queries.detach(), points.detach()
+    Nq, Np = q.shape[0], p.shape[0]
+    idx = torch.empty((Nq,), dtype=torch.long, device=q.device)
+    d2 = torch.empty((Nq,), dtype=q.dtype, device=q.device)
+    chunk = max(1, (1 << 24) // max(Np, 1))
+    ar = torch.arange(Np, device=q.device)
+    for s in range(0, Nq, chunk):
+        e = min(s + chunk, Nq)
+        dx, dy, dz = q[s:e, None, 0] - p[None, :, 0], q[s:e, None, 1] - p[None, :, 1], q[s:e, None, 2] - p[None, :, 2]
+        d = (dx * dx + dy * dy) + dz * dz
+        m = d.min(dim=1).values
+        d2[s:e] = m
+        idx[s:e] = torch.where(d == m[:, None], ar[None, :], Np).min(dim=1).values
+    return idx, d2
+
+
+def chamfer_term(x, y, single_directional=False, point_reduction="mean", return_indices=False):
+    """Chamfer distance of two clouds (PyTorch3D's chamfer_distance at norm=2, without lengths and weights; an extension here):
+    x [Nx,3], y [Ny,3],
+
+        (1 / Nx) sum_i min_j |x_i - y_j|^2 + (1 / Ny) sum_j min_i |y_j - x_i|^2,
+
+    point_reduction="sum" without the two divisors, single_directional the first sum alone.  The nearest indices come from
+    nearest_rows (a tie keeps the lower index) and are constants of the graph, as the argmin of a min is; the distances are
+    recomputed from them, so both clouds get gradients.  return_indices=True: (loss, nn_x, nn_y | None), int64.  Differentiable torch
+    on any device / dtype: the definition ops._Chamfer is tested against and the route for everything it does not take."""
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError(f"chamfer_term: point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != 3 or y.shape[1] != 3 or x.shape[0] == 0 or y.shape[0] == 0:
+        raise ValueError(f"chamfer_term: non-empty x [Nx,3] and y [Ny,3] expected, got {tuple(x.shape)} / {tuple(y.shape)}")
+    y = y.to(x.dtype)
+    reduce = torch.mean if point_reduction == "mean" else torch.sum
+    nn_x = nearest_rows(x, y)[0]
+    loss = reduce(((x - y[nn_x]) ** 2).sum(-1))
+    nn_y = None
+    if not single_directional:
+        nn_y = nearest_rows(y, x)[0]
+        loss = loss + reduce(((y - x[nn_y]) ** 2).sum(-1))
+    return (loss, nn_x, nn_y) if return_indices else loss

@@ -198,6 +198,35 @@ def knn_points(points, k, include_self=False, cell_size=None, return_grid=False)
     return idx, d2
 
 
+def nearest_points(queries, points, cell_size=None, route=None):
+    """The nearest point of `points` [Np,3] for every row of `queries` [Nq,3] -> (idx [Nq] int32, d2 [Nq] fp32); an extension
+    (knn_points searches inside one cloud; this is the search between two that the chamfer distance needs).
+
+    d2 = (dx*dx + dy*dy) + dz*dz, every operation a single fp32 operation -- knn_points' convention --, and a query gets the
+    lexicographically smallest (d2, index) over the points: an exact tie keeps the lower index.  Nq == 0 gives empty outputs,
+    Np == 0 raises ValueError.  Not differentiable.
+
+    The torch form (Aggregation.nearest_rows on the fp32 values: rows of the Nq x Np matrix in chunks) is the definition, and what
+    host tensors and other dtypes (cast to fp32) get.  fp32 tensors on a HIP device go to the kernels of ops.nearest_points, which
+    return the same bits: route "brute" (all pairs, the points tiled through LDS), "grid" (a uniform grid over both clouds, chosen
+    on the device: no host synchronisation, capturable) or None (chosen by Nq Np); cell_size asks the grid for a cell of that
+    edge.  Both arguments are ignored by the definition, which validates them all the same."""
+    if not torch.is_tensor(queries) or not torch.is_tensor(points) or queries.dim() != 2 or points.dim() != 2 \
+            or queries.shape[1] != 3 or points.shape[1] != 3:
+        raise ValueError("nearest_points: queries [Nq,3] and points [Np,3] tensors expected")
+    if points.shape[0] == 0:
+        raise ValueError("nearest_points: points is empty")
+    from .. import Aggregation, ops
+    if route not in ops.CHAMFER_ROUTES:
+        raise ValueError(f"nearest_points: route must be None, 'brute' or 'grid', got {route!r}")
+    if cell_size is not None and not (0.0 < float(cell_size) < 3.0e38):
+        raise ValueError(f"nearest_points: cell_size must be a positive finite fp32 number, got {cell_size}")
+    if _on_hip(queries) and _on_hip(points) and queries.device == points.device:
+        return ops.nearest_points(queries.detach(), points.detach(), cell_size, route)
+    idx, d2 = Aggregation.nearest_rows(queries.detach().to(torch.float32), points.detach().to(torch.float32).to(queries.device))
+    return idx.to(torch.int32), d2
+
+
 def _rotation_to_quaternion(R):
     """[n,3,3] rotations -> [n,4] unit quaternions (w, x, y, z) with w >= 0, in R's dtype (the branch on the largest of the
     trace and the diagonal entries, so that no branch divides by a small number)."""

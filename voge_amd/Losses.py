@@ -6,7 +6,12 @@ mesh_regularisers evaluates the three terms of a vertex set over it as ONE autog
 Aggregation.mesh_edge_term / mesh_laplacian_term / mesh_normal_term; fp32 vertices on the HIP device that holds the tables take
 the kernels of voge_amd/csrc/mesh_reg.hip (ops._MeshReg: two launches forward, one backward, no atomics, the same bits on every
 run), everything else -- host tensors, other dtypes, vertices on another device than the tables -- takes the definitions.
-The cotangent ("cot", "cotcurv") Laplacians of PyTorch3D and a normal term on per-vertex normals are out of scope."""
+The cotangent ("cot", "cotcurv") Laplacians of PyTorch3D and a normal term on per-vertex normals are out of scope.
+
+chamfer_distance is the fourth loss that demo imports: the score of a fit against the points it should reach.  Its definition is
+Aggregation.chamfer_term; fp32 clouds on a HIP device take the kernels of voge_amd/csrc/chamfer.hip (ops._Chamfer: exact nearest
+points over a grid chosen on the device, fp64 sums in a fixed order, an integer-atomic backward -- the same bits on every run and
+nothing read back on the host, so it runs inside a captured iteration)."""
 import numpy as np
 import torch
 
@@ -171,3 +176,62 @@ def mesh_laplacian_smoothing(verts, topo):
 def mesh_normal_consistency(verts, topo):
     """(1 / P) sum (1 - cos) over the pairs of faces that share an edge: mesh_regularisers with the normal term alone."""
     return mesh_regularisers(verts, topo, 0.0, ("normal",))[2]
+
+
+def _normals_term(n_own, n_other, nn, reduce):
+    """PyTorch3D's normal term of one direction: reduce(1 - |cos(n_own_i, n_other_nn(i))|), cosine_similarity with eps 1e-6"""
+    cos = torch.nn.functional.cosine_similarity(n_own, n_other[nn.long()], dim=-1, eps=1e-6)
+    return reduce(1 - cos.abs())
+
+
+def _chamfer_pair(x, y, x_normals, y_normals, single_directional, point_reduction):
+    if x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and y.device == x.device:
+        loss, nn_x, nn_y = ops.chamfer(x, y, point_reduction == "sum", single_directional)
+    else:
+        loss, nn_x, nn_y = Aggregation.chamfer_term(x, y, single_directional, point_reduction, return_indices=True)
+    loss_normals = None
+    if x_normals is not None:
+        reduce = torch.mean if point_reduction == "mean" else torch.sum
+        loss_normals = _normals_term(x_normals, y_normals, nn_x, reduce)
+        if not single_directional:
+            loss_normals = loss_normals + _normals_term(y_normals, x_normals, nn_y, reduce)
+    return loss, loss_normals
+
+
+def chamfer_distance(x, y, x_normals=None, y_normals=None, single_directional=False, point_reduction="mean", **unsupported):
+    """(loss, loss_normals) of two clouds x [Nx,3] and y [Ny,3] -- PyTorch3D's return shape, `loss, _ = chamfer_distance(a, b)`:
+
+        loss = (1 / Nx) sum_i min_j |x_i - y_j|^2 + (1 / Ny) sum_j min_i |y_j - x_i|^2,
+
+    point_reduction="sum" without the two divisors, single_directional the first sum alone.  Both clouds get gradients.  The
+    definition is Aggregation.chamfer_term, and what host tensors and other dtypes get; fp32 clouds on one HIP device are ONE
+    autograd node (ops._Chamfer, no double backward) with no host synchronisation.  A batch x [B,Nx,3], y [B,Ny,3] is a HOST LOOP
+    over the B pairs whose losses are averaged (PyTorch3D's batch_reduction="mean"): the kernels handle one pair of clouds.
+    loss_normals is None without normals; with x_normals [.., Nx,3] and y_normals [.., Ny,3] it is PyTorch3D's 1 - |cos| between a
+    point's normal and the normal at its nearest point, reduced and summed over the directions like the loss -- a plain torch
+    expression on the node's saved indices, differentiable in the normals only.
+    Out of scope, ValueError by name: norm=1, x_lengths / y_lengths, weights, batch_reduction other than "mean", and
+    point_reduction other than "mean" / "sum"; wrong shapes and an empty cloud raise ValueError too."""
+    for name, value in unsupported.items():
+        if name not in ("norm", "x_lengths", "y_lengths", "weights", "batch_reduction", "abs_cosine"):
+            raise TypeError(f"chamfer_distance: unexpected argument {name!r}")
+        if value is not None and not (name == "norm" and value == 2) and not (name == "batch_reduction" and value == "mean") \
+                and not (name == "abs_cosine" and value is True):
+            raise ValueError(f"chamfer_distance: {name}={value!r} is out of scope")
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError(f"chamfer_distance: point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    if not torch.is_tensor(x) or not torch.is_tensor(y) or x.dim() not in (2, 3) or y.dim() != x.dim() or x.shape[-1] != 3 \
+            or y.shape[-1] != 3 or (x.dim() == 3 and x.shape[0] != y.shape[0]):
+        raise ValueError("chamfer_distance: x [Nx,3] and y [Ny,3], or [B,Nx,3] and [B,Ny,3], expected")
+    if x.shape[-2] == 0 or y.shape[-2] == 0 or (x.dim() == 3 and x.shape[0] == 0):
+        raise ValueError("chamfer_distance: an empty cloud")
+    if (x_normals is None) != (y_normals is None):
+        raise ValueError("chamfer_distance: give both x_normals and y_normals, or neither")
+    if x_normals is not None and (x_normals.shape != x.shape or y_normals.shape != y.shape):
+        raise ValueError("chamfer_distance: the normals must have their clouds' shapes")
+    if x.dim() == 2:
+        return _chamfer_pair(x, y, x_normals, y_normals, single_directional, point_reduction)
+    pairs = [_chamfer_pair(x[b], y[b], None if x_normals is None else x_normals[b], None if y_normals is None else y_normals[b],
+                           single_directional, point_reduction) for b in range(x.shape[0])]
+    loss = torch.stack([p[0] for p in pairs]).mean()
+    return loss, (None if x_normals is None else torch.stack([p[1] for p in pairs]).mean())

@@ -125,6 +125,12 @@ SIGNATURES = {
     "voge_mesh_reg_workspace_bytes": (_c_size_t, [_c_int] * 4),
     "voge_mesh_reg_fwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 5 + [_c_float, _c_void_p, _c_void_p, _c_size_t] + [_c_void_p] * 2),
     "voge_mesh_reg_bwd": (_c_int, [_c_void_p] * 10 + [_c_int] * 5 + [_c_float] + [_c_void_p] * 2),
+    "voge_chamfer_workspace_bytes": (_c_size_t, [_c_long] * 2),
+    "voge_nearest_points": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_int, _c_float] + [_c_void_p] * 3
+                            + [_c_size_t, _c_void_p]),
+    "voge_chamfer_fwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 5 + [_c_size_t, _c_void_p]),
+    "voge_chamfer_bwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
+                         + [_c_size_t, _c_void_p]),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

@@ -1,0 +1,621 @@
+// Chamfer distance (EXTENSION: the reference's demo/ShapeFitting.py imports chamfer_distance from PyTorch3D; the torch form is a
+// cdist + min over all Nx Ny pairs): exact nearest points between TWO clouds, the loss over them and its backward.
+//
+// voge_nearest_points.  d2(q, p) = (dx*dx + dy*dy) + dz*dz with dx = xq - xp, ..., every operation one IEEE fp32 operation (the
+// library is built with -ffp-contract=off); a query gets the lexicographically smallest (d2, index) over the points, held as ONE
+// 64-bit key (d2 bits << 32 | index; d2 >= 0, so its bits order as the value does) in a register.  That is a property of the SET
+// of candidates, so the two routes return the same bits:
+//   brute  chamfer_brute_kernel, one launch a direction: 64 queries a workgroup, the points tiled through LDS 1024 at a time, the
+//          four waves take a quarter of a tile each and the four keys of a query meet in LDS (a minimum: no order to depend on);
+//   grid   the search of knn.hip between two clouds, over a grid chosen ON THE DEVICE -- nothing of the call depends on a value
+//          the host would have to read, so it can be captured into a graph:
+//     (a) chamfer_box_kernel / chamfer_grid_kernel: the bounding box of the UNION of the clouds, and one thread that runs the rule
+//         of ops.knn_grid: about 2 n cubic cells (n = max(Nx, Ny)), cell >= max extent / 1023, G_a = floor(extent_a / cell) + 1 <=
+//         1024 on every axis, G = Gx Gy Gz <= max(8 n, 2^15); the loop that enlarges the cell has 64 trips at most, and a box that
+//         is not finite or a loop that did not end gives the one-cell grid (every point a candidate of ring 0: a brute force).
+//         The grid goes into the workspace's head, every later kernel reads it from there; the workspace and the launches are
+//         sized for the cap on G, which depends on (Nx, Ny) alone, and the scan reads the real G from memory;
+//     (b) both clouds binned in that one grid: integer atomic counts, the scan of knn_grid.h, the fill -- as knn.hip does;
+//     (c) chamfer_search_kernel: one query per lane, in its OWN cloud's cell order (a wave's lanes share their candidate cells),
+//         against the other cloud's cell-ordered array; rings r = 0, 1, 2, ... of cells around the query's cell.
+// The stopping rule is knn.hip's at k = 1.  After ring r every cell within Chebyshev distance r of the query's has been visited,
+// so an unvisited point p differs from the query q by >= r + 1 in the cell index of some axis.  With t(x) = (x - lo) / cell and
+// u(x) = fl(fl(x - lo) * fl(1 / cell)) = t(x) (1 + e), |e| < 2^-22: floorf and the clamp are monotone and the clamp never widens a
+// difference, so u_p - u_q > r, hence t_p - t_q > r - 2^-22 (t_p + t_q) > r - 2^-11 -- t < 1024 for EVERY point and EVERY query,
+// which is why the box must be the union's: G_a <= 1024 is made from the box that holds both clouds.  So p is farther than
+// cell (r - 2^-11) from q on that axis, and the search stops after ring r once it holds a candidate whose d2 <= b * b,
+// b = cell (r - 2^-10) (1 - 2^-20) > 0 (the factor covers the roundings of b, b * b and of an fp32 d2 >= dx^2): every unvisited
+// point has an fp32 d2 strictly above the kept one -- no tie can be missed.  A query whose own cell holds no point of the other
+// cloud simply holds no candidate yet: the rule cannot fire (and never fires at r = 0, where b < 0), the rings go on until one
+// does or until the cube covers the grid, which bounds every loop.  A NaN or an infinity lands on a valid cell (knn_axis_cell) and
+// walks at most the whole grid; the values are then out of contract, the indices still in range (an index that is not is written
+// as -1, and the backward skips it).
+//
+// voge_chamfer_fwd.  The two searches write d2 by the query's own index; chamfer_loss_partial_kernel leaves one fp64 sum (and the
+// largest d2) per 1024 queries, chamfer_loss_final_kernel -- ONE workgroup -- adds them in an order fixed by the shapes (the
+// mesh_reg.hip pattern) and rounds sum_x / Nx + sum_y / Ny to fp32 once.
+//
+// voge_chamfer_bwd, three launches.  g_x[i] = g (2 / Nx) (x_i - y_nn(i)) + g (2 / Ny) sum_{j: nn(j) = i} (x_i - y_j): a gather and
+// a scatter whose lists can be as long as the other cloud (coincident points all pick index 0).  The scatter is done in FIXED
+// POINT: every fp32 difference is scaled by 2^s, rounded to an int64 and added with a 64-bit INTEGER atomic into a zero-filled
+// [N][3] accumulator -- integer addition is exact, so the sum does not depend on the order and the bits are the same on every run,
+// at a cost linear in the points.  s is chosen on the device by the forward's last kernel and saved in meta[0]: with
+// D = sqrt(max d2 (1 + 2^-20) + 2^-148) < 2^e bounding every component of every scattered difference (they are the differences
+// the d2 were made of) and n = max(Nx, Ny) <= 2^L bounding every list, s = 62 - L - e, so |sum| <= 2^62 cannot overflow.  The
+// quantum is q = 2^-s <= 2^(L - 61) D: a list of m terms is off by at most m q / 2 <= m 2^(L - 62) D per component, 2^-34 D a
+// term for the largest clouds this library holds (L = 28).  chamfer_finish_kernel turns the accumulators into fp64, adds
+// the gather term (one fp32 difference), scales by the upstream gradient and writes EVERY element of g_x and g_y, rounded to fp32
+// once.  No float atomics anywhere, no wait on another workgroup.
+#include <math.h>
+
+#include "knn_grid.h"
+
+namespace voge {
+
+constexpr long kChamferMaxN = 268435455l;
+constexpr double kChamferBruteMaxPairs = 8388608.0;      // Nx Ny at or below this: the brute route (measured: profiles/r17_chamfer.txt)
+constexpr int kChSearchBlock = 128;
+constexpr int kChBoxItems = 8;          // points a thread of the box pass: 2048 a workgroup
+constexpr int kChLossItems = 4;         // d2 a thread of the partial sums: 1024 a workgroup
+constexpr int kChTile = 1024;           // points of a brute-force tile
+constexpr int kChGridTrips = 64;
+
+// the most cells a grid for clouds of at most n points may have (ops.knn_grid's cap; G and G + 1 stay ints)
+__host__ __device__ inline long chamfer_cell_cap(const long n) {
+  const long cap = 8 * n > 32768l ? 8 * n : 32768l;
+  return cap < 2147483646l ? cap : 2147483646l;
+}
+
+struct ChamferHead {      // the workspace's first 64 bytes
+  KnnGrid g;
+  int G;
+  int pad[7];
+};
+static_assert(sizeof(ChamferHead) == 64, "ChamferHead is 64 bytes");
+
+// ---- the grid, chosen on the device -------------------------------------------------------------------------------------------
+
+// fminf / fmaxf drop a NaN: a cloud with some NaN coordinates still gets the box of its numbers
+__global__ void __launch_bounds__(256)
+chamfer_box_kernel(const float *__restrict__ x, const int Nx, const float *__restrict__ y, const int Ny, float *__restrict__ partial) {
+  const size_t n = (size_t)Nx + (size_t)Ny;
+  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < kChBoxItems; ++k) {
+    const size_t i = ((size_t)blockIdx.x * kChBoxItems + k) * 256 + threadIdx.x;
+    if (i < n) {
+      const float *p = i < (size_t)Nx ? x + 3 * i : y + 3 * (i - (size_t)Nx);
+      const float a = p[0], b = p[1], c = p[2];
+      lo0 = fminf(lo0, a); lo1 = fminf(lo1, b); lo2 = fminf(lo2, c);
+      hi0 = fmaxf(hi0, a); hi1 = fmaxf(hi1, b); hi2 = fmaxf(hi2, c);
+    }
+  }
+  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
+  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
+  __shared__ float red[4][6];
+  if ((threadIdx.x & 63) == 0) {
+    float *r = red[threadIdx.x >> 6];
+    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    const int c = threadIdx.x;
+    const float a = red[0][c], b = red[1][c], d = red[2][c], e = red[3][c];
+    partial[(size_t)blockIdx.x * 6 + c] = c < 3 ? fminf(fminf(a, b), fminf(d, e)) : fmaxf(fmaxf(a, b), fmaxf(d, e));
+  }
+}
+
+// ONE workgroup: the box of the partial boxes, then thread 0 chooses the grid (the rule of ops.knn_grid; n = max(Nx, Ny),
+// cell_size > 0 asks for a cell of that size and goes through the same enlargement)
+__global__ void __launch_bounds__(256)
+chamfer_grid_kernel(const float *__restrict__ partial, const int nb, const long n, const float cell_size, ChamferHead *__restrict__ head) {
+  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
+  for (int i = threadIdx.x; i < nb; i += 256) {
+    const float *p = partial + (size_t)i * 6;
+    lo0 = fminf(lo0, p[0]); lo1 = fminf(lo1, p[1]); lo2 = fminf(lo2, p[2]);
+    hi0 = fmaxf(hi0, p[3]); hi1 = fmaxf(hi1, p[4]); hi2 = fmaxf(hi2, p[5]);
+  }
+  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
+  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
+  __shared__ float red[4][6];
+  if ((threadIdx.x & 63) == 0) {
+    float *r = red[threadIdx.x >> 6];
+    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float lo[3], hi[3];
+  for (int c = 0; c < 3; ++c) {
+    lo[c] = fminf(fminf(red[0][c], red[1][c]), fminf(red[2][c], red[3][c]));
+    hi[c] = fmaxf(fmaxf(red[0][c + 3], red[1][c + 3]), fmaxf(red[2][c + 3], red[3][c + 3]));
+  }
+  double ext[3], mx = 0.0;
+  bool fin = true;
+  for (int c = 0; c < 3; ++c) {
+    const float e = hi[c] - lo[c];
+    fin = fin && fabsf(lo[c]) < INFINITY && fabsf(hi[c]) < INFINITY && fabsf(e) < INFINITY;
+    ext[c] = e > 0.0f ? (double)e : 0.0;
+    mx = fmax(mx, ext[c]);
+  }
+  ChamferHead h;
+  h.g = KnnGrid{fin ? lo[0] : 0.0f, fin ? lo[1] : 0.0f, fin ? lo[2] : 0.0f, 1.0f, 1.0f, 1, 1, 1};      // the one-cell fallback
+  h.G = 1;
+  for (int k = 0; k < 7; ++k) h.pad[k] = 0;
+  if (fin) {
+    const double cap = (double)chamfer_cell_cap(n);
+    double cell;
+    if (cell_size > 0.0f && cell_size < INFINITY) {
+      cell = (double)cell_size;
+    } else {
+      int np = 0;
+      double vol = 1.0;
+      for (int c = 0; c < 3; ++c)
+        if (ext[c] > 0.0) { vol *= ext[c]; ++np; }
+      cell = np ? pow(vol / (2.0 * (double)(n > 1 ? n : 1)), 1.0 / (double)np) : 1.0;
+    }
+    cell = fmax(cell, fmax(mx / 1023.0, 1e-30));
+    for (int trip = 0; trip < kChGridTrips; ++trip) {
+      const float cf = (float)cell;
+      const float inv = 1.0f / cf;
+      if (!(cf > 0.0f) || !(cf < INFINITY) || !(inv > 0.0f) || !(inv < INFINITY)) break;
+      double cells = 1.0;
+      bool fits = true;
+      int g[3];
+      for (int c = 0; c < 3; ++c) {
+        const double q = floor(ext[c] / (double)cf) + 1.0;
+        fits = fits && q <= (double)kKnnMaxAxis;
+        g[c] = (int)fmin(q, (double)kKnnMaxAxis);
+        cells *= q;
+      }
+      if (fits && cells <= cap) {
+        h.g.cell = cf; h.g.inv = inv;
+        h.g.gx = g[0]; h.g.gy = g[1]; h.g.gz = g[2];
+        h.G = g[0] * g[1] * g[2];
+        break;
+      }
+      cell = (double)cf * fmax(1.05, cbrt(cells / cap));      // (every round grows the cell)
+    }
+  }
+  *head = h;
+}
+
+// ---- both clouds binned in the one grid ---------------------------------------------------------------------------------------
+
+struct ChamferCloud {
+  const float *pts;
+  int N;
+  int *cellid, *counts, *start;
+  float4 *sorted;
+};
+
+__global__ void __launch_bounds__(256)
+chamfer_zero_kernel(const ChamferHead *__restrict__ head, int *__restrict__ c0, int *__restrict__ c1) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)head->G) return;
+  c0[i] = 0;
+  c1[i] = 0;
+}
+
+__global__ void __launch_bounds__(256)
+chamfer_count_kernel(const ChamferCloud a, const ChamferCloud b, const unsigned nba, const ChamferHead *__restrict__ head) {
+  const bool first = blockIdx.x < nba;
+  const size_t i = (size_t)(blockIdx.x - (first ? 0u : nba)) * 256 + threadIdx.x;
+  const int N = first ? a.N : b.N;
+  if (i >= (size_t)N) return;
+  const KnnGrid g = head->g;
+  const float *p = (first ? a.pts : b.pts) + 3 * i;
+  const int cx = knn_axis_cell(p[0], g.lox, g.inv, g.gx), cy = knn_axis_cell(p[1], g.loy, g.inv, g.gy),
+            cz = knn_axis_cell(p[2], g.loz, g.inv, g.gz);
+  const int c = (cz * g.gy + cy) * g.gx + cx;
+  (first ? a.cellid : b.cellid)[i] = c;
+  atomicAdd((first ? a.counts : b.counts) + c, 1);
+}
+
+// counts[c] falls back to zero, one slot a point: slot = the value after the decrement, in [0, count)
+__global__ void __launch_bounds__(256)
+chamfer_fill_kernel(const ChamferCloud a, const ChamferCloud b, const unsigned nba, const ChamferHead *__restrict__ head) {
+  const bool first = blockIdx.x < nba;
+  const size_t i = (size_t)(blockIdx.x - (first ? 0u : nba)) * 256 + threadIdx.x;
+  const int N = first ? a.N : b.N;
+  if (i >= (size_t)N) return;
+  const int c = (first ? a.cellid : b.cellid)[i];
+  if (c < 0 || c >= head->G) return;      // (the count pass wrote a cell of this grid: a guard, not a route)
+  const int slot = atomicSub((first ? a.counts : b.counts) + c, 1) - 1;
+  const int pos = (first ? a.start : b.start)[c] + slot;
+  if (slot < 0 || pos < 0 || pos >= N) return;      // (cannot happen after the count pass over the same cellid: a guard, not a route)
+  const float *p = (first ? a.pts : b.pts) + 3 * i;
+  (first ? a.sorted : b.sorted)[pos] = make_float4(p[0], p[1], p[2], __int_as_float((int)i));
+}
+
+// ---- the two searches ---------------------------------------------------------------------------------------------------------
+
+struct ChamferDir {      // Nq queries in their cloud's cell order against the Nd points of the other cloud in theirs
+  const float4 *q;
+  int Nq;
+  const float4 *db;
+  const int *start;
+  int Nd;
+  int32_t *idx;
+  float *d2;
+};
+
+__device__ __forceinline__ void chamfer_store(const uint64_t best, const int Nd, int32_t *__restrict__ idx, float *__restrict__ d2,
+                                              const size_t at) {
+  const uint32_t pi = (uint32_t)(best & 0xffffffffull);
+  const bool ok = best != ~0ull && pi < (uint32_t)Nd;
+  idx[at] = ok ? (int32_t)pi : -1;
+  d2[at] = ok ? __uint_as_float((uint32_t)(best >> 32)) : INFINITY;
+}
+
+__global__ void __launch_bounds__(kChSearchBlock)
+chamfer_search_kernel(const ChamferDir d0, const ChamferDir d1, const unsigned nb0, const ChamferHead *__restrict__ head) {
+  const bool first = blockIdx.x < nb0;
+  const size_t t = (size_t)(blockIdx.x - (first ? 0u : nb0)) * kChSearchBlock + threadIdx.x;
+  const int Nq = first ? d0.Nq : d1.Nq, Nd = first ? d0.Nd : d1.Nd;
+  if (t >= (size_t)Nq) return;      // (no barrier below)
+  const float4 *__restrict__ sorted = first ? d0.db : d1.db;
+  const int *__restrict__ start = first ? d0.start : d1.start;
+  const float4 q = (first ? d0.q : d1.q)[t];
+  const int qi = __float_as_int(q.w);
+  if (qi < 0 || qi >= Nq) return;      // (every slot of the query array was filled with an index below Nq: a guard on the output row)
+  const KnnGrid g = head->g;
+  const int cx = knn_axis_cell(q.x, g.lox, g.inv, g.gx), cy = knn_axis_cell(q.y, g.loy, g.inv, g.gy),
+            cz = knn_axis_cell(q.z, g.loz, g.inv, g.gz);
+  uint64_t best = ~0ull;
+  // the ring at which the cube covers the grid
+  const int rmax = max(max(max(cx, g.gx - 1 - cx), max(cy, g.gy - 1 - cy)), max(cz, g.gz - 1 - cz));
+  for (int r = 0; r <= rmax; ++r) {
+    const int x0 = max(cx - r, 0), x1 = min(cx + r, g.gx - 1);
+    const int y0 = max(cy - r, 0), y1 = min(cy + r, g.gy - 1);
+    const int z0 = max(cz - r, 0), z1 = min(cz + r, g.gz - 1);
+    for (int zz = z0; zz <= z1; ++zz) {
+      for (int yy = y0; yy <= y1; ++yy) {
+        const int row = (zz * g.gy + yy) * g.gx;
+        // a row of the shell's faces in y or z: cells x0 .. x1 are consecutive in cell order, one range; an inner row:
+        // the two cells at x = cx -+ r (r >= 1 there), where the grid has them
+        const bool face = (abs(zz - cz) == r) || (abs(yy - cy) == r);
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+          int ca, cb;      // cells [ca, cb] of the row
+          if (face) {
+            if (part == 1) break;
+            ca = x0; cb = x1;
+          } else {
+            ca = cb = part == 0 ? cx - r : cx + r;
+            if (ca < 0 || ca >= g.gx) continue;
+          }
+          const int j0 = max(start[row + ca], 0), j1 = min(start[row + cb + 1], Nd);
+          for (int j = j0; j < j1; ++j) {
+            const float4 p = sorted[j];
+            const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+            const float d = (dx * dx + dy * dy) + dz * dz;
+            const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)__float_as_int(p.w);
+            best = key < best ? key : best;
+          }
+        }
+      }
+    }
+    if (best != ~0ull) {
+      const float b = g.cell * ((float)r - 0x1p-10f) * (1.0f - 0x1p-20f);
+      if (b > 0.0f && __uint_as_float((uint32_t)(best >> 32)) <= b * b) break;
+    }
+  }
+  chamfer_store(best, Nd, first ? d0.idx : d1.idx, first ? d0.d2 : d1.d2, (size_t)qi);
+}
+
+// 64 queries a workgroup (lane = query), wave w takes entries [256 w, 256 w + 256) of every tile
+__global__ void __launch_bounds__(256)
+chamfer_brute_kernel(const float *__restrict__ qs, const int Nq, const float *__restrict__ db, const int Nd, int32_t *__restrict__ idx,
+                     float *__restrict__ d2) {
+  __shared__ float4 tile[kChTile];
+  __shared__ uint64_t keys[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t qi = (size_t)blockIdx.x * 64 + lane;
+  const size_t qr = qi < (size_t)Nq ? qi : (size_t)Nq - 1;      // (a lane past the end repeats the last query and writes nothing)
+  const float qx = qs[3 * qr], qy = qs[3 * qr + 1], qz = qs[3 * qr + 2];
+  uint64_t best = ~0ull;
+  for (int t0 = 0; t0 < Nd; t0 += kChTile) {
+    const int n = min(kChTile, Nd - t0);
+    __syncthreads();
+    for (int k = threadIdx.x; k < n; k += 256) {
+      const float *p = db + 3 * ((size_t)t0 + k);
+      tile[k] = make_float4(p[0], p[1], p[2], 0.0f);
+    }
+    __syncthreads();
+    const int k0 = wave * (kChTile / 4), k1 = min(k0 + kChTile / 4, n);
+#pragma unroll 4
+    for (int k = k0; k < k1; ++k) {
+      const float4 p = tile[k];
+      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+      const float d = (dx * dx + dy * dy) + dz * dz;
+      const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)(t0 + k);
+      best = key < best ? key : best;
+    }
+  }
+  keys[wave][lane] = best;
+  __syncthreads();
+  if (wave == 0 && qi < (size_t)Nq) {
+    const uint64_t a = keys[0][lane], b = keys[1][lane], c = keys[2][lane], d = keys[3][lane];
+    const uint64_t ab = a < b ? a : b, cd = c < d ? c : d;
+    chamfer_store(ab < cd ? ab : cd, Nd, idx, d2, qi);
+  }
+}
+
+// ---- the loss -----------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ double chamfer_wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// workgroups [0, nba): d2a, the rest: d2b; one fp64 sum and the largest d2 a workgroup
+__global__ void __launch_bounds__(256)
+chamfer_loss_partial_kernel(const float *__restrict__ d2a, const int Na, const float *__restrict__ d2b, const int Nb, const unsigned nba,
+                            double *__restrict__ psum, float *__restrict__ pmax) {
+  const bool first = blockIdx.x < nba;
+  const float *__restrict__ d = first ? d2a : d2b;
+  const int N = first ? Na : Nb;
+  const size_t base = (size_t)(blockIdx.x - (first ? 0u : nba)) * (256 * kChLossItems) + threadIdx.x;
+  double s = 0.0;
+  float m = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kChLossItems; ++k) {
+    const size_t i = base + (size_t)k * 256;
+    const float v = i < (size_t)N ? d[i] : 0.0f;
+    s += (double)v;
+    m = fmaxf(m, v);
+  }
+  s = chamfer_wave_sum_f64(s);
+  m = wave_max(m);
+  __shared__ double rs[4];
+  __shared__ float rm[4];
+  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rm[threadIdx.x >> 6] = m; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    psum[blockIdx.x] = (rs[0] + rs[1]) + (rs[2] + rs[3]);
+    pmax[blockIdx.x] = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+  }
+}
+
+// ONE workgroup: loss = sum_a / div_a + sum_b / div_b in fp64, rounded once; meta[0] = the backward's scale exponent s (header)
+__global__ void __launch_bounds__(256)
+chamfer_loss_final_kernel(const double *__restrict__ psum, const float *__restrict__ pmax, const unsigned nba, const unsigned nbb,
+                          const double div_a, const double div_b, const int list_bits, float *__restrict__ loss,
+                          int32_t *__restrict__ meta) {
+  double sa = 0.0, sb = 0.0;
+  float m = 0.0f;
+  for (unsigned i = threadIdx.x; i < nba; i += 256) { sa += psum[i]; m = fmaxf(m, pmax[i]); }
+  for (unsigned i = threadIdx.x; i < nbb; i += 256) { sb += psum[nba + i]; m = fmaxf(m, pmax[nba + i]); }
+  __shared__ double red[2][256];
+  __shared__ float redm[256];
+  red[0][threadIdx.x] = sa; red[1][threadIdx.x] = sb; redm[threadIdx.x] = m;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+      redm[threadIdx.x] = fmaxf(redm[threadIdx.x], redm[threadIdx.x + h]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  loss[0] = (float)(red[0][0] / div_a + (nbb ? red[1][0] / div_b : 0.0));
+  int s = 0;
+  const double D = sqrt((double)redm[0] * (1.0 + 0x1p-20) + 0x1p-148);
+  if (D < (double)INFINITY) {      // (false for a NaN too: s = 0, the values are out of contract)
+    int e;
+    frexp(D, &e);      // D = f 2^e, f in [0.5, 1): D < 2^e
+    s = 62 - list_bits - e;
+  }
+  meta[0] = s; meta[1] = 0; meta[2] = 0; meta[3] = 0;
+}
+
+// ---- backward -----------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ void chamfer_add(long long *acc, const float diff, const double scale) {
+  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)llrint((double)diff * scale));
+}
+
+// workgroups [0, nbx): point i of x adds (y_nn(i) - x_i) 2^s to acc_y[nn(i)]; the rest: point j of y adds (x_nn(j) - y_j) 2^s to
+// acc_x[nn(j)] (nn_y == nullptr, the single-directional form: no such workgroups)
+__global__ void __launch_bounds__(256)
+chamfer_scatter_kernel(const float *__restrict__ x, const int Nx, const float *__restrict__ y, const int Ny,
+                       const int32_t *__restrict__ nn_x, const int32_t *__restrict__ nn_y, const int32_t *__restrict__ meta,
+                       long long *__restrict__ acc_x, long long *__restrict__ acc_y, const unsigned nbx) {
+  const bool first = blockIdx.x < nbx;
+  const size_t i = (size_t)(blockIdx.x - (first ? 0u : nbx)) * 256 + threadIdx.x;
+  const int Nown = first ? Nx : Ny, Nother = first ? Ny : Nx;
+  if (i >= (size_t)Nown) return;
+  const int j = (first ? nn_x : nn_y)[i];
+  if (j < 0 || j >= Nother) return;
+  const double scale = ldexp(1.0, meta[0]);
+  const float *p = (first ? x : y) + 3 * i, *o = (first ? y : x) + 3 * (size_t)j;
+  long long *acc = (first ? acc_y : acc_x) + 3 * (size_t)j;
+  chamfer_add(acc, o[0] - p[0], scale);
+  chamfer_add(acc + 1, o[1] - p[1], scale);
+  chamfer_add(acc + 2, o[2] - p[2], scale);
+}
+
+// one point a thread, x then y: g = G (w_gather (own - nearest) + w_scatter acc 2^-s), every element written
+__global__ void __launch_bounds__(256)
+chamfer_finish_kernel(const float *__restrict__ x, const int Nx, const float *__restrict__ y, const int Ny,
+                      const int32_t *__restrict__ nn_x, const int32_t *__restrict__ nn_y, const int32_t *__restrict__ meta,
+                      const long long *__restrict__ acc_x, const long long *__restrict__ acc_y, const float *__restrict__ g_loss,
+                      const double w_x, const double w_y, float *__restrict__ g_x, float *__restrict__ g_y) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)Nx + (size_t)Ny) return;
+  const bool first = t < (size_t)Nx;
+  const size_t i = first ? t : t - (size_t)Nx;
+  const int Nother = first ? Ny : Nx;
+  const int32_t *nn = first ? nn_x : nn_y;
+  const double G = (double)g_loss[0], unscale = ldexp(1.0, -meta[0]);
+  const double w_gather = first ? w_x : w_y, w_scatter = first ? w_y : w_x;      // (a list into x holds points of y, weighted 2 / Ny)
+  const float *p = (first ? x : y) + 3 * i;
+  const long long *acc = (first ? acc_x : acc_y) + 3 * i;
+  float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+  const int j = nn ? nn[i] : -1;
+  if (j >= 0 && j < Nother) {
+    const float *o = (first ? y : x) + 3 * (size_t)j;
+    d0 = p[0] - o[0]; d1 = p[1] - o[1]; d2 = p[2] - o[2];
+  }
+  // (a member of the list added (its nearest - itself) = (this point - the member): the sign this point's gradient wants)
+  float *g = (first ? g_x : g_y) + 3 * i;
+  g[0] = (float)(G * (w_gather * (double)d0 + w_scatter * ((double)acc[0] * unscale)));
+  g[1] = (float)(G * (w_gather * (double)d1 + w_scatter * ((double)acc[1] * unscale)));
+  g[2] = (float)(G * (w_gather * (double)d2 + w_scatter * ((double)acc[2] * unscale)));
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+
+enum { kChamferSum = 1, kChamferSingle = 2 };
+enum { kRouteAuto = 0, kRouteBrute = 1, kRouteGrid = 2 };
+
+struct ChamferLayout {
+  size_t head, boxp, sorted[2], cellid[2], counts[2], start[2], bsum[2], d2[2], psum, pmax, total;
+  long cap;
+  int nb_scan, nb_box;
+  unsigned nb_loss[2];
+};
+static ChamferLayout chamfer_layout(const long Nx, const long Ny) {
+  ChamferLayout l;
+  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
+  const long N[2] = {Nx, Ny}, n = Nx > Ny ? Nx : Ny;
+  l.cap = chamfer_cell_cap(n);
+  l.nb_scan = (int)((l.cap + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
+  l.nb_box = (int)((Nx + Ny + 256 * kChBoxItems - 1) / (256 * kChBoxItems));
+  size_t at = 0;
+  l.head = at; at += sizeof(ChamferHead);
+  l.boxp = at; at += up16((size_t)l.nb_box * 6 * sizeof(float));
+  for (int c = 0; c < 2; ++c) {
+    l.nb_loss[c] = (unsigned)((N[c] + 256 * kChLossItems - 1) / (256 * kChLossItems));
+    l.sorted[c] = at; at += (size_t)N[c] * 16;
+    l.cellid[c] = at; at += up16((size_t)N[c] * 4);
+    l.counts[c] = at; at += up16((size_t)l.cap * 4);
+    l.start[c] = at; at += up16((size_t)(l.cap + 1) * 4);
+    l.bsum[c] = at; at += up16((size_t)l.nb_scan * 4);
+    l.d2[c] = at; at += up16((size_t)N[c] * 4);
+  }
+  l.psum = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(double));
+  l.pmax = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(float));
+  const size_t bwd = (size_t)(Nx + Ny) * 3 * sizeof(long long);      // the backward's accumulators, a call of its own
+  l.total = at > bwd ? at : bwd;
+  return l;
+}
+
+static bool chamfer_sizes_ok(const long Nx, const long Ny) { return Nx >= 1 && Ny >= 1 && Nx <= kChamferMaxN && Ny <= kChamferMaxN; }
+
+static bool chamfer_brute(const int route, const long Nx, const long Ny) {
+  return route == kRouteBrute || (route == kRouteAuto && (double)Nx * (double)Ny <= kChamferBruteMaxPairs);
+}
+
+// the nearest point of y for every x (idx_x, d2_x) and -- both -- of x for every y; the pointers were validated by the caller
+static void chamfer_searches(const float *x, const long Nx, const float *y, const long Ny, const bool brute, const float cell_size,
+                             const bool both, int32_t *idx_x, float *d2_x, int32_t *idx_y, float *d2_y, char *ws, const ChamferLayout &l,
+                             hipStream_t st) {
+  if (brute) {
+    hipLaunchKernelGGL(chamfer_brute_kernel, dim3((unsigned)((Nx + 63) / 64)), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, idx_x, d2_x);
+    if (both)
+      hipLaunchKernelGGL(chamfer_brute_kernel, dim3((unsigned)((Ny + 63) / 64)), dim3(256), 0, st, y, (int)Ny, x, (int)Nx, idx_y, d2_y);
+    return;
+  }
+  ChamferHead *head = reinterpret_cast<ChamferHead *>(ws + l.head);
+  float *boxp = reinterpret_cast<float *>(ws + l.boxp);
+  ChamferCloud c[2];
+  const float *pts[2] = {x, y};
+  const long N[2] = {Nx, Ny};
+  int *bsum[2];
+  for (int k = 0; k < 2; ++k) {
+    c[k] = ChamferCloud{pts[k], (int)N[k], reinterpret_cast<int *>(ws + l.cellid[k]), reinterpret_cast<int *>(ws + l.counts[k]),
+                        reinterpret_cast<int *>(ws + l.start[k]), reinterpret_cast<float4 *>(ws + l.sorted[k])};
+    bsum[k] = reinterpret_cast<int *>(ws + l.bsum[k]);
+  }
+  const long n = Nx > Ny ? Nx : Ny;
+  const unsigned nbx = (unsigned)((Nx + 255) / 256), nby = (unsigned)((Ny + 255) / 256);
+  hipLaunchKernelGGL(chamfer_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, boxp);
+  hipLaunchKernelGGL(chamfer_grid_kernel, dim3(1), dim3(256), 0, st, boxp, l.nb_box, n, cell_size, head);
+  hipLaunchKernelGGL(chamfer_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, head, c[0].counts, c[1].counts);
+  hipLaunchKernelGGL(chamfer_count_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
+  for (int k = 0; k < 2; ++k) {
+    hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, c[k].counts, 0, &head->G, bsum[k]);
+    hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum[k], l.nb_scan);
+    hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, c[k].counts, 0, &head->G, bsum[k],
+                       c[k].N, c[k].start);
+  }
+  hipLaunchKernelGGL(chamfer_fill_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
+  const ChamferDir d0{c[0].sorted, (int)Nx, c[1].sorted, c[1].start, (int)Ny, idx_x, d2_x};
+  const ChamferDir d1{c[1].sorted, (int)Ny, c[0].sorted, c[0].start, (int)Nx, idx_y, d2_y};
+  const unsigned sb0 = (unsigned)((Nx + kChSearchBlock - 1) / kChSearchBlock);
+  const unsigned sb1 = both ? (unsigned)((Ny + kChSearchBlock - 1) / kChSearchBlock) : 0u;
+  hipLaunchKernelGGL(chamfer_search_kernel, dim3(sb0 + sb1), dim3(kChSearchBlock), 0, st, d0, d1, sb0, head);
+}
+
+static bool chamfer_ws_bad(const void *ws) { return !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0; }
+
+}  // namespace voge
+
+using namespace voge;
+
+extern "C" size_t voge_chamfer_workspace_bytes(long Nx, long Ny) {
+  if (!chamfer_sizes_ok(Nx, Ny)) return 0;
+  return chamfer_layout(Nx, Ny).total;
+}
+
+extern "C" int voge_nearest_points(const float *queries, long Nq, const float *points, long Np, int route, float cell_size,
+                                   int32_t *idx, float *d2, void *workspace, size_t workspace_bytes, voge_stream_t stream) {
+  if (Nq < 0 || Nq > kChamferMaxN || Np < 1 || Np > kChamferMaxN || route < kRouteAuto || route > kRouteGrid) return VOGE_ERR_BAD_ARG;
+  if (!(cell_size >= 0.0f) || !(cell_size < INFINITY)) return VOGE_ERR_BAD_ARG;      // (0: the default cell)
+  if (Nq == 0) return 0;
+  if (!queries || !points || !idx || !d2 || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  const ChamferLayout l = chamfer_layout(Nq, Np);
+  if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
+  chamfer_searches(queries, Nq, points, Np, chamfer_brute(route, Nq, Np), cell_size, false, idx, d2, nullptr, nullptr,
+                   static_cast<char *>(workspace), l, (hipStream_t)stream);
+  return launch_status();
+}
+
+extern "C" int voge_chamfer_fwd(const float *x, long Nx, const float *y, long Ny, int route, int flags, float *loss, int32_t *nn_x,
+                                int32_t *nn_y, int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream) {
+  if (!chamfer_sizes_ok(Nx, Ny) || route < kRouteAuto || route > kRouteGrid || (flags & ~3)) return VOGE_ERR_BAD_ARG;
+  const bool both = !(flags & kChamferSingle);
+  if (!x || !y || !loss || !nn_x || (both && !nn_y) || !meta || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  const ChamferLayout l = chamfer_layout(Nx, Ny);
+  if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
+  char *ws = static_cast<char *>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  float *d2x = reinterpret_cast<float *>(ws + l.d2[0]), *d2y = reinterpret_cast<float *>(ws + l.d2[1]);
+  chamfer_searches(x, Nx, y, Ny, chamfer_brute(route, Nx, Ny), 0.0f, both, nn_x, d2x, nn_y, d2y, ws, l, st);
+  double *psum = reinterpret_cast<double *>(ws + l.psum);
+  float *pmax = reinterpret_cast<float *>(ws + l.pmax);
+  const unsigned nba = l.nb_loss[0], nbb = both ? l.nb_loss[1] : 0u;
+  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2x, (int)Nx, d2y, (int)Ny, nba, psum, pmax);
+  const long n = Nx > Ny ? Nx : Ny;
+  int bits = 0;
+  while ((1l << bits) < n) ++bits;      // n <= 2^bits: every scatter list of the backward
+  const bool sum = flags & kChamferSum;
+  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)Nx,
+                     sum ? 1.0 : (double)Ny, bits, loss, meta);
+  return launch_status();
+}
+
+extern "C" int voge_chamfer_bwd(const float *x, long Nx, const float *y, long Ny, const int32_t *nn_x, const int32_t *nn_y,
+                                const int32_t *meta, const float *g_loss, int flags, float *g_x, float *g_y, void *workspace,
+                                size_t workspace_bytes, voge_stream_t stream) {
+  if (!chamfer_sizes_ok(Nx, Ny) || (flags & ~3)) return VOGE_ERR_BAD_ARG;
+  const bool both = !(flags & kChamferSingle);
+  if (!x || !y || !nn_x || (both && !nn_y) || !meta || !g_loss || !g_x || !g_y || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  const size_t acc_bytes = (size_t)(Nx + Ny) * 3 * sizeof(long long);
+  if (workspace_bytes < acc_bytes) return VOGE_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  long long *acc_x = static_cast<long long *>(workspace), *acc_y = acc_x + 3 * (size_t)Nx;
+  const hipError_t fe = voge_fill_async(workspace, 0, acc_bytes, st);
+  if (fe != hipSuccess) return (int)fe;
+  const unsigned nbx = (unsigned)((Nx + 255) / 256), nby = both ? (unsigned)((Ny + 255) / 256) : 0u;
+  hipLaunchKernelGGL(chamfer_scatter_kernel, dim3(nbx + nby), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, nn_x, both ? nn_y : nullptr, meta,
+                     acc_x, acc_y, nbx);
+  const bool sum = flags & kChamferSum;
+  const double w_x = sum ? 2.0 : 2.0 / (double)Nx, w_y = both ? (sum ? 2.0 : 2.0 / (double)Ny) : 0.0;
+  hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)((Nx + Ny + 255) / 256)), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, nn_x,
+                     both ? nn_y : nullptr, meta, acc_x, acc_y, g_loss, w_x, w_y, g_x, g_y);
+  return launch_status();
+}

@@ -29,27 +29,12 @@
 // the largest, R = [t1, n x t1, n] as a quaternion (w, x, y, z) with w >= 0.  Entries of idx outside [0, N) are skipped.
 #include <math.h>
 
-#include "voge_common.h"
+#include "knn_grid.h"      // the grid, knn_axis_cell and the scan, shared with chamfer.hip
 
 namespace voge {
 
 constexpr int kKnnMaxK = 32;
-constexpr int kKnnMaxAxis = 1024;
 constexpr int kKnnSearchBlock = 128;      // lanes (queries) a workgroup: k * 128 * 8 bytes of LDS, 32 KB at k = 32
-constexpr int kKnnScanBlock = 256;
-constexpr int kKnnScanItems = 8;          // cells a thread of the scan: 2048 a workgroup
-
-struct KnnGrid {
-  float lox, loy, loz, cell, inv;
-  int gx, gy, gz;
-};
-
-// (the clamp happens in float: the same value as clamping the converted integer for every in-range input, and a NaN or an
-// infinity lands on a valid cell instead of an undefined conversion)
-__device__ __forceinline__ int knn_axis_cell(const float x, const float lo, const float inv, const int g) {
-  const float u = floorf((x - lo) * inv);
-  return (int)fminf(fmaxf(u, 0.0f), (float)(g - 1));
-}
 
 __global__ void __launch_bounds__(256)
 knn_count_kernel(const float *__restrict__ pts, const int N, const KnnGrid g, int *__restrict__ cellid, int *__restrict__ counts) {
@@ -61,70 +46,6 @@ knn_count_kernel(const float *__restrict__ pts, const int N, const KnnGrid g, in
   const int c = (cz * g.gy + cy) * g.gx + cx;
   cellid[i] = c;
   atomicAdd(counts + c, 1);
-}
-
-// exclusive scan of one int per thread over a workgroup of full waves; total: the workgroup's sum.  red: one int per wave.
-__device__ __forceinline__ int knn_block_excl_scan(const int v, int *red, int &total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int incl = wave_incl_scan_i32(v);
-  if (lane == 63) red[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) {
-    const int s = red[w];
-    off += w < wave ? s : 0;
-    tot += s;
-  }
-  __syncthreads();
-  total = tot;
-  return off + incl - v;
-}
-
-__global__ void __launch_bounds__(kKnnScanBlock)
-knn_scan_partial_kernel(const int *__restrict__ counts, const int G, int *__restrict__ bsum) {
-  __shared__ int red[kKnnScanBlock / 64];
-  const size_t base = ((size_t)blockIdx.x * kKnnScanBlock + threadIdx.x) * kKnnScanItems;
-  int s = 0;
-#pragma unroll
-  for (int j = 0; j < kKnnScanItems; ++j) s += base + j < (size_t)G ? counts[base + j] : 0;
-  int total;
-  knn_block_excl_scan(s, red, total);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup of 1024: bsum [nb] -> its exclusive scan, in place, 1024 entries a step with the carry in a register
-__global__ void __launch_bounds__(1024)
-knn_scan_sums_kernel(int *__restrict__ bsum, const int nb) {
-  __shared__ int red[16];
-  int carry = 0;
-  for (int s0 = 0; s0 < nb; s0 += 1024) {
-    const int i = s0 + (int)threadIdx.x;
-    const int v = i < nb ? bsum[i] : 0;
-    int total;
-    const int ex = knn_block_excl_scan(v, red, total);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += total;
-  }
-}
-
-__global__ void __launch_bounds__(kKnnScanBlock)
-knn_scan_final_kernel(const int *__restrict__ counts, const int G, const int *__restrict__ bsum, const int N, int *__restrict__ start) {
-  __shared__ int red[kKnnScanBlock / 64];
-  const size_t base = ((size_t)blockIdx.x * kKnnScanBlock + threadIdx.x) * kKnnScanItems;
-  int c[kKnnScanItems], s = 0;
-#pragma unroll
-  for (int j = 0; j < kKnnScanItems; ++j) {
-    c[j] = base + j < (size_t)G ? counts[base + j] : 0;
-    s += c[j];
-  }
-  int total;
-  int run = knn_block_excl_scan(s, red, total) + bsum[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < kKnnScanItems; ++j) {
-    if (base + j < (size_t)G) start[base + j] = run;
-    run += c[j];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) start[G] = N;
 }
 
 // counts[c] falls back to zero, one slot a point: slot = the value after the decrement, in [0, count)
@@ -390,9 +311,9 @@ extern "C" int voge_knn_points(const float *points, long N, int k, int include_s
   const hipError_t fe = voge_fill_async(counts, 0, (size_t)G * 4, st);
   if (fe != hipSuccess) return (int)fe;
   hipLaunchKernelGGL(knn_count_kernel, dim3(nblk), dim3(256), 0, st, points, (int)N, g, cellid, counts);
-  hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, bsum);
+  hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, nullptr, bsum);
   hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, l.nb);
-  hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, bsum, (int)N, start);
+  hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, nullptr, bsum, (int)N, start);
   hipLaunchKernelGGL(knn_fill_kernel, dim3(nblk), dim3(256), 0, st, points, (int)N, cellid, counts, start, sorted);
   const unsigned sblk = (unsigned)((N + kKnnSearchBlock - 1) / kKnnSearchBlock);
   const size_t lds = (size_t)k * kKnnSearchBlock * sizeof(uint64_t);

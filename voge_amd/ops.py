@@ -2021,6 +2021,110 @@ def knn_frames(points, idx, toward=None):
     return quats, eig
 
 
+CHAMFER_ROUTES = {None: 0, "brute": 1, "grid": 2}
+
+
+def _chamfer_route(route):
+    if route not in CHAMFER_ROUTES:
+        raise ValueError(f"route must be None, 'brute' or 'grid', got {route!r}")
+    return CHAMFER_ROUTES[route]
+
+
+def _cloud(t, name):
+    t = _dev(t, torch.float32, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} [N,3] expected, got {tuple(t.shape)}")
+    return t
+
+
+def nearest_points(queries, points, cell_size=None, route=None, return_grid=False):
+    """The nearest point of `points` [Np,3] for every row of `queries` [Nq,3] (extension; voge_nearest_points) on a HIP device ->
+    (idx [Nq] int32, d2 [Nq] fp32), the values of Converters.nearest_points bit for bit on either route.  route None chooses by
+    Nq Np; "brute": one launch, "grid": a grid over both clouds chosen on the device -- nothing is read back on the host, so the
+    call may be captured into a graph.  cell_size asks the grid for a cell of that edge.  return_grid=True appends a [8] int32
+    device tensor, the first 32 bytes of the workspace: after a grid-route call the bits of (lo[3], cell, 1 / cell) and gx, gy, gz
+    -- what the tests read to see which grid ran."""
+    q, p = _cloud(queries, "queries"), _cloud(points, "points")
+    r = _chamfer_route(route)
+    cell = 0.0 if cell_size is None else float(cell_size)
+    if cell_size is not None and not (cell > 0.0 and cell < 3.0e38):
+        raise ValueError(f"nearest_points: cell_size must be a positive finite fp32 number, got {cell_size}")
+    Nq, Np = q.shape[0], p.shape[0]
+    if Np == 0:
+        raise ValueError("nearest_points: points is empty")
+    lib = _lib.load()
+    idx = torch.empty((Nq,), dtype=torch.int32, device=q.device)
+    d2 = torch.empty((Nq,), dtype=torch.float32, device=q.device)
+    grid = None
+    if Nq > 0:
+        with _on(q.device):
+            nbytes = lib.voge_chamfer_workspace_bytes(Nq, Np)
+            ws = _workspace(q.device, nbytes)
+            rc = lib.voge_nearest_points(_p(q), Nq, _p(p), Np, r, cell, _p(idx), _p(d2), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_nearest_points")
+        if return_grid:
+            grid = ws[:32].clone().view(torch.int32)
+    return (idx, d2, grid) if return_grid else (idx, d2)
+
+
+class _Chamfer(torch.autograd.Function):
+    """Chamfer distance (extension; voge_chamfer_fwd / _bwd): forward(x [Nx,3], y [Ny,3], flags, route) -> (loss 0-dim, nn_x [Nx],
+    nn_y [Ny] | None), the value of Aggregation.chamfer_term and the indices of Converters.nearest_points in both directions
+    (int32, not differentiable).  flags: bit 0 "sum", bit 1 single_directional (nn_y is None).  The searches, the fp64 partial sums
+    and the one workgroup that adds them run on the current stream from the stream's cached workspace with nothing read back on
+    the host; the node saves the clouds, the indices and meta [4] int32 (the backward's scale exponent, chosen on the device).
+    Backward: three launches (zero fill, integer-atomic scatter, finish), every element of g_x and g_y written: the same bits on
+    every run.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, y, flags, route):
+        x, y = _cloud(x, "x"), _cloud(y, "y")
+        if y.device != x.device:
+            raise _lib.VogeHipError(f"chamfer_distance: x on {x.device}, y on {y.device}")
+        Nx, Ny = x.shape[0], y.shape[0]
+        if Nx == 0 or Ny == 0:
+            raise ValueError("chamfer_distance: an empty cloud")
+        lib = _lib.load()
+        dev = x.device
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        nn_x = torch.empty((Nx,), dtype=torch.int32, device=dev)
+        nn_y = None if flags & 2 else torch.empty((Ny,), dtype=torch.int32, device=dev)
+        meta = torch.empty((4,), dtype=torch.int32, device=dev)
+        with _on(dev):
+            nbytes = lib.voge_chamfer_workspace_bytes(Nx, Ny)
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_chamfer_fwd(_p(x), Nx, _p(y), Ny, route, flags, _p(loss), _p(nn_x), _p(nn_y), _p(meta), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_chamfer_fwd")
+        ctx.save_for_backward(x, y, nn_x, nn_y, meta)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*([nn_x] if nn_y is None else [nn_x, nn_y]))
+        return loss[0], nn_x, nn_y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _gx, _gy):
+        if g_loss is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        lib = _lib.load()
+        x, y, nn_x, nn_y, meta = ctx.saved_tensors
+        Nx, Ny = x.shape[0], y.shape[0]
+        g = _dev(g_loss, torch.float32, "grad_loss")
+        g_x, g_y = torch.empty_like(x), torch.empty_like(y)
+        with _on(x.device):
+            nbytes = lib.voge_chamfer_workspace_bytes(Nx, Ny)
+            ws = _workspace(x.device, nbytes)
+            rc = lib.voge_chamfer_bwd(_p(x), Nx, _p(y), Ny, _p(nn_x), _p(nn_y), _p(meta), _p(g), ctx.flags, _p(g_x), _p(g_y), _p(ws),
+                                      nbytes, _stream())
+        _lib.check(rc, "voge_chamfer_bwd")
+        return (g_x if ctx.needs_input_grad[0] else None), (g_y if ctx.needs_input_grad[1] else None), None, None
+
+
+def chamfer(x, y, sum_reduction=False, single_directional=False, route=None):
+    """(loss, nn_x, nn_y) of ONE pair of clouds on a HIP device: _Chamfer.apply."""
+    return _Chamfer.apply(x, y, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1), _chamfer_route(route))
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
