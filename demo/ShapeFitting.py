@@ -10,7 +10,10 @@ from iteration 400 on (:247,:276-277).  The edge / normal / laplacian entries of
 (weights 1.0 / 0 / 0.1) are never filled in its loop (:255-280); here they are off by default and --regularise adds them
 (VoGE.Losses.mesh_regularisers over the sphere's faces: one autograd node, HIP kernels) with the table's weights.
 --w-chamfer W (default 0: nothing is computed) adds W * chamfer_distance(vertices, ground-truth vertices), the 3-D supervision a
-fit has when target points exist; it runs inside the captured iteration.
+fit has when target points exist; it runs inside the captured iteration.  --chamfer-samples S (default 0: the vertices, as above)
+puts that term on S points drawn afresh every iteration from the SURFACE of the fitted mesh and S from the ground-truth surface
+(VoGE.Losses.sample_points_from_meshes, area-weighted, gradients to the three vertices of every sampled face) -- what PyTorch3D's
+tutorial does: a coarse region is pulled too, and faces that cut through the target no longer score zero.
 
 What differs, and why: the reference renders its TARGET images with PyTorch3D's mesh rasteriser from
 data/cow.obj (:110-182); neither is available here, so the targets are rendered by this renderer from a
@@ -19,7 +22,7 @@ match; the run is pinned by the loss going down (tests/test_gpu_parity.py::test_
 and by the gradient checks of the kernels it uses.
 
 usage: python demo/ShapeFitting.py [--iters 2000] [--level 4] [--size 128] [--save DIR]
-                                   [--regularise [--w-edge 1.0] [--w-laplacian 0.1] [--w-normal 0.0]] [--w-chamfer 0.0]"""
+                                   [--regularise [--w-edge 1.0] [--w-laplacian 0.1] [--w-normal 0.0]] [--w-chamfer 0.0 [--chamfer-samples 0]]"""
 import argparse
 import os
 import sys
@@ -30,7 +33,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from VoGE.Converter import Converters                                                  # noqa: E402
-from VoGE.Losses import MeshTopology, chamfer_distance, mesh_regularisers              # noqa: E402
+from VoGE.Losses import MeshTopology, SurfaceSampler, chamfer_distance, mesh_regularisers, sample_points_from_meshes  # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_silhouette, interpolate_attr  # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
 
@@ -92,6 +95,19 @@ def regulariser_loss(verts, regularisers):
     return sum(w[k] * terms[k] for k in on)
 
 
+def chamfer_loss(verts, chamfer):
+    """weight * chamfer_distance of the fit against its target.  chamfer = (weight, target points [M,3]): between the vertices
+    and the points; chamfer = (weight, target vertices, S, SurfaceSampler of the fit, SurfaceSampler of the target): between S
+    fresh surface samples of each mesh (the target's carry no gradient)."""
+    if len(chamfer) == 2:
+        return chamfer[0] * chamfer_distance(verts, chamfer[1])[0]
+    weight, target, S, src_sampler, tgt_sampler = chamfer
+    x = sample_points_from_meshes(verts, src_sampler, S)
+    with torch.no_grad():
+        y = sample_points_from_meshes(target, tgt_sampler, S)
+    return weight * chamfer_distance(x, y)[0]
+
+
 def gauss_renderer(render, gmesh, R, T, color):
     """[H, W, 4] = interpolated colour + silhouette (ShapeFitting.py:219-222)."""
     frag = render(gmesh, R=R, T=T)
@@ -107,7 +123,8 @@ class BatchedIteration:
     The mean over a [B,H,W(,3)] batch equals the reference's sum over views of per-view means / B.
     regularisers (see regulariser_loss; default None: nothing is added) puts the weighted mesh regularisers of gsrc.verts
     into the loss, inside the same graph; chamfer = (weight, target points [M,3]) (default None) adds
-    weight * chamfer_distance(gsrc.verts, target points) the same way."""
+    weight * chamfer_distance(gsrc.verts, target points) the same way, and the five-entry form of chamfer_loss the chamfer
+    distance between fresh surface samples of both meshes (torch.rand under capture: every replay draws new samples)."""
 
     def __init__(self, render, gsrc, vert_color, optimizer, R_all, T_all, target_rgb, target_silhouette, views_per_iter,
                  graph=False, regularisers=None, chamfer=None):
@@ -156,7 +173,7 @@ class BatchedIteration:
         if self.regularisers is not None:
             loss = loss + regulariser_loss(self.gsrc.verts, self.regularisers)
         if self.chamfer is not None:
-            loss = loss + self.chamfer[0] * chamfer_distance(self.gsrc.verts, self.chamfer[1])[0]
+            loss = loss + chamfer_loss(self.gsrc.verts, self.chamfer)
         loss.backward()
         self.optimizer.step()
         self.losses.copy_(torch.stack((l_sil.detach(), l_rgb.detach())))
@@ -176,13 +193,14 @@ class BatchedIteration:
 
 def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assign=25, rgb_on=400, seed=0,
         device="cuda:0", log_every=100, save=None, quiet=False, per_view=False, graph=False, timed_from=0, regularise=None,
-        w_chamfer=0.0):
+        w_chamfer=0.0, chamfer_samples=0):
     """Runs the optimisation; returns {"silhouette": [...], "rgb": [...], "sec_per_iter": s}.
     per_view=True renders the views of an iteration one at a time, as the reference's loop is written (:258-259);
     the default renders them as one batch (BatchedIteration; graph=True replays the iteration as a HIP graph).
     regularise: None, or the weights {"edge": w, "laplacian": w, "normal": w} of the mesh regularisers over the sphere's faces
     (a missing one is REGULARISER_WEIGHTS').  w_chamfer: the weight of chamfer_distance(vertices, ground-truth vertices); 0 (the
-    default) computes nothing."""
+    default) computes nothing.  chamfer_samples S > 0 puts that term on S fresh surface samples of both meshes instead (two
+    SurfaceSamplers built once, here); 0 (the default) is the vertex form."""
     device = torch.device(device)
     rng = np.random.RandomState(seed)
     focal, pp = 126.0 * size / 128.0, (size / 2.0, size / 2.0)
@@ -211,6 +229,9 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
     optimizer = torch.optim.SGD(list(gsrc.grad_parameters()) + [vert_color], lr=0.8, momentum=0.9)
     regularisers = None if regularise is None else dict(regularise, topo=MeshTopology(faces=sf, num_verts=sv.shape[0], device=device))
     chamfer = None if not w_chamfer else (float(w_chamfer), torch.from_numpy(gv).to(device))
+    if chamfer is not None and chamfer_samples:
+        chamfer = chamfer + (int(chamfer_samples), SurfaceSampler(sf, num_verts=sv.shape[0], device=device),
+                             SurfaceSampler(gf, num_verts=gv.shape[0], device=device))
     weights = {"rgb": 0.0, "silhouette": 1.0}
     history = {"rgb": [], "silhouette": []}
     step = None if per_view else BatchedIteration(render, gsrc, vert_color, optimizer, R, T, target_rgb, target_silhouette,
@@ -243,7 +264,7 @@ def fit(iters=2000, level=4, size=128, num_views=20, views_per_iter=5, max_assig
             if regularisers is not None:
                 total = total + regulariser_loss(gsrc.verts, regularisers)
             if chamfer is not None:
-                total = total + chamfer[0] * chamfer_distance(gsrc.verts, chamfer[1])[0]
+                total = total + chamfer_loss(gsrc.verts, chamfer)
             total.backward()
             optimizer.step()
             trace[i].copy_(torch.stack((loss["silhouette"].detach(), loss["rgb"].detach())))
@@ -281,10 +302,12 @@ if __name__ == "__main__":
     ap.add_argument("--w-laplacian", type=float, default=REGULARISER_WEIGHTS["laplacian"])
     ap.add_argument("--w-normal", type=float, default=REGULARISER_WEIGHTS["normal"])
     ap.add_argument("--w-chamfer", type=float, default=0.0, help="weight of the chamfer distance to the ground-truth vertices (0: off)")
+    ap.add_argument("--chamfer-samples", type=int, default=0,
+                    help="with --w-chamfer: compare this many fresh surface samples of both meshes instead of the vertices (0: vertices)")
     a = ap.parse_args()
     reg = {"edge": a.w_edge, "laplacian": a.w_laplacian, "normal": a.w_normal} if a.regularise else None
     h = fit(iters=a.iters, level=a.level, size=a.size, rgb_on=a.rgb_on, save=a.save, per_view=a.per_view, graph=a.graph,
-            regularise=reg, w_chamfer=a.w_chamfer)
+            regularise=reg, w_chamfer=a.w_chamfer, chamfer_samples=a.chamfer_samples)
     n = max(1, len(h["silhouette"]) // 20)
     print(f"silhouette loss {np.mean(h['silhouette'][:n]):.5f} -> {np.mean(h['silhouette'][-n:]):.5f}; "
           f"rgb loss {np.mean(h['rgb'][:n]):.5f} -> {np.mean(h['rgb'][-n:]):.5f}; "

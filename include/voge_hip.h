@@ -981,6 +981,39 @@ int voge_chamfer_bwd(const float *x, long Nx, const float *y, long Ny, const int
                      const int32_t *meta, const float *g_loss, int flags, float *g_x, float *g_y, void *workspace,
                      size_t workspace_bytes, voge_stream_t stream);
 
+/*
+ * Points on the surface of a triangle mesh, chosen by area (EXTENSION: PyTorch3D's sample_points_from_meshes, what its shape
+ * fitting tutorial -- the one the reference's demo/ShapeFitting.py was written from -- puts the chamfer term on).  Replaces
+ * voge_amd/Aggregation.py mesh_surface_points (cross, norm, cumsum, searchsorted, gathers, lerps; a backward of three index_adds
+ * with float atomics).  verts [V,3] fp32, faces [F,3] int32, u [S,3] fp32 (clamped to [0, 1 - 2^-24], a NaN taken as 0), one mesh:
+ *   A2_f = |(b - a) x (c - a)| in fp32, operation by operation the definition's; cdf = the inclusive sum of A2 in fp64;
+ *   face_idx[s] = the smallest f with cdf[f] > double(u_s0) cdf[F-1], strictly: a face of area 0 is never chosen;
+ *   r = sqrt(u_s1), bary[s] = (1 - r, r (1 - u_s2), r u_s2), points[s] = a + (w1 (b - a) + w2 (c - a)), normals[s] = cr / A2.
+ * Three launches: areas with a scan per 256 faces, one workgroup that scans the block totals, one sample per lane with a
+ * two-level binary search whose trip counts are bounded by the table sizes.  The sums are made in an order fixed by the shapes
+ * (the same bits on every run) and differ from the definition's by at most F 2^-52 of the total.  A total that is 0 or not finite
+ * (a NaN vertex): every face_idx is -1 and points, normals, bary are 0; so is a sample whose face names a vertex outside [0, V).
+ * normals may be null (not written); a2_out [F] (may be null) receives A2, for the tests.  Nothing is read back on the host.
+ * Backward: g_verts [V,3], EVERY element written, from g_points [S,3] and g_normals [S,3] (either may be null: 0).  Four
+ * launches: a zero fill of the int64 accumulators in the workspace, the largest |g| by an integer atomic max, a scatter that
+ * adds round(w_r g 2^s) to the face's three vertices (w = (1 - w1 - w2, w1, w2) from bary) and round(g_n 2^s) to the face with
+ * 64-bit INTEGER atomics -- s = 62 - ceil(log2 S) - e with 2^e > max |g|, chosen on the device; exact, so the order does not
+ * matter and a list of m samples is off by at most m 2^-s / 2 per component --, and a finish, one thread a vertex, that adds in
+ * fp64 the face-normal Jacobian of every corner of the vertex (corner_off [V+1] / corner [3F]: entries face * 3 + role, ascending;
+ * needed with g_normals only) and rounds once.  A sample with face_idx outside [0, F) is skipped.  No float atomics.
+ * workspace: voge_mesh_sample_workspace_bytes(V, F, S) bytes on a 16-byte boundary serves both calls (0: V or F below 1, S below
+ * 0, a size above 2^28 - 1).  Such sizes, a null pointer with work to do, a workspace that is null or off the 16-byte boundary:
+ * VOGE_ERR_BAD_ARG; a workspace too small: VOGE_ERR_WORKSPACE -- all before any HIP call.  S == 0: the forward launches nothing
+ * (unless a2_out is given), the backward writes zeros.
+ */
+size_t voge_mesh_sample_workspace_bytes(long V, long F, long S);
+int voge_mesh_sample_fwd(const float *verts, long V, const int32_t *faces, long F, const float *u, long S, float *points,
+                         float *normals, int32_t *face_idx, float *bary, float *a2_out, void *workspace, size_t workspace_bytes,
+                         voge_stream_t stream);
+int voge_mesh_sample_bwd(const float *verts, long V, const int32_t *faces, long F, const int32_t *corner_off, const int32_t *corner,
+                         const int32_t *face_idx, const float *bary, long S, const float *g_points, const float *g_normals,
+                         float *g_verts, void *workspace, size_t workspace_bytes, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -430,3 +430,84 @@ def chamfer_term(x, y, single_directional=False, point_reduction="mean", return_
         nn_y = nearest_rows(y, x)[0]
         loss = loss + reduce(((y - x[nn_y]) ** 2).sum(-1))
     return (loss, nn_x, nn_y) if return_indices else loss
+
+
+def _face_cross(e1, e2):
+    """e1 x e2 over the last axis, each component (p * q) - (r * s) as separate operations"""
+    return torch.stack(((e1[..., 1] * e2[..., 2]) - (e1[..., 2] * e2[..., 1]),
+                        (e1[..., 2] * e2[..., 0]) - (e1[..., 0] * e2[..., 2]),
+                        (e1[..., 0] * e2[..., 1]) - (e1[..., 1] * e2[..., 0])), -1)
+
+
+def _ieee_sqrt(x):
+    """sqrt(x), correctly rounded for fp32: torch's vectorised fp32 sqrt on the host is not always (a last-bit difference in
+    about 0.6 % of random arguments on an AVX-512 build), its fp64 one rounded to fp32 is -- the square root of a 24-bit number
+    never lies within 2^-53 of the midpoint of two fp32 numbers, so the second rounding changes nothing.  Other dtypes: torch.sqrt."""
+    return torch.sqrt(x.double()).to(x.dtype) if x.dtype == torch.float32 else torch.sqrt(x)
+
+
+def mesh_face_areas2(verts, faces):
+    """A2 [F]: the doubled area of every face of verts [V,3], faces [F,3] integer, in the vertices' dtype and not differentiable:
+    e1 = b - a, e2 = c - a (positions are differenced first), cr = e1 x e2, A2 = sqrt((crx^2 + cry^2) + crz^2), every operation a
+    separate torch op (the square root through _ieee_sqrt) -- what mesh_surface_points chooses faces by, and bit for bit what voge_mesh_sample_fwd computes."""
+    v, f = verts.detach(), faces.long()
+    a = v[f[:, 0]]
+    cr = _face_cross(v[f[:, 1]] - a, v[f[:, 2]] - a)
+    return _ieee_sqrt((cr[:, 0] * cr[:, 0] + cr[:, 1] * cr[:, 1]) + cr[:, 2] * cr[:, 2])
+
+
+def mesh_surface_points(verts, faces, u, return_normals=False, face_idx=None):
+    """Points on the surface of a triangle mesh, faces chosen by area (PyTorch3D's sample_points_from_meshes for one mesh and a
+    GIVEN random table; an extension here): verts [V,3], faces [F,3] integer (F >= 1), u [S,3] in [0,1) ->
+    (points [S,3], normals [S,3] | None, face_idx [S] int64, bary [S,3]).
+
+      faces   A2 = mesh_face_areas2 in the vertices' dtype; cdf = its inclusive cumulative sum in fp64, total = cdf[F-1];
+              t_s = float64(u_s0) * total; face_idx_s = the smallest f with cdf[f] > t_s, strictly -- a face of area 0 is never
+              chosen, wherever it sits.  u is clamped to [0, 1 - 2^-24] first and a NaN becomes 0;
+      points  PyTorch3D's _rand_barycentric_coords: r = sqrt(u_s1), w0 = 1 - r, w1 = r (1 - u_s2), w2 = r u_s2,
+              p = a + (w1 e1 + w2 e2), bary = (w0, w1, w2);
+      normals cr / A2 of the chosen face.
+
+    total == 0 or not finite (every face degenerate, a NaN vertex): every face_idx is -1, points, normals and bary are 0 and
+    verts get a zero gradient; nothing raises and nothing is read back on the host.  The face choice and u are constants of the
+    graph; verts get gradients through a, e1, e2 and through the normals.  face_idx (integer [S]) overrides the choice -- the
+    expression evaluated at given faces, what the tests compare a kernel's output with; an entry below 0 gives a zero sample.
+    Every operation is a separate torch op, so the host result is plain IEEE arithmetic of the vertices' dtype.  Differentiable
+    torch on any device / dtype: the definition ops._MeshSample is tested against and the route for everything it does not take."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or u.dim() != 2 or u.shape[1] != 3:
+        raise ValueError(f"mesh_surface_points: verts [V,3], faces [F,3], u [S,3] expected, got {tuple(verts.shape)} / "
+                         f"{tuple(faces.shape)} / {tuple(u.shape)}")
+    F = faces.shape[0]
+    if F == 0:
+        raise ValueError("mesh_surface_points: a mesh without faces")
+    f = faces.long()
+    u = u.detach().to(verts.dtype)
+    u = torch.where(torch.isnan(u), torch.zeros_like(u), u).clamp(0.0, 1.0 - 2.0 ** -24)
+    cdf = torch.cumsum(mesh_face_areas2(verts, f).double(), 0)
+    total = cdf[-1]
+    ok = (total > 0) & torch.isfinite(total)
+    if face_idx is None:
+        idx = torch.searchsorted(cdf, u[:, 0].double() * total, right=True).clamp(max=F - 1)
+        valid = ok.expand(idx.shape)
+    else:
+        valid = ok & (face_idx >= 0)
+        idx = face_idx.long().clamp(0, F - 1)
+    # a degenerate mesh is evaluated on zeros: finite values everywhere, and `where` passes the vertices a zero gradient
+    v = torch.where(ok, verts, torch.zeros_like(verts))
+    tri = f[idx]
+    a = v[tri[:, 0]]
+    e1, e2 = v[tri[:, 1]] - a, v[tri[:, 2]] - a
+    r = _ieee_sqrt(u[:, 1])
+    w0, w1, w2 = 1 - r, r * (1 - u[:, 2]), r * u[:, 2]
+    p = a + (w1[:, None] * e1 + w2[:, None] * e2)
+    zero = torch.zeros_like(p)
+    points = torch.where(valid[:, None], p, zero)
+    bary = torch.where(valid[:, None], torch.stack((w0, w1, w2), -1), zero)
+    normals = None
+    if return_normals:
+        cr = _face_cross(e1, e2)
+        s = (cr[:, 0] * cr[:, 0] + cr[:, 1] * cr[:, 1]) + cr[:, 2] * cr[:, 2]
+        pos = s.detach() > 0
+        A2 = _ieee_sqrt(torch.where(pos, s, torch.ones_like(s)))
+        normals = torch.where((valid & pos)[:, None], cr / A2[:, None], zero)
+    return points, normals, torch.where(valid, idx, torch.full_like(idx, -1)), bary

@@ -11,7 +11,13 @@ The cotangent ("cot", "cotcurv") Laplacians of PyTorch3D and a normal term on pe
 chamfer_distance is the fourth loss that demo imports: the score of a fit against the points it should reach.  Its definition is
 Aggregation.chamfer_term; fp32 clouds on a HIP device take the kernels of voge_amd/csrc/chamfer.hip (ops._Chamfer: exact nearest
 points over a grid chosen on the device, fp64 sums in a fixed order, an integer-atomic backward -- the same bits on every run and
-nothing read back on the host, so it runs inside a captured iteration)."""
+nothing read back on the host, so it runs inside a captured iteration).
+
+sample_points_from_meshes is what feeds that loss in practice: area-weighted points (and normals) on a mesh's surface, redrawn
+every iteration, with gradients to the three vertices of each sampled face.  A SurfaceSampler is built ONCE on the host from the
+faces; the definition is Aggregation.mesh_surface_points, and fp32 vertices on the HIP device of the sampler's tables take the
+kernels of voge_amd/csrc/mesh_sample.hip (ops._MeshSample: three launches forward, an integer-atomic backward, the same bits on
+every run, capturable)."""
 import numpy as np
 import torch
 
@@ -235,3 +241,108 @@ def chamfer_distance(x, y, x_normals=None, y_normals=None, single_directional=Fa
                            single_directional, point_reduction) for b in range(x.shape[0])]
     loss = torch.stack([p[0] for p in pairs]).mean()
     return loss, (None if x_normals is None else torch.stack([p[1] for p in pairs]).mean())
+
+
+class SurfaceSampler:
+    """What sample_points_from_meshes needs of a mesh's connectivity, built once on the host with numpy (never per step).
+
+    SurfaceSampler(faces=[F,3]); num_verts defaults to the largest index + 1, and a vertex no face uses is allowed.  ValueError
+    (MeshTopology's): an index out of range, a face that names a vertex twice.  int32 tensors on `device` (default: the host):
+      faces      [F,3]   the faces as given;
+      corner_off [V+1], corner [3F]   per vertex the entries face * 3 + role (role = the column of `faces` that names it),
+                 ascending: corner[corner_off[v] : corner_off[v+1]] are the corners at v -- what the backward of the normals walks.
+    num_verts and num_faces are Python ints; .to(device) gives the same tables on another device."""
+
+    _TABLES = ("faces", "corner_off", "corner")
+
+    def __init__(self, faces, num_verts=None, device=None):
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        given = np.asarray(faces)
+        if given.size == 0:
+            given = np.zeros((0, 3), np.int64)
+        if given.ndim != 2 or given.shape[1] != 3 or not np.issubdtype(given.dtype, np.integer):
+            raise ValueError(f"SurfaceSampler: faces must be an integer array [F,3], got {given.dtype} {tuple(given.shape)}")
+        given = given.astype(np.int64)
+        V = int(given.max()) + 1 if num_verts is None and given.size else int(num_verts or 0)
+        if V < 0 or V > 2 ** 28 - 1 or (given.size and (given.min() < 0 or given.max() >= V)):
+            raise ValueError(f"SurfaceSampler: indices must lie in [0, {V})")
+        s = np.sort(given, axis=1)
+        if (s[:, 1:] == s[:, :-1]).any():
+            raise ValueError("SurfaceSampler: a face names a vertex twice")
+        F = given.shape[0]
+        if F > 2 ** 28 - 1:
+            raise ValueError("SurfaceSampler: too many faces for the int32 tables")
+        vert = given.ravel()
+        self.num_verts, self.num_faces = V, F
+        self._host = {"faces": given, "corner_off": _csr(vert, V), "corner": np.argsort(vert, kind="stable")}
+        self._place(torch.device("cpu" if device is None else device))
+
+    def _place(self, device):
+        for name in self._TABLES:
+            setattr(self, name, torch.from_numpy(np.ascontiguousarray(self._host[name], dtype=np.int32)).to(device))
+        self.device = self.faces.device
+
+    def to(self, device):
+        """The same sampler with its tables on `device` (self when they are there already)."""
+        device = torch.device(device)
+        if device == self.faces.device:
+            return self
+        other = object.__new__(SurfaceSampler)
+        other.num_verts, other.num_faces, other._host = self.num_verts, self.num_faces, self._host
+        other._place(device)
+        return other
+
+
+def _sample_one(verts, sampler, u, return_normals):
+    if verts.is_cuda and verts.dtype == torch.float32 and sampler.faces.device == verts.device:
+        return ops.mesh_sample(verts, sampler, u.to(device=verts.device, dtype=torch.float32), return_normals)
+    return Aggregation.mesh_surface_points(verts, sampler.to(verts.device).faces, u.to(verts.device), return_normals)
+
+
+def sample_points_from_meshes(verts, faces_or_sampler, num_samples=10000, return_normals=False, generator=None, u=None,
+                              return_faces=False):
+    """Points on the surface of the mesh (verts [V,3], faces), each face chosen with probability proportional to its area --
+    PyTorch3D's name and return shape: points [S,3], or (points, normals) with return_normals=True; return_faces=True appends
+    face_idx [S] and bary [S,3], what a caller needs to interpolate anything else at the samples (face_idx is int32 from the
+    kernels, int64 from the definition; -1 everywhere for a mesh without area).  The definition is
+    Aggregation.mesh_surface_points.  verts get gradients through the three vertices of every sampled face (and through the
+    normals); the face choice and the random numbers are constants.
+
+    u [S,3] in [0,1) is the random table (column 0 chooses the face, 1 and 2 the point inside it); u=None draws
+    torch.rand((num_samples, 3)) on the vertices' device with `generator` -- one more launch, and capturable: every replay draws
+    anew (the default generator is known to a captured graph; one of the caller's own has to be registered with the graph first,
+    CUDAGraph.register_generator_state(generator), and then draws in a replay what an eager call draws after the same seed).  A captured step must keep no output of an earlier step alive with its grad_fn.
+    faces_or_sampler: a SurfaceSampler, or a faces tensor / array [F,3], from which a sampler is built ON THE SPOT -- a host round
+    trip (the faces are copied to the host, sorted with numpy and copied back): a loop builds the SurfaceSampler once and passes it.
+    fp32 verts on the HIP device of the sampler's tables are ONE autograd node (ops._MeshSample, no double backward, no host
+    synchronisation); everything else -- host tensors, other dtypes, a sampler on another device -- takes the definition.
+    verts [B,V,3] is a HOST LOOP over the B meshes, which share the faces, with u [B,S,3]: the kernels handle one mesh.
+    S = 0 returns empty tensors; a mesh without faces raises ValueError, and so do wrong shapes."""
+    if not torch.is_tensor(verts) or verts.dim() not in (2, 3) or verts.shape[-1] != 3:
+        raise ValueError("sample_points_from_meshes: verts [V,3] or [B,V,3] expected")
+    sampler = faces_or_sampler
+    if not isinstance(sampler, SurfaceSampler):
+        sampler = SurfaceSampler(faces_or_sampler, num_verts=verts.shape[-2], device=verts.device)
+    if sampler.num_faces == 0:
+        raise ValueError("sample_points_from_meshes: a mesh without faces")
+    if verts.shape[-2] != sampler.num_verts:
+        raise ValueError(f"sample_points_from_meshes: the sampler was built for {sampler.num_verts} vertices, verts has {verts.shape[-2]}")
+    lead = tuple(verts.shape[:-2])
+    if u is None:
+        u = torch.rand(lead + (int(num_samples), 3), generator=generator, device=verts.device,
+                       dtype=verts.dtype if verts.dtype in (torch.float32, torch.float64) else torch.float32)
+    elif not torch.is_tensor(u) or tuple(u.shape[:-2]) != lead or u.dim() != verts.dim() or u.shape[-1] != 3:
+        raise ValueError(f"sample_points_from_meshes: u {list(lead) + ['S', 3]} expected, got {tuple(u.shape) if torch.is_tensor(u) else u}")
+    if verts.dim() == 2:
+        out = _sample_one(verts, sampler, u, return_normals)
+    else:
+        if verts.shape[0] == 0:
+            raise ValueError("sample_points_from_meshes: an empty batch")
+        per = [_sample_one(verts[b], sampler, u[b], return_normals) for b in range(verts.shape[0])]
+        out = tuple(None if per[0][k] is None else torch.stack([p[k] for p in per]) for k in range(4))
+    points, normals, face_idx, bary = out
+    res = (points, normals) if return_normals else (points,)
+    if return_faces:
+        res = res + (face_idx, bary)
+    return res[0] if len(res) == 1 else res

@@ -131,6 +131,11 @@ SIGNATURES = {
     "voge_chamfer_fwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 5 + [_c_size_t, _c_void_p]),
     "voge_chamfer_bwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3
                          + [_c_size_t, _c_void_p]),
+    "voge_mesh_sample_workspace_bytes": (_c_size_t, [_c_long] * 3),
+    "voge_mesh_sample_fwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 6
+                             + [_c_size_t, _c_void_p]),
+    "voge_mesh_sample_bwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 4 + [_c_long] + [_c_void_p] * 4
+                             + [_c_size_t, _c_void_p]),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

@@ -2125,6 +2125,78 @@ def chamfer(x, y, sum_reduction=False, single_directional=False, route=None):
     return _Chamfer.apply(x, y, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1), _chamfer_route(route))
 
 
+MESH_SAMPLE_BLOCK = 256      # kMsBlock of mesh_sample.hip: the faces of one scan block (the tests build meshes around it)
+MESH_SAMPLE_LDS_BLOCKS = 2048      # kMsLdsBlocks: more scan blocks than this and the sampler searches the block table in memory
+
+
+class _MeshSample(torch.autograd.Function):
+    """Mesh surface sampling (extension; voge_mesh_sample_fwd / _bwd): forward(verts [V,3], sampler, u [S,3], return_normals,
+    return_areas) -> (points [S,3], normals [S,3] | None, face_idx [S] int32, bary [S,3], A2 [F] | None), the values of
+    Aggregation.mesh_surface_points over the tables of a Losses.SurfaceSampler on the same device; face_idx, bary and A2 are not
+    differentiable.  Three launches forward and four backward on the current stream from the stream's cached workspace, nothing
+    read back on the host; the node saves verts, u's outputs face_idx and bary.  The backward adds fixed-point terms with integer
+    atomics and writes every element of g_verts: the same bits on every run.  Only verts get a gradient; no double backward."""
+
+    @staticmethod
+    def forward(ctx, verts, sampler, u, return_normals, return_areas):
+        v = _dev(verts, torch.float32, "verts")
+        u = _dev(u, torch.float32, "u")
+        V, F = sampler.num_verts, sampler.num_faces
+        if tuple(v.shape) != (V, 3):
+            raise ValueError(f"mesh_sample: verts [{V},3] expected, got {tuple(v.shape)}")
+        if u.dim() != 2 or u.shape[1] != 3:
+            raise ValueError(f"mesh_sample: u [S,3] expected, got {tuple(u.shape)}")
+        if F == 0:
+            raise ValueError("mesh_sample: a mesh without faces")
+        if sampler.faces.device != v.device or u.device != v.device:
+            raise _lib.VogeHipError(f"mesh_sample: verts on {v.device}, the sampler on {sampler.faces.device}, u on {u.device}")
+        lib = _lib.load()
+        S, dev = u.shape[0], v.device
+        points = torch.empty((S, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((S, 3), dtype=torch.float32, device=dev) if return_normals else None
+        face_idx = torch.empty((S,), dtype=torch.int32, device=dev)
+        bary = torch.empty((S, 3), dtype=torch.float32, device=dev)
+        a2 = torch.empty((F,), dtype=torch.float32, device=dev) if return_areas else None
+        with _on(dev):
+            nbytes = lib.voge_mesh_sample_workspace_bytes(V, F, S)
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_mesh_sample_fwd(_p(v), V, _p(sampler.faces), F, _p(u), S, _p(points), _p(normals), _p(face_idx), _p(bary),
+                                          _p(a2), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_mesh_sample_fwd")
+        ctx.save_for_backward(v, face_idx, bary)
+        ctx.sampler = sampler
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*[t_ for t_ in (face_idx, bary, a2) if t_ is not None])
+        return points, normals, face_idx, bary, a2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_points, g_normals, _gf, _gb, _ga):
+        if not ctx.needs_input_grad[0] or (g_points is None and g_normals is None):
+            return None, None, None, None, None
+        lib = _lib.load()
+        v, face_idx, bary = ctx.saved_tensors
+        sampler = ctx.sampler
+        V, F, S = sampler.num_verts, sampler.num_faces, face_idx.shape[0]
+        gp = None if g_points is None else _dev(g_points, torch.float32, "grad_points")
+        gn = None if g_normals is None else _dev(g_normals, torch.float32, "grad_normals")
+        g_verts = torch.empty_like(v)
+        with _on(v.device):
+            nbytes = lib.voge_mesh_sample_workspace_bytes(V, F, S)
+            ws = _workspace(v.device, nbytes)
+            rc = lib.voge_mesh_sample_bwd(_p(v), V, _p(sampler.faces), F, _p(sampler.corner_off), _p(sampler.corner), _p(face_idx),
+                                          _p(bary), S, _p(gp), _p(gn), _p(g_verts), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_mesh_sample_bwd")
+        return g_verts, None, None, None, None
+
+
+def mesh_sample(verts, sampler, u, return_normals=False, return_areas=False):
+    """(points, normals | None, face_idx int32, bary) of ONE mesh on a HIP device: _MeshSample.apply.  return_areas=True appends
+    A2 [F], the doubled face areas the kernel chose by (a debug output: what the tests compare with the definition's bits)."""
+    out = _MeshSample.apply(verts, sampler, u, bool(return_normals), bool(return_areas))
+    return out if return_areas else out[:4]
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
