@@ -332,13 +332,26 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
   if (any_e && active) {
     float cPhi[NS], cphi[NS], cphil[NS];
     if (sorted) {
-      float rj[NS];
-      v2f aH[NS], aP[NS], aL[NS], bH[NS], bP[NS], bL[NS];   // per own column: rows behind (a*) / in front (b*)
+      // ONE accumulator set per own column for the rows behind and the rows in front: with d = len_row - len_col in both
+      // directions the column's three sums are  cPhi = suf - H,  cphi = P,  cphil = L  with
+      //   H = sum_behind u h - sum_front u h,   P = sum u g,   L = sum u g d   (h, g at x' = |d| s' >= 0).
+      // The front walk keeps |d| = len_col - len_row (what h and g are evaluated at) and accumulates -u h and (-u g) |d|:
+      // a negation is exact, so each term has the bits it would have in a second set subtracted at the end.
+      v2f H[NS], P[NS], L[NS];
+      // One bound per walk, as in compn_fwd_rows: a row pair behind is walked while its first len lies inside the window
+      // kSat / s_j of any LIVE own column, one in front while its second does.  An empty column (len = the empty slot's
+      // sentinel) is not folded in: a lane with no live column keeps -kBig / +kBig and leaves at the first pair.  The
+      // per-column test this replaces, len_row - len_col < r_j in fp32, holds only where len_row < len_col + r_j exactly
+      // (fp32 subtraction is monotone and r_j is a float), and then len_row <= fl(len_col + r_j): with <= the bound never
+      // drops a row that test walked; what it adds sits at the window's edge, where phi <= 4.8e-6.
+      float reachB = -kBig, reachF = kBig;
 #pragma unroll
       for (int b2 = 0; b2 < NS; ++b2) {
-        rj[b2] = (em[b2] != 0.0f) ? kSat * __builtin_amdgcn_rcpf(sm[b2]) : 0.0f;   // an empty column needs no rows
-        aH[b2] = (v2f){um[b2] * h0, 0.0f}; aP[b2] = (v2f){um[b2], 0.0f}; aL[b2] = splat(0.0f);   // self
-        bH[b2] = splat(0.0f); bP[b2] = splat(0.0f); bL[b2] = splat(0.0f);
+        const bool live = em[b2] != 0.0f;
+        const float r = kSat * __builtin_amdgcn_rcpf(sm[b2]);
+        reachB = live ? fmaxf(reachB, lm[b2] + r) : reachB;
+        reachF = live ? fminf(reachF, lm[b2] - r) : reachF;
+        H[b2] = (v2f){um[b2] * h0, 0.0f}; P[b2] = (v2f){um[b2], 0.0f}; L[b2] = splat(0.0f);   // self
       }
       // diagonal block: for own slots a < b, row b is behind column a and row a in front of column b
 #pragma unroll
@@ -348,17 +361,14 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
           const float gap = lm[b2] - lm[a];
           const v2f xp = (v2f){gap * sp[a], gap * sp[b2]};      // (row b, col a), (row a, col b)
           const v2f g = gauss_pair(xp), h = h_pair(xp);
-          aH[a].y = fmaf(um[b2], h.x, aH[a].y); aP[a].y = fmaf(um[b2], g.x, aP[a].y); aL[a].y = fmaf(um[b2] * g.x, gap, aL[a].y);
-          bH[b2].y = fmaf(um[a], h.y, bH[b2].y); bP[b2].y = fmaf(um[a], g.y, bP[b2].y); bL[b2].y = fmaf(um[a] * g.y, gap, bL[b2].y);
+          H[a].y = fmaf(um[b2], h.x, H[a].y); P[a].y = fmaf(um[b2], g.x, P[a].y); L[a].y = fmaf(um[b2] * g.x, gap, L[a].y);
+          H[b2].y = fmaf(-um[a], h.y, H[b2].y); P[b2].y = fmaf(um[a], g.y, P[b2].y); L[b2].y = fmaf(-(um[a] * g.y), gap, L[b2].y);
         }
       }
       for (int e = d0 + NS;; e += 2) {     // row pairs behind every own column
         const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
         v2f racc = ld2(LR, e);
-        bool need = false;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) need = need || (l2.x - lm[b2] < rj[b2]);
-        if (!need) break;
+        if (!(l2.x <= reachB)) break;
         CW_COUNT(2);
 #pragma unroll
         for (int b2 = 0; b2 < NS; ++b2) {
@@ -366,7 +376,7 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
           const v2f xp = d * splat(sp[b2]);
           const v2f g = gauss_pair(xp);
           const v2f y = u2 * g;
-          aH[b2] = pk_fma(u2, h_pair(xp), aH[b2]); aP[b2] = aP[b2] + y; aL[b2] = pk_fma(y, d, aL[b2]);
+          H[b2] = pk_fma(u2, h_pair(xp), H[b2]); P[b2] = P[b2] + y; L[b2] = pk_fma(y, d, L[b2]);
           racc = pk_fma(splat(Es[b2]), g, racc);
         }
         *reinterpret_cast<v2f *>(LR + e) = racc;
@@ -375,10 +385,7 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
       for (int e = d0 - 2;; e -= 2) {      // row pairs in front of every own column
         const v2f l2 = ld2(Llen, e), u2 = ld2(Lu, e);
         v2f racc = ld2(LR, e);
-        bool need = false;
-#pragma unroll
-        for (int b2 = 0; b2 < NS; ++b2) need = need || (lm[b2] - l2.y < rj[b2]);
-        if (!need) break;
+        if (!(l2.y >= reachF)) break;
         CW_COUNT(2);
 #pragma unroll
         for (int b2 = 0; b2 < NS; ++b2) {
@@ -386,7 +393,7 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
           const v2f xp = d * splat(sp[b2]);
           const v2f g = gauss_pair(xp);
           const v2f y = u2 * g;
-          bH[b2] = pk_fma(u2, h_pair(xp), bH[b2]); bP[b2] = bP[b2] + y; bL[b2] = pk_fma(y, d, bL[b2]);
+          H[b2] = pk_fma(-u2, h_pair(xp), H[b2]); P[b2] = P[b2] + y; L[b2] = pk_fma(-y, d, L[b2]);
           racc = pk_fma(splat(Es[b2]), g, racc);
         }
         *reinterpret_cast<v2f *>(LR + e) = racc;
@@ -400,9 +407,9 @@ __device__ __forceinline__ void compn_bwd_wave(const float (&lm)[NS], const floa
 #pragma unroll
       for (int b2 = NS - 1; b2 >= 0; --b2) {
         suf += um[b2];                                                   // inclusive suffix sum of u
-        cPhi[b2] = (suf - (aH[b2].x + aH[b2].y)) + (bH[b2].x + bH[b2].y);
-        cphi[b2] = ((aP[b2].x + aP[b2].y) + (bP[b2].x + bP[b2].y)) * kRsqrtPi;
-        cphil[b2] = ((aL[b2].x + aL[b2].y) - (bL[b2].x + bL[b2].y)) * kRsqrtPi;
+        cPhi[b2] = suf - (H[b2].x + H[b2].y);
+        cphi[b2] = (P[b2].x + P[b2].y) * kRsqrtPi;
+        cphil[b2] = (L[b2].x + L[b2].y) * kRsqrtPi;
       }
     } else {
 #pragma unroll
