@@ -284,6 +284,13 @@ composite_recompute_bwd_kernel(const int32_t *, const float *__restrict__ act, c
 #ifndef VOGE_COMP_WPE
 #define VOGE_COMP_WPE 1
 #endif
+// Element i of an output array.  NARROW (the FRAME launches): scalar base + 32-bit byte offset, the form at_bytes gives the
+// streams -- no 64-bit address arithmetic on the vector unit (host: every byte offset of the launch fits 32 bits).
+template <bool NARROW, typename T>
+__device__ __forceinline__ T &out_at(T *const base, const long i) {
+  if constexpr (NARROW) return at_bytes_w<T>(base, (uint32_t)i * (uint32_t)sizeof(T));
+  else return base[i];
+}
 // WAVE: every pixel's lanes sit inside ONE wave (64 / LP pixels per wave, the remaining lanes idle), so the
 // per-pixel scans, flags and reductions are wave shuffles / ballots and the kernel has no workgroup barrier at
 // all: each wave runs from its loads to its stores on its own.  (Needs LP <= 64.)
@@ -316,7 +323,13 @@ struct CompShade {
 // (voge_trace_lean_fwd); act / dsd come from make_eval + pair_eval, the operations of the sweep's own epilogue.
 // GEN 2 (round 6): the compact per-axis records (mu, a0, a1, a2, 0, 0), two float4 per Gaussian (voge_frame_trace_fwd_gen, kind 1);
 // act / dsd from pair_eval_diag -- the general chain's bits without its zero coefficients.
-template <int MODE, int NS, bool WAVE, typename OffT, int SC = 0, int GEN = 0>   // MODE 0: forward, 2: backward with weights; OffT: composite_core.h at_bytes
+// FRAME (the wave-form forward with a shade or depth stage): what the host knows of every launch of the frame path is a template
+// fact -- the counts are given, the fragments come from the records (act == NULL), K is a multiple of NS (whole groups: no short
+// last group, has[] all true), the workgroup is one wave and every byte offset of the launch fits 32 bits.  The arms the other
+// launches need (the act / dsd loader, the slot-by-slot accesses, the ballot count, the shuffle-tree reduction of a workgroup of
+// several waves) are not instantiated, the count is read once, and the outputs are addressed as scalar base + 32-bit byte offset
+// (out_at).  No arithmetic on a value differs: every output has the bits of the unflagged instantiation.
+template <int MODE, int NS, bool WAVE, typename OffT, int SC = 0, int GEN = 0, bool FRAME = false>   // MODE 0: forward, 2: backward with weights; OffT: composite_core.h at_bytes
 __global__ void __launch_bounds__(kCompThreads) __attribute__((amdgpu_waves_per_eu(VOGE_COMP_WPE)))
 compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act,
                   const float *__restrict__ len, const float *__restrict__ dsd,
@@ -327,15 +340,17 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
                   const float4 *__restrict__ rec /* forward with act == NULL: [P] (mu, a) */, const float *__restrict__ rays,
                   const CompShade sh = CompShade{}) {
   static_assert(SC == 0 || (MODE == 0 && WAVE && SC <= 4 && SC >= -1), "the shade stage rides in the wave-form forward only");
+  static_assert(!FRAME || (SC != 0 && sizeof(OffT) == 4), "the frame form: a shade / depth stage and 32-bit offsets");
   constexpr bool BWD = MODE != 0;
-  if (SC != 0 && (long)blockIdx.x * blockDim.x < sh.zero_n4) {      // (uniform; the launch covers zero_n4: comp_zero_rider)
-    const long zi = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int bdim = FRAME ? 64 : (int)blockDim.x;      // (FRAME: one-wave workgroups, comp_plan)
+  if (SC != 0 && (long)blockIdx.x * bdim < sh.zero_n4) {      // (uniform; the launch covers zero_n4: comp_zero_rider)
+    const long zi = (long)blockIdx.x * bdim + threadIdx.x;
     if (zi < sh.zero_n4) sh.zero_p[zi] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   constexpr int NP = NS / 2;       // own aligned pairs
   extern __shared__ __attribute__((aligned(16))) unsigned char comp_smem[];
   CompLds &L = *reinterpret_cast<CompLds *>(comp_smem);      // (workgroup form only: its flags are set up before the forms part)
-  const int rows = compn_rows(K, NS, (int)blockDim.x, WAVE);
+  const int rows = compn_rows(K, NS, bdim, WAVE);
   float *const Llen = reinterpret_cast<float *>(comp_smem + (WAVE ? 0 : sizeof(CompLds)));
   float *const Lsp = Llen + rows;
   float *const LE = Lsp + rows;     // E (forward) or E * s' (backward)
@@ -367,32 +382,43 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
   const int RS = compn_stride(K, NS);
   const int PAD = comp_pad(K);
   const int d0 = (in_wg ? p : 0) * RS + PAD + (in_wg ? k0 : 0);   // own group in the padded arrays (even index)
-  const bool vec = (K % NS) == 0;                                    // whole groups, 4 NS-byte aligned accesses
+  const bool vec = FRAME || (K % NS) == 0;                           // whole groups, 4 NS-byte aligned accesses
   bool has[NS];
 #pragma unroll
-  for (int a = 0; a < NS; ++a) has[a] = k0 + a < K;
-  int lead = K;
-  if (cnt_in != nullptr) {
-    lead = active ? min(K, max(0, cnt_in[pix])) : 0;
+  for (int a = 0; a < NS; ++a) has[a] = FRAME || k0 + a < K;
+  const bool counted = FRAME || cnt_in != nullptr;
+  int lead = K, cnt_raw = 0;      // (cnt_raw, FRAME: the count as given, for valid_num)
+  if (counted) {
+    if constexpr (FRAME) {
+      if (active) cnt_raw = at_bytes<int32_t>(cnt_in, (uint32_t)pix * 4u);
+      lead = min(K, max(0, cnt_raw));
+    } else {
+      lead = active ? min(K, max(0, cnt_in[pix])) : 0;
+    }
     if (WAVE ? !__any(lead > 0) : !__syncthreads_or(lead > 0)) {      // every pixel of the workgroup (wave) is empty
       if (active) {
+        if constexpr (FRAME && NS == 4) {      // whole groups: one 16-byte store per array
+          at_bytes_w<float4>(out0, fb) = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (SC > 0) at_bytes_w<int4>(sh.idx_fix, fb) = make_int4(0, 0, 0, 0);
+        } else {
 #pragma unroll
-        for (int a = 0; a < NS; ++a)
-          if (has[a]) { out0[f + a] = 0.0f; if constexpr (BWD) { out1[f + a] = 0.0f; out2[f + a] = 0.0f; } if constexpr (SC > 0) sh.idx_fix[f + a] = 0; }
-        if (!BWD && q == 0) valid_num[pix] = 0;
+          for (int a = 0; a < NS; ++a)
+            if (has[a]) { out0[f + a] = 0.0f; if constexpr (BWD) { out1[f + a] = 0.0f; out2[f + a] = 0.0f; } if constexpr (SC > 0) sh.idx_fix[f + a] = 0; }
+        }
+        if (!BWD && q == 0) out_at<FRAME>(valid_num, pix) = 0;
         if constexpr (SC > 0) if (q == 0) {      // nothing was hit: the background
-          sh.wsum[pix] = 0.0f;
-          if (sh.sil != nullptr) sh.sil[pix] = 0.0f;
+          out_at<FRAME>(sh.wsum, pix) = 0.0f;
+          if (sh.sil != nullptr) out_at<FRAME>(sh.sil, pix) = 0.0f;
 #pragma unroll
           for (int c = 0; c < SC; ++c) {
-            sh.rgb[pix * SC + c] = 0.0f;
-            if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(sh.bg[c], 1.0f);
+            out_at<FRAME>(sh.rgb, pix * SC + c) = 0.0f;
+            if (sh.img != nullptr) out_at<FRAME>(sh.img, pix * SC + c) = fminf(sh.bg[c], 1.0f);
           }
         }
         if constexpr (SC < 0) if (q == 0) {      // nothing was hit: the background depth (normalised) or an empty sum
-          sh.wsum[pix] = 0.0f;
-          if (sh.sil != nullptr) sh.sil[pix] = 0.0f;
-          sh.depth[pix] = sh.normalize != 0 ? sh.depth_bg : 0.0f;
+          out_at<FRAME>(sh.wsum, pix) = 0.0f;
+          if (sh.sil != nullptr) out_at<FRAME>(sh.sil, pix) = 0.0f;
+          out_at<FRAME>(sh.depth, pix) = sh.normalize != 0 ? sh.depth_bg : 0.0f;
         }
       }
       return;
@@ -405,7 +431,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
   int ivk[NS];      // (SC > 0) the lane's indices, kept for the colour gathers
 #pragma unroll
   for (int a = 0; a < NS; ++a) { lm[a] = VOGE_SENT_LEN; sm[a] = 1e-5f; em[a] = 0.0f; gw[a] = 0.0f; wg[a] = 0.0f; id[a] = -1; ivk[a] = -1; }
-  if (!BWD && act == nullptr) {
+  if (!BWD && (FRAME || act == nullptr)) {
     // Fragments without act / dsd in memory (voge_fragments_fwd_iso*): the sweep wrote index and len only; act and dsd
     // of A = a I are re-derived here from the SAME records with the SAME operations its epilogue would have used
     // (pair_eval_iso_at), so the weights are bit-identical to the two-call form.  (host: counts given)
@@ -492,14 +518,14 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
 #pragma unroll
       for (int a = 0; a < NS; ++a) {
         em[a] = FAST_EXP(-av[a]); lm[a] = lv[a]; sm[a] = FAST_SQRT(dv[a] + 1e-10f);
-        if (!BWD && cnt_in == nullptr) id[a] = idx[f + a];
+        if (!BWD && !counted) id[a] = idx[f + a];
       }
     } else {
 #pragma unroll
       for (int a = 0; a < NS; ++a) {
         if (has[a] && k0 + a < lead) {
           em[a] = FAST_EXP(-act[f + a]); lm[a] = len[f + a]; sm[a] = FAST_SQRT(dsd[f + a] + 1e-10f);
-          if (BWD) { gw[a] = g_weight[f + a]; wg[a] = w_in[f + a]; } else if (cnt_in == nullptr) id[a] = idx[f + a];
+          if (BWD) { gw[a] = g_weight[f + a]; wg[a] = w_in[f + a]; } else if (!counted) id[a] = idx[f + a];
         }
       }
     }
@@ -538,7 +564,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
   const bool wave_unsorted = WAVE && ((__ballot(uns) & seg) != 0ull);
   const bool head = in_wg && (lane == 0 || q == 0);
   int wave_cnt = 0;
-  if (!BWD && cnt_in == nullptr) {   // assigned-slot count: NS ballots, one LDS atomic per (wave, pixel) run
+  if (!BWD && !counted) {   // assigned-slot count: NS ballots, one LDS atomic per (wave, pixel) run
     int c = 0;
 #pragma unroll
     for (int a = 0; a < NS; ++a) c += __popcll(__ballot(id[a] >= 0) & seg);
@@ -580,7 +606,8 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
 #pragma unroll
           for (int a = 0; a < NS; ++a) if (has[a]) out0[f + a] = w[a];
         }
-        if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)wave_cnt;
+        if constexpr (FRAME) { if (q == 0) out_at<true>(valid_num, pix) = (int64_t)cnt_raw; }      // (the count is still in its register)
+        else if (q == 0) valid_num[pix] = (cnt_in != nullptr) ? (int64_t)cnt_in[pix] : (int64_t)wave_cnt;
       }
       if constexpr (SC > 0) {
         // ---- shade: sum_k w_k colour[idx_k] and sum_k w_k over the pixel's lanes; blend over the background ----
@@ -593,7 +620,8 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
           if (SC == 3 || SC == 4) {
             // (no exec-mask region per slot: a slot that contributes nothing reads colour row 0 and multiplies a zero; the
             //  row is selected to zero first, so a non-finite colour there cannot leak)
-            const bool on = p2 >= 0 && p2 < sh.Nattr && w[a] != 0.0f;
+            // (FRAME: 0 <= p2 < Nattr as ONE unsigned 32-bit compare -- Nattr < 2^30: host -- the same truth value)
+            const bool on = (FRAME ? (uint32_t)p2 < (uint32_t)sh.Nattr : (p2 >= 0 && p2 < sh.Nattr)) && w[a] != 0.0f;
             const uint32_t o = (uint32_t)(on ? p2 : 0) * (uint32_t)(4 * SC);      // (bytes; Nattr * SC < 2^30: host)
             if (SC == 3) {
               const float3 v = at_bytes<float3>(sh.colors, o);
@@ -613,7 +641,7 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
           }
           part[SC] += w[a];
         }
-        if (SC == 3 && LP >= 3 && blockDim.x == 64) {      // (uniform; one-wave workgroups: the scratch below is the wave's OWN rows -- in a
+        if (SC == 3 && LP >= 3 && bdim == 64) {      // (uniform; one-wave workgroups: the scratch below is the wave's OWN rows -- in a
                                                             //  workgroup of several waves another wave may still be walking them)
           // Three colour sums and sum w over the pixel's lanes.  Round 6: through LDS -- every lane leaves its four partial sums in the
           // (now idle) row arrays, the pixel's lanes 0 .. 2 each add up ONE colour's column and the weights' column in lane order:
@@ -633,16 +661,16 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
             // merge_final rewrites empty slots of the index list in place, -1 -> 0 (Aggregation.py:131)
             if (k0 + NS > lead) {
 #pragma unroll
-              for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) sh.idx_fix[f + a] = 0;
+              for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) out_at<FRAME>(sh.idx_fix, f + a) = 0;
             }
             if (q < 3) {
               float sil = fminf(ws, 1.0f);
               if (sh.thr > 0.0f) sil = sil > sh.thr ? 1.0f : 0.0f;
-              sh.rgb[pix * SC + q] = xs;
-              if (sh.img != nullptr) sh.img[pix * SC + q] = fminf(fmaf(1.0f - sil, sh.bg[q], xs), 1.0f);
+              out_at<FRAME>(sh.rgb, pix * SC + q) = xs;
+              if (sh.img != nullptr) out_at<FRAME>(sh.img, pix * SC + q) = fminf(fmaf(1.0f - sil, sh.bg[q], xs), 1.0f);
               if (q == 0) {
-                sh.wsum[pix] = ws;
-                if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+                out_at<FRAME>(sh.wsum, pix) = ws;
+                if (sh.sil != nullptr) out_at<FRAME>(sh.sil, pix) = fminf(ws, 1.0f);
               }
             }
           }
@@ -662,18 +690,18 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
           // merge_final rewrites empty slots of the index list in place, -1 -> 0 (Aggregation.py:131)
           if (k0 + NS > lead) {
 #pragma unroll
-            for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) sh.idx_fix[f + a] = 0;
+            for (int a = 0; a < NS; ++a) if (has[a] && k0 + a >= lead) out_at<FRAME>(sh.idx_fix, f + a) = 0;
           }
           if (q == 0) {
             const float ws = part[SC];
             float sil = fminf(ws, 1.0f);
             if (sh.thr > 0.0f) sil = sil > sh.thr ? 1.0f : 0.0f;
-            sh.wsum[pix] = ws;
-            if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
+            out_at<FRAME>(sh.wsum, pix) = ws;
+            if (sh.sil != nullptr) out_at<FRAME>(sh.sil, pix) = fminf(ws, 1.0f);
 #pragma unroll
             for (int c = 0; c < SC; ++c) {
-              sh.rgb[pix * SC + c] = part[c];
-              if (sh.img != nullptr) sh.img[pix * SC + c] = fminf(fmaf(1.0f - sil, sh.bg[c], part[c]), 1.0f);
+              out_at<FRAME>(sh.rgb, pix * SC + c) = part[c];
+              if (sh.img != nullptr) out_at<FRAME>(sh.img, pix * SC + c) = fminf(fmaf(1.0f - sil, sh.bg[c], part[c]), 1.0f);
             }
           }
         }
@@ -699,9 +727,9 @@ compositen_kernel(const int32_t *__restrict__ idx, const float *__restrict__ act
         }
         if (active && q == 0) {
           const float ws = part[1];
-          sh.wsum[pix] = ws;
-          if (sh.sil != nullptr) sh.sil[pix] = fminf(ws, 1.0f);
-          sh.depth[pix] = sh.normalize != 0 ? (ws > 0.0f ? part[0] / ws : sh.depth_bg) : part[0];
+          out_at<FRAME>(sh.wsum, pix) = ws;
+          if (sh.sil != nullptr) out_at<FRAME>(sh.sil, pix) = fminf(ws, 1.0f);
+          out_at<FRAME>(sh.depth, pix) = sh.normalize != 0 ? (ws > 0.0f ? part[0] / ws : sh.depth_bg) : part[0];
         }
       }
     }
@@ -999,6 +1027,7 @@ using namespace voge;
 struct CompPlan {
   int NS, lanes, threads, ppw;
   bool wave, small;
+  bool frame;      // compositen_kernel's FRAME instantiation (where there is a shade / depth stage)
   dim3 grid;
   size_t lds;
 };
@@ -1015,6 +1044,9 @@ static CompPlan comp_plan(const int K, const long npix, const int mode, const bo
   P.grid = dim3((unsigned)((npix + P.ppw - 1) / P.ppw));
   P.lds = compn_lds_bytes(K, P.NS, mode != 0, P.threads, P.wave);
   P.small = (double)npix * K < (double)(1l << 30);      // every byte offset fits 32 bits
+  // whole groups of four in one-wave workgroups, 32-bit offsets (with K >= 4, npix < 2^28: the per-pixel outputs' offsets fit too --
+  // 8 bytes of valid_num, at most 16 of rgb / img); the one-pass entries always give counts and records
+  P.frame = onepass && P.wave && P.threads == 64 && P.small && K % P.NS == 0;
   return P;
 }
 
@@ -1033,6 +1065,13 @@ struct CompArgs {
 template <int MODE, int NS, bool WAVE, int SC = 0, int GEN = 0>
 static void launch_compn(const CompPlan &P, const CompArgs &A, const CompShade &sh, hipStream_t st) {
   const float4 *rec = reinterpret_cast<const float4 *>(A.rec);
+  if constexpr (SC != 0) {
+    if (P.frame) {
+      hipLaunchKernelGGL((compositen_kernel<MODE, NS, WAVE, uint32_t, SC, GEN, true>), P.grid, dim3(P.threads), P.lds, st, A.idx, A.act, A.len,
+                         A.dsd, A.w_in, A.g_weight, A.cnt, A.occ, A.npix, A.K, P.ppw, A.o0, A.o1, A.o2, A.valid_num, rec, A.rays, sh);
+      return;
+    }
+  }
   if (P.small)
     hipLaunchKernelGGL((compositen_kernel<MODE, NS, WAVE, uint32_t, SC, GEN>), P.grid, dim3(P.threads), P.lds, st, A.idx, A.act, A.len,
                        A.dsd, A.w_in, A.g_weight, A.cnt, A.occ, A.npix, A.K, P.ppw, A.o0, A.o1, A.o2, A.valid_num, rec, A.rays, sh);
