@@ -10,7 +10,8 @@ What it follows:
 The projection goes through PyTorch3D (un-vendored, absent): PerspectiveCameras in screen space,
 get_full_projection_transform().compose(get_ndc_camera_transform()), restated here from its documentation
 ([recall]) -- that part is "parity unpinned" like the ray convention.  The kernel part is
-restated statement by statement.  Two things the CUDA kernel leaves to the scheduler are fixed here: chunks are
+restated statement by statement and pinned to the reference's own kernel (bins as sorted sets: tests/golden/ref_kernels.npz,
+tests/test_gpu_reference_kernels.py).  Two things the CUDA kernel leaves to the scheduler are fixed here: chunks are
 taken in ascending order (the reference's order between chunks depends on which block's atomicAdd lands first),
 so a bin's list is ascending in index and, when a bin overflows, it is the LATER chunks that are dropped.
 """

@@ -4,9 +4,9 @@ dense trace / backward  VoGE/csrc/voge_ray_tracing_ray/voge_ray_tracing_ray.cu:1
 find_nearest_k          voge_ray_tracing_ray.cu:191-239, host init :344-347
 sample_voge (+backward) VoGE/csrc/sample_voge/sample_voge.cu:35-66, :173-209
 scatter_max             sample_voge.cu:69-92
-The reference ships no test or CPU build for any of them (CUDA only): parity unpinned beyond the
-line-by-line restatement; sample_features is additionally checked against the dense formulation
-its docstring quotes (Sampler.py:7-11)."""
+Pinned to the reference's own kernels: their recorded outputs (tests/golden/ref_kernels.npz, tests/test_oracle_cpu.py) and,
+on the GPU, the kernels themselves (tests/test_gpu_reference_kernels.py); sample_features is additionally checked against
+the dense formulation its docstring quotes (Sampler.py:7-11)."""
 import numpy as np
 
 
@@ -21,6 +21,7 @@ def ray_dense_fwd(mus, isg, rays):
 
 def ray_dense_bwd(mus, isg, rays, g_len, g_act, g_dsd):
     mu, A, d = (np.asarray(x, np.float64) for x in (mus, isg, rays))
+    g_len, g_act, g_dsd = (np.asarray(g, np.float64) for g in (g_len, g_act, g_dsd))      # (fp32 gradients would be SUMMED in fp32 below)
     Ad = np.einsum("mij,nj->nmi", A, d)
     Atd = np.einsum("mji,nj->nmi", A, d)
     ksk = np.einsum("ni,nmi->nm", d, Ad)

@@ -18,9 +18,10 @@
  *     Aggregation.py / Renderer.py in the build container; fixtures committed).
  *   - trace backward chain rule: PINNED by the reference's embedded known-answer
  *     proof (ray_trace_voge.cu:381-448; fixture trace_bwd_known_answer.npz).
- *   - trace forward (forms, threshold, top-K order): the reference ships no test,
- *     fixture or runnable CPU build for it (CUDA only) -> "parity unpinned" for
- *     that row beyond line-by-line restatement + a dense torch cross-check.
+ *   - trace forward (forms, threshold, top-K order) and backward: PINNED to the
+ *     reference's own kernels -- recorded outputs of its extension built for
+ *     gfx950 (oracle/build_ref.py; fixture tests/golden/ref_kernels.npz), and
+ *     run beside this oracle on the GPU (tests/test_gpu_reference_kernels.py).
  *
  * Two precisions are built from voge_oracle_impl.h:
  *   *_f64 : fp64 evaluation of the reference formulas on the fp32 inputs (truth)

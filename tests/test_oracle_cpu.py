@@ -312,3 +312,97 @@ def test_torch_tensor_program_merge_blend_and_dense_trace():
     assert same.mean() > 0.99
     for got, want in ((ln, ref[1]), (act, ref[2]), (dsd, ref[3])):
         assert np.abs(got.numpy().reshape(want.shape)[same] - want[same]).max() < 1e-6 * max(1.0, np.abs(want[same]).max())
+
+
+# ---- the reference's OWN KERNELS, recorded on the GPU (tests/golden/make_ref_kernel_golden.py) ---------------------------------------
+def _ref_kernels():
+    return np.load(os.path.join(GOLDEN, "ref_kernels.npz"))
+
+
+def _within(label, got, terms):
+    """The recorded sums were accumulated by float atomics: per element (m - 1) 2^-24 sum|terms| + TOL of the scale."""
+    import ref_kernel_cases as rc
+    s, a, m = terms
+    err = np.abs(np.asarray(got, np.float64).reshape(s.shape) - s)
+    bound = rc.atomic_bound(a, m, s)
+    assert (err <= bound).all(), f"{label}: error / bound {float((err / bound).max()):.3f}"
+
+
+@pytest.mark.parametrize("name", ["fa", "fb", "fc"])
+def test_oracle_reproduces_the_recorded_fine_trace_of_the_reference_kernel(name):
+    """Index lists exactly (the scenes keep every decision TOL / 2 from its switch, checked here), values within TOL relative to
+    max(1, |recorded|), sentinels exactly; the backward in all nine entries of grad_isigmas, unsymmetrised."""
+    import ref_kernel_cases as rc
+    from util import TOL, close
+    g = _ref_kernels()
+    mus, isg, rays, bins = (g[f"{name}_{k}"] for k in ("mus", "isg", "rays", "bins"))
+    K, thr_act = int(g[name + "_meta"][0]), float(g[name + "_thr_act"])
+    B, H, W, _ = rays.shape
+    c = dict(mus=mus, isg=isg, rays=rays, bins=bins, K=K, thr_act=thr_act, B=B, H=H, W=W, N=mus.shape[0] // B)
+    assert min(rc.decision_margins(c)) > TOL / 2 and H * W <= 400 and K <= 12
+    rec = [g[f"{name}_out_{k}"] for k in ("idx", "len", "act", "dsd")]
+    live = rec[0] >= 0
+    assert live.any() and (name == "fc" or (~live).any())
+    for precision in ("f64", "f32"):
+        got = oracle.trace_fwd(mus, isg, rays, K, thr_act, bin_points=bins, bin_size=rc.BIN_SIZE, precision=precision)
+        assert np.array_equal(got[0], rec[0]), f"{precision}: {int((got[0] != rec[0]).any(-1).sum())} pixels' lists differ"
+        for k, a, b in zip(("len", "act", "dsd"), got[1:], rec[1:]):
+            assert close(a[live], b[live]).all(), (precision, k)
+            assert np.array_equal(a[~live].astype(np.float32), b[~live]), (precision, k)
+    if name == "fa":
+        assert (rec[1][live] < 0).any()      # hits behind the camera are kept
+    gl, ga, gd = (g[f"{name}_{k}"] * live for k in ("g_len", "g_act", "g_dsd"))
+    want = oracle.trace_bwd(mus, isg, rays, rec[0], gl, ga, gd)
+    terms = rc.trace_bwd_terms(mus, isg, rays.reshape(-1, 3), rec[0].reshape(-1, K), gl.reshape(-1, K), ga.reshape(-1, K), gd.reshape(-1, K))
+    for key, w in zip(("ray", "mus", "isg"), want):
+        assert np.abs(terms[key][0] - w.reshape(terms[key][0].shape)).max() <= 1e-9 * max(1.0, np.abs(w).max())
+        _within(f"{name} grad_{key}", g[f"{name}_out_g_{key}"], terms[key])
+    if name == "fa":      # non-symmetric forms: a transposed grad_isigmas would not pass
+        gi = want[2]
+        assert np.abs(gi - gi.transpose(0, 2, 1)).max() > 1e-2 * np.abs(gi).max()
+
+
+def test_extras_np_reproduces_the_recorded_dense_trace_and_nearest_k_of_the_reference_kernels():
+    import ref_kernel_cases as rc
+    from oracle import extras_np
+    from util import close
+    g = _ref_kernels()
+    mus, isg, rays = g["dense_mus"], g["dense_isg"], g["dense_rays"]
+    N, M = rays.shape[0], mus.shape[0]
+    for k, got in zip(("len", "act", "dsd"), extras_np.ray_dense_fwd(mus, isg, rays)):
+        assert g["dense_out_" + k].shape == (N, M) and close(got, g["dense_out_" + k]).all(), k
+    every = np.ascontiguousarray(np.broadcast_to(np.arange(M, dtype=np.int32), (N, M)))
+    terms = rc.trace_bwd_terms(mus, isg, rays, every, g["dense_g_len"], g["dense_g_act"], g["dense_g_dsd"])
+    want = extras_np.ray_dense_bwd(mus, isg, rays, g["dense_g_len"], g["dense_g_act"], g["dense_g_dsd"])
+    for key, w in zip(("ray", "mus", "isg"), want):
+        assert np.abs(terms[key][0] - w).max() <= 1e-9 * max(1.0, np.abs(w).max())
+        _within(f"dense grad_{key}", g["dense_out_g_" + key], terms[key])
+    # find_nearest_k selects copies of its fp32 input: everything exactly, the empty slots' -1 / 1e10 / 0 / 0 included
+    ln, act, dsd = (g["dense_out_" + k] for k in ("len", "act", "dsd"))
+    for K in (1, 5, 15):
+        got = extras_np.find_nearest_k(ln, act, dsd, K, np.float32(g["nearest_thr_act"]))
+        for k, a in zip(("idx", "len", "act", "dsd"), got):
+            rec = g[f"nearest_k{K}_out_{k}"]
+            assert np.array_equal(np.asarray(a).astype(rec.dtype), rec), (K, k)
+    assert (g["nearest_k15_out_idx"][:, -3:] == -1).all() and (g["nearest_k15_out_idx"][:, 0] >= 0).all()
+
+
+def test_extras_np_and_coarse_np_reproduce_the_recorded_sampler_and_coarse_bins_of_the_reference_kernels():
+    import ref_kernel_cases as rc
+    from oracle import coarse_np, extras_np
+    g = _ref_kernels()
+    case = {k: g["sampler_" + k] for k in ("image", "weight", "idx", "g_feat", "g_wsum")}
+    case.update(n_vert=int(g["sampler_n_vert"]), C=int(g["sampler_C"]), K=int(g["sampler_K"]))
+    terms = rc.sampler_terms(case)
+    feat, wsum = extras_np.sample_voge(case["image"], case["weight"], case["idx"], case["n_vert"])
+    g_img, g_w = extras_np.sample_voge_bwd(case["image"], case["weight"], case["idx"], case["g_feat"], case["g_wsum"])
+    for key, w in (("feat", feat), ("wsum", wsum), ("g_image", g_img), ("g_weight", g_w)):
+        assert np.abs(terms[key][0] - w).max() <= 1e-12 * max(1.0, np.abs(w).max())
+        _within("sampler " + key, g["sampler_out_" + key], terms[key])
+    assert (g["sampler_out_feat"][-2:] == 0).all() and (g["sampler_out_wsum"][-2:] == 0).all()      # vertices nobody references
+    assert np.array_equal(extras_np.scatter_max(case["weight"], case["idx"], case["n_vert"]).astype(np.float32), g["sampler_out_max"])
+    size = tuple(int(v) for v in g["coarse_image_size"])
+    bins = coarse_np.rasterize_points_coarse(g["coarse_points"], g["coarse_first"], g["coarse_num"], size, g["coarse_radius"],
+                                             int(g["coarse_bin_size"]), int(g["coarse_max_points_per_bin"]))
+    assert np.array_equal(rc.sorted_bins(bins), g["coarse_out_bins_sorted"])
+    assert (g["coarse_out_bins_sorted"] >= 0).any() and (g["coarse_points"][:, 2] < 0).any()
