@@ -722,186 +722,14 @@ extern "C" int voge_fragment_act_dsd_iso(const float *records, const float *rays
 
 // (the isotropic forms use the first 32 | 16 bytes per Gaussian; the general ones 48 of packed records + 64 | 48 of sums)
 extern "C" size_t voge_fragment_bwd_workspace_bytes(int P) { return P <= 0 ? 0 : (size_t)P * 112; }
-
-namespace {
-struct FbArgs {      // what every form of the fused backward hands its kernel
-  const float4 *rec; const float *rays, *colors; const int32_t *idx, *cnt; const float *weight, *act, *len, *dsd, *rgb, *wsum, *bg;
-  float thr; const float *g; long gs_pix, gs_c; const float *g_hitlen; float occ; int P; long nrows; int W, K; long Nattr; float *acc;
-};
-template <int SRC, int C, int NS, typename OffT, bool ISO, bool NOAD>
-void fb_launch(const FbArgs &a, hipStream_t st) {
-  const long blocks = (long)((a.W + kFbGW - 1) / kFbGW) * ((a.nrows + kFbGH - 1) / kFbGH);
-  // (the kernel's gathers are unconditional at clamped ids: row 0 of the records (P >= 1 here) and of the colour table must be
-  //  readable.  An empty colour table reads its dropped row out of the records instead.)
-  const float *colors = (a.Nattr > 0 && a.colors != nullptr) ? a.colors : reinterpret_cast<const float *>(a.rec);
-  hipLaunchKernelGGL((fragment_bwd_kernel<SRC, C, NS, OffT, ISO, NOAD>), dim3((unsigned)blocks), dim3(64), 0, st, a.rec, a.rays,
-                     colors, a.idx, a.cnt, a.weight, a.act, a.len, a.dsd, a.rgb, a.wsum, a.bg, a.thr, a.g, a.gs_pix, a.gs_c,
-                     a.g_hitlen, a.occ, a.P, a.nrows, a.W, a.K, a.Nattr, a.acc);
-}
-template <int SRC, int C, int NS, typename OffT>
-void fb_launch_diag_t(const FbArgs &a, hipStream_t st) {
-  const long blocks = (long)((a.W + kFbGW - 1) / kFbGW) * ((a.nrows + kFbGH - 1) / kFbGH);
-  const float *colors = (a.Nattr > 0 && a.colors != nullptr) ? a.colors : reinterpret_cast<const float *>(a.rec);
-  hipLaunchKernelGGL((fragment_bwd_kernel<SRC, C, NS, OffT, false, true, true>), dim3((unsigned)blocks), dim3(64), 0, st, a.rec, a.rays,
-                     colors, a.idx, a.cnt, a.weight, a.act, a.len, a.dsd, a.rgb, a.wsum, a.bg, a.thr, a.g, a.gs_pix, a.gs_c,
-                     a.g_hitlen, a.occ, a.P, a.nrows, a.W, a.K, a.Nattr, a.acc);
-}
-template <int SRC, int C, int NS>
-void fb_launch_diag(const FbArgs &a, hipStream_t st) {
-  if ((double)a.nrows * a.W * a.K < (double)(1l << 30)) fb_launch_diag_t<SRC, C, NS, uint32_t>(a, st); else fb_launch_diag_t<SRC, C, NS, size_t>(a, st);
-}
-template <int SRC, int C, int NS, bool ISO>
-void fb_launch_off(const FbArgs &a, hipStream_t st) {
-  const bool small = (double)a.nrows * a.W * a.K < (double)(1l << 30);      // every byte offset fits 32 bits
-  if (a.act == nullptr) { if (small) fb_launch<SRC, C, NS, uint32_t, ISO, true>(a, st); else fb_launch<SRC, C, NS, size_t, ISO, true>(a, st); }
-  else { if (small) fb_launch<SRC, C, NS, uint32_t, ISO, false>(a, st); else fb_launch<SRC, C, NS, size_t, ISO, false>(a, st); }
-}
-template <bool ISO>
-void fb_launch_shade(const FbArgs &a, int C, hipStream_t st) {
-  switch (C) {
-    case 1: fb_launch_off<0, 1, 2, ISO>(a, st); break;
-    case 2: fb_launch_off<0, 2, 2, ISO>(a, st); break;
-    case 3: fb_launch_off<0, 3, 2, ISO>(a, st); break;
-    default: fb_launch_off<0, 4, 2, ISO>(a, st); break;
-  }
-}
-template <bool ISO>
-void fb_launch_gw(const FbArgs &a, hipStream_t st) {
-  if (a.K <= 128) fb_launch_off<1, 0, 2, ISO>(a, st); else fb_launch_off<1, 0, 4, ISO>(a, st);
-}
-}  // namespace
-
-extern "C" int voge_fragment_shade_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
-                                           const float *rays, const float *colors, const int32_t *idx, const int32_t *cnt,
-                                           const float *weight, const float *act, const float *len, const float *dsd,
-                                           const float *rgb, const float *wsum, const float *bg, float thr,
-                                           const float *g_img, long g_stride_pix, long g_stride_c, float occ, int B, int N,
-                                           long nrows, int W, int K, int C, long Nattr, void *workspace, size_t workspace_bytes, float *g_verts,
-                                           float *g_sigmas, float *g_colors, voge_stream_t stream) {
-  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || C <= 0 || C > 4 || Nattr < 0 || sigma_mode < 0 || sigma_mode > 2)
-    return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;      // a lane owns a pair of slots; a pixel's lanes fit one wave
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0 || nrows * W == 0) {
-    if (g_colors && Nattr > 0) return (int)voge_fill_async(g_colors, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return 0;
-  }
-  if (!records || !rays || !colors || !idx || !cnt || !weight || !len || !rgb || !wsum || !bg || !g_img || !workspace)
-    return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;      // both or neither (neither: re-derived from the records)
-  if ((g_verts == nullptr) != (g_sigmas == nullptr) || (sigma_mode == 2 && g_sigmas && !sigmas)) return VOGE_ERR_BAD_ARG;
-  if (workspace_bytes < (size_t)P * 32) return VOGE_ERR_WORKSPACE;
-  if (Nattr * C >= (1l << 30) || P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the gathers
-  float *acc = reinterpret_cast<float *>(workspace);
-  { const hipError_t e = voge_fill_async(acc, 0, (size_t)P * 32, st); if (e != hipSuccess) return (int)e; }
-  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, colors, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g_img,
-                 g_stride_pix, g_stride_c, nullptr, occ, P, nrows, W, K, Nattr, acc};
-  fb_launch_shade<true>(a, C, st);
-  const long n_fin = (Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, acc, 8, sigmas, P, N, B,
-                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, C, Nattr, g_verts, g_sigmas, g_colors);
-  return launch_status();
-}
-
-// Round 6, the frame's backward: voge_fragment_shade_bwd_iso / voge_fragment_merge_bwd_iso WITHOUT the fill launch in front --
-// `acc` (voge_frame_bwd_acc_bytes(B * N) bytes) arrives zeroed: the frame's forward does that on its way
-// (voge_frame_shade_fwd_iso's bwd_acc), and it is good for ONE backward.  The fused kernel + the finishing pass.
+// The frame path's accumulators arrive zeroed (the frame's forward does that on its way: voge_frame_shade_fwd_iso's bwd_acc) and
+// are good for ONE backward.
 extern "C" size_t voge_frame_bwd_acc_bytes(int P) { return P <= 0 ? 0 : (size_t)P * 32; }
+extern "C" size_t voge_frame_bwd_gen_acc_bytes(int P) { return P <= 0 ? 0 : (size_t)P * 64; }      // (kind 1 uses 48 | 32 of them)
 
-static int frame_bwd_impl(const bool merge, const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
-                          const float *colors, const int32_t *idx, const int32_t *cnt, const float *weight, const float *len,
-                          const float *rgb, const float *wsum, const float *bg, float thr, const float *g, long g_stride_pix,
-                          long g_stride_c, float occ, int B, int N, long nrows, int W, int K, int C, long Nattr, void *acc_zeroed,
-                          size_t acc_bytes, float *g_verts, float *g_sigmas, float *g_colors, voge_stream_t stream) {
-  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || C <= 0 || C > 4 || Nattr < 0 || sigma_mode < 0 || sigma_mode > 2)
-    return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0 || nrows * W == 0) {
-    if (g_colors && Nattr > 0) return (int)voge_fill_async(g_colors, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return 0;
-  }
-  if (!records || !rays || !colors || !idx || !cnt || !weight || !len || !g || !acc_zeroed) return VOGE_ERR_BAD_ARG;
-  if (!merge && (!rgb || !wsum || !bg)) return VOGE_ERR_BAD_ARG;
-  if ((g_verts == nullptr) != (g_sigmas == nullptr) || (sigma_mode == 2 && g_sigmas && !sigmas)) return VOGE_ERR_BAD_ARG;
-  if (acc_bytes < voge_frame_bwd_acc_bytes(P)) return VOGE_ERR_WORKSPACE;
-  if (Nattr * C >= (1l << 30) || P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the gathers
-  float *acc = reinterpret_cast<float *>(acc_zeroed);
-  // (merge form: bg = NULL selects it inside the kernel; its `wsum` operand carries g_wsum)
-  // (merge form: bg = NULL selects it inside the kernel; its `wsum` operand carries g_wsum -- or, with `rgb` = the forward's weight
-  //  sums, the silhouette's gradient)
-  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, colors, idx, cnt, weight, nullptr, len, nullptr, rgb, wsum,
-                 merge ? nullptr : bg, merge ? -1.0f : thr, g, g_stride_pix, g_stride_c, nullptr, occ, P, nrows, W, K, Nattr, acc};
-  fb_launch_shade<true>(a, C, st);
-  const long n_fin = (Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, acc, 8, sigmas, P, N, B,
-                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, C, Nattr, g_verts, g_sigmas, g_colors);
-  return launch_status();
-}
-
-extern "C" int voge_frame_shade_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
-                                        const float *rays, const float *colors, const int32_t *idx, const int32_t *cnt,
-                                        const float *weight, const float *len, const float *rgb, const float *wsum,
-                                        const float *bg, float thr, const float *g_img, long g_stride_pix, long g_stride_c,
-                                        float occ, int B, int N, long nrows, int W, int K, int C, long Nattr, void *acc_zeroed,
-                                        size_t acc_bytes, float *g_verts, float *g_sigmas, float *g_colors, voge_stream_t stream) {
-  return frame_bwd_impl(false, records, sigmas, shared, sigma_mode, rays, colors, idx, cnt, weight, len, rgb, wsum, bg, thr, g_img,
-                        g_stride_pix, g_stride_c, occ, B, N, nrows, W, K, C, Nattr, acc_zeroed, acc_bytes, g_verts, g_sigmas, g_colors, stream);
-}
-
-extern "C" int voge_frame_merge_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
-                                        const float *rays, const float *attr, const int32_t *idx, const int32_t *cnt,
-                                        const float *weight, const float *len, const float *g_rgb, long g_stride_pix,
-                                        long g_stride_c, const float *g_wsum, const float *wsum_fwd, float occ, int B, int N, long nrows,
-                                        int W, int K, int C, long Nattr, void *acc_zeroed, size_t acc_bytes, float *g_verts,
-                                        float *g_sigmas, float *g_attr, voge_stream_t stream) {
-  return frame_bwd_impl(true, records, sigmas, shared, sigma_mode, rays, attr, idx, cnt, weight, len, wsum_fwd, g_wsum, nullptr, -1.0f, g_rgb,
-                        g_stride_pix, g_stride_c, occ, B, N, nrows, W, K, C, Nattr, acc_zeroed, acc_bytes, g_verts, g_sigmas, g_attr, stream);
-}
-
-// get_depth's backward on the frame path (extension): modelled on voge_frame_merge_bwd_iso -- the accumulator the forward
-// (voge_frame_depth_fwd_iso) zeroed, ONE fused launch (SRC = 2: the two per-pixel scalars are formed inside the kernel), the
-// finishing pass.  Four sums per Gaussian (g_mu, g_a): acc is [B * N][4] floats, 16 bytes per Gaussian.
-extern "C" int voge_frame_depth_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
-                                        const int32_t *idx, const int32_t *cnt, const float *weight, const float *len,
-                                        const float *depth, const float *wsum, const float *g_depth, long g_stride_pix,
-                                        const float *g_sil, int normalize, float occ, int B, int N, long nrows, int W, int K,
-                                        void *acc_zeroed, size_t acc_bytes, float *g_verts, float *g_sigmas, voge_stream_t stream) {
-  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || g_stride_pix < 0 || sigma_mode < 0 || sigma_mode > 2) return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;      // a lane owns a pair of slots; a pixel's lanes fit one wave
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  const long n_out = shared ? N : P;
-  if (n_out == 0) return 0;      // no Gaussians: nothing to write
-  if (!g_verts || !g_sigmas) return VOGE_ERR_BAD_ARG;
-  if (P == 0 || nrows * W == 0) {
-    hipError_t e0 = voge_fill_async(g_verts, 0, sizeof(float) * 3 * (size_t)n_out, st);
-    if (e0 == hipSuccess) e0 = voge_fill_async(g_sigmas, 0, sizeof(float) * (size_t)n_out, st);
-    return (int)e0;
-  }
-  if (!records || !rays || !idx || !cnt || !weight || !len || !depth || !wsum || !acc_zeroed) return VOGE_ERR_BAD_ARG;
-  if ((!g_depth && !g_sil) || (sigma_mode == 2 && !sigmas)) return VOGE_ERR_BAD_ARG;
-  if (acc_bytes < (size_t)P * 16) return VOGE_ERR_WORKSPACE;
-  if (P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the record gathers
-  float *acc = reinterpret_cast<float *>(acc_zeroed);
-  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, nullptr, idx, cnt, weight, nullptr, len, nullptr, depth, wsum, g_sil,
-                 normalize ? 1.0f : -1.0f, g_depth, g_stride_pix, 0, nullptr, occ, P, nrows, W, K, 0, acc};
-  if ((double)nrows * W * K < (double)(1l << 30)) fb_launch<2, 0, 2, uint32_t, true, true>(a, st);      // (every byte offset fits 32 bits)
-  else fb_launch<2, 0, 2, size_t, true, true>(a, st);
-  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, 4, sigmas, P, N, B,
-                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, 0, 0l, g_verts, g_sigmas, (float *)nullptr);
-  return launch_status();
-}
-
-// ---- the general forms on the frame path: every backward route of fragments made by voge_frame_trace_fwd_gen.  The packed
-// (mu, A) records come from the forward (no pack launch), `acc` [P][16 | 12] floats is either zeroed already (acc_is_zero: the
-// frame's composite did it on its way) or filled here, and the finishing pass applies the renderer's own chain rule
-// (Renderer.py:130-137 backwards: the sum over the views of a shared set; d A / d sigma = 2 on the diagonal for per-axis sigmas,
-// 2 everywhere for [3][3] ones) -- no general_preamble_bwd launch behind it.
-//   form 0: the image's gradient (to_colored_background: rgb, wsum, bg, thr, g = g_img);   form 1: merge_final's (interpolate_attr:
-//   g = g_rgb, wsum = g_wsum | NULL -- or, with rgb = the forward's weight sums [pix], the gradient of get_silhouette);   form 2: the weights' own (g = g_weight with strides, g_hitlen | NULL; C = 0, no attr).
+// ---- the finishing passes of the general forms on the frame path (fragments made by voge_frame_trace_fwd_gen / _ori): the
+// renderer's own chain rule (Renderer.py:130-137 backwards: the sum over the views of a shared set; d A / d sigma = 2 on the
+// diagonal for per-axis sigmas, 2 everywhere for [3][3] ones) -- no general_preamble_bwd launch behind it.
 // thread t of a finishing pass: the attributes' gradient (acc[..][attr_at ..]) and the vertices' (acc[..][0..2]; a shared set: its
 // views in a fixed order)
 __device__ __forceinline__ void finish_attr_verts(const float *__restrict__ acc, const int S, const int P, const int N, const int B,
@@ -948,8 +776,6 @@ fragment_bwd_finish_view_kernel(const float *__restrict__ acc, const int S, cons
     for (int i = 0; i < 9; ++i) g_sigmas[9 * t + i] = 2.0f * v[i];
   }
 }
-
-extern "C" size_t voge_frame_bwd_gen_acc_bytes(int P) { return P <= 0 ? 0 : (size_t)P * 64; }      // (kind 1 uses 48 | 32 of them)
 
 // The oriented form's finishing pass (voge_frame_bwd_ori): kind 2's accumulator, G = the raw 3x3 sums acc[..][3..11] (a shared
 // set: its views in a fixed order), through A = R diag(d) R^T backwards -- g_d[k] = r_k^T G r_k (r_k: column k of R), g_s = 2 g_d
@@ -1005,80 +831,237 @@ fragment_bwd_finish_ori_kernel(const float *__restrict__ acc, const int S, const
   reinterpret_cast<float4 *>(g_quats)[t] = out;
 }
 
-static int frame_bwd_gen_impl(int form, const float *records, int shared_verts, int shared_sigmas, int kind, const float *rays,
-                              const float *attr, const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
-                              const float *len, const float *dsd, const float *rgb, const float *wsum, const float *bg, float thr,
-                              const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ, int B, int N,
-                              long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
-                              float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream,
-                              // (the oriented form: kind 2 with g_sigmas = the scales' gradient [.., 3], finished by fragment_bwd_finish_ori_kernel)
-                              const float *ori_scales = nullptr, const float *ori_quats = nullptr, int ori_mode = 0, float *g_quats = nullptr) {
-  const bool ori = ori_mode != 0;
-  if (form < 0 || form > 2 || (kind != 1 && kind != 2) || B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || Nattr < 0) return VOGE_ERR_BAD_ARG;
-  if (form != 2 && (C <= 0 || C > 4)) return VOGE_ERR_BAD_ARG;
-  if (K > (form == 2 ? VOGE_MAX_K : 128)) return VOGE_ERR_K_TOO_LARGE;
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  const long nv = shared_verts ? N : P, ns = (long)(shared_sigmas ? N : P) * (kind == 1 || ori ? 3 : 9);
-  if (P == 0 || nrows * W == 0) {      // nothing was traced: zero gradients
-    hipError_t e = hipSuccess;
-    if (g_verts && nv > 0) e = voge_fill_async(g_verts, 0, sizeof(float) * 3 * (size_t)nv, st);
-    if (e == hipSuccess && g_sigmas && ns > 0) e = voge_fill_async(g_sigmas, 0, sizeof(float) * (size_t)ns, st);
-    if (e == hipSuccess && g_quats && ns > 0) e = voge_fill_async(g_quats, 0, sizeof(float) * (size_t)(ns / 3) * 4, st);
-    if (e == hipSuccess && g_attr && Nattr > 0 && form != 2) e = voge_fill_async(g_attr, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return (int)e;
+// ---- the host side: eleven entries, each a description (FbCall) handed to the ONE launcher, fb_run ----
+namespace {
+// What fragment_bwd_kernel is handed.  One kernel serves every form by reusing its operands:
+//   shade (SRC 0; the image's gradient, to_colored_background): colors [Nattr,C]; rgb, wsum = the forward's image and weight sums;
+//     bg, thr = the background stage; g = g_img with strides (pixel, channel).
+//   merge (SRC 0; interpolate_attr): bg = NULL selects it inside the kernel, thr = -1; colors = the attributes; g = g_rgb with
+//     strides; wsum = g_wsum | NULL and rgb = NULL -- or, with rgb = the forward's weight sums [pix], wsum = get_silhouette's gradient.
+//   weights (SRC 1; their own gradient, any consumer): g = g_weight | NULL with strides (pixel, slot), g_hitlen | NULL; colors = rgb =
+//     wsum = bg = NULL, thr = -1, Nattr = 0.
+//   depth (SRC 2): rgb = the forward's depth, wsum = its weight sums, g = g_depth | NULL with gs_pix, bg = g_sil | NULL, thr = +1 | -1:
+//     normalize on | off; no colors, Nattr = 0.
+// act = dsd = NULL (NOAD): both are re-derived from the records.  fb_run sets P and acc, and for merge / weights the constants above.
+struct FbArgs {
+  const float4 *rec; const float *rays, *colors; const int32_t *idx, *cnt; const float *weight, *act, *len, *dsd, *rgb, *wsum, *bg;
+  float thr; const float *g; long gs_pix, gs_c; const float *g_hitlen; float occ; int P; long nrows; int W, K; long Nattr; float *acc;
+};
+enum FbForm { FB_SHADE, FB_MERGE, FB_WEIGHTS, FB_DEPTH };      // K <= 128 (a lane owns a pair of slots; a pixel's lanes fit one wave);
+                                                               // FB_WEIGHTS: K <= VOGE_MAX_K, four slots on a lane (NS = 4) above 128
+// The finishing pass, and with it the records and the accumulator acc [P][S] (S floats of sums per Gaussian):
+//   FIN_ISO      fragment_bwd_finish_kernel: 16-byte records (ISO), S = 8 | 4 without attributes; g1 = g_sigmas [.., 1], p1 = sigmas
+//                (read for mode = sigma_mode 2), one `shared` flag for both gradients.
+//   FIN_GENERAL  fragment_bwd_finish_general_kernel: the records are packed HERE from (mus, p1 = isigmas) into the workspace -- 48
+//                bytes each at offset 0, acc behind them, zeroed by the same launch; S = 16 | 12; g1 = g_isigmas [P, 9].
+//   FIN_VIEW     fragment_bwd_finish_view_kernel: the frame's packed records, mode = kind: 2 as FIN_GENERAL, 1 per-axis records (DIAG:
+//                no act / dsd, S = 12 | 8, g1 [.., 3]).
+//   FIN_ORI      fragment_bwd_finish_ori_kernel: kind 2's records and accumulator; p1 = scales, quats, mode = sigma_mode, g1 =
+//                g_scales [.., 3], g_quats [.., 4].
+enum FbFinish { FIN_ISO, FIN_GENERAL, FIN_VIEW, FIN_ORI };
+struct FbCall {
+  FbForm form; FbFinish fin; FbArgs k; int B, N, C;      // (the general forms: B = 1, N = P)
+  void *ws; size_t ws_bytes;      // the workspace | the accumulator
+  bool zero_here;                 // false: acc arrives zeroed (the frame entries, acc_is_zero)
+  float *g0, *g1, *g_attr;        // the gradients of the means, of the second parameter, of the attributes [Nattr, C]
+  const float *p1 = nullptr; int shared_v = 0, shared_s = 0, mode = 0; const float *mus = nullptr, *quats = nullptr; float *g_quats = nullptr;
+};
+const float4 *fb_rec(const float *records) { return reinterpret_cast<const float4 *>(records); }
+
+template <int SRC, int C, int NS, bool ISO, bool NOAD, bool DIAG>
+void fb_launch(const FbArgs &a, hipStream_t st) {
+  const long blocks = (long)((a.W + kFbGW - 1) / kFbGW) * ((a.nrows + kFbGH - 1) / kFbGH);
+  // (the kernel's gathers are unconditional at clamped ids: row 0 of the records (P >= 1 here) and of the colour table must be
+  //  readable.  An empty colour table reads its dropped row out of the records instead.)
+  const float *colors = (a.Nattr > 0 && a.colors != nullptr) ? a.colors : reinterpret_cast<const float *>(a.rec);
+  auto launch = [&](auto off) {
+    hipLaunchKernelGGL((fragment_bwd_kernel<SRC, C, NS, decltype(off), ISO, NOAD, DIAG>), dim3((unsigned)blocks), dim3(64), 0, st, a.rec,
+                       a.rays, colors, a.idx, a.cnt, a.weight, a.act, a.len, a.dsd, a.rgb, a.wsum, a.bg, a.thr, a.g, a.gs_pix, a.gs_c,
+                       a.g_hitlen, a.occ, a.P, a.nrows, a.W, a.K, a.Nattr, a.acc);
+  };
+  if ((double)a.nrows * a.W * a.K < (double)(1l << 30)) launch(uint32_t{}); else launch(size_t{});      // (every byte offset fits 32 bits)
+}
+// The instantiations are the ones listed here and no product of the parameters: depth has one form, DIAG one (ISO, NOAD) pair.
+template <int SRC, int C, int NS>
+void fb_launch_form(const FbArgs &a, const bool iso, const bool diag, hipStream_t st) {
+  if constexpr (SRC == 2) fb_launch<2, 0, 2, true, true, false>(a, st);
+  else if (diag) fb_launch<SRC, C, NS, false, true, true>(a, st);
+  else if (iso) { if (a.act == nullptr) fb_launch<SRC, C, NS, true, true, false>(a, st); else fb_launch<SRC, C, NS, true, false, false>(a, st); }
+  else { if (a.act == nullptr) fb_launch<SRC, C, NS, false, true, false>(a, st); else fb_launch<SRC, C, NS, false, false, false>(a, st); }
+}
+void fb_dispatch(const FbArgs &a, const FbForm form, const int C, const bool iso, const bool diag, hipStream_t st) {
+  if (form == FB_DEPTH) fb_launch_form<2, 0, 2>(a, iso, diag, st);
+  else if (form == FB_WEIGHTS) { if (a.K <= 128) fb_launch_form<1, 0, 2>(a, iso, diag, st); else fb_launch_form<1, 0, 4>(a, iso, diag, st); }
+  else switch (C) {
+    case 1: fb_launch_form<0, 1, 2>(a, iso, diag, st); break;
+    case 2: fb_launch_form<0, 2, 2>(a, iso, diag, st); break;
+    case 3: fb_launch_form<0, 3, 2>(a, iso, diag, st); break;
+    default: fb_launch_form<0, 4, 2>(a, iso, diag, st); break;
   }
-  if (!records || !rays || !idx || !cnt || !weight || !len || !acc || (act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;
-  if (form != 2 && (!attr || !g)) return VOGE_ERR_BAD_ARG;
-  if (form == 0 && (!rgb || !wsum || !bg)) return VOGE_ERR_BAD_ARG;
-  if ((g_verts == nullptr) != (g_sigmas == nullptr)) return VOGE_ERR_BAD_ARG;
-  const int S = kind == 1 ? (form == 2 ? 8 : 12) : (form == 2 ? 12 : 16);
-  if (kind == 1 && (act || dsd)) return VOGE_ERR_BAD_ARG;      // (the per-axis form keeps neither: re-derived from its 32-byte records)
-  if (acc_bytes < (size_t)P * S * 4) return VOGE_ERR_WORKSPACE;
-  if (P >= (1 << 26) || (form != 2 && Nattr * C >= (1l << 30))) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the gathers
-  float *accf = reinterpret_cast<float *>(acc);
-  if (!acc_is_zero) { const hipError_t e = voge_fill_async(accf, 0, (size_t)P * S * 4, st); if (e != hipSuccess) return (int)e; }
-  const float4 *rec = reinterpret_cast<const float4 *>(records);
-  if (form == 2) {
-    const FbArgs a{rec, rays, nullptr, idx, cnt, weight, act, len, dsd, nullptr, nullptr, nullptr, -1.0f, g, g_stride0, g_stride1, g_hitlen,
-                   occ, P, nrows, W, K, 0, accf};
-    if (kind == 1) { if (K <= 128) fb_launch_diag<1, 0, 2>(a, st); else fb_launch_diag<1, 0, 4>(a, st); }
-    else fb_launch_gw<false>(a, st);
-  } else {
-    const FbArgs a{rec, rays, attr, idx, cnt, weight, act, len, dsd, rgb /* (form 1: NULL | the forward's weight sums) */, wsum, form == 0 ? bg : nullptr,
-                   form == 0 ? thr : -1.0f, g, g_stride0, g_stride1, nullptr, occ, P, nrows, W, K, Nattr, accf};
-    if (kind == 1) {
-      switch (C) {
-        case 1: fb_launch_diag<0, 1, 2>(a, st); break;
-        case 2: fb_launch_diag<0, 2, 2>(a, st); break;
-        case 3: fb_launch_diag<0, 3, 2>(a, st); break;
-        default: fb_launch_diag<0, 4, 2>(a, st); break;
-      }
-    } else {
-      fb_launch_shade<false>(a, C, st);
-    }
-  }
-  const long n_fin = (form != 2 && Nattr > P) ? Nattr : P;
-  if (ori)
-    hipLaunchKernelGGL(fragment_bwd_finish_ori_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, accf, S, P, N, B,
-                       shared_verts ? 1 : 0, shared_sigmas ? 1 : 0, ori_mode, ori_scales, ori_quats, form == 2 ? 0 : C,
-                       form == 2 ? 0l : Nattr, g_verts, g_sigmas, g_quats, form == 2 ? nullptr : g_attr);
-  else
-    hipLaunchKernelGGL(fragment_bwd_finish_view_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, accf, S, P, N, B,
-                       shared_verts ? 1 : 0, shared_sigmas ? 1 : 0, kind, form == 2 ? 0 : C, form == 2 ? 0l : Nattr, g_verts, g_sigmas,
-                       form == 2 ? nullptr : g_attr);
-  return launch_status();
 }
 
+// validate -> empty case -> accumulator -> the fused kernel -> the finishing pass.  The order of the refusals is part of the ABI:
+// sizes (-1), K (-3), the empty case (0), pointers (-1), the workspace (-2), the 32-bit offsets (-1).
+int fb_run(FbCall c, voge_stream_t stream) {
+  FbArgs &k = c.k;
+  hipStream_t st = (hipStream_t)stream;
+  const bool attr = c.form <= FB_MERGE, iso = c.fin == FIN_ISO, pack = c.fin == FIN_GENERAL, diag = c.fin == FIN_VIEW && c.mode == 1;
+  if (c.B < 0 || c.N < 0 || k.nrows < 0 || k.W < 0 || k.K <= 0 || k.Nattr < 0 || (attr && (c.C <= 0 || c.C > 4)) ||
+      (iso && (c.mode < 0 || c.mode > 2)))
+    return VOGE_ERR_BAD_ARG;
+  if (k.K > (c.form == FB_WEIGHTS ? VOGE_MAX_K : 128)) return VOGE_ERR_K_TOO_LARGE;
+  const int P = k.P = c.B * c.N, C = attr ? c.C : 0;
+  if (!attr) k.Nattr = 0;
+  if (c.form != FB_WEIGHTS) k.g_hitlen = nullptr;
+  if (c.form == FB_MERGE || c.form == FB_WEIGHTS) { k.bg = nullptr; k.thr = -1.0f; }
+  if (c.form == FB_WEIGHTS) k.colors = k.rgb = k.wsum = nullptr;
+  float *g_attr = attr ? c.g_attr : nullptr;
+  // Three asymmetries between the entries, kept as they grew:
+  //  (1) the weights' and the depth entries of their own (not voge_frame_bwd_gen's form 2) insist on both outputs -- unless there is
+  //      no Gaussian to write to -- and zero them in the empty case; the others allow both to be NULL;
+  const bool own = !attr && c.fin <= FIN_GENERAL;
+  const long nv = c.shared_v ? c.N : P, ns = c.shared_s ? c.N : P;
+  if (own && nv == 0) return 0;
+  if (own && (!c.g0 || !c.g1)) return VOGE_ERR_BAD_ARG;
+  if (P == 0 || k.nrows * k.W == 0) {      // nothing was traced: zero gradients
+    hipError_t e = hipSuccess;
+    auto zero = [&](float *p, const long n) { if (e == hipSuccess && p && n > 0) e = voge_fill_async(p, 0, sizeof(float) * (size_t)n, st); };
+    //  (2) the attribute forms outside the frame's general entries zero only g_attr here and leave g0 / g1 unwritten;
+    if (own || c.fin >= FIN_VIEW) { zero(c.g0, 3 * nv); zero(c.g1, ns * (iso ? 1 : (diag || c.fin == FIN_ORI) ? 3 : 9)); zero(c.g_quats, 4 * ns); }
+    zero(g_attr, k.Nattr * C);
+    return (int)e;
+  }
+  if (!(pack ? c.mus && c.p1 : k.rec != nullptr) || !k.rays || !k.idx || !k.cnt || !k.weight || !k.len || !c.ws) return VOGE_ERR_BAD_ARG;
+  if (attr && (!k.colors || !k.g)) return VOGE_ERR_BAD_ARG;
+  if (c.form == FB_SHADE && (!k.rgb || !k.wsum || !k.bg)) return VOGE_ERR_BAD_ARG;
+  if (c.form == FB_DEPTH && (!k.rgb || !k.wsum || (!k.g && !k.bg))) return VOGE_ERR_BAD_ARG;
+  if ((k.act == nullptr) != (k.dsd == nullptr) || (diag && k.act)) return VOGE_ERR_BAD_ARG;      // both or neither; per-axis records keep neither
+  if ((c.g0 == nullptr) != (c.g1 == nullptr) || (iso && c.mode == 2 && c.g1 && !c.p1)) return VOGE_ERR_BAD_ARG;
+  const int S = iso ? (attr ? 8 : 4) : (diag ? 8 : 12) + (attr ? 4 : 0);
+  //  (3) the packing forms ask for the 112 bytes per Gaussian of voge_fragment_bwd_workspace_bytes, with and without attributes; the
+  //      others for the accumulator they use.
+  const size_t acc_bytes = (size_t)P * S * 4;
+  if (c.ws_bytes < (pack ? voge_fragment_bwd_workspace_bytes(P) : acc_bytes)) return VOGE_ERR_WORKSPACE;
+  if (P >= (1 << 26) || (attr && k.Nattr * C >= (1l << 30))) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the gathers
+  k.acc = reinterpret_cast<float *>(c.ws);
+  if (pack) {
+    float4 *rec = reinterpret_cast<float4 *>(c.ws);
+    k.rec = rec;
+    k.acc += (size_t)P * 12;
+    hipLaunchKernelGGL(fragment_bwd_pack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c.mus, c.p1, P, rec,
+                       reinterpret_cast<float4 *>(k.acc), S / 4);
+  } else if (c.zero_here) {
+    const hipError_t e = voge_fill_async(k.acc, 0, acc_bytes, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  fb_dispatch(k, c.form, C, iso, diag, st);
+  const long n_fin = (k.Nattr > P) ? k.Nattr : P;
+  const dim3 grid((unsigned)(((pack ? 16 : 1) * n_fin + 255) / 256)), block(256);
+  switch (c.fin) {
+    case FIN_ISO:
+      hipLaunchKernelGGL(fragment_bwd_finish_kernel, grid, block, 0, st, k.acc, S, c.p1, P, c.N, c.B, IsoView{nullptr, c.shared_v ? 1 : 0, c.mode},
+                         C, k.Nattr, c.g0, c.g1, g_attr);
+      break;
+    case FIN_GENERAL:
+      hipLaunchKernelGGL(fragment_bwd_finish_general_kernel, grid, block, 0, st, k.acc, S, P, C, k.Nattr, c.g0, c.g1, g_attr);
+      break;
+    case FIN_VIEW:
+      hipLaunchKernelGGL(fragment_bwd_finish_view_kernel, grid, block, 0, st, k.acc, S, P, c.N, c.B, c.shared_v ? 1 : 0, c.shared_s ? 1 : 0,
+                         c.mode, C, k.Nattr, c.g0, c.g1, g_attr);
+      break;
+    case FIN_ORI:
+      hipLaunchKernelGGL(fragment_bwd_finish_ori_kernel, grid, block, 0, st, k.acc, S, P, c.N, c.B, c.shared_v ? 1 : 0, c.shared_s ? 1 : 0,
+                         c.mode, c.p1, c.quats, C, k.Nattr, c.g0, c.g1, c.g_quats, g_attr);
+      break;
+  }
+  return launch_status();
+}
+}  // namespace
+
+// ---- the record (_iso) forms: the image's gradient; interpolate_attr's (+ get_silhouette's); the weights' own ----
+extern "C" int voge_fragment_shade_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
+                                           const float *rays, const float *colors, const int32_t *idx, const int32_t *cnt,
+                                           const float *weight, const float *act, const float *len, const float *dsd,
+                                           const float *rgb, const float *wsum, const float *bg, float thr,
+                                           const float *g_img, long g_stride_pix, long g_stride_c, float occ, int B, int N,
+                                           long nrows, int W, int K, int C, long Nattr, void *workspace, size_t workspace_bytes, float *g_verts,
+                                           float *g_sigmas, float *g_colors, voge_stream_t stream) {
+  return fb_run({FB_SHADE, FIN_ISO, {fb_rec(records), rays, colors, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g_img, g_stride_pix,
+                                     g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, workspace, workspace_bytes, true, g_verts, g_sigmas, g_colors, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+extern "C" int voge_fragment_merge_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
+                                           const float *rays, const float *attr, const int32_t *idx, const int32_t *cnt,
+                                           const float *weight, const float *act, const float *len, const float *dsd,
+                                           const float *g_rgb, long g_stride_pix, long g_stride_c, const float *g_wsum,
+                                           float occ, int B, int N, long nrows, int W, int K, int C, long Nattr,
+                                           void *workspace, size_t workspace_bytes, float *g_verts, float *g_sigmas,
+                                           float *g_attr, voge_stream_t stream) {
+  return fb_run({FB_MERGE, FIN_ISO, {fb_rec(records), rays, attr, idx, cnt, weight, act, len, dsd, nullptr, g_wsum, nullptr, -1.0f, g_rgb,
+                                     g_stride_pix, g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, workspace, workspace_bytes, true, g_verts, g_sigmas, g_attr, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+extern "C" int voge_fragment_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
+                                     const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
+                                     const float *len, const float *dsd, const float *g_weight, long gw_stride_pix,
+                                     long gw_stride_k, const float *g_hitlen, float occ, int B, int N, long nrows, int W, int K,
+                                     void *workspace, size_t workspace_bytes, float *g_verts, float *g_sigmas,
+                                     voge_stream_t stream) {
+  return fb_run({FB_WEIGHTS, FIN_ISO, {fb_rec(records), rays, nullptr, idx, cnt, weight, act, len, dsd, nullptr, nullptr, nullptr, -1.0f,
+                                       g_weight, gw_stride_pix, gw_stride_k, g_hitlen, occ, 0, nrows, W, K, 0, nullptr},
+                 B, N, 0, workspace, workspace_bytes, true, g_verts, g_sigmas, nullptr, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+// ---- the frame path: the record forms on the accumulator that the frame's forward zeroed (no fill launch, no act / dsd) ----
+extern "C" int voge_frame_shade_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
+                                        const float *rays, const float *colors, const int32_t *idx, const int32_t *cnt,
+                                        const float *weight, const float *len, const float *rgb, const float *wsum,
+                                        const float *bg, float thr, const float *g_img, long g_stride_pix, long g_stride_c,
+                                        float occ, int B, int N, long nrows, int W, int K, int C, long Nattr, void *acc_zeroed,
+                                        size_t acc_bytes, float *g_verts, float *g_sigmas, float *g_colors, voge_stream_t stream) {
+  return fb_run({FB_SHADE, FIN_ISO, {fb_rec(records), rays, colors, idx, cnt, weight, nullptr, len, nullptr, rgb, wsum, bg, thr, g_img,
+                                     g_stride_pix, g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, acc_zeroed, acc_bytes, false, g_verts, g_sigmas, g_colors, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+extern "C" int voge_frame_merge_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
+                                        const float *rays, const float *attr, const int32_t *idx, const int32_t *cnt,
+                                        const float *weight, const float *len, const float *g_rgb, long g_stride_pix,
+                                        long g_stride_c, const float *g_wsum, const float *wsum_fwd, float occ, int B, int N, long nrows,
+                                        int W, int K, int C, long Nattr, void *acc_zeroed, size_t acc_bytes, float *g_verts,
+                                        float *g_sigmas, float *g_attr, voge_stream_t stream) {
+  return fb_run({FB_MERGE, FIN_ISO, {fb_rec(records), rays, attr, idx, cnt, weight, nullptr, len, nullptr, wsum_fwd, g_wsum, nullptr, -1.0f,
+                                     g_rgb, g_stride_pix, g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, acc_zeroed, acc_bytes, false, g_verts, g_sigmas, g_attr, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+// get_depth's backward (extension): the two per-pixel scalars are formed inside the kernel; four sums per Gaussian (g_mu, g_a).
+extern "C" int voge_frame_depth_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
+                                        const int32_t *idx, const int32_t *cnt, const float *weight, const float *len,
+                                        const float *depth, const float *wsum, const float *g_depth, long g_stride_pix,
+                                        const float *g_sil, int normalize, float occ, int B, int N, long nrows, int W, int K,
+                                        void *acc_zeroed, size_t acc_bytes, float *g_verts, float *g_sigmas, voge_stream_t stream) {
+  if (g_stride_pix < 0) return VOGE_ERR_BAD_ARG;
+  return fb_run({FB_DEPTH, FIN_ISO, {fb_rec(records), rays, nullptr, idx, cnt, weight, nullptr, len, nullptr, depth, wsum, g_sil,
+                                     normalize ? 1.0f : -1.0f, g_depth, g_stride_pix, 0, nullptr, occ, 0, nrows, W, K, 0, nullptr},
+                 B, N, 0, acc_zeroed, acc_bytes, false, g_verts, g_sigmas, nullptr, sigmas, shared, shared, sigma_mode}, stream);
+}
+
+// Every backward route of fragments made by voge_frame_trace_fwd_gen -- form 0: shade, 1: merge, 2: the weights' own (C, Nattr and
+// g_attr unused) -- on the packed (mu, A) records of the forward (no pack launch); acc is zeroed here unless acc_is_zero (the
+// frame's composite did it on its way).
 extern "C" int voge_frame_bwd_gen(int form, const float *records, int shared_verts, int shared_sigmas, int kind, const float *rays,
                                   const float *attr, const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
                                   const float *len, const float *dsd, const float *rgb, const float *wsum, const float *bg, float thr,
                                   const float *g, long g_stride0, long g_stride1, const float *g_hitlen, float occ, int B, int N,
                                   long nrows, int W, int K, int C, long Nattr, void *acc, size_t acc_bytes, int acc_is_zero,
                                   float *g_verts, float *g_sigmas, float *g_attr, voge_stream_t stream) {
-  return frame_bwd_gen_impl(form, records, shared_verts, shared_sigmas, kind, rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg,
-                            thr, g, g_stride0, g_stride1, g_hitlen, occ, B, N, nrows, W, K, C, Nattr, acc, acc_bytes, acc_is_zero, g_verts,
-                            g_sigmas, g_attr, stream);
+  if (form < 0 || form > 2 || (kind != 1 && kind != 2)) return VOGE_ERR_BAD_ARG;
+  return fb_run({(FbForm)form, FIN_VIEW, {fb_rec(records), rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g, g_stride0,
+                                          g_stride1, g_hitlen, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, acc, acc_bytes, !acc_is_zero, g_verts, g_sigmas, g_attr, nullptr, shared_verts, shared_sigmas, kind}, stream);
 }
 
 // Every backward route of fragments made by voge_frame_trace_fwd_ori: voge_frame_bwd_gen(kind 2)'s fused kernel as it is, on the
@@ -1091,16 +1074,17 @@ extern "C" int voge_frame_bwd_ori(int form, const float *records, const float *s
                                   long g_stride1, const float *g_hitlen, float occ, int B, int N, long nrows, int W, int K, int C,
                                   long Nattr, void *acc, size_t acc_bytes, int acc_is_zero, float *g_verts, float *g_scales,
                                   float *g_quats, float *g_attr, voge_stream_t stream) {
-  if (sigma_mode != 1 && sigma_mode != 2) return VOGE_ERR_BAD_ARG;
-  if ((g_scales == nullptr) != (g_quats == nullptr)) return VOGE_ERR_BAD_ARG;
-  if (g_scales != nullptr && (long)B * N > 0 &&
+  if (form < 0 || form > 2 || (sigma_mode != 1 && sigma_mode != 2) || (g_scales == nullptr) != (g_quats == nullptr)) return VOGE_ERR_BAD_ARG;
+  if (g_scales != nullptr && (long)B * N > 0 &&      // (the finishing pass reads and writes the quaternions as float4)
       (!scales || !quats || ((reinterpret_cast<uintptr_t>(quats) | reinterpret_cast<uintptr_t>(g_quats)) & 15) != 0))
     return VOGE_ERR_BAD_ARG;
-  return frame_bwd_gen_impl(form, records, shared_verts, shared_sigmas, 2, rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr,
-                            g, g_stride0, g_stride1, g_hitlen, occ, B, N, nrows, W, K, C, Nattr, acc, acc_bytes, acc_is_zero, g_verts,
-                            g_scales, g_attr, stream, scales, quats, sigma_mode, g_quats);
+  return fb_run({(FbForm)form, FIN_ORI, {fb_rec(records), rays, attr, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g, g_stride0,
+                                         g_stride1, g_hitlen, occ, 0, nrows, W, K, Nattr, nullptr},
+                 B, N, C, acc, acc_bytes, !acc_is_zero, g_verts, g_scales, g_attr, scales, shared_verts, shared_sigmas, sigma_mode, nullptr,
+                 quats, g_quats}, stream);
 }
 
+// ---- the general 3x3 forms: the records are packed here from (mus, isigmas) ----
 extern "C" int voge_fragment_shade_bwd(const float *mus, const float *isigmas, const float *rays, const float *colors,
                                        const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
                                        const float *len, const float *dsd, const float *rgb, const float *wsum,
@@ -1108,130 +1092,20 @@ extern "C" int voge_fragment_shade_bwd(const float *mus, const float *isigmas, c
                                        float occ, int P, long nrows, int W, int K, int C, long Nattr, void *workspace,
                                        size_t workspace_bytes, float *g_mus, float *g_isigmas, float *g_colors,
                                        voge_stream_t stream) {
-  if (P < 0 || nrows < 0 || W < 0 || K <= 0 || C <= 0 || C > 4 || Nattr < 0) return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0 || nrows * W == 0) {
-    if (g_colors && Nattr > 0) return (int)voge_fill_async(g_colors, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return 0;
-  }
-  if (!mus || !isigmas || !rays || !colors || !idx || !cnt || !weight || !len || !rgb || !wsum || !bg || !g_img || !workspace)
-    return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;      // both or neither (neither: re-derived from (mu, A))
-  if ((g_mus == nullptr) != (g_isigmas == nullptr)) return VOGE_ERR_BAD_ARG;
-  if (workspace_bytes < voge_fragment_bwd_workspace_bytes(P)) return VOGE_ERR_WORKSPACE;
-  if (Nattr * C >= (1l << 30) || P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the gathers
-  float4 *rec = reinterpret_cast<float4 *>(workspace);
-  float *acc = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + (size_t)P * 48);
-  hipLaunchKernelGGL(fragment_bwd_pack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, mus, isigmas, P, rec,
-                     reinterpret_cast<float4 *>(acc), 4);
-  const FbArgs a{rec, rays, colors, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g_img, g_stride_pix, g_stride_c, nullptr, occ,
-                 P, nrows, W, K, Nattr, acc};
-  fb_launch_shade<false>(a, C, st);
-  const long n_fin = (Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_general_kernel, dim3((unsigned)((n_fin * 16 + 255) / 256)), dim3(256), 0, st, acc, 16, P, C,
-                     Nattr, g_mus, g_isigmas, g_colors);
-  return launch_status();
+  return fb_run({FB_SHADE, FIN_GENERAL, {nullptr, rays, colors, idx, cnt, weight, act, len, dsd, rgb, wsum, bg, thr, g_img, g_stride_pix,
+                                         g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 1, P, C, workspace, workspace_bytes, true, g_mus, g_isigmas, g_colors, isigmas, 0, 0, 0, mus}, stream);
 }
 
-// The merge form (below) for general 3x3 forms: interpolate_attr (+ get_silhouette) on the fragments of voge_trace_lean_fwd.
 extern "C" int voge_fragment_merge_bwd(const float *mus, const float *isigmas, const float *rays, const float *attr,
                                        const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
                                        const float *len, const float *dsd, const float *g_rgb, long g_stride_pix,
                                        long g_stride_c, const float *g_wsum, float occ, int P, long nrows, int W, int K, int C,
                                        long Nattr, void *workspace, size_t workspace_bytes, float *g_mus, float *g_isigmas,
                                        float *g_attr, voge_stream_t stream) {
-  if (P < 0 || nrows < 0 || W < 0 || K <= 0 || C <= 0 || C > 4 || Nattr < 0) return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0 || nrows * W == 0) {
-    if (g_attr && Nattr > 0) return (int)voge_fill_async(g_attr, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return 0;
-  }
-  if (!mus || !isigmas || !rays || !attr || !idx || !cnt || !weight || !len || !g_rgb || !workspace) return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;
-  if ((g_mus == nullptr) != (g_isigmas == nullptr)) return VOGE_ERR_BAD_ARG;
-  if (workspace_bytes < voge_fragment_bwd_workspace_bytes(P)) return VOGE_ERR_WORKSPACE;
-  if (Nattr * C >= (1l << 30) || P >= (1 << 26)) return VOGE_ERR_BAD_ARG;
-  float4 *rec = reinterpret_cast<float4 *>(workspace);
-  float *acc = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + (size_t)P * 48);
-  hipLaunchKernelGGL(fragment_bwd_pack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, mus, isigmas, P, rec,
-                     reinterpret_cast<float4 *>(acc), 4);
-  const FbArgs a{rec, rays, attr, idx, cnt, weight, act, len, dsd, nullptr, g_wsum, nullptr, -1.0f, g_rgb, g_stride_pix, g_stride_c,
-                 nullptr, occ, P, nrows, W, K, Nattr, acc};
-  fb_launch_shade<false>(a, C, st);
-  const long n_fin = (Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_general_kernel, dim3((unsigned)((n_fin * 16 + 255) / 256)), dim3(256), 0, st, acc, 16, P, C,
-                     Nattr, g_mus, g_isigmas, g_attr);
-  return launch_status();
-}
-
-// ---- interpolate_attr (+ get_silhouette) on deferred-composite fragments: merge_final's backward, the weight sum's
-// gradient, the composite and the trace backward in the one pass (the shade kernel with no background stage) ----
-extern "C" int voge_fragment_merge_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode,
-                                           const float *rays, const float *attr, const int32_t *idx, const int32_t *cnt,
-                                           const float *weight, const float *act, const float *len, const float *dsd,
-                                           const float *g_rgb, long g_stride_pix, long g_stride_c, const float *g_wsum,
-                                           float occ, int B, int N, long nrows, int W, int K, int C, long Nattr,
-                                           void *workspace, size_t workspace_bytes, float *g_verts, float *g_sigmas,
-                                           float *g_attr, voge_stream_t stream) {
-  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || C <= 0 || C > 4 || Nattr < 0 || sigma_mode < 0 || sigma_mode > 2)
-    return VOGE_ERR_BAD_ARG;
-  if (K > 128) return VOGE_ERR_K_TOO_LARGE;
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0 || nrows * W == 0) {
-    if (g_attr && Nattr > 0) return (int)voge_fill_async(g_attr, 0, sizeof(float) * (size_t)Nattr * C, st);
-    return 0;
-  }
-  if (!records || !rays || !attr || !idx || !cnt || !weight || !len || !g_rgb || !workspace) return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;
-  if ((g_verts == nullptr) != (g_sigmas == nullptr) || (sigma_mode == 2 && g_sigmas && !sigmas)) return VOGE_ERR_BAD_ARG;
-  if (workspace_bytes < (size_t)P * 32) return VOGE_ERR_WORKSPACE;
-  if (Nattr * C >= (1l << 30) || P >= (1 << 26)) return VOGE_ERR_BAD_ARG;
-  float *acc = reinterpret_cast<float *>(workspace);
-  { const hipError_t e = voge_fill_async(acc, 0, (size_t)P * 32, st); if (e != hipSuccess) return (int)e; }
-  // (bg = NULL selects the merge form inside the kernel; its `wsum` operand carries g_wsum)
-  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, attr, idx, cnt, weight, act, len, dsd, nullptr, g_wsum, nullptr, -1.0f,
-                 g_rgb, g_stride_pix, g_stride_c, nullptr, occ, P, nrows, W, K, Nattr, acc};
-  fb_launch_shade<true>(a, C, st);
-  const long n_fin = (Nattr > P) ? Nattr : P;
-  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((n_fin + 255) / 256)), dim3(256), 0, st, acc, 8, sigmas, P, N, B,
-                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, C, Nattr, g_verts, g_sigmas, g_attr);
-  return launch_status();
-}
-
-// ---- the same pass driven by the gradient of the weights itself (any consumer) ----
-extern "C" int voge_fragment_bwd_iso(const float *records, const float *sigmas, int shared, int sigma_mode, const float *rays,
-                                     const int32_t *idx, const int32_t *cnt, const float *weight, const float *act,
-                                     const float *len, const float *dsd, const float *g_weight, long gw_stride_pix,
-                                     long gw_stride_k, const float *g_hitlen, float occ, int B, int N, long nrows, int W, int K,
-                                     void *workspace, size_t workspace_bytes, float *g_verts, float *g_sigmas,
-                                     voge_stream_t stream) {
-  if (B < 0 || N < 0 || nrows < 0 || W < 0 || K <= 0 || sigma_mode < 0 || sigma_mode > 2) return VOGE_ERR_BAD_ARG;
-  if (K > VOGE_MAX_K) return VOGE_ERR_K_TOO_LARGE;
-  const int P = B * N;
-  hipStream_t st = (hipStream_t)stream;
-  const long n_out = shared ? N : P;
-  if (n_out == 0) return 0;      // no Gaussians: nothing to write
-  if (!g_verts || !g_sigmas) return VOGE_ERR_BAD_ARG;
-  if (P == 0 || nrows * W == 0) {
-    hipError_t e0 = voge_fill_async(g_verts, 0, sizeof(float) * 3 * (size_t)n_out, st);
-    if (e0 == hipSuccess) e0 = voge_fill_async(g_sigmas, 0, sizeof(float) * (size_t)n_out, st);
-    return (int)e0;
-  }
-  if (!records || !rays || !idx || !cnt || !weight || !len || !workspace) return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr) || (sigma_mode == 2 && !sigmas)) return VOGE_ERR_BAD_ARG;
-  if (workspace_bytes < (size_t)P * 16) return VOGE_ERR_WORKSPACE;
-  if (P >= (1 << 26)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the record gathers
-  float *acc = reinterpret_cast<float *>(workspace);
-  { const hipError_t e = voge_fill_async(acc, 0, (size_t)P * 16, st); if (e != hipSuccess) return (int)e; }
-  const FbArgs a{reinterpret_cast<const float4 *>(records), rays, nullptr, idx, cnt, weight, act, len, dsd, nullptr, nullptr, nullptr,
-                 -1.0f, g_weight, gw_stride_pix, gw_stride_k, g_hitlen, occ, P, nrows, W, K, 0, acc};
-  fb_launch_gw<true>(a, st);
-  hipLaunchKernelGGL(fragment_bwd_finish_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, acc, 4, sigmas, P, N, B,
-                     IsoView{nullptr, shared ? 1 : 0, sigma_mode}, 0, 0l, g_verts, g_sigmas, (float *)nullptr);
-  return launch_status();
+  return fb_run({FB_MERGE, FIN_GENERAL, {nullptr, rays, attr, idx, cnt, weight, act, len, dsd, nullptr, g_wsum, nullptr, -1.0f, g_rgb,
+                                         g_stride_pix, g_stride_c, nullptr, occ, 0, nrows, W, K, Nattr, nullptr},
+                 1, P, C, workspace, workspace_bytes, true, g_mus, g_isigmas, g_attr, isigmas, 0, 0, 0, mus}, stream);
 }
 
 extern "C" int voge_fragment_bwd(const float *mus, const float *isigmas, const float *rays, const int32_t *idx,
@@ -1239,28 +1113,8 @@ extern "C" int voge_fragment_bwd(const float *mus, const float *isigmas, const f
                                  const float *dsd, const float *g_weight, long gw_stride_pix, long gw_stride_k,
                                  const float *g_hitlen, float occ, int P, long nrows, int W, int K, void *workspace,
                                  size_t workspace_bytes, float *g_mus, float *g_isigmas, voge_stream_t stream) {
-  if (P < 0 || nrows < 0 || W < 0 || K <= 0) return VOGE_ERR_BAD_ARG;
-  if (K > VOGE_MAX_K) return VOGE_ERR_K_TOO_LARGE;
-  hipStream_t st = (hipStream_t)stream;
-  if (P == 0) return 0;      // no Gaussians: nothing to write
-  if (!g_mus || !g_isigmas) return VOGE_ERR_BAD_ARG;
-  if (nrows * W == 0) {
-    hipError_t e0 = voge_fill_async(g_mus, 0, sizeof(float) * 3 * (size_t)P, st);
-    if (e0 == hipSuccess) e0 = voge_fill_async(g_isigmas, 0, sizeof(float) * 9 * (size_t)P, st);
-    return (int)e0;
-  }
-  if (!mus || !isigmas || !rays || !idx || !cnt || !weight || !len || !workspace) return VOGE_ERR_BAD_ARG;
-  if ((act == nullptr) != (dsd == nullptr)) return VOGE_ERR_BAD_ARG;      // both or neither (neither: re-derived from (mu, A))
-  if (workspace_bytes < voge_fragment_bwd_workspace_bytes(P)) return VOGE_ERR_WORKSPACE;
-  if (P >= (1 << 26)) return VOGE_ERR_BAD_ARG;
-  float4 *rec = reinterpret_cast<float4 *>(workspace);
-  float *acc = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + (size_t)P * 48);
-  hipLaunchKernelGGL(fragment_bwd_pack_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, mus, isigmas, P, rec,
-                     reinterpret_cast<float4 *>(acc), 3);
-  const FbArgs a{rec, rays, nullptr, idx, cnt, weight, act, len, dsd, nullptr, nullptr, nullptr, -1.0f, g_weight, gw_stride_pix,
-                 gw_stride_k, g_hitlen, occ, P, nrows, W, K, 0, acc};
-  fb_launch_gw<false>(a, st);
-  hipLaunchKernelGGL(fragment_bwd_finish_general_kernel, dim3((unsigned)(((long)P * 16 + 255) / 256)), dim3(256), 0, st, acc, 12, P, 0,
-                     0l, g_mus, g_isigmas, (float *)nullptr);
-  return launch_status();
+  return fb_run({FB_WEIGHTS, FIN_GENERAL, {nullptr, rays, nullptr, idx, cnt, weight, act, len, dsd, nullptr, nullptr, nullptr, -1.0f,
+                                           g_weight, gw_stride_pix, gw_stride_k, g_hitlen, occ, 0, nrows, W, K, 0, nullptr},
+                 1, P, 0, workspace, workspace_bytes, true, g_mus, g_isigmas, nullptr, isigmas, 0, 0, 0, mus}, stream);
 }
+
