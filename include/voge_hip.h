@@ -1016,6 +1016,56 @@ int voge_mesh_sample_bwd(const float *verts, long V, const int32_t *faces, long 
                          const int32_t *face_idx, const float *bary, long S, const float *g_points, const float *g_normals,
                          float *g_verts, void *workspace, size_t workspace_bytes, voge_stream_t stream);
 
+/*
+ * Depth maps fused into a truncated signed distance volume (EXTENSION: the reference has no mesh extraction; this and
+ * voge_mtet_* are the last step of the 2D Gaussian splatting pipeline).  Replaces voge_amd/Aggregation.py tsdf_integrate, the
+ * definition, operation by operation in fp32.  tsdf, weight [nz,ny,nx] fp32, updated IN PLACE; grid point (ix,iy,iz) sits at
+ * lo + (ix hx, iy hy, iz hz).  depth [B,H,W]: the distance along the UNIT pixel ray from the camera centre (voge_depth_fwd's), not
+ * view z; R [B,3,3], T [B,3], focal [B,2], pp [B,2]: the cameras of voge_rays_fwd (X_view = X_world @ R + T, pixel (i,j) looks along
+ * ((px - j - 0.5)/fx, (py - i - 0.5)/fy, 1)); centre [B,3] = -T @ R^-1.  For a grid point x and the views b = 0 .. B-1 in that order:
+ *   p = x @ R_b + T_b, skipped unless p_z > 0; j = floor(px - fx p_x / p_z), i = floor(py - fy p_y / p_z), skipped unless inside the
+ *   image; d = depth[b,i,j], skipped unless finite and > 0; sdf = d - |x - centre_b|, skipped if sdf < -trunc;
+ *   tsdf <- (tsdf w + min(1, sdf / trunc)) / (w + 1); w <- w + 1, or min(w + 1, max_weight) when max_weight > 0.
+ * One launch, one grid point per thread with the loop over the views inside: 16 bytes a grid point per call, no atomics, the
+ * same bits on every run, and one call with B views gives the bits of B calls with one view each.  Nothing is read back.
+ * A dimension below 2, B < 0, H or W < 1, trunc or a voxel size that is not positive and finite, a lo that is not finite, a NaN
+ * max_weight, a null pointer: VOGE_ERR_BAD_ARG; nx ny nz 7 >= 2^31 (the extraction's 32-bit indices): VOGE_ERR_K_TOO_LARGE -- all
+ * before any HIP call.  B == 0: success, nothing is launched.
+ */
+int voge_tsdf_integrate(float *tsdf, float *weight, int nx, int ny, int nz, float lox, float loy, float loz, float hx, float hy,
+                        float hz, const float *depth, int B, int H, int W, const float *R, const float *T, const float *centre,
+                        const float *focal, const float *pp, float trunc, float max_weight, voge_stream_t stream);
+
+/*
+ * The level set of a scalar field on a regular grid as a triangle mesh: marching tetrahedra on Kuhn's six-tetrahedron split of
+ * every cell (EXTENSION).  Replaces voge_amd/Aggregation.py marching_tets, the definition (its docstring has the tetrahedra,
+ * the 16 cases and the winding: normals from inside to outside).  values [nz,ny,nx] fp32, weight the same or null; a grid point is
+ * observed when its value is finite (and its weight > 0) and inside when value < level, strictly; linear index q = (iz ny + iy) nx + ix.
+ * Three entries and one read-back between the second and the third:
+ *   voge_mtet_count   a grid point per thread, 256 a workgroup: edge_mask [n] (bit d - 1: the edge of direction d = 1 .. 7 -- bit 0 = +x,
+ *                     bit 1 = +y, bit 2 = +z -- from the point carries a vertex), face_count [n] (0 .. 12, the triangles of the cell the
+ *                     point is the low corner of), vloc / floc [n] (the exclusive prefixes of both counts inside the workgroup) and
+ *                     block_v / block_f [ceil(n / 256)] (the workgroups' totals): 6 bytes a grid point;
+ *   voge_mtet_scan    ONE workgroup: block_v / block_f become their exclusive scans in place, 1024 entries a round, and
+ *                     totals[0] = V, totals[1] = F.  The caller reads totals back to allocate verts [V,3] and faces [F,3]: the
+ *                     one synchronisation of an extraction, which is a one-off step and not a step of an iteration;
+ *   voge_mtet_emit    a grid point per thread: the vertex of edge (q, d) has the id block_v[q / 256] + vloc[q] +
+ *                     popcount(edge_mask[q] & ((1 << (d - 1)) - 1)) and sits at p_a + t (p_b - p_a), t = (level - v_a) / (v_b - v_a),
+ *                     p = lo + i h, a = q: vertices ascend by (q, d), faces by (cell, tetrahedron, triangle); int32 vertex ids.
+ *                     values, weight, level and the grid must be those of the count.  Writes are guarded by V and F.
+ * Integer sums only, no atomics: the same bits on every run.  A dimension below 2, a null pointer (weight may be null; verts
+ * with V == 0 and faces with F == 0 too), a NaN level, a negative V or F, nblocks < 1, a voxel size that is not positive and finite:
+ * VOGE_ERR_BAD_ARG; nx ny nz 7 >= 2^31, V or F above 2^31 - 1, nblocks above what such a grid has: VOGE_ERR_K_TOO_LARGE -- all before
+ * any HIP call.  V == 0 and F == 0: emit launches nothing.
+ */
+int voge_mtet_count(const float *values, const float *weight, int nx, int ny, int nz, float level, uint8_t *edge_mask,
+                    uint8_t *face_count, uint16_t *vloc, uint16_t *floc, uint32_t *block_v, uint32_t *block_f, voge_stream_t stream);
+int voge_mtet_scan(uint32_t *block_v, uint32_t *block_f, long nblocks, long long *totals, voge_stream_t stream);
+int voge_mtet_emit(const float *values, const float *weight, int nx, int ny, int nz, float level, float lox, float loy, float loz,
+                   float hx, float hy, float hz, const uint8_t *edge_mask, const uint8_t *face_count, const uint16_t *vloc,
+                   const uint16_t *floc, const uint32_t *block_v, const uint32_t *block_f, long V, long F, float *verts,
+                   int32_t *faces, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

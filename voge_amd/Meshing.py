@@ -1,0 +1,154 @@
+"""Mesh extraction (an extension: the reference has none; the step the 2D Gaussian splatting pipeline ends with).
+
+    vol = TSDFVolume(lo, hi=None, voxel_size=None, resolution=None, device=...)
+    vol.integrate(depth, cameras, trunc, max_weight=None)      # in place, returns vol
+    verts, faces = extract_mesh(vol, level=0.0)
+    verts, faces = extract_mesh(values, weight=None, level=0.0, lo=(0, 0, 0), voxel_size=1.0)
+
+TSDFVolume fuses depth maps -- what Renderer.get_depth returns: the distance along the unit pixel ray, under the cameras of
+cameras.pixel_rays -- into a truncated signed distance volume; extract_mesh turns the volume, or any scalar field such as an
+analytic SDF, into verts [V,3] fp32 and faces [F,3] int32 by marching tetrahedra, ready for Losses.MeshTopology,
+mesh_regularisers, sample_points_from_meshes, chamfer_distance and Converter.IO.save_off.  Aggregation.tsdf_integrate and
+Aggregation.marching_tets ARE the definitions; fp32 tensors on a HIP device take the kernels of csrc/meshing.hip, everything
+else (host tensors, other dtypes) the definitions.
+
+NEITHER STEP IS DIFFERENTIABLE, by design: the fusion chooses a nearest pixel and the extraction a topology.  Gradients reach
+a surface here through the renderer (get_depth, get_normals) or through a mesh's vertices (Losses), not through this module.
+
+extract_mesh on the device reads TWO integers back on the host, the vertex and the face count, to size its outputs: one
+synchronisation per call.  Extraction is a one-off step after a fit, not a step of an iteration, and cannot be captured into a
+graph; integrate reads nothing back.
+"""
+import torch
+
+from . import Aggregation, cameras as _cameras, ops
+
+__all__ = ["TSDFVolume", "extract_mesh"]
+
+
+def _triple(v, name, integer=False):
+    t = torch.as_tensor(v, dtype=torch.float64, device="cpu").reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(3)
+    if t.numel() != 3:
+        raise ValueError(f"{name}: a scalar or three values (x, y, z) expected, got {tuple(t.shape)}")
+    return [int(x) for x in t.tolist()] if integer else [float(x) for x in t.tolist()]
+
+
+def _check_dims(nx, ny, nz, what):
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"{what}: every grid dimension must be >= 2, got (nx, ny, nz) = ({nx}, {ny}, {nz})")
+    if nx * ny * nz * 7 >= 2 ** 31:
+        raise ValueError(f"{what}: nx ny nz 7 = {nx * ny * nz * 7} does not fit the 32-bit indices of the extraction")
+
+
+class TSDFVolume:
+    """A truncated signed distance volume over a box.  Exactly two of hi / voxel_size / resolution:
+
+      hi + resolution       h = (hi - lo) / (resolution - 1): the last grid point sits at hi;
+      hi + voxel_size       resolution = floor((hi - lo) / h + 1e-6) + 1: the grid ends at or before hi;
+      voxel_size + resolution   as given.
+
+    voxel_size and resolution are scalars or (x, y, z).  Grid point (ix,iy,iz) sits at lo + (ix hx, iy hy, iz hz);
+    tsdf and weight are [nz,ny,nx] fp32 (index order [iz,iy,ix]) and start at 0.  lo and voxel_size are kept as the fp32
+    numbers the kernels see."""
+
+    def __init__(self, lo, hi=None, voxel_size=None, resolution=None, device="cpu"):
+        if sum(a is not None for a in (hi, voxel_size, resolution)) != 2:
+            raise ValueError("TSDFVolume: exactly two of hi / voxel_size / resolution")
+        lo = _triple(lo, "lo")
+        if voxel_size is not None:
+            h = _triple(voxel_size, "voxel_size")
+            if not all(x > 0 and x < float("inf") for x in h):
+                raise ValueError(f"TSDFVolume: voxel_size must be positive and finite, got {h}")
+        if resolution is not None:
+            res = _triple(resolution, "resolution", integer=True)
+        if hi is not None:
+            hi = _triple(hi, "hi")
+            if not all(b > a for a, b in zip(lo, hi)):
+                raise ValueError(f"TSDFVolume: hi {hi} must lie above lo {lo}")
+            if resolution is not None:
+                if min(res) < 2:
+                    raise ValueError(f"TSDFVolume: resolution must be >= 2, got {res}")
+                h = [(b - a) / (r - 1) for a, b, r in zip(lo, hi, res)]
+            else:
+                res = [int((b - a) / s + 1e-6) + 1 for a, b, s in zip(lo, hi, h)]
+        _check_dims(res[0], res[1], res[2], "TSDFVolume")
+        f32 = lambda xs: tuple(float(x) for x in torch.tensor(xs, dtype=torch.float32).tolist())
+        self.lo, self.voxel_size, self.resolution = f32(lo), f32(h), tuple(res)
+        self.device = torch.device(device)
+        nx, ny, nz = self.resolution
+        self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+
+    @property
+    def hi(self):
+        return tuple(a + (r - 1) * s for a, s, r in zip(self.lo, self.voxel_size, self.resolution))
+
+    def to(self, device):
+        self.device = torch.device(device)
+        self.tsdf, self.weight = self.tsdf.to(self.device), self.weight.to(self.device)
+        return self
+
+    def integrate(self, depth, cameras, trunc, max_weight=None):
+        """Fuse depth [B,H,W] (get_depth's: the distance along the unit pixel ray; not finite or <= 0: no surface) seen by
+        `cameras` (R, T, focal_length, principal_point, as cameras.pixel_rays reads them; B views or one for all) into the
+        volume, in place, the views in their order: Aggregation.tsdf_integrate's rule.  rows= bands and distributed.Stripes
+        are not taken.  One launch on a HIP device, nothing read back; not differentiable.  Returns the volume."""
+        if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+            raise ValueError(f"integrate: depth [B,H,W] expected, got {tuple(getattr(depth, 'shape', ()))}")
+        if not float(trunc) > 0 or float(trunc) == float("inf"):
+            raise ValueError(f"integrate: trunc must be positive and finite, got {trunc}")
+        if max_weight is not None and not float(max_weight) >= 1:
+            raise ValueError(f"integrate: max_weight must be >= 1, got {max_weight}")
+        B = depth.shape[0]
+        dev = self.device
+        R = torch.as_tensor(cameras.R, device=dev).detach().to(torch.float32).reshape(-1, 3, 3)
+        T = torch.as_tensor(cameras.T, device=dev).detach().to(torch.float32).reshape(-1, 3)
+        Bc = max(R.shape[0], T.shape[0])
+        if Bc not in (1, B) or R.shape[0] not in (1, Bc) or T.shape[0] not in (1, Bc):
+            raise ValueError(f"integrate: {B} depth maps but {R.shape[0]} rotations and {T.shape[0]} translations")
+        if B == 0:
+            return self
+        try:
+            focal = _cameras._as_b2(torch.as_tensor(cameras.focal_length).detach(), B, dev)
+            pp = _cameras._as_b2(torch.as_tensor(cameras.principal_point).detach(), B, dev)
+        except RuntimeError as e:
+            raise ValueError(f"integrate: {B} depth maps do not match the cameras' focal_length / principal_point") from e
+        R, T = R.expand(B, 3, 3), T.expand(B, 3)
+        depth = depth.detach().to(dev)
+        # the centres in fp64, rounded once: what |x - c| is measured from
+        centre = Aggregation.camera_centres(R.double(), T.double()).to(torch.float32)
+        if dev.type == "cuda":
+            ops.tsdf_integrate(self.tsdf, self.weight, depth, R, T, centre, focal, pp, self.lo, self.voxel_size, float(trunc), max_weight)
+        else:
+            t, w = Aggregation.tsdf_integrate(self.tsdf, self.weight, depth, R, T, focal, pp, self.lo, self.voxel_size, float(trunc),
+                                              max_weight, centre=centre)
+            self.tsdf.copy_(t)
+            self.weight.copy_(w)
+        return self
+
+
+def extract_mesh(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=1.0):
+    """(verts [V,3] fp32, faces [F,3] int32) of the level set of a TSDFVolume (its own weight, lo and voxel_size; the grid
+    points no view has seen are unobserved) or of any scalar field values [nz,ny,nx] -- an analytic SDF for example -- with
+    grid point (ix,iy,iz) at lo + (ix hx, iy hy, iz hz): Aggregation.marching_tets' rule, inside <=> value < level, normals from
+    inside to outside.  An empty result is a pair of [0,3] tensors.  Raises ValueError when a dimension is < 2 or
+    nx ny nz 7 >= 2^31.  On a HIP device: three launches, the two totals read back on the host (ONE synchronisation, see the
+    module's header), one launch that writes the mesh.  Not differentiable."""
+    if isinstance(values, TSDFVolume):
+        vol = values
+        values, weight, lo, voxel_size = vol.tsdf, vol.weight, vol.lo, vol.voxel_size
+    if not isinstance(values, torch.Tensor) or values.dim() != 3:
+        raise ValueError(f"extract_mesh: a TSDFVolume or values [nz,ny,nx] expected, got {tuple(getattr(values, 'shape', ()))}")
+    nz, ny, nx = values.shape
+    _check_dims(nx, ny, nz, "extract_mesh")
+    if weight is not None and (not isinstance(weight, torch.Tensor) or weight.shape != values.shape):
+        raise ValueError(f"extract_mesh: weight must match values {tuple(values.shape)}")
+    lo, h = _triple(lo, "lo"), _triple(voxel_size, "voxel_size")
+    values = values.detach()
+    w = None if weight is None else weight.detach().to(values.device)
+    if values.is_cuda and values.dtype == torch.float32:
+        return ops.marching_tets(values, w, float(level), lo, h)
+    verts, faces = Aggregation.marching_tets(values, w, float(level), lo, h)
+    return verts.to(torch.float32), faces.to(torch.int32)

@@ -2197,6 +2197,91 @@ def mesh_sample(verts, sampler, u, return_normals=False, return_areas=False):
     return out if return_areas else out[:4]
 
 
+MTET_BLOCK = 256      # kMtBlock of meshing.hip: the grid points of one scan block
+MTET_TOP = 1024       # kMtTop: the block totals one round of the top-level scan takes (the tests build grids around both)
+
+
+def _grid_volume(t, name):
+    """An fp32 [nz,ny,nx] tensor on a HIP device that a kernel may write in place"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+        raise _lib.VogeHipError(f"{name}: a contiguous fp32 [nz,ny,nx] tensor on a HIP device expected (no CPU fallback)")
+    return t
+
+
+def tsdf_integrate(tsdf, weight, depth, R, T, centre, focal, pp, lo, voxel_size, trunc, max_weight=None):
+    """Fuse depth [B,H,W] into tsdf / weight [nz,ny,nx] IN PLACE (extension; voge_tsdf_integrate): the values of
+    Aggregation.tsdf_integrate in fp32.  R [B,3,3], T [B,3], centre [B,3], focal [B,2], pp [B,2] on the volume's device; lo and
+    voxel_size three numbers each.  One launch on the current stream, nothing read back; not differentiable."""
+    tsdf, weight = _grid_volume(tsdf, "tsdf"), _grid_volume(weight, "weight")
+    if weight.shape != tsdf.shape or weight.device != tsdf.device:
+        raise ValueError(f"tsdf_integrate: weight {tuple(weight.shape)} on {weight.device} does not match tsdf {tuple(tsdf.shape)}")
+    dev = tsdf.device
+    depth = _dev(depth, torch.float32, "depth")
+    if depth.dim() != 3:
+        raise ValueError(f"tsdf_integrate: depth [B,H,W] expected, got {tuple(depth.shape)}")
+    B, H, W = depth.shape
+    cam = []
+    for t_, shape, name in ((R, (B, 3, 3), "R"), (T, (B, 3), "T"), (centre, (B, 3), "centre"), (focal, (B, 2), "focal"), (pp, (B, 2), "pp")):
+        t_ = _dev(t_.detach(), torch.float32, name)
+        if tuple(t_.shape) != shape:
+            raise ValueError(f"tsdf_integrate: {name} {list(shape)} expected for {B} depth maps, got {tuple(t_.shape)}")
+        if t_.device != dev:
+            raise _lib.VogeHipError(f"tsdf_integrate: {name} on {t_.device}, the volume on {dev}")
+        cam.append(t_)
+    if depth.device != dev:
+        raise _lib.VogeHipError(f"tsdf_integrate: depth on {depth.device}, the volume on {dev}")
+    nz, ny, nx = tsdf.shape
+    lib = _lib.load()
+    with _on(dev):
+        rc = lib.voge_tsdf_integrate(_p(tsdf), _p(weight), nx, ny, nz, *[float(x) for x in lo], *[float(x) for x in voxel_size], _p(depth), B, H, W,
+                                     *[_p(t_) for t_ in cam], float(trunc), 0.0 if max_weight is None else float(max_weight), _stream())
+    _lib.check(rc, "voge_tsdf_integrate")
+    return tsdf, weight
+
+
+def marching_tets(values, weight, level, lo, voxel_size, return_tables=False):
+    """(verts [V,3] fp32, faces [F,3] int32) of the level set of values [nz,ny,nx] fp32 on a HIP device (extension; voge_mtet_count /
+    _scan / _emit): the values of Aggregation.marching_tets.  Count and scan on the current stream, then the two totals are read
+    back on the host -- ONE synchronisation, what sizes the outputs -- and one launch writes the mesh.  Not differentiable, not
+    capturable.  return_tables=True appends (edge_mask, face_count) for the tests."""
+    v = _dev(values.detach(), torch.float32, "values")
+    if v.dim() != 3:
+        raise ValueError(f"marching_tets: values [nz,ny,nx] expected, got {tuple(v.shape)}")
+    w = None
+    if weight is not None:
+        w = _dev(weight.detach(), torch.float32, "weight")
+        if w.shape != v.shape or w.device != v.device:
+            raise ValueError(f"marching_tets: weight {tuple(w.shape)} on {w.device} does not match values {tuple(v.shape)} on {v.device}")
+    nz, ny, nx = v.shape
+    n = nx * ny * nz
+    if min(nx, ny, nz) < 2 or n * 7 >= 2 ** 31:
+        raise ValueError(f"marching_tets: every dimension >= 2 and nx ny nz 7 < 2^31 expected, got (nx, ny, nz) = ({nx}, {ny}, {nz})")
+    dev = v.device
+    nb = (n + MTET_BLOCK - 1) // MTET_BLOCK
+    edge_mask = torch.empty((n,), dtype=torch.uint8, device=dev)
+    face_count = torch.empty((n,), dtype=torch.uint8, device=dev)
+    loc = torch.empty((2, n), dtype=torch.int16, device=dev)      # (16-bit prefixes: the kernels read them as unsigned)
+    blocks = torch.empty((2, nb), dtype=torch.int32, device=dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    grid = [float(x) for x in lo] + [float(x) for x in voxel_size]
+    lib = _lib.load()
+    with _on(dev):
+        st = _stream()
+        rc = lib.voge_mtet_count(_p(v), _p(w), nx, ny, nz, float(level), _p(edge_mask), _p(face_count), _p(loc[0]), _p(loc[1]), _p(blocks[0]),
+                                 _p(blocks[1]), st)
+        _lib.check(rc, "voge_mtet_count")
+        _lib.check(lib.voge_mtet_scan(_p(blocks[0]), _p(blocks[1]), nb, _p(totals), st), "voge_mtet_scan")
+        V, F = (int(x) for x in totals.tolist())      # the synchronisation
+        if V >= 2 ** 31 or F >= 2 ** 31:
+            raise ValueError(f"marching_tets: {V} vertices and {F} faces do not fit 32-bit indices")
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        rc = lib.voge_mtet_emit(_p(v), _p(w), nx, ny, nz, float(level), *grid, _p(edge_mask), _p(face_count), _p(loc[0]), _p(loc[1]),
+                                _p(blocks[0]), _p(blocks[1]), V, F, _p(verts) if V else None, _p(faces) if F else None, st)
+        _lib.check(rc, "voge_mtet_emit")
+    return (verts, faces, edge_mask, face_count) if return_tables else (verts, faces)
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
