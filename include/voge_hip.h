@@ -1017,6 +1017,58 @@ int voge_mesh_sample_bwd(const float *verts, long V, const int32_t *faces, long 
                          float *g_verts, void *workspace, size_t workspace_bytes, voge_stream_t stream);
 
 /*
+ * The nearest triangle of a mesh for every point (EXTENSION: the search inside PyTorch3D's point_mesh_face_distance; what an
+ * extracted mesh is scored with against ground-truth points).  Replaces the rows of the P x F matrix of voge_amd/Aggregation.py
+ * point_triangle_closest.  points [P,3], verts [V,3] fp32, faces [F,3] int32, one mesh.  d2(p, T), every operation one IEEE fp32
+ * operation: e0 = b - a, e1 = c - a, v = p - a first; the interior candidate (n = e0 x e1, w2 = ((e0 x v).n) / nn, w1 = ((v x e1).n) / nn,
+ * w0 = (1 - w1) - w2, only if nn > 0 and all three >= 0) and the segments ab, bc, ca (t = clamp((p - s).e / e.e, 0, 1), t = 0 when
+ * e.e = 0); the smallest |p - q|^2 wins, a tie keeps the earlier candidate.  A triangle without area is its three segments, an edge
+ * without length a point; no area threshold.  The reciprocals are taken once per triangle: no division per pair.
+ * face_idx [P] / d2 [P]: the lexicographically smallest (d2, face) -- an exact tie keeps the lower index; bary [P,3]: the weights of
+ * the closest point on (a, b, c), from one more evaluation of the winner's pair.  One launch: a point per lane, 64 a workgroup, the
+ * triangles' records (16 floats, built by the workgroup while staging) tiled through LDS 256 at a time, the four waves take a quarter
+ * of a tile each and meet in LDS.  A face that names a vertex outside [0, V) never wins.  Nothing is read back: capturable.
+ * P == 0: success, nothing is launched.  V or F below 1, a size above 2^28 - 1, a null pointer: VOGE_ERR_BAD_ARG; P F above the pair
+ * cap 2^38 (an exact search is a brute force; larger pairs go through sampled points and voge_chamfer_fwd): VOGE_ERR_K_TOO_LARGE --
+ * all before any HIP call.
+ */
+int voge_closest_faces(const float *points, long P, const float *verts, long V, const int32_t *faces, long F, int32_t *face_idx,
+                       float *d2, float *bary, voge_stream_t stream);
+
+/*
+ * Point-to-mesh distance (EXTENSION: PyTorch3D's point_mesh_face_distance).  Replaces voge_amd/Aggregation.py point_mesh_term
+ * (the P x F matrix in chunks of points):
+ *   loss[0] = (1 / P) sum_i min_f d2(p_i, T_f) + (1 / F) sum_f min_i d2(p_i, T_f),      d2 of voge_closest_faces
+ * flags bit 0: the sums without their divisors ("sum"); bit 1: the first sum alone (single_directional; point_idx and bary_f are
+ * not touched).  face_idx [P], bary_p [P,3]: the values of voge_closest_faces; point_idx [F], bary_f [F,3]: the nearest point of
+ * every face (a triangle per lane with its record in registers, the points tiled through LDS 1024 at a time; a tie keeps the lower
+ * index) and the weights of the closest point on it; meta [4] int32: meta[0] = s, the scale exponent of the backward's fixed-point
+ * sums, chosen on the device from the largest d2 and ceil(log2(P + F)).  Every d2 is fp32; the sums are fp64 -- one partial per
+ * 1024 items, added by ONE workgroup in an order that depends on the shapes alone -- and the loss is rounded to fp32 once.  Four
+ * launches (two with bit 1 less one), the same bits on every run, no host read-back: capturable.
+ * Backward: g_verts [V,3], g_points [P,3], EVERY element written, from g_loss (ONE float on the device); with r = p - q of a chosen
+ * pair and w the weights of q (q minimises over the triangle: the weights' own derivative drops out),
+ *   g_points[i] = g (2 / P) r_i + g (2 / F) sum_{f: nn(f) = i} r_f
+ *   g_verts[v]  = - g (2 / P) sum_{i, k: faces[f_i][k] = v} w_ik r_i - g (2 / F) sum_{f, k: faces[f][k] = v} w_fk r_f;
+ * three launches: a zero fill of the [V + P][3] int64 accumulators in the workspace, one scatter over the P + F items that adds
+ * every term, scaled by 2^s and rounded to an integer, with 64-bit INTEGER atomics (exact: the sum does not depend on the order; a
+ * list of m terms is off by at most m 2^-s / 2 per component; linear cost however the items crowd), and a finish that adds a point's
+ * own term in fp64 and rounds once.  An index outside its range is skipped.  No float atomics.
+ * workspace: voge_point_mesh_workspace_bytes(V, F, P) bytes on a 16-byte boundary serves both calls (0: a size below 1 or above
+ * 2^28 - 1).  Such a size, an unknown flag, a null pointer (point_idx and bary_f may be null with flags bit 1), a workspace that is
+ * null or off the 16-byte boundary: VOGE_ERR_BAD_ARG; P F above the pair cap 2^38: VOGE_ERR_K_TOO_LARGE; a workspace too small:
+ * VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+size_t voge_point_mesh_workspace_bytes(long V, long F, long P);
+int voge_point_mesh_fwd(const float *verts, long V, const int32_t *faces, long F, const float *points, long P, int flags,
+                        float *loss, int32_t *face_idx, float *bary_p, int32_t *point_idx, float *bary_f, int32_t *meta,
+                        void *workspace, size_t workspace_bytes, voge_stream_t stream);
+int voge_point_mesh_bwd(const float *verts, long V, const int32_t *faces, long F, const float *points, long P,
+                        const int32_t *face_idx, const float *bary_p, const int32_t *point_idx, const float *bary_f,
+                        const int32_t *meta, const float *g_loss, int flags, float *g_verts, float *g_points, void *workspace,
+                        size_t workspace_bytes, voge_stream_t stream);
+
+/*
  * Depth maps fused into a truncated signed distance volume (EXTENSION: the reference has no mesh extraction; this and
  * voge_mtet_* are the last step of the 2D Gaussian splatting pipeline).  Replaces voge_amd/Aggregation.py tsdf_integrate, the
  * definition, operation by operation in fp32.  tsdf, weight [nz,ny,nx] fp32, updated IN PLACE; grid point (ix,iy,iz) sits at

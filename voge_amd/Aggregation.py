@@ -513,6 +513,125 @@ def mesh_surface_points(verts, faces, u, return_normals=False, face_idx=None):
     return points, normals, torch.where(valid, idx, torch.full_like(idx, -1)), bary
 
 
+def _dot3(x, y):
+    """(x0 y0 + x1 y1) + x2 y2 over the last axis, every operation a separate torch op"""
+    return (x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1]) + x[..., 2] * y[..., 2]
+
+
+def _recip_or_zero(x):
+    """1 / x where x > 0 and the reciprocal is finite, else 0 -- the zero cases of point_triangle_closest, folded into the factor"""
+    pos = x > 0
+    r = 1 / torch.where(pos, x, torch.ones_like(x))
+    return torch.where(pos & torch.isfinite(r), r, torch.zeros_like(r))
+
+
+def point_triangle_closest(points, a, b, c):
+    """The closest point of the triangle (a, b, c) to every point (PyTorch3D's point-to-face distance without its
+    min_triangle_area; an extension here): points, a, b, c [..., 3], broadcast against each other -> (d2 [...], bary [..., 3]).
+
+    Differences first: e0 = b - a, e1 = c - a, v = p - a -- nothing below sees a position, so a mesh at (1000, 1000, 1000) keeps
+    the bounds of one at the origin.  Four candidates, each a point of the triangle, in this order:
+
+      interior  n = e0 x e1, nn = n.n; w2 = ((e0 x v).n) (1 / nn), w1 = ((v x e1).n) (1 / nn), w0 = (1 - w1) - w2; it EXISTS only if
+                nn > 0 and w0, w1, w2 >= 0; r = v - (w1 e0 + w2 e1), weights (w0, w1, w2);
+      ab        t = clamp((v.e0) (1 / e0.e0), 0, 1), r = v - t e0, weights (1 - t, t, 0);
+      bc        vb = v - e0, eb = e1 - e0, t = clamp((vb.eb) (1 / eb.eb), 0, 1), r = vb - t eb, weights (0, 1 - t, t);
+      ca        walked from a: t = clamp((v.e1) (1 / e1.e1), 0, 1), r = v - t e1, weights (1 - t, 0, t);
+
+    d2 = (rx rx + ry ry) + rz rz of the candidate, every operation one operation of the tensors' dtype; a reciprocal is taken
+    once and multiplied with (what the kernels do: no division per pair), and is 0 where its argument is 0 or where it would
+    not be finite -- t = 0 on an edge of length 0, no interior candidate on a triangle without area.  The result is the smallest
+    d2; an exact tie keeps the EARLIER candidate.  The minimum over all four, not a walk through Voronoi regions: every candidate
+    is a point of the triangle, so a candidate whose weights are poor (a sliver's interior) can only lose.  Two consequences:
+    a zero-area triangle is the union of its three segments, and a zero-length edge is a point (a = b = c: the point a, weights
+    (1, 0, 0)).  Nothing is NaN for finite inputs whose squares do not overflow, and there is NO area threshold: PyTorch3D's
+    min_triangle_area depends on the scale of the mesh and is the one deliberate deviation.
+
+    The weights are constants of the graph, as the argmin of a min is: q minimises over the triangle, so their derivative drops
+    out (the envelope theorem) and d d2 / dp = 2 (p - q), d d2 / d(a, b, c) = -2 w_r (p - q).  bary carries no gradient."""
+    pd, ad, bd, cd = points.detach(), a.detach(), b.detach(), c.detach()
+    e0, e1, v = bd - ad, cd - ad, pd - ad
+    n = _face_cross(e0, e1)
+    inn = _recip_or_zero(_dot3(n, n))
+    w2 = _dot3(_face_cross(e0, v), n) * inn
+    w1 = _dot3(_face_cross(v, e1), n) * inn
+    w0 = (1 - w1) - w2
+    inside = (inn > 0) & (w0 >= 0) & (w1 >= 0) & (w2 >= 0)
+    t_ab = (_dot3(v, e0) * _recip_or_zero(_dot3(e0, e0))).clamp(0, 1)
+    vb, eb = v - e0, e1 - e0
+    t_bc = (_dot3(vb, eb) * _recip_or_zero(_dot3(eb, eb))).clamp(0, 1)
+    t_ca = (_dot3(v, e1) * _recip_or_zero(_dot3(e1, e1))).clamp(0, 1)
+    # the same residuals once more on the attached inputs, the weights as constants
+    e0, e1, v = b - a, c - a, points - a
+    r = v - (w1[..., None] * e0 + w2[..., None] * e1)
+    d_in = _dot3(r, r)
+    r = v - t_ab[..., None] * e0
+    d_ab = _dot3(r, r)
+    r = (v - e0) - t_bc[..., None] * (e1 - e0)
+    d_bc = _dot3(r, r)
+    r = v - t_ca[..., None] * e1
+    d_ca = _dot3(r, r)
+    zero = torch.zeros_like(t_ab)
+    take = ~inside | (d_ab.detach() < d_in.detach())
+    d2 = torch.where(take, d_ab, d_in)
+    bary = torch.where(take[..., None], torch.stack((1 - t_ab, t_ab, zero), -1), torch.stack((w0, w1, w2), -1))
+    for d, w in ((d_bc, torch.stack((zero, 1 - t_bc, t_bc), -1)), (d_ca, torch.stack((1 - t_ca, zero, t_ca), -1))):
+        take = d.detach() < d2.detach()
+        d2 = torch.where(take, d, d2)
+        bary = torch.where(take[..., None], w, bary)
+    return d2, bary
+
+
+POINT_MESH_CHUNK_PAIRS = 1 << 20      # pairs of one chunk of point_mesh_term's P x F matrix
+
+
+def point_mesh_term(verts, faces, points, single_directional=False, point_reduction="mean", return_indices=False):
+    """Point-to-mesh distance (PyTorch3D's point_mesh_face_distance for one mesh and one cloud; an extension here):
+    verts [V,3], faces [F,3] integer, points [P,3], with d2(p, T) of point_triangle_closest,
+
+        (1 / P) sum_i min_f d2(p_i, T_f) + (1 / F) sum_f min_i d2(p_i, T_f),
+
+    point_reduction="sum" without the two divisors, single_directional the first sum alone.  The P x F matrix is evaluated in
+    chunks of points and never exists whole; an exact tie keeps the LOWER index in both directions, and the chosen pairs are
+    constants of the graph: the distances are evaluated once more on them, so verts and points get gradients.
+    return_indices=True: (loss, face_idx [P], point_idx [F] | None), int64.  Differentiable torch on any device / dtype: the
+    definition ops._PointMesh is tested against and the route for everything it does not take."""
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError(f"point_mesh_term: point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    if verts.dim() != 2 or points.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or points.shape[1] != 3 or faces.shape[1] != 3 \
+            or 0 in (verts.shape[0], faces.shape[0], points.shape[0]):
+        raise ValueError(f"point_mesh_term: non-empty verts [V,3], faces [F,3] and points [P,3] expected, got {tuple(verts.shape)} / "
+                         f"{tuple(faces.shape)} / {tuple(points.shape)}")
+    points = points.to(verts.dtype)
+    f = faces.long()
+    P, F = points.shape[0], f.shape[0]
+    vd, pd = verts.detach(), points.detach()
+    a, b, c = vd[f[:, 0]], vd[f[:, 1]], vd[f[:, 2]]
+    face_idx = torch.empty((P,), dtype=torch.long, device=verts.device)
+    best_f = torch.full((F,), float("inf"), dtype=verts.dtype, device=verts.device)
+    point_idx = torch.zeros((F,), dtype=torch.long, device=verts.device)
+    ar_f = torch.arange(F, device=verts.device)
+    chunk = max(1, POINT_MESH_CHUNK_PAIRS // F)
+    for s in range(0, P, chunk):
+        e = min(s + chunk, P)
+        d = point_triangle_closest(pd[s:e, None], a[None], b[None], c[None])[0]      # [e - s, F]
+        m = d.min(dim=1).values
+        face_idx[s:e] = torch.where(d == m[:, None], ar_f[None, :], F).min(dim=1).values
+        if not single_directional:
+            m = d.min(dim=0).values
+            first = torch.where(d == m[None, :], torch.arange(s, e, device=d.device)[:, None], P).min(dim=0).values
+            better = m < best_f                                                     # (strictly: an earlier chunk keeps a tie)
+            best_f = torch.where(better, m, best_f)
+            point_idx = torch.where(better, first, point_idx)
+    reduce = torch.mean if point_reduction == "mean" else torch.sum
+    tri = f[face_idx]
+    loss = reduce(point_triangle_closest(points, verts[tri[:, 0]], verts[tri[:, 1]], verts[tri[:, 2]])[0])
+    if single_directional:
+        return (loss, face_idx, None) if return_indices else loss
+    loss = loss + reduce(point_triangle_closest(points[point_idx], verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]])[0])
+    return (loss, face_idx, point_idx) if return_indices else loss
+
+
 def camera_centres(R, T):
     """C [B,3] = -T @ R^-1 in the tensors' dtype (row vectors, X_view = X_world @ R + T): the point every pixel ray of a view leaves."""
     return -torch.einsum("bj,bjk->bk", T, torch.linalg.inv(R))

@@ -17,7 +17,13 @@ sample_points_from_meshes is what feeds that loss in practice: area-weighted poi
 every iteration, with gradients to the three vertices of each sampled face.  A SurfaceSampler is built ONCE on the host from the
 faces; the definition is Aggregation.mesh_surface_points, and fp32 vertices on the HIP device of the sampler's tables take the
 kernels of voge_amd/csrc/mesh_sample.hip (ops._MeshSample: three launches forward, an integer-atomic backward, the same bits on
-every run, capturable)."""
+every run, capturable).
+
+point_mesh_face_distance measures a mesh against a cloud exactly -- every point to its nearest triangle, every triangle to its
+nearest point --, point_mesh_edge_distance the same over segments, and closest_faces is the search alone, the score of an
+extracted mesh against ground-truth points.  The definitions are Aggregation.point_triangle_closest / point_mesh_term; fp32
+tensors on a HIP device take the kernels of voge_amd/csrc/point_mesh.hip (ops._PointMesh: two exact searches through LDS, fp64
+sums in a fixed order, an integer-atomic backward -- the same bits on every run, capturable)."""
 import numpy as np
 import torch
 
@@ -346,3 +352,127 @@ def sample_points_from_meshes(verts, faces_or_sampler, num_samples=10000, return
     if return_faces:
         res = res + (face_idx, bary)
     return res[0] if len(res) == 1 else res
+
+
+_FACES_CHECKED = {}      # (data_ptr, version, F, device) of a faces tensor -> the largest V it was refused for / smallest it passed for
+
+
+def _checked_faces(faces, V, what, width=3):
+    """faces as an integer tensor [F,width] whose entries lie in [0, V); ValueError otherwise.  The range check of a device tensor
+    reads two numbers back, so it is made once per tensor (keyed by its storage and version) and never inside a stream capture:
+    the kernels themselves skip a face that names a vertex out of range."""
+    if isinstance(faces, np.ndarray):
+        faces = torch.from_numpy(faces)
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != width or faces.dtype.is_floating_point or faces.dtype == torch.bool \
+            or faces.dtype.is_complex:
+        raise ValueError(f"{what}: an integer tensor [n,{width}] expected, got "
+                         f"{(faces.dtype, tuple(faces.shape)) if torch.is_tensor(faces) else type(faces).__name__}")
+    if faces.shape[0] == 0:
+        raise ValueError(f"{what}: an empty mesh")
+    key = (faces.data_ptr(), faces._version, tuple(faces.shape), str(faces.device))
+    if _FACES_CHECKED.get(key) != V and not (faces.is_cuda and torch.cuda.is_current_stream_capturing()):
+        lo, hi = int(faces.min()), int(faces.max())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"{what}: indices must lie in [0, {V}), got [{lo}, {hi}]")
+        if len(_FACES_CHECKED) > 64:
+            _FACES_CHECKED.clear()
+        _FACES_CHECKED[key] = V
+    return faces
+
+
+def closest_faces(points, verts, faces):
+    """For every row of points [P,3] the nearest triangle of the mesh (verts [V,3], faces [F,3] of any integer dtype) ->
+    (d2 [P], face_idx [P], bary [P,3]) without gradient: the squared distance of Aggregation.point_triangle_closest, the lowest
+    face index among exact ties (int32 from the kernels, int64 from the definition) and the weights of the closest point on the
+    face's (a, b, c).  What an extracted mesh is scored with against ground-truth points: sqrt(d2).mean() is the accuracy of a
+    reconstruction's points against a reference mesh, (d2 <= tau^2).float().mean() its precision at tau, and the same with the
+    roles swapped completeness and recall.  fp32 tensors on one HIP device take the kernel of ops.closest_faces (one launch, no
+    host synchronisation); everything else takes the definition in chunks of points.  P = 0 returns empty tensors; wrong shapes,
+    an empty mesh or a face that names a vertex outside [0, V) raise ValueError."""
+    if not torch.is_tensor(points) or not torch.is_tensor(verts) or points.dim() != 2 or verts.dim() != 2 or points.shape[1] != 3 \
+            or verts.shape[1] != 3:
+        raise ValueError("closest_faces: points [P,3] and verts [V,3] expected")
+    if verts.shape[0] == 0:
+        raise ValueError("closest_faces: an empty mesh")
+    faces = _checked_faces(faces, verts.shape[0], "closest_faces: faces")
+    points, verts = points.detach(), verts.detach()
+    if verts.is_cuda and verts.dtype == torch.float32 and points.dtype == torch.float32 and points.device == verts.device:
+        return ops.closest_faces(points, verts, faces.to(verts.device))
+    f = faces.to(verts.device).long()
+    points = points.to(verts.dtype)
+    a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
+    P, F = points.shape[0], f.shape[0]
+    face_idx = torch.empty((P,), dtype=torch.long, device=verts.device)
+    ar = torch.arange(F, device=verts.device)
+    chunk = max(1, (1 << 20) // F)
+    for s in range(0, P, chunk):
+        d = Aggregation.point_triangle_closest(points[s:s + chunk, None], a[None], b[None], c[None])[0]
+        face_idx[s:s + chunk] = torch.where(d == d.min(dim=1).values[:, None], ar[None, :], F).min(dim=1).values
+    d2, bary = Aggregation.point_triangle_closest(points, a[face_idx], b[face_idx], c[face_idx])
+    return d2, face_idx, bary
+
+
+_POINT_MESH_UNSUPPORTED = ("min_triangle_area", "meshes", "pcls", "weights", "norm", "batch_reduction", "x_lengths", "y_lengths")
+
+
+def _point_mesh_pair(verts, faces, points, single_directional, point_reduction):
+    if verts.is_cuda and verts.dtype == torch.float32 and points.dtype == torch.float32 and points.device == verts.device:
+        return ops.point_mesh(verts, faces.to(verts.device), points, point_reduction == "sum", single_directional)[0]
+    return Aggregation.point_mesh_term(verts, faces.to(verts.device), points.to(verts.device), single_directional, point_reduction)
+
+
+def _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported):
+    for name, value in unsupported.items():
+        if name not in _POINT_MESH_UNSUPPORTED:
+            raise TypeError(f"{what}: unexpected argument {name!r}")
+        raise ValueError(f"{what}: {name}={value!r} is out of scope" + (
+            " (there is no area threshold: a triangle without area is its three segments)" if name == "min_triangle_area" else ""))
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError(f"{what}: point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    if not torch.is_tensor(verts) or not torch.is_tensor(points) or verts.dim() not in (2, 3) or points.dim() != verts.dim() \
+            or verts.shape[-1] != 3 or points.shape[-1] != 3 or (verts.dim() == 3 and verts.shape[0] != points.shape[0]):
+        raise ValueError(f"{what}: verts [V,3] and points [P,3], or [B,V,3] and [B,P,3], expected")
+    if points.shape[-2] == 0 or (verts.dim() == 3 and verts.shape[0] == 0):
+        raise ValueError(f"{what}: an empty cloud")
+    if verts.shape[-2] == 0:
+        raise ValueError(f"{what}: an empty mesh")
+    if verts.dim() == 2:
+        return _point_mesh_pair(verts, faces, points, single_directional, point_reduction)
+    return torch.stack([_point_mesh_pair(verts[b], faces, points[b], single_directional, point_reduction)
+                        for b in range(verts.shape[0])]).mean()
+
+
+def point_mesh_face_distance(verts, faces, points, single_directional=False, point_reduction="mean", **unsupported):
+    """The distance between a mesh (verts [V,3], faces [F,3] of any integer dtype; an int32 tensor on the vertices' device is used
+    as it is) and a cloud points [P,3] -- PyTorch3D's point_mesh_face_distance on tensors, a 0-dim tensor:
+
+        loss = (1 / P) sum_i min_f d2(p_i, T_f) + (1 / F) sum_f min_i d2(p_i, T_f),
+
+    d2 the squared distance to the closest point of the triangle (Aggregation.point_triangle_closest), point_reduction="sum"
+    without the two divisors, single_directional the first sum alone.  Unlike the chamfer distance of surface samples it is 0 on
+    a perfect fit, does not change with a draw and moves no vertex along the surface.  verts and points get gradients.  The
+    definition is Aggregation.point_mesh_term, and what host tensors and other dtypes get; fp32 tensors on one HIP device are ONE
+    autograd node (ops._PointMesh, no double backward) with no host synchronisation, so it runs inside a captured iteration.  Both
+    searches are exact and brute force: P F is capped (ops.POINT_MESH_MAX_PAIRS); beyond it, score sample_points_from_meshes
+    against the points with chamfer_distance.  verts [B,V,3] with points [B,P,3] is a HOST LOOP over the B pairs, which share
+    the faces, averaged.  There is NO min_triangle_area: it depends on the scale of the mesh; a triangle without area is its
+    three segments.  That and every other PyTorch3D keyword (meshes, pcls, weights, norm, ...) is rejected by name (ValueError);
+    wrong shapes, an empty cloud, an empty mesh or a face that names a vertex outside [0, V) raise ValueError too."""
+    what = "point_mesh_face_distance"
+    if torch.is_tensor(verts) and verts.dim() in (2, 3):
+        faces = _checked_faces(faces, verts.shape[-2], what + ": faces")
+    return _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported)
+
+
+def point_mesh_edge_distance(verts, edges, points, single_directional=False, point_reduction="mean", **unsupported):
+    """PyTorch3D's point_mesh_edge_distance on tensors: point_mesh_face_distance with the segments edges [E,2] (an integer
+    tensor, or a MeshTopology, whose unique edges are taken) in the triangles' place.  A segment (i, j) is the triangle (i, j, j),
+    which point_triangle_closest's rule for a triangle without area makes exactly the segment: the same node on the index table
+    [i, j, j], no kernel of its own."""
+    what = "point_mesh_edge_distance"
+    if isinstance(edges, MeshTopology):
+        edges = edges.edges
+    if torch.is_tensor(verts) and verts.dim() in (2, 3):
+        edges = _checked_faces(edges, verts.shape[-2], what + ": edges", width=2)
+        edges = edges[:, [0, 1, 1]]
+    return _point_mesh_distance(what, verts, edges, points, single_directional, point_reduction, unsupported)

@@ -31,7 +31,7 @@
 // walks at most the whole grid; the values are then out of contract, the indices still in range (an index that is not is written
 // as -1, and the backward skips it).
 //
-// voge_chamfer_fwd.  The two searches write d2 by the query's own index; chamfer_loss_partial_kernel leaves one fp64 sum (and the
+// voge_chamfer_fwd.  The two searches write d2 by the query's own index; chamfer_loss_partial_kernel (chamfer_loss.h) leaves one fp64 sum (and the
 // largest d2) per 1024 queries, chamfer_loss_final_kernel -- ONE workgroup -- adds them in an order fixed by the shapes (the
 // mesh_reg.hip pattern) and rounds sum_x / Nx + sum_y / Ny to fp32 once.
 //
@@ -48,6 +48,7 @@
 // once.  No float atomics anywhere, no wait on another workgroup.
 #include <math.h>
 
+#include "chamfer_loss.h"
 #include "knn_grid.h"
 
 namespace voge {
@@ -56,7 +57,6 @@ constexpr long kChamferMaxN = 268435455l;
 constexpr double kChamferBruteMaxPairs = 8388608.0;      // Nx Ny at or below this: the brute route (measured: profiles/r17_chamfer.txt)
 constexpr int kChSearchBlock = 128;
 constexpr int kChBoxItems = 8;          // points a thread of the box pass: 2048 a workgroup
-constexpr int kChLossItems = 4;         // d2 a thread of the partial sums: 1024 a workgroup
 constexpr int kChTile = 1024;           // points of a brute-force tile
 constexpr int kChGridTrips = 64;
 
@@ -339,76 +339,6 @@ chamfer_brute_kernel(const float *__restrict__ qs, const int Nq, const float *__
     const uint64_t ab = a < b ? a : b, cd = c < d ? c : d;
     chamfer_store(ab < cd ? ab : cd, Nd, idx, d2, qi);
   }
-}
-
-// ---- the loss -----------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ double chamfer_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// workgroups [0, nba): d2a, the rest: d2b; one fp64 sum and the largest d2 a workgroup
-__global__ void __launch_bounds__(256)
-chamfer_loss_partial_kernel(const float *__restrict__ d2a, const int Na, const float *__restrict__ d2b, const int Nb, const unsigned nba,
-                            double *__restrict__ psum, float *__restrict__ pmax) {
-  const bool first = blockIdx.x < nba;
-  const float *__restrict__ d = first ? d2a : d2b;
-  const int N = first ? Na : Nb;
-  const size_t base = (size_t)(blockIdx.x - (first ? 0u : nba)) * (256 * kChLossItems) + threadIdx.x;
-  double s = 0.0;
-  float m = 0.0f;
-#pragma unroll
-  for (int k = 0; k < kChLossItems; ++k) {
-    const size_t i = base + (size_t)k * 256;
-    const float v = i < (size_t)N ? d[i] : 0.0f;
-    s += (double)v;
-    m = fmaxf(m, v);
-  }
-  s = chamfer_wave_sum_f64(s);
-  m = wave_max(m);
-  __shared__ double rs[4];
-  __shared__ float rm[4];
-  if ((threadIdx.x & 63) == 0) { rs[threadIdx.x >> 6] = s; rm[threadIdx.x >> 6] = m; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    psum[blockIdx.x] = (rs[0] + rs[1]) + (rs[2] + rs[3]);
-    pmax[blockIdx.x] = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
-  }
-}
-
-// ONE workgroup: loss = sum_a / div_a + sum_b / div_b in fp64, rounded once; meta[0] = the backward's scale exponent s (header)
-__global__ void __launch_bounds__(256)
-chamfer_loss_final_kernel(const double *__restrict__ psum, const float *__restrict__ pmax, const unsigned nba, const unsigned nbb,
-                          const double div_a, const double div_b, const int list_bits, float *__restrict__ loss,
-                          int32_t *__restrict__ meta) {
-  double sa = 0.0, sb = 0.0;
-  float m = 0.0f;
-  for (unsigned i = threadIdx.x; i < nba; i += 256) { sa += psum[i]; m = fmaxf(m, pmax[i]); }
-  for (unsigned i = threadIdx.x; i < nbb; i += 256) { sb += psum[nba + i]; m = fmaxf(m, pmax[nba + i]); }
-  __shared__ double red[2][256];
-  __shared__ float redm[256];
-  red[0][threadIdx.x] = sa; red[1][threadIdx.x] = sb; redm[threadIdx.x] = m;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + h];
-      red[1][threadIdx.x] += red[1][threadIdx.x + h];
-      redm[threadIdx.x] = fmaxf(redm[threadIdx.x], redm[threadIdx.x + h]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x != 0) return;
-  loss[0] = (float)(red[0][0] / div_a + (nbb ? red[1][0] / div_b : 0.0));
-  int s = 0;
-  const double D = sqrt((double)redm[0] * (1.0 + 0x1p-20) + 0x1p-148);
-  if (D < (double)INFINITY) {      // (false for a NaN too: s = 0, the values are out of contract)
-    int e;
-    frexp(D, &e);      // D = f 2^e, f in [0.5, 1): D < 2^e
-    s = 62 - list_bits - e;
-  }
-  meta[0] = s; meta[1] = 0; meta[2] = 0; meta[3] = 0;
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------

@@ -2125,6 +2125,106 @@ def chamfer(x, y, sum_reduction=False, single_directional=False, route=None):
     return _Chamfer.apply(x, y, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1), _chamfer_route(route))
 
 
+POINT_MESH_FACE_TILE = 256      # kPmFaceTile of point_mesh.hip: triangle records of an LDS tile (the tests build meshes around it)
+POINT_MESH_POINT_TILE = 1024    # kPmPointTile: points of an LDS tile
+POINT_MESH_MAX_PAIRS = 1 << 38  # kPmMaxPairs: the entries refuse P F above it (an exact search is a brute force)
+
+
+def _point_mesh_args(verts, faces, points, what):
+    verts, points = _cloud(verts, "verts"), _cloud(points, "points")
+    faces = _dev(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces [F,3] expected, got {tuple(faces.shape)}")
+    if points.device != verts.device or faces.device != verts.device:
+        raise _lib.VogeHipError(f"{what}: verts on {verts.device}, faces on {faces.device}, points on {points.device}")
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        raise ValueError(f"{what}: an empty mesh")
+    if faces.shape[0] * points.shape[0] > POINT_MESH_MAX_PAIRS:
+        raise ValueError(f"{what}: {points.shape[0]} points x {faces.shape[0]} faces is above the {POINT_MESH_MAX_PAIRS} pairs an exact "
+                         "search takes (a brute force); for such sizes score sample_points_from_meshes against the points with "
+                         "chamfer_distance")
+    return verts, faces, points
+
+
+def closest_faces(points, verts, faces):
+    """The nearest triangle of the mesh (verts [V,3], faces [F,3] integer) for every row of points [P,3] (extension;
+    voge_closest_faces) on a HIP device -> (d2 [P] fp32, face_idx [P] int32, bary [P,3] fp32): the squared distance of
+    Aggregation.point_triangle_closest, the lowest face index among exact ties and the weights of the closest point.  One launch,
+    nothing read back on the host; no gradient."""
+    verts, faces, points = _point_mesh_args(verts, faces, points, "closest_faces")
+    P = points.shape[0]
+    d2 = torch.empty((P,), dtype=torch.float32, device=points.device)
+    face_idx = torch.empty((P,), dtype=torch.int32, device=points.device)
+    bary = torch.empty((P, 3), dtype=torch.float32, device=points.device)
+    if P > 0:
+        lib = _lib.load()
+        with _on(points.device):
+            rc = lib.voge_closest_faces(_p(points), P, _p(verts), verts.shape[0], _p(faces), faces.shape[0], _p(face_idx), _p(d2), _p(bary),
+                                        _stream())
+        _lib.check(rc, "voge_closest_faces")
+    return d2, face_idx, bary
+
+
+class _PointMesh(torch.autograd.Function):
+    """Point-to-mesh distance (extension; voge_point_mesh_fwd / _bwd): forward(verts [V,3], faces [F,3] int, points [P,3], flags) ->
+    (loss 0-dim, face_idx [P], bary_p [P,3], point_idx [F] | None, bary_f [F,3] | None), the value of Aggregation.point_mesh_term
+    with the chosen pairs and the weights of their closest points (not differentiable).  flags: bit 0 "sum", bit 1
+    single_directional.  The two searches, the fp64 partial sums and the one workgroup that adds them run on the current stream
+    from the stream's cached workspace with nothing read back on the host; the node saves the inputs, the indices, the weights and
+    meta [4] int32 (the backward's scale exponent, chosen on the device).  Backward: three launches (zero fill, integer-atomic
+    scatter, finish), every element of g_verts and g_points written: the same bits on every run.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, points, flags):
+        verts, faces, points = _point_mesh_args(verts, faces, points, "point_mesh_face_distance")
+        V, F, P = verts.shape[0], faces.shape[0], points.shape[0]
+        if P == 0:
+            raise ValueError("point_mesh_face_distance: an empty cloud")
+        lib = _lib.load()
+        dev = verts.device
+        single = bool(flags & 2)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        face_idx = torch.empty((P,), dtype=torch.int32, device=dev)
+        bary_p = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        point_idx = None if single else torch.empty((F,), dtype=torch.int32, device=dev)
+        bary_f = None if single else torch.empty((F, 3), dtype=torch.float32, device=dev)
+        meta = torch.empty((4,), dtype=torch.int32, device=dev)
+        with _on(dev):
+            nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
+            ws = _workspace(dev, nbytes)
+            rc = lib.voge_point_mesh_fwd(_p(verts), V, _p(faces), F, _p(points), P, flags, _p(loss), _p(face_idx), _p(bary_p), _p(point_idx),
+                                         _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_point_mesh_fwd")
+        ctx.save_for_backward(verts, faces, points, face_idx, bary_p, point_idx, bary_f, meta)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*[t for t in (face_idx, bary_p, point_idx, bary_f) if t is not None])
+        return loss[0], face_idx, bary_p, point_idx, bary_f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, *_unused):
+        if g_loss is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
+            return None, None, None, None
+        lib = _lib.load()
+        verts, faces, points, face_idx, bary_p, point_idx, bary_f, meta = ctx.saved_tensors
+        V, F, P = verts.shape[0], faces.shape[0], points.shape[0]
+        g = _dev(g_loss, torch.float32, "grad_loss")
+        g_verts, g_points = torch.empty_like(verts), torch.empty_like(points)
+        with _on(verts.device):
+            nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
+            ws = _workspace(verts.device, nbytes)
+            rc = lib.voge_point_mesh_bwd(_p(verts), V, _p(faces), F, _p(points), P, _p(face_idx), _p(bary_p), _p(point_idx), _p(bary_f),
+                                         _p(meta), _p(g), ctx.flags, _p(g_verts), _p(g_points), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_point_mesh_bwd")
+        return (g_verts if ctx.needs_input_grad[0] else None), None, (g_points if ctx.needs_input_grad[2] else None), None
+
+
+def point_mesh(verts, faces, points, sum_reduction=False, single_directional=False):
+    """(loss, face_idx, bary_p, point_idx, bary_f) of ONE mesh and ONE cloud on a HIP device: _PointMesh.apply."""
+    return _PointMesh.apply(verts, faces, points, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1))
+
+
 MESH_SAMPLE_BLOCK = 256      # kMsBlock of mesh_sample.hip: the faces of one scan block (the tests build meshes around it)
 MESH_SAMPLE_LDS_BLOCKS = 2048      # kMsLdsBlocks: more scan blocks than this and the sampler searches the block table in memory
 
