@@ -95,6 +95,11 @@ int voge_trace_pool_usage(const void *workspace, size_t workspace_bytes, int B, 
  * unused slots hold idx=-1, len=1e10, act=1e10, dsd=0 (ray_trace_voge.cu:184-214,:244-247).
  * idx holds the global index b*N+i.  Outputs need no pre-fill.  cnt: NULL, or [B,H,W] int32
  * receiving the number of hits kept per pixel (the filled prefix of the K slots).
+ * A ray need not be unit: len scales with 1 / |d| as the formula says (a tile with a ray whose |d|^2 is not within 4e-5 of 1 only switches
+ * the early exit off for its tile); a zero or non-finite ray, and one so short that every len is beyond 1e10, yields an empty
+ * pixel (cnt 0, sentinels); a form with d^T A d == 0 (A = 0 included) is never a hit, as in the reference, whose len is 0 / 0
+ * there (tests/test_gpu_trace_bounds.py).  This holds for the entry points that cull and sweep (this one, its scalar and view
+ * forms, the fragments and frame entries); voge_trace_topk_list_fwd evaluates A = 0 I as a finite len with act = 0.
  *
  * cam_fwd: NULL, or [B,3] unit view axis in the rays' frame: Gaussians with mu.fwd < 0
  * are skipped, which is the candidate rule of the reference's coarse stage

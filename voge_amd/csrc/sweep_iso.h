@@ -459,7 +459,9 @@ sweep_iso_kernel(const float4 *__restrict__ cull, const float4 *__restrict__ ms,
         for (int r = 0; r < 11; ++r)
           if (ghas(r)) grow(r)[sl] = ev[r];
       };
-      const float a_st = cgen ? e0.x : mrec.w;
+      // (a == 0: dsd = 0 and len = 0 / 0 in the reference -- never a hit; staged as +inf, whose act is inf or NaN, where
+      //  len = mu . d / |d|^2 would be finite and act = 0 below every threshold: tests/test_gpu_trace_bounds.py, invalid_scalar)
+      const float a_st = cgen ? e0.x : (mrec.w == 0.0f ? INFINITY : mrec.w);
       if (pref) {
         S.x[lane] = mrec.x; S.y[lane] = mrec.y; S.z[lane] = mrec.z; S.a[lane] = a_st;      // (behind the list: never-hit records)
         S.lb[lane] = lbv;

@@ -4,6 +4,8 @@
 // (voge_debug_sweep_variant) sends launch_trace here instead of to sweep_iso_kernel: tests/test_gpu_configs.py compares the two
 // bit for bit, scalar-sigma and general forms, and tools/needle_scene_ab.py times one against the other.  What was removed, and how
 // the removal was checked: HISTORY.md, "sweep_r3.h".
+// (One input on which the two differ: a scalar form with a == 0.  This kernel evaluates it through pair_eval_iso -- a finite len and
+//  act = 0, a hit --, sweep_iso_kernel stages it as never hit, as the reference's 0 / 0 has it: DESIGN.md section 3.)
 //
 // One workgroup = one wave = an 8x8 pixel tile, one ray per lane.  Its candidate stream is the tile's own sorted list (binB;
 // pooled when long) or, if that overflowed, its quad's list, or else every Gaussian of the batch element, read in chunks of 64:

@@ -467,14 +467,16 @@ constexpr int kST = 32;            // super-tile edge (pixels): the unit of the 
 struct RayDir {
   float ux, uy, uz;
   bool ok;      // finite, non-zero direction
-  bool unit;    // |d| == 1 within 1e-4 (the depth bound of the early exit assumes unit rays)
+  bool unit;    // |d| == 1 within 2e-5 (the depth bound of the early exit assumes unit rays: a ray of length s has len = depth / s,
+                // below a bin's bound by (s - 1) |mu|; the bounds carry 1e-5 |edge| and 1.13 x the >= 1e-5 |mu| inside every reach,
+                // 2.13e-5 |mu| in all -- DESIGN.md section 3, tests/test_gpu_trace_bounds.py near_unit_*)
 };
 __device__ __forceinline__ RayDir ray_dir(const float dx, const float dy, const float dz) {
   RayDir r;
   const float dn2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
   const float inv = 1.0f / sqrtf(dn2);
   r.ok = (dn2 > 0.0f) && (inv < 3e38f) && (inv == inv);
-  r.unit = fabsf(dn2 - 1.0f) < 1e-4f;
+  r.unit = fabsf(dn2 - 1.0f) < 4e-5f;
   r.ux = dx * inv; r.uy = dy * inv; r.uz = dz * inv;
   return r;
 }
