@@ -378,7 +378,8 @@ def get_depth(fragments: Fragments, normalize: bool = True, background: float = 
     fragments, K > 128, weights that already exist -- takes ops._Depth on the fragments' tensors.  For an RGB-D loss call
     get_depth BEFORE to_colored_background: the colours then take the fused-backward shade on the finished weights (two
     fused backward launches a step); the other order is just as correct, with the depth's gradient going through autograd's
-    [.., K] arrays."""
+    [.., K] arrays (tests/test_gpu_consumers.py holds every order of nine consumers of one Fragments, this pair among them, to
+    the fp64 gradients)."""
     lz = getattr(fragments, "_lazy", None)
     if lz is not None:
         out = ops.composite_depth(lz, bool(normalize), float(background))
