@@ -24,6 +24,8 @@ nearest point --, point_mesh_edge_distance the same over segments, and closest_f
 extracted mesh against ground-truth points.  The definitions are Aggregation.point_triangle_closest / point_mesh_term; fp32
 tensors on a HIP device take the kernels of voge_amd/csrc/point_mesh.hip (ops._PointMesh: two exact searches through LDS, fp64
 sums in a fixed order, an integer-atomic backward -- the same bits on every run, capturable)."""
+import weakref
+
 import numpy as np
 import torch
 
@@ -354,13 +356,16 @@ def sample_points_from_meshes(verts, faces_or_sampler, num_samples=10000, return
     return res[0] if len(res) == 1 else res
 
 
-_FACES_CHECKED = {}      # (data_ptr, version, F, device) of a faces tensor -> the largest V it was refused for / smallest it passed for
+_FACES_CHECKED = {}      # id of a faces tensor -> (weak reference to it, its version when it passed, the V it passed for)
 
 
 def _checked_faces(faces, V, what, width=3):
     """faces as an integer tensor [F,width] whose entries lie in [0, V); ValueError otherwise.  The range check of a device tensor
-    reads two numbers back, so it is made once per tensor (keyed by its storage and version) and never inside a stream capture:
-    the kernels themselves skip a face that names a vertex out of range."""
+    reads two numbers back, so it is made once per tensor and never inside a stream capture: the kernels themselves skip a face
+    that names a vertex out of range.  "Once per tensor" is the tensor OBJECT at its version, held by weak reference as
+    cameras._INTR holds its pair: an address says nothing (the allocator hands a freed tensor's block to the next one of its
+    size, whose version is 0 again), so a new tensor, a new view of one or an array wrapped afresh is always checked, and an
+    in-place edit of a tensor or of the base of a view bumps the version they share."""
     if isinstance(faces, np.ndarray):
         faces = torch.from_numpy(faces)
     if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != width or faces.dtype.is_floating_point or faces.dtype == torch.bool \
@@ -369,14 +374,16 @@ def _checked_faces(faces, V, what, width=3):
                          f"{(faces.dtype, tuple(faces.shape)) if torch.is_tensor(faces) else type(faces).__name__}")
     if faces.shape[0] == 0:
         raise ValueError(f"{what}: an empty mesh")
-    key = (faces.data_ptr(), faces._version, tuple(faces.shape), str(faces.device))
-    if _FACES_CHECKED.get(key) != V and not (faces.is_cuda and torch.cuda.is_current_stream_capturing()):
+    hit = _FACES_CHECKED.get(id(faces))
+    if hit is not None and hit[0]() is faces and hit[1:] == (faces._version, V):
+        return faces
+    if not (faces.is_cuda and torch.cuda.is_current_stream_capturing()):
         lo, hi = int(faces.min()), int(faces.max())
         if lo < 0 or hi >= V:
             raise ValueError(f"{what}: indices must lie in [0, {V}), got [{lo}, {hi}]")
         if len(_FACES_CHECKED) > 64:
             _FACES_CHECKED.clear()
-        _FACES_CHECKED[key] = V
+        _FACES_CHECKED[id(faces)] = (weakref.ref(faces), faces._version, V)
     return faces
 
 

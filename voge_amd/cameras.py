@@ -43,7 +43,8 @@ _INTR = {}      # (one entry per device: the last (focal_length, principal_point
 def _intrinsics(focal, pp, B, device):
     """focal_length / principal_point as contiguous fp32 [B,2] tensors.  The same two objects come in on every frame of a loop
     (only R / T move), so the last pair is remembered per device -- by identity and version of the tensors, held weakly --
-    instead of being re-expanded and re-copied by two tiny kernels per frame."""
+    instead of being re-expanded and re-copied by two tiny kernels per frame.  A value changed behind torch's back (through
+    `.data`, or through a numpy array the tensor aliases) bumps no version and is not seen: replace the tensor or edit it in place."""
     import weakref
     key = str(device)
     # (while a HIP graph is being captured the cache is neither read nor written, like ops._workspace: a pair prepared inside
