@@ -5,9 +5,10 @@ Meshing.extract_mesh, written with save_off -- an extension, the reference has n
 get_depth is the distance along each pixel's UNIT ray, which is what integrate takes; pixels the silhouette covers by less than a
 half are handed over as 0 ("no surface").  Neither step is differentiable: this is what one does AFTER a fit.  Prints V, F, the
 Euler characteristic and the number of boundary edges (a bunny seen from a ring of views keeps holes where no view looks: under
-the chin, between the ears).
+the chin, between the ears).  --keep-largest K and / or --min-faces M run Meshing.clean_mesh on the extraction -- the floaters of a
+fused volume go, the K largest components with at least M faces stay -- and print the report before and after.
 
-usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off]"""
+usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]"""
 import argparse
 import os
 import sys
@@ -19,7 +20,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 from VoGE.Converter.IO import save_off                                                 # noqa: E402
 from VoGE.Meshes import GaussianMeshesNaive                                            # noqa: E402
-from VoGE.Meshing import TSDFVolume, extract_mesh                                      # noqa: E402
+from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh    # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_depth, get_silhouette   # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
 
@@ -33,7 +34,7 @@ def mesh_report(verts, faces):
     return len(verts), len(f), used - len(counts) + len(f), int((counts == 1).sum())
 
 
-def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0"):
+def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None):
     g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_gaussians.npz"))
     verts, sigmas = (torch.from_numpy(g[k]) for k in ("verts", "isigma"))
     meshes = GaussianMeshesNaive(verts, sigmas, None).to(device)
@@ -59,6 +60,12 @@ def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:
     V, F, chi, boundary = mesh_report(mesh_verts, faces)
     report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
     print(f"bunny at {resolution}^3 from {views} views of {image}^2: {report}")
+    if keep_largest is not None or min_faces is not None:
+        before = connected_components(faces, len(mesh_verts))[2]
+        mesh_verts, faces = clean_mesh(mesh_verts, faces, keep_largest=keep_largest, min_faces=1 if min_faces is None else min_faces)
+        V, F, chi, boundary = mesh_report(mesh_verts, faces)
+        report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
+        print(f"cleaned (keep_largest {keep_largest}, min_faces {min_faces}): {before} -> {connected_components(faces, V)[2]} components: {report}")
     if out:
         save_off(out, mesh_verts, faces)
         print("->", out)
@@ -71,5 +78,7 @@ if __name__ == "__main__":
     ap.add_argument("--views", type=int, default=24)
     ap.add_argument("--image", type=int, default=256)
     ap.add_argument("--out", default="bunny_mesh.off")
+    ap.add_argument("--keep-largest", type=int, default=None)
+    ap.add_argument("--min-faces", type=int, default=None)
     a = ap.parse_args()
-    run(a.resolution, a.views, a.image, a.out)
+    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces)

@@ -1123,6 +1123,60 @@ int voge_mtet_emit(const float *values, const float *weight, int nx, int ny, int
                    const uint16_t *floc, const uint32_t *block_v, const uint32_t *block_f, long V, long F, float *verts,
                    int32_t *faces, voge_stream_t stream);
 
+/*
+ * Connected components of a triangle mesh (EXTENSION: the clean-up the 2D Gaussian splatting pipeline runs between extracting a
+ * mesh and scoring it).  Replaces voge_amd/Aggregation.py mesh_components, the definition: two vertices are connected when a chain
+ * of faces links them (each face joins its three vertices), and a component's label is its smallest vertex index.  faces [F,3]
+ * int32, V vertices.  A lock-free union-find over parent [V] (csrc/mesh_clean.hip's header has the invariant and the argument);
+ * `stages` is a bit mask of the launches to make, 7 for a call:
+ *   1  init     parent[x] = x, count[x] = 0, meta[0 .. 3] = 0;
+ *   2  link     one face per thread;
+ *   4  labels   vert_label [V] (a vertex no face names: its own index), face_label [F] = the label of the face's first vertex,
+ *               count [V] = the faces of the component at its label and 0 elsewhere, meta[1] = the number of components.
+ * meta [4] int32: meta[0] is an error word the caller reads back with meta[1] -- bit 0: a loop reached its trip cap or met a
+ * pointer that does not lead downwards (never in a correct run), bit 1: a face names a vertex outside [0, V) (it joins nothing and
+ * gets the label -1).  Integer atomics only: the same numbers on every run.  V or F negative or above 2^28 - 1, a null pointer
+ * that a size above 0 needs, stages outside 1 .. 7: VOGE_ERR_BAD_ARG before any HIP call.
+ */
+int voge_mesh_components(const int32_t *faces, long F, long V, int32_t *parent, int32_t *vert_label, int32_t *face_label,
+                         int32_t *count, int32_t *meta, int stages, voge_stream_t stream);
+
+/*
+ * The component filter (EXTENSION).  Replaces voge_amd/Aggregation.py mesh_clean, the definition, given its choice of components:
+ * keep_root [V] bytes, non-zero at the labels that stay; face_label [F] from voge_mesh_components.  A face stays when its label
+ * does, a vertex when a face that stays names it; both keep their order, and the faces are renumbered.
+ *   voge_mesh_clean_scan   `stages` is a bit mask of its launches, 15 for a call: 1 the zero fill of vflag [V rounded up to 4]
+ *                          and err [1]; 2 the kept faces mark vflag; 4 the exclusive prefixes of the flags inside blocks of 256 --
+ *                          loc [V + F], the vertices' first -- and the blocks' totals -- blocks [ceil(V / 256) + ceil(F / 256)]; 8 ONE
+ *                          workgroup turns the totals into their exclusive scans in place, 1024 entries a round, and writes
+ *                          totals [3] = (V', F', error word: bit 1 when a label or an index lies outside [0, V)).  The caller
+ *                          reads totals back to allocate the outputs: the one synchronisation of the filter;
+ *   voge_mesh_clean_emit   one launch: verts_out [V',3] (the kept vertices' bits), faces_out [F',3], vert_index [V'] and face_index [F']
+ *                          (the old indices).  Writes are guarded by V' and F'.
+ * Integer sums only: the same bits on every run.  V or F below 1 or above 2^28 - 1, a null pointer (the outputs of a size 0 may
+ * be null), V' or F' negative or above V or F, stages outside 1 .. 15: VOGE_ERR_BAD_ARG before any HIP call.
+ */
+int voge_mesh_clean_scan(const int32_t *faces, long F, long V, const int32_t *face_label, const uint8_t *keep_root, uint8_t *vflag,
+                         uint16_t *loc, uint32_t *blocks, int32_t *err, long long *totals, int stages, voge_stream_t stream);
+int voge_mesh_clean_emit(const float *verts, const int32_t *faces, long F, long V, const int32_t *face_label,
+                         const uint8_t *keep_root, const uint8_t *vflag, const uint16_t *loc, const uint32_t *blocks, long Vk, long Fk,
+                         float *verts_out, int32_t *faces_out, int32_t *vert_index, int32_t *face_index, voge_stream_t stream);
+
+/*
+ * Area-weighted vertex normals (EXTENSION: PyTorch3D's verts_normals_packed).  Replaces voge_amd/Aggregation.py
+ * mesh_vertex_normals, the definition: normals [V,3] = the normalised sum of (b - a) x (c - a) over the corners that name the
+ * vertex; (0, 0, 0) where the sum is zero, where a term is not finite and for a vertex no face names.  The cross product has the
+ * bits of voge_mesh_sample_fwd's; the sum is made in fixed point with 64-bit integer atomics (csrc/mesh_clean.hip's header), so the
+ * bits do not depend on the order of the faces.  `stages` is a bit mask of the launches, 15 for a call: 1 the zero fill of the
+ * workspace, 2 the largest |component|, 4 the scatter, 8 the finish.  Nothing is read back.  A face that names a vertex outside
+ * [0, V) is skipped.  V below 1, V or F above 2^28 - 1, a null pointer, a workspace that is null or off the 16-byte boundary, stages
+ * outside 1 .. 15: VOGE_ERR_BAD_ARG; a workspace below voge_vertex_normals_workspace_bytes(V): VOGE_ERR_WORKSPACE -- all before any
+ * HIP call.
+ */
+size_t voge_vertex_normals_workspace_bytes(long V);
+int voge_vertex_normals(const float *verts, long V, const int32_t *faces, long F, float *normals, void *workspace,
+                        size_t workspace_bytes, int stages, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -847,3 +847,98 @@ def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size
         all_keep.append(keep)
     faces = torch.stack(all_faces, 1)[torch.stack(all_keep, 1)]      # [cells,6,2,3] under [cells,6,2]: the order of the faces
     return verts, faces.reshape(-1, 3)
+
+
+def mesh_components(faces, num_verts):
+    """Connected components of a triangle mesh (an extension here) -> (vert_label [V] int64, face_label [F] int64,
+    num_components: int).  Two vertices are connected when a chain of faces links them, each face joining its three vertices; a
+    component's label is its SMALLEST VERTEX INDEX; a vertex no face names keeps its own index and is no component;
+    face_label[f] = vert_label[faces[f, 0]].  Min-label propagation to a fixed point: label[faces].amin(1) scattered with amin to
+    the three vertices and to their present labels, then label = label[label] until flat, until nothing changes -- every label
+    stays a vertex of the same component that is not above its owner, and at the fixed point a face's vertices agree, so a
+    component carries one label, an index of its own not above any of them: its smallest.  An index outside [0, V) raises
+    ValueError; a face may name a vertex twice.  Torch on any device, with one comparison read back per round: the definition
+    voge_mesh_components is tested against and the route for everything it does not take."""
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_components: faces [F,3] expected, got {tuple(faces.shape)}")
+    V, F = int(num_verts), faces.shape[0]
+    f = faces.detach().long()
+    if V < 0 or (F > 0 and (V == 0 or int(f.min()) < 0 or int(f.max()) >= V)):
+        raise ValueError(f"mesh_components: a face names a vertex outside [0, {V})")
+    label = torch.arange(V, dtype=torch.int64, device=f.device)
+    corners = f.reshape(-1)
+    while F > 0:
+        low = label[f].amin(1).repeat_interleave(3)
+        new = label.scatter_reduce(0, corners, low, "amin", include_self=True)
+        # the corners' present labels take it too (a label is a vertex of the same component, not below the minimum): whole
+        # trees hang under one another, and a long strip with shuffled indices takes tens of rounds, not tens of thousands
+        new = new.scatter_reduce(0, label[corners], low, "amin", include_self=True)
+        while True:
+            nxt = new[new]
+            if torch.equal(nxt, new):
+                break
+            new = nxt
+        if torch.equal(new, label):
+            break
+        label = new
+    face_label = label[f[:, 0]]
+    return label, face_label, int(torch.unique(face_label).numel())
+
+
+def mesh_keep_roots(count, keep_largest=None, min_faces=1):
+    """keep [V] bool: the labels of the components that stay, from count [V] (the faces of a component at its label, 0 elsewhere):
+    at least min_faces faces, and among the keep_largest first when the components are ranked by face count descending, then by
+    label ascending (None: all).  The rank is a topk over the int64 key (count << 32) | (2^32 - 1 - label), -1 for what min_faces
+    drops.  Torch on the counts' device, nothing read back."""
+    V = count.shape[0]
+    c = count.long()
+    keep = c >= max(int(min_faces), 1)
+    if keep_largest is None or V == 0:
+        return keep
+    idx = torch.arange(V, dtype=torch.int64, device=c.device)
+    key = torch.where(keep, (c << 32) | (0xffffffff - idx), torch.full_like(c, -1))
+    top_val, top_idx = torch.topk(key, min(int(keep_largest), V))
+    return torch.zeros_like(keep).scatter_(0, top_idx, top_val >= 0)
+
+
+def mesh_clean(verts, faces, keep_largest=None, min_faces=1):
+    """The mesh without its small components (an extension here: the filter the 2D Gaussian splatting pipeline runs on an extracted
+    mesh) -> (verts' [V',3], faces' [F',3] int64, vert_index [V'] int64, face_index [F'] int64).  A component (mesh_components)
+    stays when mesh_keep_roots says so; kept faces keep their order and are renumbered; vertices no kept face names are dropped,
+    the others keep their order and their bits; the index tables give the old indices.  keep_largest or min_faces below 1 raise
+    ValueError.  Torch on any device: the definition voge_mesh_clean_* are tested against and the route for everything they do
+    not take."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_clean: verts [V,3] and faces [F,3] expected, got {tuple(verts.shape)} / {tuple(faces.shape)}")
+    if (keep_largest is not None and int(keep_largest) < 1) or int(min_faces) < 1:
+        raise ValueError(f"mesh_clean: keep_largest (None or >= 1) and min_faces >= 1 expected, got {keep_largest} / {min_faces}")
+    V = verts.shape[0]
+    f = faces.detach().long()
+    _, face_label, _ = mesh_components(f, V)
+    keep = mesh_keep_roots(torch.bincount(face_label, minlength=V), keep_largest, min_faces)
+    face_index = torch.nonzero(keep[face_label])[:, 0]
+    kept = f[face_index]
+    used = torch.zeros((V,), dtype=torch.bool, device=f.device)
+    used[kept.reshape(-1)] = True
+    vert_index = torch.nonzero(used)[:, 0]
+    new_id = torch.cumsum(used, 0) - 1
+    return verts[vert_index], new_id[kept], vert_index, face_index
+
+
+def mesh_vertex_normals(verts, faces):
+    """Area-weighted vertex normals [V,3] in the vertices' dtype (PyTorch3D's verts_normals_packed; an extension here): the
+    normalised sum, over the corners that name a vertex, of cr = (b - a) x (c - a) of the corner's face -- a face that names a
+    vertex twice counts twice there.  cr is _face_cross of the rounded differences in the vertices' dtype (for fp32 the bits of
+    voge_mesh_sample_fwd's and voge_vertex_normals'); the sum, its norm sqrt((x^2 + y^2) + z^2) and the quotient are fp64, rounded
+    once.  (0, 0, 0) where the sum is zero or not finite, and for a vertex no face names.  Differentiable torch on any device: the
+    definition voge_vertex_normals is tested against and the route for everything it does not take."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_vertex_normals: verts [V,3] and faces [F,3] expected, got {tuple(verts.shape)} / {tuple(faces.shape)}")
+    f = faces.detach().long()
+    a = verts[f[:, 0]]
+    cr = _face_cross(verts[f[:, 1]] - a, verts[f[:, 2]] - a)
+    acc = torch.zeros((verts.shape[0], 3), dtype=torch.float64, device=verts.device).index_add(0, f.reshape(-1), cr.double().repeat_interleave(3, 0))
+    ok = torch.isfinite(acc.detach()).all(-1, keepdim=True) & (acc.detach() != 0).any(-1, keepdim=True)
+    acc = torch.where(ok, acc, torch.ones_like(acc))
+    n = torch.sqrt((acc[:, 0] * acc[:, 0] + acc[:, 1] * acc[:, 1]) + acc[:, 2] * acc[:, 2])[:, None]
+    return torch.where(ok, acc / n, torch.zeros_like(acc)).to(verts.dtype)

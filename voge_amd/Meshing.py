@@ -18,12 +18,26 @@ a surface here through the renderer (get_depth, get_normals) or through a mesh's
 extract_mesh on the device reads TWO integers back on the host, the vertex and the face count, to size its outputs: one
 synchronisation per call.  Extraction is a one-off step after a fit, not a step of an iteration, and cannot be captured into a
 graph; integrate reads nothing back.
+
+Mesh clean-up, what the same pipeline runs on the extracted mesh before it scores or saves it (a TSDF fused from rendered depth
+carries floaters: small closed blobs where a few views disagree, shells behind silhouettes):
+
+    vert_label, face_label, n = connected_components(faces, num_verts=None)
+    verts, faces = clean_mesh(verts, faces, keep_largest=None, min_faces=1, return_index=False)
+    normals = vertex_normals(verts, faces)
+
+Aggregation.mesh_components, Aggregation.mesh_clean and Aggregation.mesh_vertex_normals ARE the definitions; fp32 / int32 tensors on
+one HIP device take the kernels of csrc/mesh_clean.hip, everything else the definitions.  NONE OF THE THREE IS DIFFERENTIABLE
+either (Aggregation.mesh_vertex_normals is, through autograd, for whoever needs that).  connected_components reads ONE pair of
+integers back on the host (the error word and the number of components: one synchronisation); clean_mesh that pair and then
+the three that size its outputs (V', F' and an error word: a second synchronisation) -- like extraction, one-off steps that
+cannot be captured into a graph.  vertex_normals reads nothing back and can be.
 """
 import torch
 
 from . import Aggregation, cameras as _cameras, ops
 
-__all__ = ["TSDFVolume", "extract_mesh"]
+__all__ = ["TSDFVolume", "extract_mesh", "connected_components", "clean_mesh", "vertex_normals"]
 
 
 def _triple(v, name, integer=False):
@@ -152,3 +166,77 @@ def extract_mesh(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=
         return ops.marching_tets(values, w, float(level), lo, h)
     verts, faces = Aggregation.marching_tets(values, w, float(level), lo, h)
     return verts.to(torch.float32), faces.to(torch.int32)
+
+
+def _check_faces(faces, what):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point:
+        raise ValueError(f"{what}: faces [F,3] of integers expected, got {tuple(getattr(faces, 'shape', ()))}")
+
+
+def _check_mesh(verts, faces, what):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
+        raise ValueError(f"{what}: verts [V,3] of floats expected, got {tuple(getattr(verts, 'shape', ()))}")
+    _check_faces(faces, what)
+
+
+def _on_device(verts, faces):
+    return verts.is_cuda and verts.dtype == torch.float32 and faces.dtype == torch.int32 and faces.device == verts.device
+
+
+def connected_components(faces, num_verts=None):
+    """(vert_label [V] int32, face_label [F] int32, num_components: int) of faces [F,3]: Aggregation.mesh_components' rule.  Two
+    vertices are connected when a chain of faces links them, each face joining its three vertices: VERTEX connectivity.  On the
+    manifold output of extract_mesh that is edge connectivity too; it differs where two surfaces touch in a vertex without
+    sharing an edge there (two cones tip to tip, the pinch of a non-manifold vertex): one component here, two for a clustering over
+    shared edges.  A component's label is its smallest vertex index; a vertex no face names is labelled with its own index and is
+    not counted in num_components; face_label[f] = vert_label[faces[f, 0]].  num_verts=None: 1 + the largest index (read back on
+    the host).  An index outside [0, V) raises ValueError; a face may name a vertex twice, it just joins fewer vertices.  int32
+    faces on a HIP device: three launches and ONE synchronisation (see the module's header).  Not differentiable."""
+    _check_faces(faces, "connected_components")
+    faces = faces.detach()
+    if num_verts is None:
+        num_verts = int(faces.max()) + 1 if faces.shape[0] else 0
+    if int(num_verts) < 0:
+        raise ValueError(f"connected_components: num_verts {num_verts}")
+    if faces.is_cuda and faces.dtype == torch.int32:
+        return ops.mesh_components(faces, int(num_verts))
+    vert_label, face_label, n = Aggregation.mesh_components(faces, int(num_verts))
+    return vert_label.to(torch.int32), face_label.to(torch.int32), n
+
+
+def clean_mesh(verts, faces, keep_largest=None, min_faces=1, return_index=False):
+    """(verts' [V',3], faces' [F',3] int32[, vert_index [V'] int32, face_index [F'] int32]) -- the mesh without its small components:
+    Aggregation.mesh_clean's rule.  A component of connected_components stays when it has at least min_faces faces and is among the
+    keep_largest components (None: all), ranked by face count descending, then by label ascending, so ties have one answer.  Kept
+    faces keep their order and are renumbered; vertices no kept face names are dropped, the others keep their order and their
+    bits; vert_index and face_index give the old indices, so colours or any other attribute can follow (colours[vert_index]).
+    keep_largest=None, min_faces=1 on a mesh without unused vertices returns its input bit for bit.  keep_largest < 1 or
+    min_faces < 1 raise ValueError, and so does an index outside [0, V).  fp32 verts and int32 faces on one HIP device: the
+    components' launches, the ranking as torch calls on the device, five launches of the filter and TWO synchronisations (see
+    the module's header); no float atomics, the same bits on every run.  Not differentiable."""
+    _check_mesh(verts, faces, "clean_mesh")
+    if (keep_largest is not None and int(keep_largest) < 1) or int(min_faces) < 1:
+        raise ValueError(f"clean_mesh: keep_largest (None or >= 1) and min_faces >= 1 expected, got {keep_largest} / {min_faces}")
+    verts, faces = verts.detach(), faces.detach()
+    if _on_device(verts, faces):
+        _, face_label, _, count = ops.mesh_components(faces, verts.shape[0], return_count=True)
+        keep = Aggregation.mesh_keep_roots(count, keep_largest, min_faces)
+        out = ops.mesh_clean(verts, faces, face_label, keep)
+    else:
+        out = Aggregation.mesh_clean(verts, faces.to(verts.device), keep_largest, min_faces)
+        out = (out[0],) + tuple(t.to(torch.int32) for t in out[1:])
+    return out if return_index else out[:2]
+
+
+def vertex_normals(verts, faces):
+    """normals [V,3] fp32: PyTorch3D's verts_normals_packed, the normalised sum of (b - a) x (c - a) over the faces at a vertex, which
+    weights them by area -- Aggregation.mesh_vertex_normals' rule; what Converters.normal_mesh_converter(..., oriented=True) takes.
+    (0, 0, 0) where the sum is zero or not finite, and for a vertex no face names.  The faces' indices must lie in [0, V) (nothing
+    is read back to check them: the kernels skip such a face, the definition raises).  fp32 verts and int32 faces on one HIP
+    device: four launches, fixed-point sums with integer atomics -- the same bits on every run and in every order of the faces --,
+    nothing read back, capturable.  Not differentiable."""
+    _check_mesh(verts, faces, "vertex_normals")
+    verts, faces = verts.detach(), faces.detach()
+    if _on_device(verts, faces):
+        return ops.vertex_normals(verts, faces)
+    return Aggregation.mesh_vertex_normals(verts, faces.to(verts.device)).to(torch.float32)

@@ -147,6 +147,11 @@ SIGNATURES = {
     "voge_mtet_count": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] + [_c_void_p] * 7),
     "voge_mtet_scan": (_c_int, [_c_void_p] * 2 + [_c_long] + [_c_void_p] * 2),
     "voge_mtet_emit": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] * 7 + [_c_void_p] * 6 + [_c_long] * 2 + [_c_void_p] * 3),
+    "voge_mesh_components": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_void_p] * 5 + [_c_int, _c_void_p]),
+    "voge_mesh_clean_scan": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_void_p] * 7 + [_c_int, _c_void_p]),
+    "voge_mesh_clean_emit": (_c_int, [_c_void_p] * 2 + [_c_long] * 2 + [_c_void_p] * 5 + [_c_long] * 2 + [_c_void_p] * 5),
+    "voge_vertex_normals_workspace_bytes": (_c_size_t, [_c_long]),
+    "voge_vertex_normals": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 2 + [_c_size_t, _c_int, _c_void_p]),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

@@ -2382,6 +2382,119 @@ def marching_tets(values, weight, level, lo, voxel_size, return_tables=False):
     return (verts, faces, edge_mask, face_count) if return_tables else (verts, faces)
 
 
+MESH_CLEAN_BLOCK = 256      # kMcBlock of mesh_clean.hip: the flags of one scan block
+MESH_CLEAN_TOP = 1024       # kMcTop: the block totals one round of the top-level scan takes (the tests build meshes around both)
+MESH_MAX = 2 ** 28 - 1      # kMcMax: the vertices and the faces of one mesh
+
+
+def _mesh_faces(faces, name):
+    f = _dev(faces.detach(), torch.int32, "faces")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"{name}: faces [F,3] expected, got {tuple(f.shape)}")
+    if f.shape[0] > MESH_MAX:
+        raise ValueError(f"{name}: {f.shape[0]} faces, at most {MESH_MAX}")
+    return f
+
+
+def mesh_components(faces, num_verts, return_count=False):
+    """(vert_label [V] int32, face_label [F] int32, num_components) of faces [F,3] int32 on a HIP device (extension;
+    voge_mesh_components): the values of Aggregation.mesh_components.  Three launches on the current stream, then the error word
+    and the number of components are read back on the host -- ONE synchronisation.  An index outside [0, V) raises ValueError, a
+    loop of the union-find that reached its trip cap VogeHipError.  Not differentiable, not capturable.  return_count=True appends
+    count [V] int32: the faces of a component at its label, 0 elsewhere."""
+    f = _mesh_faces(faces, "mesh_components")
+    V, F, dev = int(num_verts), f.shape[0], f.device
+    if V < 0 or V > MESH_MAX:
+        raise ValueError(f"mesh_components: {V} vertices, 0 .. {MESH_MAX} expected")
+    if V == 0 and F > 0:
+        raise ValueError("mesh_components: a face names a vertex outside [0, 0)")
+    parent = torch.empty((V,), dtype=torch.int32, device=dev)
+    vert_label = torch.empty((V,), dtype=torch.int32, device=dev)
+    face_label = torch.empty((F,), dtype=torch.int32, device=dev)
+    count = torch.empty((V,), dtype=torch.int32, device=dev)
+    meta = torch.empty((4,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    with _on(dev):
+        rc = lib.voge_mesh_components(_p(f) if F else None, F, V, _p(parent) if V else None, _p(vert_label) if V else None,
+                                      _p(face_label) if F else None, _p(count) if V else None, _p(meta), 7, _stream())
+        _lib.check(rc, "voge_mesh_components")
+        err, num = meta[:2].tolist()      # the synchronisation
+    if err & 2:
+        raise ValueError(f"mesh_components: a face names a vertex outside [0, {V})")
+    if err:
+        raise _lib.VogeHipError(f"voge_mesh_components: a loop of the union-find reached its trip cap (error word {err})")
+    return (vert_label, face_label, int(num), count) if return_count else (vert_label, face_label, int(num))
+
+
+def mesh_clean(verts, faces, face_label, keep_root):
+    """(verts' [V',3], faces' [F',3] int32, vert_index [V'] int32, face_index [F'] int32) of verts [V,3] fp32, faces [F,3] int32 on a
+    HIP device (extension; voge_mesh_clean_scan / _emit): the values of Aggregation.mesh_clean for the components keep_root [V]
+    (bool or bytes, at the labels) names, face_label [F] int32 from mesh_components.  Four launches, then V', F' and the error word
+    are read back on the host -- ONE synchronisation, what sizes the outputs -- and one launch writes them.  Not differentiable,
+    not capturable."""
+    v = _dev(verts.detach(), torch.float32, "verts")
+    f = _mesh_faces(faces, "mesh_clean")
+    fl = _dev(face_label, torch.int32, "face_label")
+    kr = _dev(keep_root, torch.uint8, "keep_root")
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    if v.dim() != 2 or v.shape[1] != 3 or tuple(fl.shape) != (F,) or tuple(kr.shape) != (V,):
+        raise ValueError(f"mesh_clean: verts [V,3], face_label [F] and keep_root [V] expected, got {tuple(v.shape)} / {tuple(fl.shape)} / "
+                         f"{tuple(kr.shape)}")
+    if V > MESH_MAX:
+        raise ValueError(f"mesh_clean: {V} vertices, at most {MESH_MAX}")
+    if f.device != dev or fl.device != dev or kr.device != dev:
+        raise _lib.VogeHipError(f"mesh_clean: verts on {dev}, faces on {f.device}, face_label on {fl.device}, keep_root on {kr.device}")
+    empty = lambda n, cols, dt: torch.empty((n, 3) if cols else (n,), dtype=dt, device=dev)
+    if V == 0 or F == 0:
+        return empty(0, True, torch.float32), empty(0, True, torch.int32), empty(0, False, torch.int32), empty(0, False, torch.int32)
+    nb = (V + MESH_CLEAN_BLOCK - 1) // MESH_CLEAN_BLOCK + (F + MESH_CLEAN_BLOCK - 1) // MESH_CLEAN_BLOCK
+    vflag = torch.empty(((V + 3) // 4 * 4,), dtype=torch.uint8, device=dev)
+    loc = torch.empty((V + F,), dtype=torch.int16, device=dev)      # (16-bit prefixes: the kernels read them as unsigned)
+    blocks = torch.empty((nb,), dtype=torch.int32, device=dev)
+    err = torch.empty((1,), dtype=torch.int32, device=dev)
+    totals = torch.empty((3,), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    with _on(dev):
+        st = _stream()
+        rc = lib.voge_mesh_clean_scan(_p(f), F, V, _p(fl), _p(kr), _p(vflag), _p(loc), _p(blocks), _p(err), _p(totals), 15, st)
+        _lib.check(rc, "voge_mesh_clean_scan")
+        Vk, Fk, bad = (int(x) for x in totals.tolist())      # the synchronisation
+        if bad:
+            raise ValueError(f"mesh_clean: a face names a vertex, or carries a label, outside [0, {V})")
+        out_v, out_f = empty(Vk, True, torch.float32), empty(Fk, True, torch.int32)
+        vert_index, face_index = empty(Vk, False, torch.int32), empty(Fk, False, torch.int32)
+        rc = lib.voge_mesh_clean_emit(_p(v), _p(f), F, V, _p(fl), _p(kr), _p(vflag), _p(loc), _p(blocks), Vk, Fk, _p(out_v) if Vk else None,
+                                      _p(out_f) if Fk else None, _p(vert_index) if Vk else None, _p(face_index) if Fk else None, st)
+        _lib.check(rc, "voge_mesh_clean_emit")
+    return out_v, out_f, vert_index, face_index
+
+
+def vertex_normals(verts, faces):
+    """normals [V,3] fp32 of verts [V,3] fp32, faces [F,3] int32 on a HIP device (extension; voge_vertex_normals): the values of
+    Aggregation.mesh_vertex_normals.  Four launches on the current stream from the stream's cached workspace, nothing read back:
+    capturable.  Fixed-point sums with integer atomics: the same bits on every run and for every order of the faces.  Not
+    differentiable."""
+    v = _dev(verts.detach(), torch.float32, "verts")
+    f = _mesh_faces(faces, "vertex_normals")
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertex_normals: verts [V,3] expected, got {tuple(v.shape)}")
+    if V > MESH_MAX:
+        raise ValueError(f"vertex_normals: {V} vertices, at most {MESH_MAX}")
+    if f.device != dev:
+        raise _lib.VogeHipError(f"vertex_normals: verts on {dev}, faces on {f.device}")
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    if V == 0:
+        return out
+    lib = _lib.load()
+    with _on(dev):
+        nbytes = lib.voge_vertex_normals_workspace_bytes(V)
+        ws = _workspace(dev, nbytes)
+        rc = lib.voge_vertex_normals(_p(v), V, _p(f) if F else None, F, _p(out), _p(ws), nbytes, 15, _stream())
+    _lib.check(rc, "voge_vertex_normals")
+    return out
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
