@@ -8,7 +8,15 @@ Euler characteristic and the number of boundary edges (a bunny seen from a ring 
 the chin, between the ears).  --keep-largest K and / or --min-faces M run Meshing.clean_mesh on the extraction -- the floaters of a
 fused volume go, the K largest components with at least M faces stay -- and print the report before and after.
 
-usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]"""
+--colour carries the Gaussians' colours through every step: a colour image (interpolate_attr of the colour table) is rendered beside
+each depth map and fused with it (TSDFVolume(channels=3), integrate(attr=...)), extract_mesh(vol, attr=True) brings the colours to the
+vertices, they follow clean_mesh through its vert_index, save_off writes them (a COFF file), and the mesh goes back into Gaussians
+-- Converters.normal_mesh_converter(..., oriented=True) on Meshing.vertex_normals, the vertex colours as the colour table -- which
+are rendered from the first camera: the report ends with "round trip", the mean absolute difference of that image from the first
+colour image.  LAST then holds vert_attr, colour_range (the least and the greatest value of the fused images) and round_trip.
+
+usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]
+                                  [--colour]"""
 import argparse
 import os
 import sys
@@ -20,9 +28,14 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 from VoGE.Converter.IO import save_off                                                 # noqa: E402
 from VoGE.Meshes import GaussianMeshesNaive                                            # noqa: E402
-from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh    # noqa: E402
-from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_depth, get_silhouette   # noqa: E402
+from VoGE.Converter.Converters import normal_mesh_converter                            # noqa: E402
+from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh, vertex_normals    # noqa: E402
+from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_depth, get_silhouette, interpolate_attr   # noqa: E402
+from voge_amd.Meshes import OrientedGaussianMeshesNaive                                # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
+
+
+LAST = {}      # what the last run(colour=True) made beyond its return value
 
 
 def mesh_report(verts, faces):
@@ -34,9 +47,22 @@ def mesh_report(verts, faces):
     return len(verts), len(f), used - len(counts) + len(f), int((counts == 1).sum())
 
 
-def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None):
+def round_trip(renderer, mesh_verts, faces, vert_attr, R, T, first, device):
+    """The coloured mesh as oriented Gaussians, rendered under (R, T): the mean absolute difference from the colour image `first`"""
+    normals = vertex_normals(mesh_verts, faces)
+    flat = normals.norm(dim=-1) < 0.5      # (a vertex whose faces' normals cancel: any direction will do for one disc)
+    normals = torch.where(flat[:, None], normals.new_tensor([0.0, 0.0, 1.0]), normals)
+    gv, scales, quats = normal_mesh_converter(mesh_verts.cpu(), faces.cpu().long(), normals.cpu(), oriented=True)
+    with torch.no_grad():
+        frag = renderer(OrientedGaussianMeshesNaive(gv, scales, quats).to(device), R=R.to(device), T=T.to(device))
+        back = interpolate_attr(frag, vert_attr.contiguous())
+    return float((back - first).abs().mean())
+
+
+def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None, colour=False):
     g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_gaussians.npz"))
     verts, sigmas = (torch.from_numpy(g[k]) for k in ("verts", "isigma"))
+    colours = torch.from_numpy(g["colors"]).to(device) if colour else None
     meshes = GaussianMeshesNaive(verts, sigmas, None).to(device)
     focal, half = 2000.0 * image / 256, image / 2      # demo/RenderBunny.py's camera, scaled with the image
     settings = GaussianRenderSettings(image_size=(image, image), max_assign=40, absorptivity=1, principal=(half, half), inverse_sigma=False)
@@ -46,28 +72,43 @@ def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:
     azim = [360.0 * k / views for k in range(views)]
     elev = [25.0 if k % 2 == 0 else -25.0 for k in range(views)]
     R, T = look_at_view_transform([6.0] * views, elev, azim, degrees=True)
-    depths = []
+    depths, images = [], []
     with torch.no_grad():
         for k in range(views):      # one view a frame: the renderer's cameras are the frame's
             cameras.R, cameras.T = R[k:k + 1].to(device), T[k:k + 1].to(device)
             frag = renderer(meshes)
             depth = get_depth(frag, normalize=True, background=0.0)      # [1, H, W]
             depths.append(torch.where(get_silhouette(frag) > 0.5, depth, torch.zeros_like(depth)))
+            if colour:
+                images.append(interpolate_attr(frag, colours))      # [1, H, W, 3]
     cameras.R, cameras.T = R.to(device), T.to(device)
-    vol = TSDFVolume((-0.36, -0.36, -0.36), hi=(0.36, 0.36, 0.36), resolution=resolution, device=device)
-    vol.integrate(torch.cat(depths), cameras, trunc=4 * vol.voxel_size[0])
-    mesh_verts, faces = extract_mesh(vol)
+    vol = TSDFVolume((-0.36, -0.36, -0.36), hi=(0.36, 0.36, 0.36), resolution=resolution, device=device, channels=3 if colour else 0)
+    if colour:
+        images = torch.cat(images)
+        vol.integrate(torch.cat(depths), cameras, trunc=4 * vol.voxel_size[0], attr=images)
+        mesh_verts, faces, vert_attr = extract_mesh(vol, attr=True)
+    else:
+        vol.integrate(torch.cat(depths), cameras, trunc=4 * vol.voxel_size[0])
+        mesh_verts, faces = extract_mesh(vol)
     V, F, chi, boundary = mesh_report(mesh_verts, faces)
     report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
     print(f"bunny at {resolution}^3 from {views} views of {image}^2: {report}")
-    if keep_largest is not None or min_faces is not None:
+    if keep_largest is not None or min_faces is not None or colour:      # (with colours always: the vertices no face names go as well)
         before = connected_components(faces, len(mesh_verts))[2]
-        mesh_verts, faces = clean_mesh(mesh_verts, faces, keep_largest=keep_largest, min_faces=1 if min_faces is None else min_faces)
+        mesh_verts, faces, vert_index, _ = clean_mesh(mesh_verts, faces, keep_largest=keep_largest, min_faces=1 if min_faces is None else min_faces,
+                                                      return_index=True)
+        if colour:
+            vert_attr = vert_attr[vert_index.long()]      # the colours follow their vertices
         V, F, chi, boundary = mesh_report(mesh_verts, faces)
         report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
         print(f"cleaned (keep_largest {keep_largest}, min_faces {min_faces}): {before} -> {connected_components(faces, V)[2]} components: {report}")
+    if colour:
+        diff = round_trip(renderer, mesh_verts, faces, vert_attr, R[:1], T[:1], images[:1], device)
+        report += f", round trip mean |dimage| {diff:.4f}"
+        print(f"coloured mesh back as {len(mesh_verts)} oriented Gaussians, rendered from the first camera: round trip mean |dimage| {diff:.4f}")
+        LAST.update(vert_attr=vert_attr, colour_range=(float(images.min()), float(images.max())), round_trip=diff)
     if out:
-        save_off(out, mesh_verts, faces)
+        save_off(out, mesh_verts, faces, vert_color=vert_attr if colour else None)
         print("->", out)
     return mesh_verts, faces, report
 
@@ -80,5 +121,6 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="bunny_mesh.off")
     ap.add_argument("--keep-largest", type=int, default=None)
     ap.add_argument("--min-faces", type=int, default=None)
+    ap.add_argument("--colour", action="store_true")
     a = ap.parse_args()
-    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces)
+    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, colour=a.colour)

@@ -1124,6 +1124,30 @@ int voge_mtet_emit(const float *values, const float *weight, int nx, int ny, int
                    int32_t *faces, voge_stream_t stream);
 
 /*
+ * Attributes through the mesh extraction (EXTENSION): C floats a pixel -- a colour, a rendered normal, any row a renderer
+ * interpolates -- fused beside the distance and carried to the vertices.  1 <= C <= 8, a compile-time number of the kernels; the
+ * volume attr [nz,ny,nx,C] and the images attr_image [B,H,W,C] are fp32, channel last.  Both replace the attr= rules of
+ * voge_amd/Aggregation.py tsdf_integrate and marching_tets, the definitions, operation by operation in fp32.
+ *   voge_tsdf_integrate_attr   voge_tsdf_integrate with its arguments, tsdf and weight updated IN PLACE with that entry's bits, and
+ *                     attr beside them: where a view updates a grid point (no other condition), for every channel and with w the
+ *                     weight BEFORE its own update, attr <- (attr w + attr_image[b,i,j]) / (w + 1), (i,j) the depth's own nearest
+ *                     pixel.  The pixel's values are not examined: a NaN poisons the grid points that read it.  One launch, the
+ *                     loop over the views inside and the C running averages in registers: 16 + 8 C bytes a grid point per call.
+ *   voge_mtet_attr    one launch after voge_mtet_emit, on the tables of that extraction (edge_mask, vloc, block_v after the scan) and
+ *                     its values, level and grid: vert_attr [V,C] row block_v[q / 256] + vloc[q] + popcount(edge_mask[q] &
+ *                     ((1 << (d - 1)) - 1)) = attr_a + t (attr_b - attr_a), t = (level - v_a) / (v_b - v_a), a = q.  Writes are guarded by V.
+ * Gathers only, no atomics: the same bits on every run.  The errors of voge_tsdf_integrate and voge_mtet_emit, and C outside 1 .. 8 or
+ * a null attr / attr_image / vert_attr (vert_attr with V == 0 may be null): VOGE_ERR_BAD_ARG -- all before any HIP call.  B == 0 and
+ * V == 0: success, nothing is launched.
+ */
+int voge_tsdf_integrate_attr(float *tsdf, float *weight, float *attr, int C, int nx, int ny, int nz, float lox, float loy, float loz,
+                             float hx, float hy, float hz, const float *depth, const float *attr_image, int B, int H, int W,
+                             const float *R, const float *T, const float *centre, const float *focal, const float *pp, float trunc,
+                             float max_weight, voge_stream_t stream);
+int voge_mtet_attr(const float *values, int nx, int ny, int nz, float level, const float *attr, int C, const uint8_t *edge_mask,
+                   const uint16_t *vloc, const uint32_t *block_v, long V, float *vert_attr, voge_stream_t stream);
+
+/*
  * Connected components of a triangle mesh (EXTENSION: the clean-up the 2D Gaussian splatting pipeline runs between extracting a
  * mesh and scoring it).  Replaces voge_amd/Aggregation.py mesh_components, the definition: two vertices are connected when a chain
  * of faces links them (each face joins its three vertices), and a component's label is its smallest vertex index.  faces [F,3]

@@ -637,7 +637,8 @@ def camera_centres(R, T):
     return -torch.einsum("bj,bjk->bk", T, torch.linalg.inv(R))
 
 
-def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, max_weight=None, centre=None, mark=None):
+def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, max_weight=None, centre=None, mark=None, *, attr=None,
+                   attr_image=None):
     """Fuse depth maps into a truncated signed distance volume (an extension here: the last step of the 2D Gaussian splatting
     pipeline, whose depth maps get_depth renders) -> (tsdf, weight), new tensors; not differentiable.
 
@@ -652,8 +653,12 @@ def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, 
       3. d = depth[b,i,j], the nearest pixel, no interpolation; skipped unless d is finite and d > 0;
       4. sdf = d - sqrt((dx dx + dy dy) + dz dz) with dx = x - c_b; skipped if sdf < -trunc;
       5. t = min(1, sdf / trunc);
-      6. tsdf <- (tsdf w + t) / (w + 1);
+      6. tsdf <- (tsdf w + t) / (w + 1); and with attr [nz,ny,nx,C], the running attribute volume, and attr_image [B,H,W,C] (both or
+         neither, channel last), for every channel, with the same w -- the weight before step 7 -- and the same nearest pixel:
+         attr <- (attr w + attr_image[b,i,j]) / (w + 1), wherever the view updates the grid point and under no other condition;
       7. w <- w + 1, or min(w + 1, max_weight) when max_weight is given.
+    attr is appended to the result, a new tensor.  tsdf and attr share ONE weight, which is why a volume takes an attribute in every
+    call or in none.  The values of attr_image are not examined: a NaN pixel poisons the grid points that read it.
     The update is sequential in b: the same bits on every run, and one call with three views gives the bits of three calls with
     one view each.  mark = (delta, rho) appends a bool volume of the grid points whose decisions a lower precision may take the
     other way: in some view with p_z > 0, u or v within delta of an integer, or |sdf + trunc| or |sdf - trunc| within
@@ -679,6 +684,13 @@ def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, 
     x0 = (lo[0] + torch.arange(nx, device=dev).to(dt) * hs[0]).view(1, 1, nx).expand(nz, ny, nx)
     x1 = (lo[1] + torch.arange(ny, device=dev).to(dt) * hs[1]).view(1, ny, 1).expand(nz, ny, nx)
     x2 = (lo[2] + torch.arange(nz, device=dev).to(dt) * hs[2]).view(nz, 1, 1).expand(nz, ny, nx)
+    if (attr is None) != (attr_image is None):
+        raise ValueError("tsdf_integrate: attr and attr_image go together")
+    if attr is not None:
+        if attr.dim() != 4 or attr.shape[:3] != tsdf.shape or attr_image.shape != (B, H, W, attr.shape[3]):
+            raise ValueError(f"tsdf_integrate: attr [nz,ny,nx,C] and attr_image [{B},{H},{W},C] expected, got {tuple(attr.shape)} / "
+                             f"{tuple(attr_image.shape)}")
+        attr, attr_image = cast(attr).clone(), cast(attr_image)
     tsdf, w = tsdf.detach().clone(), weight.detach().clone()
     marked = torch.zeros(tsdf.shape, dtype=torch.bool, device=dev)
     one, zero = torch.ones((), dtype=dt, device=dev), torch.zeros((), dtype=dt, device=dev)
@@ -698,6 +710,8 @@ def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, 
         sdf = torch.where(valid, d, zero) - dist
         upd = valid & ~(sdf < -trunc_t)
         t = torch.minimum(one, sdf / trunc_t)
+        if attr is not None:
+            attr = torch.where(upd[..., None], (attr * w[..., None] + attr_image[b][i, j]) / (w + 1)[..., None], attr)
         tsdf = torch.where(upd, (tsdf * w + t) / (w + 1), tsdf)
         w1 = w + 1
         if max_weight is not None:
@@ -708,7 +722,8 @@ def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, 
             near = lambda a: (a - torch.round(a)).abs() <= delta
             marked |= front & (near(u) | near(v))
             marked |= valid & (((sdf + trunc_t).abs() <= rho * dist) | ((sdf - trunc_t).abs() <= rho * dist))
-    return (tsdf, w) if mark is None else (tsdf, w, marked)
+    out = (tsdf, w) if mark is None else (tsdf, w, marked)
+    return out if attr is None else out + (attr,)
 
 
 def _mtet_tables():
@@ -763,7 +778,7 @@ def _mtet_tables():
 _MTET = {}
 
 
-def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=1.0):
+def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=1.0, *, attr=None):
     """The level set of a scalar field on a regular grid as a triangle mesh: marching tetrahedra on Kuhn's six-tetrahedron
     split of every cell (an extension here) -> (verts [V,3] in the field's dtype, faces [F,3] int64); not differentiable.
     values [nz,ny,nx] (every dimension >= 2, nx ny nz 7 < 2^31), weight of the same shape or None; grid point (ix,iy,iz) sits at
@@ -786,8 +801,10 @@ def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size
     The geometric normal of every face points from inside to outside.  Kuhn's split is invariant under translation, so the cells
     agree on their shared faces: on a fully observed grid whose border is outside the mesh is closed and every vertex is used; a
     value exactly at the level gives coincident vertices and faces of no area; next to unobserved points the mesh has a boundary
-    and a vertex there may belong to no face.  Vectorised torch on any device / dtype: the definition voge_mtet_* are tested
-    against and the route for everything they do not take."""
+    and a vertex there may belong to no face.  attr [nz,ny,nx,C] (channel last: a colour, or anything else a grid point carries)
+    appends vert_attr [V,C] in the field's dtype: for the vertex on the edge (a, b), with its own t, attr_a + t (attr_b - attr_a), every
+    operation a separate one; both ends of such an edge are observed by construction.  Vectorised torch on any device / dtype: the
+    definition voge_mtet_* are tested against and the route for everything they do not take."""
     v = values.detach()
     if v.dim() != 3 or min(v.shape) < 2:
         raise ValueError(f"marching_tets: values [nz,ny,nx] with every dimension >= 2 expected, got {tuple(v.shape)}")
@@ -797,6 +814,8 @@ def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size
         raise ValueError(f"marching_tets: nx ny nz 7 = {n * 7} does not fit 32-bit indices")
     if weight is not None and weight.shape != v.shape:
         raise ValueError(f"marching_tets: weight {tuple(weight.shape)} does not match values {tuple(v.shape)}")
+    if attr is not None and (attr.dim() != 4 or attr.shape[:3] != v.shape):
+        raise ValueError(f"marching_tets: attr {tuple(attr.shape)} does not match values {tuple(v.shape)}")
     dt, dev = v.dtype, v.device
     if not _MTET:
         _MTET["t"] = _mtet_tables()
@@ -827,6 +846,10 @@ def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size
     t = (torch.as_tensor(level, device=dev).to(dt) - va) / (vb - va)
     pa, pb = lo_t + ia.to(dt) * hs, lo_t + (ia + bits).to(dt) * hs
     verts = pa + t[:, None] * (pb - pa)
+    if attr is not None:
+        rows = attr.detach().to(device=dev, dtype=dt).reshape(n, -1)
+        aa, ab = rows[q], rows[q + bits[:, 0] + bits[:, 1] * nx + bits[:, 2] * (nx * ny)]
+        vert_attr = aa + t[:, None] * (ab - aa)
     # the faces: every cell, six tetrahedra, up to two triangles
     lin = torch.arange(n, device=dev).view(nz, ny, nx)[:-1, :-1, :-1].reshape(-1)
     cins = [sl(ins, c, 1).reshape(-1) for c in range(8)]
@@ -846,7 +869,8 @@ def marching_tets(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size
         all_faces.append(vid[key])
         all_keep.append(keep)
     faces = torch.stack(all_faces, 1)[torch.stack(all_keep, 1)]      # [cells,6,2,3] under [cells,6,2]: the order of the faces
-    return verts, faces.reshape(-1, 3)
+    faces = faces.reshape(-1, 3)
+    return (verts, faces) if attr is None else (verts, faces, vert_attr)
 
 
 def mesh_components(faces, num_verts):

@@ -32,6 +32,22 @@ either (Aggregation.mesh_vertex_normals is, through autograd, for whoever needs 
 integers back on the host (the error word and the number of components: one synchronisation); clean_mesh that pair and then
 the three that size its outputs (V', F' and an error word: a second synchronisation) -- like extraction, one-off steps that
 cannot be captured into a graph.  vertex_normals reads nothing back and can be.
+
+Attributes -- colour, rendered normals, any [B,H,W,C] image a renderer makes -- go through both steps beside the geometry:
+
+    vol = TSDFVolume(lo, ..., channels=C)                       # vol.attr [nz,ny,nx,C] fp32, channel last
+    vol.integrate(depth, cameras, trunc, attr=images)           # images [B,H,W,C]; in every call of such a volume
+    verts, faces, vert_attr = extract_mesh(vol, attr=True)      # vert_attr [V,C] fp32
+    verts, faces, vert_attr = extract_mesh(values, ..., attr=field)      # any field [nz,ny,nx,C] beside any scalar field
+
+One rule each (Aggregation.tsdf_integrate, step 6, and Aggregation.marching_tets): where a view updates a grid point its attribute
+becomes (attr w + pixel) / (w + 1) with the depth's own nearest pixel and the weight the distance is averaged by; the vertex on an
+edge gets attr_a + t (attr_b - attr_a) with the edge's own t.  On a HIP device: voge_tsdf_integrate_attr, still ONE launch with
+the C running averages in registers (16 + 8 C bytes a grid point however many views), and voge_mtet_attr, one launch after the
+emit on its tables; tsdf, weight, verts and faces keep the bits of the calls without an attribute.  The kernels are compiled for
+C <= 8: a volume of more channels on the device is fused by the definition (torch, on the device), a field of more channels is
+carried to the vertices eight channels a launch.  Not here: gradients through either step, bilinear pixel sampling, per-view
+confidence weights, colouring an existing mesh by projecting its vertices into images with a visibility test, textures and UV maps.
 """
 import torch
 
@@ -65,9 +81,12 @@ class TSDFVolume:
 
     voxel_size and resolution are scalars or (x, y, z).  Grid point (ix,iy,iz) sits at lo + (ix hx, iy hy, iz hz);
     tsdf and weight are [nz,ny,nx] fp32 (index order [iz,iy,ix]) and start at 0.  lo and voxel_size are kept as the fp32
-    numbers the kernels see."""
+    numbers the kernels see.  channels = C > 0: the volume also fuses an attribute of C floats a pixel (a colour, a normal) in
+    attr [nz,ny,nx,C] fp32, channel last, zeros at the start, and integrate takes attr= in every call; C = 0: attr is None."""
 
-    def __init__(self, lo, hi=None, voxel_size=None, resolution=None, device="cpu"):
+    def __init__(self, lo, hi=None, voxel_size=None, resolution=None, device="cpu", channels=0):
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 0:
+            raise ValueError(f"TSDFVolume: channels must be an integer >= 0, got {channels!r}")
         if sum(a is not None for a in (hi, voxel_size, resolution)) != 2:
             raise ValueError("TSDFVolume: exactly two of hi / voxel_size / resolution")
         lo = _triple(lo, "lo")
@@ -94,6 +113,8 @@ class TSDFVolume:
         nx, ny, nz = self.resolution
         self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
         self.weight = torch.zeros((nz, ny, nx), dtype=torch.float32, device=self.device)
+        self.channels = channels
+        self.attr = torch.zeros((nz, ny, nx, channels), dtype=torch.float32, device=self.device) if channels else None
 
     @property
     def hi(self):
@@ -102,13 +123,21 @@ class TSDFVolume:
     def to(self, device):
         self.device = torch.device(device)
         self.tsdf, self.weight = self.tsdf.to(self.device), self.weight.to(self.device)
+        if self.attr is not None:
+            self.attr = self.attr.to(self.device)
         return self
 
-    def integrate(self, depth, cameras, trunc, max_weight=None):
+    def integrate(self, depth, cameras, trunc, max_weight=None, attr=None):
         """Fuse depth [B,H,W] (get_depth's: the distance along the unit pixel ray; not finite or <= 0: no surface) seen by
         `cameras` (R, T, focal_length, principal_point, as cameras.pixel_rays reads them; B views or one for all) into the
         volume, in place, the views in their order: Aggregation.tsdf_integrate's rule.  rows= bands and distributed.Stripes
-        are not taken.  One launch on a HIP device, nothing read back; not differentiable.  Returns the volume."""
+        are not taken.  One launch on a HIP device, nothing read back; not differentiable.  Returns the volume.
+        attr [B,H,W,C] -- the layout of the renderer's images and of interpolate_attr's outputs -- is required if and only if the
+        volume has channels = C > 0: the attribute of the depth's own nearest pixel enters vol.attr as a running average under the
+        weight of the distance, wherever the view updates the grid point (step 6 of the rule).  Its VALUES ARE NOT EXAMINED: a NaN
+        pixel poisons the grid points that read it.  ValueError for a missing or an unexpected attr, one that is no tensor, a wrong
+        C or a wrong B, H, W.  C <= 8 on a HIP device: still one launch (voge_tsdf_integrate_attr); more channels there: the
+        definition in torch, on the device.  No bilinear sampling, no per-view confidence weights, no gradients."""
         if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
             raise ValueError(f"integrate: depth [B,H,W] expected, got {tuple(getattr(depth, 'shape', ()))}")
         if not float(trunc) > 0 or float(trunc) == float("inf"):
@@ -117,6 +146,14 @@ class TSDFVolume:
             raise ValueError(f"integrate: max_weight must be >= 1, got {max_weight}")
         B = depth.shape[0]
         dev = self.device
+        if self.channels == 0 and attr is not None:
+            raise ValueError("integrate: attr given, but the volume has channels = 0")
+        if self.channels > 0:
+            if not isinstance(attr, torch.Tensor):
+                raise ValueError(f"integrate: a volume with channels = {self.channels} takes attr [B,H,W,{self.channels}] in every call, got "
+                                 f"{type(attr).__name__}")
+            if tuple(attr.shape) != tuple(depth.shape) + (self.channels,):
+                raise ValueError(f"integrate: attr {list(depth.shape) + [self.channels]} expected, got {tuple(attr.shape)}")
         R = torch.as_tensor(cameras.R, device=dev).detach().to(torch.float32).reshape(-1, 3, 3)
         T = torch.as_tensor(cameras.T, device=dev).detach().to(torch.float32).reshape(-1, 3)
         Bc = max(R.shape[0], T.shape[0])
@@ -133,7 +170,18 @@ class TSDFVolume:
         depth = depth.detach().to(dev)
         # the centres in fp64, rounded once: what |x - c| is measured from
         centre = Aggregation.camera_centres(R.double(), T.double()).to(torch.float32)
-        if dev.type == "cuda":
+        if self.channels > 0:
+            attr = attr.detach().to(device=dev, dtype=torch.float32)
+            if dev.type == "cuda" and self.channels <= ops.MTET_MAX_CHANNELS:
+                ops.tsdf_integrate(self.tsdf, self.weight, depth, R, T, centre, focal, pp, self.lo, self.voxel_size, float(trunc), max_weight,
+                                   attr=self.attr, attr_image=attr)
+            else:      # (the host, or more channels than the kernel is compiled for: the definition, on the volume's device)
+                t, w, a = Aggregation.tsdf_integrate(self.tsdf, self.weight, depth, R, T, focal, pp, self.lo, self.voxel_size, float(trunc),
+                                                     max_weight, centre=centre, attr=self.attr, attr_image=attr)
+                self.tsdf.copy_(t)
+                self.weight.copy_(w)
+                self.attr.copy_(a)
+        elif dev.type == "cuda":
             ops.tsdf_integrate(self.tsdf, self.weight, depth, R, T, centre, focal, pp, self.lo, self.voxel_size, float(trunc), max_weight)
         else:
             t, w = Aggregation.tsdf_integrate(self.tsdf, self.weight, depth, R, T, focal, pp, self.lo, self.voxel_size, float(trunc),
@@ -143,29 +191,45 @@ class TSDFVolume:
         return self
 
 
-def extract_mesh(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=1.0):
+def extract_mesh(values, weight=None, level=0.0, lo=(0.0, 0.0, 0.0), voxel_size=1.0, attr=None):
     """(verts [V,3] fp32, faces [F,3] int32) of the level set of a TSDFVolume (its own weight, lo and voxel_size; the grid
     points no view has seen are unobserved) or of any scalar field values [nz,ny,nx] -- an analytic SDF for example -- with
     grid point (ix,iy,iz) at lo + (ix hx, iy hy, iz hz): Aggregation.marching_tets' rule, inside <=> value < level, normals from
     inside to outside.  An empty result is a pair of [0,3] tensors.  Raises ValueError when a dimension is < 2 or
     nx ny nz 7 >= 2^31.  On a HIP device: three launches, the two totals read back on the host (ONE synchronisation, see the
-    module's header), one launch that writes the mesh.  Not differentiable."""
+    module's header), one launch that writes the mesh.  Not differentiable.
+    attr=True with a TSDFVolume of channels > 0 (its own attr), or attr=field [nz,ny,nx,C] beside any scalar field (an analytic
+    colour beside an analytic SDF): the result is (verts, faces, vert_attr [V,C] fp32), the vertex on an edge getting
+    attr_a + t (attr_b - attr_a) with the edge's own t -- Aggregation.marching_tets' rule; verts and faces are those of the call
+    without attr, and an empty mesh has a vert_attr of [0,C].  On a HIP device: one more launch (voge_mtet_attr; one per eight
+    channels).  ValueError for attr=True without a volume that has channels.  Not differentiable either; no textures or UV maps,
+    and no colouring of an existing mesh by projecting its vertices into images."""
     if isinstance(values, TSDFVolume):
         vol = values
         values, weight, lo, voxel_size = vol.tsdf, vol.weight, vol.lo, vol.voxel_size
+        if attr is True:
+            if vol.channels == 0:
+                raise ValueError("extract_mesh: attr=True, but the volume has channels = 0")
+            attr = vol.attr
+    if attr is True:
+        raise ValueError("extract_mesh: attr=True needs a TSDFVolume with channels > 0; give the field [nz,ny,nx,C] itself")
     if not isinstance(values, torch.Tensor) or values.dim() != 3:
         raise ValueError(f"extract_mesh: a TSDFVolume or values [nz,ny,nx] expected, got {tuple(getattr(values, 'shape', ()))}")
     nz, ny, nx = values.shape
     _check_dims(nx, ny, nz, "extract_mesh")
     if weight is not None and (not isinstance(weight, torch.Tensor) or weight.shape != values.shape):
         raise ValueError(f"extract_mesh: weight must match values {tuple(values.shape)}")
+    if attr is not None and (not isinstance(attr, torch.Tensor) or attr.dim() != 4 or attr.shape[:3] != values.shape or attr.shape[3] < 1):
+        raise ValueError(f"extract_mesh: attr [nz,ny,nx,C] over values {tuple(values.shape)} expected, got {tuple(getattr(attr, 'shape', ()))}")
     lo, h = _triple(lo, "lo"), _triple(voxel_size, "voxel_size")
     values = values.detach()
     w = None if weight is None else weight.detach().to(values.device)
+    if attr is not None:
+        attr = attr.detach().to(values.device)
     if values.is_cuda and values.dtype == torch.float32:
-        return ops.marching_tets(values, w, float(level), lo, h)
-    verts, faces = Aggregation.marching_tets(values, w, float(level), lo, h)
-    return verts.to(torch.float32), faces.to(torch.int32)
+        return ops.marching_tets(values, w, float(level), lo, h, attr=attr)
+    out = Aggregation.marching_tets(values, w, float(level), lo, h, attr=attr)
+    return (out[0].to(torch.float32), out[1].to(torch.int32)) + tuple(a.to(torch.float32) for a in out[2:])
 
 
 def _check_faces(faces, what):

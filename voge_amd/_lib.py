@@ -147,6 +147,9 @@ SIGNATURES = {
     "voge_mtet_count": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] + [_c_void_p] * 7),
     "voge_mtet_scan": (_c_int, [_c_void_p] * 2 + [_c_long] + [_c_void_p] * 2),
     "voge_mtet_emit": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] * 7 + [_c_void_p] * 6 + [_c_long] * 2 + [_c_void_p] * 3),
+    "voge_tsdf_integrate_attr": (_c_int, [_c_void_p] * 3 + [_c_int] * 4 + [_c_float] * 6 + [_c_void_p] * 2 + [_c_int] * 3 + [_c_void_p] * 5
+                                 + [_c_float, _c_float, _c_void_p]),
+    "voge_mtet_attr": (_c_int, [_c_void_p] + [_c_int] * 3 + [_c_float, _c_void_p, _c_int] + [_c_void_p] * 3 + [_c_long] + [_c_void_p] * 2),
     "voge_mesh_components": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_void_p] * 5 + [_c_int, _c_void_p]),
     "voge_mesh_clean_scan": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_void_p] * 7 + [_c_int, _c_void_p]),
     "voge_mesh_clean_emit": (_c_int, [_c_void_p] * 2 + [_c_long] * 2 + [_c_void_p] * 5 + [_c_long] * 2 + [_c_void_p] * 5),

@@ -34,6 +34,19 @@
 //     operations in fp32.  Tetrahedra and the 16 cases: kMtCorner and kMtEdge below, derived by Aggregation._mtet_tables.
 //     Every write is guarded by V and F, the sizes the caller allocated.
 // Indices are 32-bit: nx ny nz 7 < 2^31 (the vertex ids), so a face offset, at most 12 nx ny nz < 2^32, fits an unsigned one.
+//
+// Attributes (colour, or any C floats a pixel carries), fused beside the distance and carried to the vertices; C is a compile-time
+// number, 1 .. 8, the volume [nz,ny,nx,C] and the images [B,H,W,C] are channel last.  Both kernels are gathers: no atomics.
+//   voge_tsdf_integrate_attr, one launch.  tsdf_integrate_attr_kernel<C> is tsdf_integrate_kernel's loop, operation by operation
+//     (tsdf and weight come out with that kernel's bits), with C more accumulators in registers: a grid point's C floats are read
+//     once and written once, a wave's rows are one contiguous span of 256 C bytes, 16 + 8 C bytes a grid point however many
+//     views.  The attribute pixel -- the depth's own nearest pixel -- is read only under the last condition, where the view
+//     updates the point, so a wave that skips a view still skips all of it:  attr <- (attr w + pixel) / (w + 1) per channel,
+//     with the weight BEFORE its own update, every operation separate.  The values of the pixel are not examined.
+//   voge_mtet_attr, one launch after voge_mtet_emit, a grid point per thread, on emit's tables (edge_mask, vloc, block_v).  A point
+//     whose mask is zero returns after one byte.  For every set bit d it recomputes t = (level - v_a) / (v_b - v_a) and writes the
+//     C floats attr_a + t (attr_b - attr_a) of vertex voff[q] + popcount(mask & ((1 << (d - 1)) - 1)): emit's numbering.  Every
+//     write is guarded by V.
 #include <math.h>
 
 #include "voge_common.h"
@@ -279,6 +292,91 @@ mtet_emit_kernel(const float *__restrict__ values, const float *__restrict__ wei
   }
 }
 
+// ---- attributes ---------------------------------------------------------------------------------------------------------------
+
+constexpr int kMtMaxChannels = 8;      // the channels of one launch; ops.MTET_MAX_CHANNELS
+
+// tsdf_integrate_kernel with C attribute accumulators: the projection, the decisions and the update of tsdf and w are that kernel's,
+// line by line; only the block under the last condition is new
+template <int C>
+__global__ void __launch_bounds__(256)
+tsdf_integrate_attr_kernel(float *__restrict__ tsdf, float *__restrict__ weight, float *__restrict__ attr, const MtGrid g,
+                           const float *__restrict__ depth, const float *__restrict__ image, const int B, const int H, const int W,
+                           const float *__restrict__ R, const float *__restrict__ T, const float *__restrict__ centre,
+                           const float *__restrict__ focal, const float *__restrict__ pp, const float trunc, const float max_weight) {
+  const uint32_t n = (uint32_t)g.nx * (uint32_t)g.ny * (uint32_t)g.nz;      // (below 2^31 / 7: the host's mt_dims -- 32-bit index arithmetic)
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t row = q / (uint32_t)g.nx;
+  const int ix = (int)(q - row * (uint32_t)g.nx), iz = (int)(row / (uint32_t)g.ny), iy = (int)(row - (uint32_t)iz * (uint32_t)g.ny);
+  const float x0 = g.lox + (float)ix * g.hx, x1 = g.loy + (float)iy * g.hy, x2 = g.loz + (float)iz * g.hz;
+  float val = tsdf[q], w = weight[q];
+  float *const arow = attr + (size_t)q * C;
+  float a[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) a[c] = arow[c];
+  const float fW = (float)W, fH = (float)H;
+  for (int b = 0; b < B; ++b) {
+    const float *Rb = R + 9 * (size_t)b, *Tb = T + 3 * (size_t)b, *cb = centre + 3 * (size_t)b;
+    const float pz = ((x0 * Rb[2] + x1 * Rb[5]) + x2 * Rb[8]) + Tb[2];
+    if (!(pz > 0.0f)) continue;
+    const float px = ((x0 * Rb[0] + x1 * Rb[3]) + x2 * Rb[6]) + Tb[0];
+    const float py = ((x0 * Rb[1] + x1 * Rb[4]) + x2 * Rb[7]) + Tb[1];
+    const float u = pp[2 * b] - (focal[2 * b] * px) / pz;
+    const float v = pp[2 * b + 1] - (focal[2 * b + 1] * py) / pz;
+    if (!(u >= 0.0f && u < fW && v >= 0.0f && v < fH)) continue;      // (a NaN fails: the definition's comparisons)
+    const int j = (int)floorf(u), i = (int)floorf(v);                  // in [0, W) x [0, H) by the test above
+    const size_t pixel = ((size_t)b * H + i) * W + j;
+    const float d = depth[pixel];
+    if (!(d > 0.0f && d < INFINITY)) continue;
+    const float dx = x0 - cb[0], dy = x1 - cb[1], dz = x2 - cb[2];
+    const float sdf = d - sqrtf((dx * dx + dy * dy) + dz * dz);
+    if (sdf < -trunc) continue;
+    const float *prow = image + pixel * C;      // (the view updates the point: only now is the pixel's attribute read)
+    const float w1 = w + 1.0f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) a[c] = (a[c] * w + prow[c]) / w1;
+    val = (val * w + fminf(1.0f, sdf / trunc)) / (w + 1.0f);
+    w = max_weight > 0.0f ? fminf(w + 1.0f, max_weight) : w + 1.0f;
+  }
+  tsdf[q] = val;
+  weight[q] = w;
+#pragma unroll
+  for (int c = 0; c < C; ++c) arow[c] = a[c];
+}
+
+// the attribute of every vertex mtet_emit_kernel numbered, from the tables it numbered them by
+template <int C>
+__global__ void __launch_bounds__(256)
+mtet_attr_kernel(const float *__restrict__ values, const int nx, const int ny, const int nz, const float level,
+                 const float *__restrict__ attr, const uint8_t *__restrict__ edge_mask, const uint16_t *__restrict__ vloc,
+                 const uint32_t *__restrict__ block_v, const long V, float *__restrict__ vert_attr) {
+  const uint32_t n = (uint32_t)nx * (uint32_t)ny * (uint32_t)nz;      // (below 2^31 / 7: the host's mt_dims -- 32-bit index arithmetic)
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t mask = edge_mask[q];
+  if (!mask) return;
+  const float va = values[q];
+  const float *const arow = attr + (size_t)q * C;
+  float aa[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) aa[c] = arow[c];
+  const long voff = (long)block_v[q / kMtBlock] + (long)vloc[q];
+#pragma unroll
+  for (int d = 1; d < 8; ++d) {
+    if (!((mask >> (d - 1)) & 1u)) continue;      // (a set bit: the other end is inside the grid -- the count kernel's test)
+    const long id = voff + (long)__popc(mask & ((1u << (d - 1)) - 1u));
+    if (id >= V) continue;
+    const uint32_t qb = q + mt_offset(d, nx, ny);
+    const float vb = values[qb];
+    const float t = (level - va) / (vb - va);
+    const float *const brow = attr + (size_t)qb * C;
+    float *const o = vert_attr + (size_t)id * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = aa[c] + t * (brow[c] - aa[c]);
+  }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
 // 0, or the error of a grid's dimensions: every one >= 2, nx ny nz 7 < 2^31
@@ -348,5 +446,57 @@ extern "C" int voge_mtet_emit(const float *values, const float *weight, int nx, 
   const size_t n = (size_t)nx * ny * nz;
   hipLaunchKernelGGL(mtet_emit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, values, weight, g, level, edge_mask,
                      face_count, vloc, floc, block_v, block_f, V, F, verts, faces);
+  return launch_status();
+}
+
+// one case of the switch over the channels: kernel<C>
+#define VOGE_MT_CHANNELS(c, launch) \
+  switch (c) {                      \
+    case 1: launch(1); break;       \
+    case 2: launch(2); break;       \
+    case 3: launch(3); break;       \
+    case 4: launch(4); break;       \
+    case 5: launch(5); break;       \
+    case 6: launch(6); break;       \
+    case 7: launch(7); break;       \
+    default: launch(8); break;      \
+  }
+
+extern "C" int voge_tsdf_integrate_attr(float *tsdf, float *weight, float *attr, int C, int nx, int ny, int nz, float lox, float loy,
+                                        float loz, float hx, float hy, float hz, const float *depth, const float *attr_image, int B, int H,
+                                        int W, const float *R, const float *T, const float *centre, const float *focal, const float *pp,
+                                        float trunc, float max_weight, voge_stream_t stream) {
+  const int de = mt_dims(nx, ny, nz);
+  if (de) return de;
+  if (C < 1 || C > kMtMaxChannels || B < 0 || H < 1 || W < 1 || !mt_pos(trunc) || !mt_pos(hx) || !mt_pos(hy) || !mt_pos(hz) ||
+      !mt_fin(lox) || !mt_fin(loy) || !mt_fin(loz) || max_weight != max_weight)
+    return VOGE_ERR_BAD_ARG;
+  if (!tsdf || !weight || !attr) return VOGE_ERR_BAD_ARG;
+  if (B == 0) return 0;
+  if (!depth || !attr_image || !R || !T || !centre || !focal || !pp) return VOGE_ERR_BAD_ARG;
+  const MtGrid g = {nx, ny, nz, lox, loy, loz, hx, hy, hz};
+  const size_t n = (size_t)nx * ny * nz;
+#define VOGE_MT_LAUNCH(c)                                                                                                                  \
+  hipLaunchKernelGGL(tsdf_integrate_attr_kernel<c>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tsdf, weight, attr, \
+                     g, depth, attr_image, B, H, W, R, T, centre, focal, pp, trunc, max_weight)
+  VOGE_MT_CHANNELS(C, VOGE_MT_LAUNCH)
+#undef VOGE_MT_LAUNCH
+  return launch_status();
+}
+
+extern "C" int voge_mtet_attr(const float *values, int nx, int ny, int nz, float level, const float *attr, int C, const uint8_t *edge_mask,
+                              const uint16_t *vloc, const uint32_t *block_v, long V, float *vert_attr, voge_stream_t stream) {
+  const int de = mt_dims(nx, ny, nz);
+  if (de) return de;
+  if (C < 1 || C > kMtMaxChannels || V < 0) return VOGE_ERR_BAD_ARG;
+  if (V > kMtMaxKeys) return VOGE_ERR_K_TOO_LARGE;
+  if (!values || !attr || !edge_mask || !vloc || !block_v || level != level || (V > 0 && !vert_attr)) return VOGE_ERR_BAD_ARG;
+  if (V == 0) return 0;
+  const size_t n = (size_t)nx * ny * nz;
+#define VOGE_MT_LAUNCH(c)                                                                                                                  \
+  hipLaunchKernelGGL(mtet_attr_kernel<c>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, values, nx, ny, nz, level, \
+                     attr, edge_mask, vloc, block_v, V, vert_attr)
+  VOGE_MT_CHANNELS(C, VOGE_MT_LAUNCH)
+#undef VOGE_MT_LAUNCH
   return launch_status();
 }

@@ -2299,6 +2299,7 @@ def mesh_sample(verts, sampler, u, return_normals=False, return_areas=False):
 
 MTET_BLOCK = 256      # kMtBlock of meshing.hip: the grid points of one scan block
 MTET_TOP = 1024       # kMtTop: the block totals one round of the top-level scan takes (the tests build grids around both)
+MTET_MAX_CHANNELS = 8      # kMtMaxChannels: the attribute channels voge_tsdf_integrate_attr and voge_mtet_attr are compiled for
 
 
 def _grid_volume(t, name):
@@ -2308,18 +2309,35 @@ def _grid_volume(t, name):
     return t
 
 
-def tsdf_integrate(tsdf, weight, depth, R, T, centre, focal, pp, lo, voxel_size, trunc, max_weight=None):
+def tsdf_integrate(tsdf, weight, depth, R, T, centre, focal, pp, lo, voxel_size, trunc, max_weight=None, attr=None, attr_image=None):
     """Fuse depth [B,H,W] into tsdf / weight [nz,ny,nx] IN PLACE (extension; voge_tsdf_integrate): the values of
     Aggregation.tsdf_integrate in fp32.  R [B,3,3], T [B,3], centre [B,3], focal [B,2], pp [B,2] on the volume's device; lo and
-    voxel_size three numbers each.  One launch on the current stream, nothing read back; not differentiable."""
+    voxel_size three numbers each.  One launch on the current stream, nothing read back; not differentiable.  attr [nz,ny,nx,C]
+    with attr_image [B,H,W,C], 1 <= C <= MTET_MAX_CHANNELS, both or neither: voge_tsdf_integrate_attr, still one launch, attr IN
+    PLACE as well and appended to the result; tsdf and weight get the bits of the call without them."""
     tsdf, weight = _grid_volume(tsdf, "tsdf"), _grid_volume(weight, "weight")
     if weight.shape != tsdf.shape or weight.device != tsdf.device:
         raise ValueError(f"tsdf_integrate: weight {tuple(weight.shape)} on {weight.device} does not match tsdf {tuple(tsdf.shape)}")
     dev = tsdf.device
+    if (attr is None) != (attr_image is None):
+        raise ValueError("tsdf_integrate: attr and attr_image go together")
+    if attr is not None:
+        if (not isinstance(attr, torch.Tensor) or not attr.is_cuda or attr.dtype != torch.float32 or attr.dim() != 4
+                or not attr.is_contiguous()):
+            raise _lib.VogeHipError("attr: a contiguous fp32 [nz,ny,nx,C] tensor on a HIP device expected (no CPU fallback)")
+        C = attr.shape[3]
+        if attr.shape[:3] != tsdf.shape or attr.device != dev or not 1 <= C <= MTET_MAX_CHANNELS:
+            raise ValueError(f"tsdf_integrate: attr {tuple(attr.shape)} on {attr.device} does not match tsdf {tuple(tsdf.shape)} with 1 .. "
+                             f"{MTET_MAX_CHANNELS} channels")
+        attr_image = _dev(attr_image.detach(), torch.float32, "attr_image")
+        if attr_image.device != dev:
+            raise _lib.VogeHipError(f"tsdf_integrate: attr_image on {attr_image.device}, the volume on {dev}")
     depth = _dev(depth, torch.float32, "depth")
     if depth.dim() != 3:
         raise ValueError(f"tsdf_integrate: depth [B,H,W] expected, got {tuple(depth.shape)}")
     B, H, W = depth.shape
+    if attr is not None and tuple(attr_image.shape) != (B, H, W, C):
+        raise ValueError(f"tsdf_integrate: attr_image {[B, H, W, C]} expected, got {tuple(attr_image.shape)}")
     cam = []
     for t_, shape, name in ((R, (B, 3, 3), "R"), (T, (B, 3), "T"), (centre, (B, 3), "centre"), (focal, (B, 2), "focal"), (pp, (B, 2), "pp")):
         t_ = _dev(t_.detach(), torch.float32, name)
@@ -2332,21 +2350,34 @@ def tsdf_integrate(tsdf, weight, depth, R, T, centre, focal, pp, lo, voxel_size,
         raise _lib.VogeHipError(f"tsdf_integrate: depth on {depth.device}, the volume on {dev}")
     nz, ny, nx = tsdf.shape
     lib = _lib.load()
+    grid = [float(x) for x in lo] + [float(x) for x in voxel_size]
+    tail = [_p(t_) for t_ in cam] + [float(trunc), 0.0 if max_weight is None else float(max_weight)]
+    if attr is not None:
+        with _on(dev):
+            rc = lib.voge_tsdf_integrate_attr(_p(tsdf), _p(weight), _p(attr), C, nx, ny, nz, *grid, _p(depth), _p(attr_image), B, H, W, *tail,
+                                              _stream())
+        _lib.check(rc, "voge_tsdf_integrate_attr")
+        return tsdf, weight, attr
     with _on(dev):
-        rc = lib.voge_tsdf_integrate(_p(tsdf), _p(weight), nx, ny, nz, *[float(x) for x in lo], *[float(x) for x in voxel_size], _p(depth), B, H, W,
-                                     *[_p(t_) for t_ in cam], float(trunc), 0.0 if max_weight is None else float(max_weight), _stream())
+        rc = lib.voge_tsdf_integrate(_p(tsdf), _p(weight), nx, ny, nz, *grid, _p(depth), B, H, W, *tail, _stream())
     _lib.check(rc, "voge_tsdf_integrate")
     return tsdf, weight
 
 
-def marching_tets(values, weight, level, lo, voxel_size, return_tables=False):
+def marching_tets(values, weight, level, lo, voxel_size, return_tables=False, attr=None):
     """(verts [V,3] fp32, faces [F,3] int32) of the level set of values [nz,ny,nx] fp32 on a HIP device (extension; voge_mtet_count /
     _scan / _emit): the values of Aggregation.marching_tets.  Count and scan on the current stream, then the two totals are read
     back on the host -- ONE synchronisation, what sizes the outputs -- and one launch writes the mesh.  Not differentiable, not
-    capturable.  return_tables=True appends (edge_mask, face_count) for the tests."""
+    capturable.  return_tables=True appends (edge_mask, face_count) for the tests.  attr [nz,ny,nx,C] fp32 on the same device
+    appends vert_attr [V,C] after the faces (voge_mtet_attr: one more launch on the tables of the emit, one per MTET_MAX_CHANNELS
+    channels); the mesh is the one of the call without it, bit for bit."""
     v = _dev(values.detach(), torch.float32, "values")
     if v.dim() != 3:
         raise ValueError(f"marching_tets: values [nz,ny,nx] expected, got {tuple(v.shape)}")
+    if attr is not None:
+        attr = _dev(attr.detach(), torch.float32, "attr")
+        if attr.dim() != 4 or attr.shape[:3] != v.shape or attr.shape[3] < 1 or attr.device != v.device:
+            raise ValueError(f"marching_tets: attr {tuple(attr.shape)} on {attr.device} does not match values {tuple(v.shape)} on {v.device}")
     w = None
     if weight is not None:
         w = _dev(weight.detach(), torch.float32, "weight")
@@ -2379,7 +2410,19 @@ def marching_tets(values, weight, level, lo, voxel_size, return_tables=False):
         rc = lib.voge_mtet_emit(_p(v), _p(w), nx, ny, nz, float(level), *grid, _p(edge_mask), _p(face_count), _p(loc[0]), _p(loc[1]),
                                 _p(blocks[0]), _p(blocks[1]), V, F, _p(verts) if V else None, _p(faces) if F else None, st)
         _lib.check(rc, "voge_mtet_emit")
-    return (verts, faces, edge_mask, face_count) if return_tables else (verts, faces)
+        if attr is not None:
+            C = attr.shape[3]
+            parts = []
+            for c0 in range(0, C, MTET_MAX_CHANNELS):      # (more channels than one launch takes: a launch per slice of them)
+                a = attr if C <= MTET_MAX_CHANNELS else attr[..., c0:c0 + MTET_MAX_CHANNELS].contiguous()
+                part = torch.empty((V, a.shape[3]), dtype=torch.float32, device=dev)
+                rc = lib.voge_mtet_attr(_p(v), nx, ny, nz, float(level), _p(a), a.shape[3], _p(edge_mask), _p(loc[0]), _p(blocks[0]), V,
+                                        _p(part) if V else None, st)
+                _lib.check(rc, "voge_mtet_attr")
+                parts.append(part)
+            vert_attr = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+    out = (verts, faces) + ((edge_mask, face_count) if return_tables else ())
+    return out if attr is None else out + (vert_attr,)
 
 
 MESH_CLEAN_BLOCK = 256      # kMcBlock of mesh_clean.hip: the flags of one scan block
