@@ -15,6 +15,11 @@ vertices, they follow clean_mesh through its vert_index, save_off writes them (a
 are rendered from the first camera: the report ends with "round trip", the mean absolute difference of that image from the first
 colour image.  LAST then holds vert_attr, colour_range (the least and the greatest value of the fused images) and round_trip.
 
+The extracted (and cleaned) mesh is then scored against the scene's own points, the Gaussians' centres, with the exact
+point-to-mesh search in both roles: the mean distance from every point to the mesh (completeness: how much of the scene the mesh
+covers) and from every face to its nearest point (accuracy: how far the mesh strays from the scene).  Both take route="grid",
+which has no pair cap: the million faces of a 256^3 volume are scored whole, neither kept small nor sampled.  LAST holds both.
+
 usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]
                                   [--colour]"""
 import argparse
@@ -26,6 +31,7 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
+from VoGE.Losses import closest_faces                                                  # noqa: E402
 from VoGE.Converter.IO import save_off                                                 # noqa: E402
 from VoGE.Meshes import GaussianMeshesNaive                                            # noqa: E402
 from VoGE.Converter.Converters import normal_mesh_converter                            # noqa: E402
@@ -45,6 +51,19 @@ def mesh_report(verts, faces):
     _, counts = np.unique(e[:, 0] * max(len(verts), 1) + e[:, 1], return_counts=True)
     used = len(np.unique(f))
     return len(verts), len(f), used - len(counts) + len(f), int((counts == 1).sum())
+
+
+def score_mesh(mesh_verts, faces, points):
+    """(completeness, accuracy): the mean distance from every point to the mesh and from every face to its nearest point, exact,
+    by the grid route (Losses.closest_faces for the first, the node's second search for the second)"""
+    from voge_amd import ops
+    if len(faces) == 0 or len(points) == 0:
+        return float("nan"), float("nan")
+    d2 = closest_faces(points, mesh_verts, faces, route="grid")[0]
+    _, _, _, point_idx, bary_f = ops.point_mesh(mesh_verts, faces.int(), points, route="grid")
+    tri = mesh_verts[faces.long()]
+    q = (bary_f[:, :, None] * tri).sum(1)                      # the closest point of every face to its nearest scene point
+    return float(d2.sqrt().mean()), float((points[point_idx.long()] - q).norm(dim=-1).mean())
 
 
 def round_trip(renderer, mesh_verts, faces, vert_attr, R, T, first, device):
@@ -102,6 +121,11 @@ def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:
         V, F, chi, boundary = mesh_report(mesh_verts, faces)
         report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
         print(f"cleaned (keep_largest {keep_largest}, min_faces {min_faces}): {before} -> {connected_components(faces, V)[2]} components: {report}")
+    completeness, accuracy = score_mesh(mesh_verts, faces, verts.to(device=device, dtype=torch.float32))
+    report += f", points -> mesh {completeness:.5f}, faces -> points {accuracy:.5f}"
+    print(f"scored against the scene's {len(verts)} points (closest_faces, route=\"grid\", {len(faces)} faces): mean distance points -> mesh "
+          f"{completeness:.5f} (completeness), faces -> points {accuracy:.5f} (accuracy)")
+    LAST.update(completeness=completeness, accuracy=accuracy)
     if colour:
         diff = round_trip(renderer, mesh_verts, faces, vert_attr, R[:1], T[:1], images[:1], device)
         report += f", round trip mean |dimage| {diff:.4f}"

@@ -9,9 +9,10 @@ the exact distance between the mesh and the cloud -- every point to its nearest 
 plus the mesh regularisers.  Unlike a chamfer distance between surface samples the first term is 0 on a perfect fit, does not
 change with a draw and pulls no vertex along the surface.  With --graph the whole iteration (both searches, the loss, the
 backward, the regularisers and the Adam step) is captured once into a HIP graph and replayed: nothing in it is read back on the
-host.  closest_faces scores the fit before and after: the distance from every scanned point to the mesh.
+host.  closest_faces scores the fit before and after: the distance from every scanned point to the mesh.  --route brute | grid
+chooses the search of both (default: by the number of pairs); the two return the same bits, and both can be captured.
 
-usage: python demo/FitMeshToScan.py [--iters 500] [--level 4] [--points 8171] [--graph] [--save fit.off]"""
+usage: python demo/FitMeshToScan.py [--iters 500] [--level 4] [--points 8171] [--graph] [--route grid] [--save fit.off]"""
 import argparse
 import os
 import sys
@@ -44,13 +45,14 @@ def scan_points(n=None, seed=0):
     return v.astype(np.float32)
 
 
-def score(points, verts, faces):
+def score(points, verts, faces, route=None):
     """(mean, median, largest) distance from the points to the mesh"""
-    d = closest_faces(points, verts.detach(), faces)[0].sqrt()
+    d = closest_faces(points, verts.detach(), faces, route=route)[0].sqrt()
     return float(d.mean()), float(d.median()), float(d.max())
 
 
-def fit(iters=500, level=4, points=None, lr=5e-3, graph=False, device="cuda:0", quiet=False, save=None, weights=None, log_every=100):
+def fit(iters=500, level=4, points=None, lr=5e-3, graph=False, device="cuda:0", quiet=False, save=None, weights=None, log_every=100,
+        route=None):
     w = dict(WEIGHTS, **(weights or {}))
     sv, sf = ico_sphere(level)
     verts = torch.from_numpy(sv * np.float32(0.6)).to(device).requires_grad_(True)
@@ -63,14 +65,14 @@ def fit(iters=500, level=4, points=None, lr=5e-3, graph=False, device="cuda:0", 
 
     def iteration():
         opt.zero_grad(set_to_none=True)
-        dist = point_mesh_face_distance(verts, faces, pts)
+        dist = point_mesh_face_distance(verts, faces, pts, route=route)
         terms = dict(zip(("edge", "laplacian", "normal"), mesh_regularisers(verts, topo, terms=on)))
         reg = sum(w[k] * terms[k] for k in on)
         (dist + reg).backward()
         opt.step()
         losses.copy_(torch.stack((dist.detach(), torch.as_tensor(reg, device=device).detach())))
 
-    before = score(pts, verts, faces)
+    before = score(pts, verts, faces, route)
     replay = iteration
     if graph:
         start = verts.detach().clone()
@@ -109,7 +111,7 @@ def fit(iters=500, level=4, points=None, lr=5e-3, graph=False, device="cuda:0", 
                 print(f"iteration {it:5d}: point-mesh distance {history[-1][1]:.6f}, regularisers {history[-1][2]:.6f}")
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
-    after = score(pts, verts, faces)
+    after = score(pts, verts, faces, route)
     if not quiet:
         for label, s in (("before", before), ("after", after)):
             print(f"closest_faces {label}: mean distance {s[0]:.5f}, median {s[1]:.5f}, largest {s[2]:.5f} ({len(pts)} points, {len(faces)} faces)")
@@ -128,6 +130,7 @@ if __name__ == "__main__":
     ap.add_argument("--points", type=int, default=None, help="a random subset of the scan (default: all 8171 points)")
     ap.add_argument("--lr", type=float, default=5e-3)
     ap.add_argument("--graph", action="store_true", help="replay the iteration as a HIP graph")
+    ap.add_argument("--route", choices=("brute", "grid"), default=None, help="the search of the distance term (default: by the number of pairs)")
     ap.add_argument("--save", default=None, help="write the fitted mesh as an OFF file")
     a = ap.parse_args()
-    fit(iters=a.iters, level=a.level, points=a.points, lr=a.lr, graph=a.graph, save=a.save)
+    fit(iters=a.iters, level=a.level, points=a.points, lr=a.lr, graph=a.graph, save=a.save, route=a.route)

@@ -1034,7 +1034,7 @@ int voge_mesh_sample_bwd(const float *verts, long V, const int32_t *faces, long 
  * triangles' records (16 floats, built by the workgroup while staging) tiled through LDS 256 at a time, the four waves take a quarter
  * of a tile each and meet in LDS.  A face that names a vertex outside [0, V) never wins.  Nothing is read back: capturable.
  * P == 0: success, nothing is launched.  V or F below 1, a size above 2^28 - 1, a null pointer: VOGE_ERR_BAD_ARG; P F above the pair
- * cap 2^38 (an exact search is a brute force; larger pairs go through sampled points and voge_chamfer_fwd): VOGE_ERR_K_TOO_LARGE --
+ * cap 2^38 (this search is a brute force; larger pairs go through voge_closest_faces_grid below): VOGE_ERR_K_TOO_LARGE --
  * all before any HIP call.
  */
 int voge_closest_faces(const float *points, long P, const float *verts, long V, const int32_t *faces, long F, int32_t *face_idx,
@@ -1061,8 +1061,8 @@ int voge_closest_faces(const float *points, long P, const float *verts, long V, 
  * own term in fp64 and rounds once.  An index outside its range is skipped.  No float atomics.
  * workspace: voge_point_mesh_workspace_bytes(V, F, P) bytes on a 16-byte boundary serves both calls (0: a size below 1 or above
  * 2^28 - 1).  Such a size, an unknown flag, a null pointer (point_idx and bary_f may be null with flags bit 1), a workspace that is
- * null or off the 16-byte boundary: VOGE_ERR_BAD_ARG; P F above the pair cap 2^38: VOGE_ERR_K_TOO_LARGE; a workspace too small:
- * VOGE_ERR_WORKSPACE -- all before any HIP call.
+ * null or off the 16-byte boundary: VOGE_ERR_BAD_ARG; P F above the pair cap 2^38: VOGE_ERR_K_TOO_LARGE (the backward with flags
+ * bit 2 -- pairs of voge_point_mesh_fwd_grid -- has no pair cap); a workspace too small: VOGE_ERR_WORKSPACE -- all before any HIP call.
  */
 size_t voge_point_mesh_workspace_bytes(long V, long F, long P);
 int voge_point_mesh_fwd(const float *verts, long V, const int32_t *faces, long F, const float *points, long P, int flags,
@@ -1072,6 +1072,32 @@ int voge_point_mesh_bwd(const float *verts, long V, const int32_t *faces, long F
                         const int32_t *face_idx, const float *bary_p, const int32_t *point_idx, const float *bary_f,
                         const int32_t *meta, const float *g_loss, int flags, float *g_verts, float *g_points, void *workspace,
                         size_t workspace_bytes, voge_stream_t stream);
+
+/*
+ * The grid route of the two searches above (EXTENSION): the same outputs, element for element the BITS of voge_closest_faces /
+ * voge_point_mesh_fwd on the same input -- the winner is the smallest key (d2 bits << 32 | index) over the candidates, and the
+ * search only proves that it never skips an item that could hold it --, without the pair cap: P F may exceed 2^38.  A uniform
+ * grid over the box of verts and points is chosen ON THE DEVICE (the rule of voge_nearest_points with n = max(F, P), and a cell
+ * of at least the mean largest bounding-box extent of a face; cell_size > 0 asks for a cell of that size, 0 for the default);
+ * every triangle is binned by the centre of its bounding box, the ones whose half-extent exceeds the cell go to a list every
+ * point tests by brute force; a point walks rings of cells over the cell-ordered records, a triangle rings over the cell-ordered
+ * points, and each stops by a proven bound (voge_amd/csrc/point_mesh_grid.h).  Nothing is read back, the workspace and every
+ * launch are sized by (V, F, P) alone: capturable.  voge_point_mesh_fwd_grid's flags, outputs, loss and meta are
+ * voge_point_mesh_fwd's; the backward is voge_point_mesh_bwd, whose flags bit 2 (4) says that the pairs came from this route and
+ * lifts its pair cap.  A mesh of mostly large triangles is a brute force with extra steps, and one huge triangle idles its
+ * wave's other lanes: correct and bounded, slow.
+ * workspace: voge_point_mesh_grid_workspace_bytes(V, F, P) bytes on a 16-byte boundary (0: a size below 1 or above 2^28 - 1); it
+ * also serves the backward.  voge_closest_faces_grid with P == 0: success, nothing is launched.  A size out of range, an unknown
+ * flag, a cell_size that is negative or not finite, a null pointer, a workspace that is null or off the 16-byte boundary:
+ * VOGE_ERR_BAD_ARG; a workspace too small: VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+size_t voge_point_mesh_grid_workspace_bytes(long V, long F, long P);
+int voge_closest_faces_grid(const float *points, long P, const float *verts, long V, const int32_t *faces, long F, float cell_size,
+                            int32_t *face_idx, float *d2, float *bary, void *workspace, size_t workspace_bytes,
+                            voge_stream_t stream);
+int voge_point_mesh_fwd_grid(const float *verts, long V, const int32_t *faces, long F, const float *points, long P, int flags,
+                             float cell_size, float *loss, int32_t *face_idx, float *bary_p, int32_t *point_idx, float *bary_f,
+                             int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream);
 
 /*
  * Depth maps fused into a truncated signed distance volume (EXTENSION: the reference has no mesh extraction; this and

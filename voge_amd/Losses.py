@@ -387,15 +387,28 @@ def _checked_faces(faces, V, what, width=3):
     return faces
 
 
-def closest_faces(points, verts, faces):
+_POINT_MESH_ROUTES = (None, "brute", "grid")
+
+
+def _checked_route(route, what):
+    if route not in _POINT_MESH_ROUTES:
+        raise ValueError(f"{what}: route must be None, 'brute' or 'grid', got {route!r}")
+    return route
+
+
+def closest_faces(points, verts, faces, route=None):
     """For every row of points [P,3] the nearest triangle of the mesh (verts [V,3], faces [F,3] of any integer dtype) ->
     (d2 [P], face_idx [P], bary [P,3]) without gradient: the squared distance of Aggregation.point_triangle_closest, the lowest
     face index among exact ties (int32 from the kernels, int64 from the definition) and the weights of the closest point on the
     face's (a, b, c).  What an extracted mesh is scored with against ground-truth points: sqrt(d2).mean() is the accuracy of a
     reconstruction's points against a reference mesh, (d2 <= tau^2).float().mean() its precision at tau, and the same with the
-    roles swapped completeness and recall.  fp32 tensors on one HIP device take the kernel of ops.closest_faces (one launch, no
-    host synchronisation); everything else takes the definition in chunks of points.  P = 0 returns empty tensors; wrong shapes,
-    an empty mesh or a face that names a vertex outside [0, V) raise ValueError."""
+    roles swapped completeness and recall.  fp32 tensors on one HIP device take the kernels of ops.closest_faces (no host
+    synchronisation): route "brute" meets all P F pairs, at most ops.POINT_MESH_MAX_PAIRS of them; "grid" searches a uniform grid
+    chosen on the device, returns the same bits and has no pair cap -- a million faces against half a million points --; None takes
+    the brute force below ops.POINT_MESH_GRID_MIN_PAIRS pairs and the grid above, and still refuses more than the cap.  Everything
+    else takes the definition in chunks of points, which has no routes.  P = 0 returns empty tensors; wrong shapes, an empty mesh,
+    an unknown route or a face that names a vertex outside [0, V) raise ValueError."""
+    _checked_route(route, "closest_faces")
     if not torch.is_tensor(points) or not torch.is_tensor(verts) or points.dim() != 2 or verts.dim() != 2 or points.shape[1] != 3 \
             or verts.shape[1] != 3:
         raise ValueError("closest_faces: points [P,3] and verts [V,3] expected")
@@ -404,7 +417,7 @@ def closest_faces(points, verts, faces):
     faces = _checked_faces(faces, verts.shape[0], "closest_faces: faces")
     points, verts = points.detach(), verts.detach()
     if verts.is_cuda and verts.dtype == torch.float32 and points.dtype == torch.float32 and points.device == verts.device:
-        return ops.closest_faces(points, verts, faces.to(verts.device))
+        return ops.closest_faces(points, verts, faces.to(verts.device), route)
     f = faces.to(verts.device).long()
     points = points.to(verts.dtype)
     a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
@@ -422,13 +435,13 @@ def closest_faces(points, verts, faces):
 _POINT_MESH_UNSUPPORTED = ("min_triangle_area", "meshes", "pcls", "weights", "norm", "batch_reduction", "x_lengths", "y_lengths")
 
 
-def _point_mesh_pair(verts, faces, points, single_directional, point_reduction):
+def _point_mesh_pair(verts, faces, points, single_directional, point_reduction, route=None):
     if verts.is_cuda and verts.dtype == torch.float32 and points.dtype == torch.float32 and points.device == verts.device:
-        return ops.point_mesh(verts, faces.to(verts.device), points, point_reduction == "sum", single_directional)[0]
+        return ops.point_mesh(verts, faces.to(verts.device), points, point_reduction == "sum", single_directional, route)[0]
     return Aggregation.point_mesh_term(verts, faces.to(verts.device), points.to(verts.device), single_directional, point_reduction)
 
 
-def _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported):
+def _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported, route=None):
     for name, value in unsupported.items():
         if name not in _POINT_MESH_UNSUPPORTED:
             raise TypeError(f"{what}: unexpected argument {name!r}")
@@ -436,6 +449,7 @@ def _point_mesh_distance(what, verts, faces, points, single_directional, point_r
             " (there is no area threshold: a triangle without area is its three segments)" if name == "min_triangle_area" else ""))
     if point_reduction not in ("mean", "sum"):
         raise ValueError(f"{what}: point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    _checked_route(route, what)
     if not torch.is_tensor(verts) or not torch.is_tensor(points) or verts.dim() not in (2, 3) or points.dim() != verts.dim() \
             or verts.shape[-1] != 3 or points.shape[-1] != 3 or (verts.dim() == 3 and verts.shape[0] != points.shape[0]):
         raise ValueError(f"{what}: verts [V,3] and points [P,3], or [B,V,3] and [B,P,3], expected")
@@ -444,12 +458,12 @@ def _point_mesh_distance(what, verts, faces, points, single_directional, point_r
     if verts.shape[-2] == 0:
         raise ValueError(f"{what}: an empty mesh")
     if verts.dim() == 2:
-        return _point_mesh_pair(verts, faces, points, single_directional, point_reduction)
-    return torch.stack([_point_mesh_pair(verts[b], faces, points[b], single_directional, point_reduction)
+        return _point_mesh_pair(verts, faces, points, single_directional, point_reduction, route)
+    return torch.stack([_point_mesh_pair(verts[b], faces, points[b], single_directional, point_reduction, route)
                         for b in range(verts.shape[0])]).mean()
 
 
-def point_mesh_face_distance(verts, faces, points, single_directional=False, point_reduction="mean", **unsupported):
+def point_mesh_face_distance(verts, faces, points, single_directional=False, point_reduction="mean", route=None, **unsupported):
     """The distance between a mesh (verts [V,3], faces [F,3] of any integer dtype; an int32 tensor on the vertices' device is used
     as it is) and a cloud points [P,3] -- PyTorch3D's point_mesh_face_distance on tensors, a 0-dim tensor:
 
@@ -460,26 +474,29 @@ def point_mesh_face_distance(verts, faces, points, single_directional=False, poi
     a perfect fit, does not change with a draw and moves no vertex along the surface.  verts and points get gradients.  The
     definition is Aggregation.point_mesh_term, and what host tensors and other dtypes get; fp32 tensors on one HIP device are ONE
     autograd node (ops._PointMesh, no double backward) with no host synchronisation, so it runs inside a captured iteration.  Both
-    searches are exact and brute force: P F is capped (ops.POINT_MESH_MAX_PAIRS); beyond it, score sample_points_from_meshes
-    against the points with chamfer_distance.  verts [B,V,3] with points [B,P,3] is a HOST LOOP over the B pairs, which share
+    searches are exact on either route: "brute" meets all P F pairs and is capped (ops.POINT_MESH_MAX_PAIRS), "grid" searches a
+    uniform grid chosen on the device, returns the same bits -- loss, pairs, weights and both gradients -- and is bound by the
+    sizes alone; None takes the brute force below ops.POINT_MESH_GRID_MIN_PAIRS pairs, the grid above, and refuses more than the
+    cap (pass route="grid" there).  The grid's weak cases are a mesh of mostly large triangles and lopsided pairs (correct, slow);
+    a hierarchy for wildly mixed triangle sizes is out of scope.  verts [B,V,3] with points [B,P,3] is a HOST LOOP over the B pairs, which share
     the faces, averaged.  There is NO min_triangle_area: it depends on the scale of the mesh; a triangle without area is its
     three segments.  That and every other PyTorch3D keyword (meshes, pcls, weights, norm, ...) is rejected by name (ValueError);
     wrong shapes, an empty cloud, an empty mesh or a face that names a vertex outside [0, V) raise ValueError too."""
     what = "point_mesh_face_distance"
     if torch.is_tensor(verts) and verts.dim() in (2, 3):
         faces = _checked_faces(faces, verts.shape[-2], what + ": faces")
-    return _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported)
+    return _point_mesh_distance(what, verts, faces, points, single_directional, point_reduction, unsupported, route)
 
 
-def point_mesh_edge_distance(verts, edges, points, single_directional=False, point_reduction="mean", **unsupported):
+def point_mesh_edge_distance(verts, edges, points, single_directional=False, point_reduction="mean", route=None, **unsupported):
     """PyTorch3D's point_mesh_edge_distance on tensors: point_mesh_face_distance with the segments edges [E,2] (an integer
     tensor, or a MeshTopology, whose unique edges are taken) in the triangles' place.  A segment (i, j) is the triangle (i, j, j),
     which point_triangle_closest's rule for a triangle without area makes exactly the segment: the same node on the index table
-    [i, j, j], no kernel of its own."""
+    [i, j, j], no kernel of its own; route as in point_mesh_face_distance."""
     what = "point_mesh_edge_distance"
     if isinstance(edges, MeshTopology):
         edges = edges.edges
     if torch.is_tensor(verts) and verts.dim() in (2, 3):
         edges = _checked_faces(edges, verts.shape[-2], what + ": edges", width=2)
         edges = edges[:, [0, 1, 1]]
-    return _point_mesh_distance(what, verts, edges, points, single_directional, point_reduction, unsupported)
+    return _point_mesh_distance(what, verts, edges, points, single_directional, point_reduction, unsupported, route)

@@ -142,6 +142,11 @@ SIGNATURES = {
                             + [_c_size_t, _c_void_p]),
     "voge_point_mesh_bwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 6 + [_c_int]
                             + [_c_void_p] * 3 + [_c_size_t, _c_void_p]),
+    "voge_point_mesh_grid_workspace_bytes": (_c_size_t, [_c_long] * 3),
+    "voge_closest_faces_grid": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_void_p, _c_long, _c_float] + [_c_void_p] * 4
+                                + [_c_size_t, _c_void_p]),
+    "voge_point_mesh_fwd_grid": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long, _c_void_p, _c_long, _c_int, _c_float]
+                                 + [_c_void_p] * 7 + [_c_size_t, _c_void_p]),
     "voge_tsdf_integrate": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] * 6 + [_c_void_p] + [_c_int] * 3 + [_c_void_p] * 5
                             + [_c_float, _c_float, _c_void_p]),
     "voge_mtet_count": (_c_int, [_c_void_p] * 2 + [_c_int] * 3 + [_c_float] + [_c_void_p] * 7),

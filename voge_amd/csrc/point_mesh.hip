@@ -45,11 +45,13 @@
 // (3) pm_finish_kernel adds a point's own term in fp64, scales by 2 g and writes EVERY element of g_verts and g_points, rounded once.
 // No float atomics, no host read-back (capturable); an index outside its range is skipped.
 //
-// The pair cap.  A brute force over 2^28 x 2^28 pairs would hold a GPU for days, so every entry refuses P F above kPmMaxPairs
-// before any HIP call (a spatial index is out of scope; sample_points_from_meshes + chamfer_distance is the route for such
-// sizes).  kPmMaxPairs = 2^38 is the largest power of two at which the slower direction stays under one second on the MI355X:
+// The pair cap.  A brute force over 2^28 x 2^28 pairs would hold a GPU for days, so the brute-force entries (voge_closest_faces,
+// voge_point_mesh_fwd, and voge_point_mesh_bwd without its grid flag) refuse P F above kPmMaxPairs before any HIP call.
+// kPmMaxPairs = 2^38 is the largest power of two at which the slower direction stays under one second on the MI355X:
 // tools/point_mesh_time.py, 524 288 points x 524 287 triangles, measured points -> faces 0.752 s and faces -> points 0.720 s
-// (2.7 ps a pair; twice that would take 1.5 s by proportion).
+// (2.7 ps a pair; twice that would take 1.5 s by proportion).  The cap does NOT bind the grid route (point_mesh_grid.h:
+// voge_closest_faces_grid, voge_point_mesh_fwd_grid, and the backward with flag bit 2), a search over a uniform grid whose items
+// are triangles and which returns the brute route's bits; its limits are the sizes (2^28 - 1) and its workspace.
 #include <math.h>
 
 #include "chamfer_loss.h"
@@ -309,9 +311,15 @@ pm_finish_kernel(const float *__restrict__ points, const int P, const float *__r
   g[2] = (float)(G * ((double)acc[3 * t + 2] * unscale + own[2]));
 }
 
+}  // namespace voge
+
+#include "point_mesh_grid.h"      // the grid route: kernels, layout and pm_grid_searches
+
+namespace voge {
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
-enum { kPmSum = 1, kPmSingle = 2 };
+enum { kPmSum = 1, kPmSingle = 2, kPmGridPairs = 4 };      // (bit 2, the backward only: the pairs came from the grid route, no pair cap)
 
 struct PmLayout {
   size_t d2p, d2f, psum, pmax, total;
@@ -427,12 +435,57 @@ extern "C" int voge_point_mesh_fwd(const float *verts, long V, const int32_t *fa
   return launch_status();
 }
 
+extern "C" size_t voge_point_mesh_grid_workspace_bytes(long V, long F, long P) {
+  if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P)) return 0;
+  return pm_grid_layout(V, F, P).total;
+}
+
+static bool pm_cell_size_ok(const float cell_size) { return cell_size >= 0.0f && cell_size < INFINITY; }      // (0: the default cell)
+
+extern "C" int voge_closest_faces_grid(const float *points, long P, const float *verts, long V, const int32_t *faces, long F,
+                                       float cell_size, int32_t *face_idx, float *d2, float *bary, void *workspace,
+                                       size_t workspace_bytes, voge_stream_t stream) {
+  if (P < 0 || P > kPmMaxN || !pm_size_ok(V) || !pm_size_ok(F) || !pm_cell_size_ok(cell_size)) return VOGE_ERR_BAD_ARG;
+  if (P == 0) return 0;
+  if (!points || !verts || !faces || !face_idx || !d2 || !bary || pm_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  const PmGridLayout l = pm_grid_layout(V, F, P);
+  if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
+  pm_grid_searches(points, P, verts, V, faces, F, cell_size, false, face_idx, d2, bary, nullptr, nullptr, nullptr,
+                   static_cast<char *>(workspace), l, (hipStream_t)stream);
+  return launch_status();
+}
+
+extern "C" int voge_point_mesh_fwd_grid(const float *verts, long V, const int32_t *faces, long F, const float *points, long P, int flags,
+                                        float cell_size, float *loss, int32_t *face_idx, float *bary_p, int32_t *point_idx,
+                                        float *bary_f, int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream) {
+  if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P) || (flags & ~3) || !pm_cell_size_ok(cell_size)) return VOGE_ERR_BAD_ARG;
+  const bool both = !(flags & kPmSingle);
+  if (!verts || !faces || !points || !loss || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || pm_ws_bad(workspace))
+    return VOGE_ERR_BAD_ARG;
+  const PmGridLayout l = pm_grid_layout(V, F, P);
+  if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
+  char *ws = static_cast<char *>(workspace);
+  hipStream_t st = (hipStream_t)stream;
+  float *d2p = reinterpret_cast<float *>(ws + l.d2p), *d2f = reinterpret_cast<float *>(ws + l.d2f);
+  pm_grid_searches(points, P, verts, V, faces, F, cell_size, both, face_idx, d2p, bary_p, point_idx, d2f, bary_f, ws, l, st);
+  double *psum = reinterpret_cast<double *>(ws + l.psum);
+  float *pmax = reinterpret_cast<float *>(ws + l.pmax);
+  const unsigned nba = l.nb_loss[0], nbb = both ? l.nb_loss[1] : 0u;
+  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2p, (int)P, d2f, (int)F, nba, psum, pmax);
+  int bits = 0;
+  while ((1l << bits) < P + F) ++bits;      // P + F <= 2^bits: every scatter list of the backward
+  const bool sum = flags & kPmSum;
+  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)P,
+                     sum ? 1.0 : (double)F, bits, loss, meta);
+  return launch_status();
+}
+
 extern "C" int voge_point_mesh_bwd(const float *verts, long V, const int32_t *faces, long F, const float *points, long P,
                                    const int32_t *face_idx, const float *bary_p, const int32_t *point_idx, const float *bary_f,
                                    const int32_t *meta, const float *g_loss, int flags, float *g_verts, float *g_points,
                                    void *workspace, size_t workspace_bytes, voge_stream_t stream) {
-  if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P) || (flags & ~3)) return VOGE_ERR_BAD_ARG;
-  if (!pm_pairs_ok(F, P)) return VOGE_ERR_K_TOO_LARGE;
+  if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P) || (flags & ~7)) return VOGE_ERR_BAD_ARG;
+  if (!(flags & kPmGridPairs) && !pm_pairs_ok(F, P)) return VOGE_ERR_K_TOO_LARGE;
   const bool both = !(flags & kPmSingle);
   if (!verts || !faces || !points || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || !g_loss || !g_verts ||
       !g_points || pm_ws_bad(workspace))

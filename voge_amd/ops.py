@@ -2127,10 +2127,55 @@ def chamfer(x, y, sum_reduction=False, single_directional=False, route=None):
 
 POINT_MESH_FACE_TILE = 256      # kPmFaceTile of point_mesh.hip: triangle records of an LDS tile (the tests build meshes around it)
 POINT_MESH_POINT_TILE = 1024    # kPmPointTile: points of an LDS tile
-POINT_MESH_MAX_PAIRS = 1 << 38  # kPmMaxPairs: the entries refuse P F above it (an exact search is a brute force)
+POINT_MESH_MAX_PAIRS = 1 << 38  # kPmMaxPairs: the brute-force entries refuse P F above it (route None and "brute")
+POINT_MESH_MAX_N = (1 << 28) - 1             # kPmMaxN: V, F and P of either route
+# point_mesh_grid.h's constants, mirrored for the tests' restatement of the grid route
+POINT_MESH_GRID_MIN_PAIRS = 1 << 38          # kPmGridMinPairs: route None takes the grid from this many pairs on -- the pair cap itself: the
+#                                              grid wins at every size with the points near the surface and loses below the cap with
+#                                              the points spread through the box (profiles/r28_point_mesh_grid.txt); shapes cannot tell
+POINT_MESH_GRID_BIG = 1.0                    # kPmGridBig: a triangle is small while its half-extent <= BIG x cell
+POINT_MESH_GRID_FLOOR = 1.0                  # kPmGridFloor: cell >= FLOOR x the mean largest bounding-box extent of a face
+POINT_MESH_GRID_BLOCK = 128                  # kPmGridBlock: queries a workgroup of the two searches
+POINT_MESH_GRID_LARGE_TILE = 256             # kPmGridLargeTile: records of an LDS tile of the large list
+POINT_MESH_GRID_HALF_UP = 1.0 + 2.0 ** -22   # a half-extent is rounded up by this factor
+POINT_MESH_GRID_RING_SLACK = 2.0 ** -10      # the stopping rule: X = cell (r - RING_SLACK) - h,
+POINT_MESH_GRID_M = 2.0 ** -8                #   b = X (1 - M) - M_H h,
+POINT_MESH_GRID_M_H = 2.0 ** -7
+POINT_MESH_GRID_B_MIN = 2.0 ** -50           #   and it fires once b > B_MIN and the kept d2 <= b b
+POINT_MESH_ROUTES = (None, "brute", "grid")
 
 
-def _point_mesh_args(verts, faces, points, what):
+def _point_mesh_route(route, F, P, what):
+    """The route a call of `what` takes on F faces and P points: "brute" or "grid".  None: the brute force below
+    POINT_MESH_GRID_MIN_PAIRS pairs, the grid from there on -- and, like "brute", bound by POINT_MESH_MAX_PAIRS (ValueError above
+    it); "grid" is bound by the sizes alone.  As measured the crossover is the cap: for points near the surface (a fit, a score)
+    route="grid" is up to 110 x faster from 10^7 pairs on and worth asking for; for points far from it, it loses."""
+    if route not in POINT_MESH_ROUTES:
+        raise ValueError(f"{what}: route must be None, 'brute' or 'grid', got {route!r}")
+    if max(F, P) > POINT_MESH_MAX_N:
+        raise ValueError(f"{what}: {P} points x {F} faces: at most {POINT_MESH_MAX_N} of either")
+    if route != "grid" and F * P > POINT_MESH_MAX_PAIRS:
+        raise ValueError(f"{what}: {P} points x {F} faces is above the {POINT_MESH_MAX_PAIRS} pairs an exact "
+                         "search takes (a brute force); for such sizes score sample_points_from_meshes against the points with "
+                         "chamfer_distance.  route=\"grid\" searches a uniform grid instead and is not bound by the pair cap")
+    if route is None:
+        return "brute" if F * P < POINT_MESH_GRID_MIN_PAIRS else "grid"
+    return route
+
+
+def _point_mesh_cell(cell_size, what):
+    if cell_size is None:
+        return 0.0
+    cell = float(cell_size)
+    if not (cell > 0.0 and cell < 3.0e38):
+        raise ValueError(f"{what}: cell_size must be a positive finite fp32 number, got {cell_size}")
+    return cell
+
+
+def _point_mesh_args(verts, faces, points, what, route=None):
+    """-> (verts, faces, points, "brute" | "grid")"""
+    if route not in POINT_MESH_ROUTES:
+        raise ValueError(f"{what}: route must be None, 'brute' or 'grid', got {route!r}")
     verts, points = _cloud(verts, "verts"), _cloud(points, "points")
     faces = _dev(faces, torch.int32, "faces")
     if faces.dim() != 2 or faces.shape[1] != 3:
@@ -2139,44 +2184,52 @@ def _point_mesh_args(verts, faces, points, what):
         raise _lib.VogeHipError(f"{what}: verts on {verts.device}, faces on {faces.device}, points on {points.device}")
     if verts.shape[0] == 0 or faces.shape[0] == 0:
         raise ValueError(f"{what}: an empty mesh")
-    if faces.shape[0] * points.shape[0] > POINT_MESH_MAX_PAIRS:
-        raise ValueError(f"{what}: {points.shape[0]} points x {faces.shape[0]} faces is above the {POINT_MESH_MAX_PAIRS} pairs an exact "
-                         "search takes (a brute force); for such sizes score sample_points_from_meshes against the points with "
-                         "chamfer_distance")
-    return verts, faces, points
+    return verts, faces, points, _point_mesh_route(route, faces.shape[0], points.shape[0], what)
 
 
-def closest_faces(points, verts, faces):
+def closest_faces(points, verts, faces, route=None, cell_size=None):
     """The nearest triangle of the mesh (verts [V,3], faces [F,3] integer) for every row of points [P,3] (extension;
-    voge_closest_faces) on a HIP device -> (d2 [P] fp32, face_idx [P] int32, bary [P,3] fp32): the squared distance of
-    Aggregation.point_triangle_closest, the lowest face index among exact ties and the weights of the closest point.  One launch,
-    nothing read back on the host; no gradient."""
-    verts, faces, points = _point_mesh_args(verts, faces, points, "closest_faces")
+    voge_closest_faces / voge_closest_faces_grid) on a HIP device -> (d2 [P] fp32, face_idx [P] int32, bary [P,3] fp32): the
+    squared distance of Aggregation.point_triangle_closest, the lowest face index among exact ties and the weights of the closest
+    point.  route "brute": one launch over all P F pairs, at most POINT_MESH_MAX_PAIRS; "grid": a search over a uniform grid chosen
+    on the device, the same bits, no pair cap (cell_size asks the grid for a cell of that edge: the tests' and the tuner's knob);
+    None: by P F (_point_mesh_route).  Nothing is read back on the host on either route; no gradient."""
+    verts, faces, points, route = _point_mesh_args(verts, faces, points, "closest_faces", route)
+    cell = _point_mesh_cell(cell_size, "closest_faces")
     P = points.shape[0]
     d2 = torch.empty((P,), dtype=torch.float32, device=points.device)
     face_idx = torch.empty((P,), dtype=torch.int32, device=points.device)
     bary = torch.empty((P, 3), dtype=torch.float32, device=points.device)
     if P > 0:
         lib = _lib.load()
+        V, F = verts.shape[0], faces.shape[0]
         with _on(points.device):
-            rc = lib.voge_closest_faces(_p(points), P, _p(verts), verts.shape[0], _p(faces), faces.shape[0], _p(face_idx), _p(d2), _p(bary),
-                                        _stream())
-        _lib.check(rc, "voge_closest_faces")
+            if route == "grid":
+                nbytes = lib.voge_point_mesh_grid_workspace_bytes(V, F, P)
+                ws = _workspace(points.device, nbytes)
+                rc = lib.voge_closest_faces_grid(_p(points), P, _p(verts), V, _p(faces), F, cell, _p(face_idx), _p(d2), _p(bary), _p(ws),
+                                                 nbytes, _stream())
+            else:
+                rc = lib.voge_closest_faces(_p(points), P, _p(verts), V, _p(faces), F, _p(face_idx), _p(d2), _p(bary), _stream())
+        _lib.check(rc, "voge_closest_faces_grid" if route == "grid" else "voge_closest_faces")
     return d2, face_idx, bary
 
 
 class _PointMesh(torch.autograd.Function):
-    """Point-to-mesh distance (extension; voge_point_mesh_fwd / _bwd): forward(verts [V,3], faces [F,3] int, points [P,3], flags) ->
-    (loss 0-dim, face_idx [P], bary_p [P,3], point_idx [F] | None, bary_f [F,3] | None), the value of Aggregation.point_mesh_term
-    with the chosen pairs and the weights of their closest points (not differentiable).  flags: bit 0 "sum", bit 1
-    single_directional.  The two searches, the fp64 partial sums and the one workgroup that adds them run on the current stream
-    from the stream's cached workspace with nothing read back on the host; the node saves the inputs, the indices, the weights and
-    meta [4] int32 (the backward's scale exponent, chosen on the device).  Backward: three launches (zero fill, integer-atomic
-    scatter, finish), every element of g_verts and g_points written: the same bits on every run.  No double backward."""
+    """Point-to-mesh distance (extension; voge_point_mesh_fwd / _fwd_grid / _bwd): forward(verts [V,3], faces [F,3] int, points
+    [P,3], flags, route, cell_size) -> (loss 0-dim, face_idx [P], bary_p [P,3], point_idx [F] | None, bary_f [F,3] | None), the
+    value of Aggregation.point_mesh_term with the chosen pairs and the weights of their closest points (not differentiable).
+    flags: bit 0 "sum", bit 1 single_directional.  route and cell_size: closest_faces's -- the two routes return the same bits.
+    The two searches, the fp64 partial sums and the one workgroup that adds them run on the current stream from the stream's
+    cached workspace with nothing read back on the host; the node saves the inputs, the indices, the weights and meta [4] int32
+    (the backward's scale exponent, chosen on the device).  Backward, the same on both routes: three launches (zero fill,
+    integer-atomic scatter, finish), every element of g_verts and g_points written: the same bits on every run.  No double
+    backward."""
 
     @staticmethod
-    def forward(ctx, verts, faces, points, flags):
-        verts, faces, points = _point_mesh_args(verts, faces, points, "point_mesh_face_distance")
+    def forward(ctx, verts, faces, points, flags, route=None, cell_size=None):
+        verts, faces, points, route = _point_mesh_args(verts, faces, points, "point_mesh_face_distance", route)
+        cell = _point_mesh_cell(cell_size, "point_mesh_face_distance")
         V, F, P = verts.shape[0], faces.shape[0], points.shape[0]
         if P == 0:
             raise ValueError("point_mesh_face_distance: an empty cloud")
@@ -2190,13 +2243,19 @@ class _PointMesh(torch.autograd.Function):
         bary_f = None if single else torch.empty((F, 3), dtype=torch.float32, device=dev)
         meta = torch.empty((4,), dtype=torch.int32, device=dev)
         with _on(dev):
-            nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
-            ws = _workspace(dev, nbytes)
-            rc = lib.voge_point_mesh_fwd(_p(verts), V, _p(faces), F, _p(points), P, flags, _p(loss), _p(face_idx), _p(bary_p), _p(point_idx),
-                                         _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
-        _lib.check(rc, "voge_point_mesh_fwd")
+            if route == "grid":
+                nbytes = lib.voge_point_mesh_grid_workspace_bytes(V, F, P)
+                ws = _workspace(dev, nbytes)
+                rc = lib.voge_point_mesh_fwd_grid(_p(verts), V, _p(faces), F, _p(points), P, flags, cell, _p(loss), _p(face_idx), _p(bary_p),
+                                                  _p(point_idx), _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
+            else:
+                nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
+                ws = _workspace(dev, nbytes)
+                rc = lib.voge_point_mesh_fwd(_p(verts), V, _p(faces), F, _p(points), P, flags, _p(loss), _p(face_idx), _p(bary_p),
+                                             _p(point_idx), _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_point_mesh_fwd_grid" if route == "grid" else "voge_point_mesh_fwd")
         ctx.save_for_backward(verts, faces, points, face_idx, bary_p, point_idx, bary_f, meta)
-        ctx.flags = flags
+        ctx.flags = flags | (4 if route == "grid" else 0)      # (bit 2 of the backward: pairs of the grid route, no pair cap)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*[t for t in (face_idx, bary_p, point_idx, bary_f) if t is not None])
         return loss[0], face_idx, bary_p, point_idx, bary_f
@@ -2205,7 +2264,7 @@ class _PointMesh(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, *_unused):
         if g_loss is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]):
-            return None, None, None, None
+            return None, None, None, None, None, None
         lib = _lib.load()
         verts, faces, points, face_idx, bary_p, point_idx, bary_f, meta = ctx.saved_tensors
         V, F, P = verts.shape[0], faces.shape[0], points.shape[0]
@@ -2217,12 +2276,13 @@ class _PointMesh(torch.autograd.Function):
             rc = lib.voge_point_mesh_bwd(_p(verts), V, _p(faces), F, _p(points), P, _p(face_idx), _p(bary_p), _p(point_idx), _p(bary_f),
                                          _p(meta), _p(g), ctx.flags, _p(g_verts), _p(g_points), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_point_mesh_bwd")
-        return (g_verts if ctx.needs_input_grad[0] else None), None, (g_points if ctx.needs_input_grad[2] else None), None
+        return (g_verts if ctx.needs_input_grad[0] else None), None, (g_points if ctx.needs_input_grad[2] else None), None, None, None
 
 
-def point_mesh(verts, faces, points, sum_reduction=False, single_directional=False):
-    """(loss, face_idx, bary_p, point_idx, bary_f) of ONE mesh and ONE cloud on a HIP device: _PointMesh.apply."""
-    return _PointMesh.apply(verts, faces, points, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1))
+def point_mesh(verts, faces, points, sum_reduction=False, single_directional=False, route=None, cell_size=None):
+    """(loss, face_idx, bary_p, point_idx, bary_f) of ONE mesh and ONE cloud on a HIP device: _PointMesh.apply.  route and
+    cell_size: closest_faces's."""
+    return _PointMesh.apply(verts, faces, points, int(bool(sum_reduction)) | (int(bool(single_directional)) << 1), route, cell_size)
 
 
 MESH_SAMPLE_BLOCK = 256      # kMsBlock of mesh_sample.hip: the faces of one scan block (the tests build meshes around it)
