@@ -11,7 +11,8 @@ loaded library checks that it did.  The tolerances are those of the nearest exis
 
 The empty cases (no pixels, no Gaussians) cannot be reached through the renderer on the frame path -- it does not take that path
 for an empty set or an empty band -- so those call the entries directly and check which outputs are zero-filled and which are left
-alone.  The 64-bit-offset instantiations need nrows * W * K >= 2^30 and are not run here."""
+alone.  The 64-bit-offset instantiations need nrows * W * K >= 2^30 (or, with K <= 3, more
+pixels than the rays' or the rgb's 32-bit byte offsets reach): tests/test_gpu_large_shapes.py runs them."""
 import numpy as np
 import pytest
 import torch

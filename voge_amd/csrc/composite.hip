@@ -1031,7 +1031,7 @@ struct CompPlan {
   dim3 grid;
   size_t lds;
 };
-static CompPlan comp_plan(const int K, const long npix, const int mode, const bool onepass) {
+static CompPlan comp_plan(const int K, const long npix, const int mode, const bool onepass, const bool from_records) {
   CompPlan P;
   // NS slots per lane: 4 when the lists are whole groups of 4, else 2
   P.NS = (onepass || ((mode == 0 ? VOGE_COMP_NS : VOGE_COMP_NS_BWD) == 4 && (K & 3) == 0)) ? 4 : 2;
@@ -1043,9 +1043,12 @@ static CompPlan comp_plan(const int K, const long npix, const int mode, const bo
   P.ppw = compn_pixels(K, P.NS, P.threads, P.wave);
   P.grid = dim3((unsigned)((npix + P.ppw - 1) / P.ppw));
   P.lds = compn_lds_bytes(K, P.NS, mode != 0, P.threads, P.wave);
-  P.small = (double)npix * K < (double)(1l << 30);      // every byte offset fits 32 bits
-  // whole groups of four in one-wave workgroups, 32-bit offsets (with K >= 4, npix < 2^28: the per-pixel outputs' offsets fit too --
-  // 8 bytes of valid_num, at most 16 of rgb / img); the one-pass entries always give counts and records
+  // 32-bit offsets where every byte offset formed in OffT fits: 4 K bytes per pixel of the slot arrays and, from the records, 12
+  // of the ray (with K <= 2 the slot arrays alone stay under 2^32 at pixels whose ray does not)
+  P.small = (double)npix * (double)((from_records && K < 3) ? 12 : 4 * K) < 4294967296.0;
+  // whole groups of four in one-wave workgroups, 32-bit offsets (K % 4 == 0 gives K >= 4, so npix < 2^28 and the per-pixel
+  // offsets out_at<NARROW> forms fit too -- 4 bytes of cnt, 8 of valid_num, 12 of the ray, at most 16 of rgb / img); the one-pass
+  // entries always give counts and records
   P.frame = onepass && P.wave && P.threads == 64 && P.small && K % P.NS == 0;
   return P;
 }
@@ -1093,7 +1096,7 @@ static int launch_composite(int mode, const int32_t *idx, const float *act, cons
                        cnt_in, occ, npix, K, ppw, o0, o1, o2, nullptr);
     return launch_status();
   }
-  const CompPlan P = comp_plan(K, npix, mode, false);
+  const CompPlan P = comp_plan(K, npix, mode, false, rec != nullptr);
   // whole groups (K % NS == 0): the kernel reads and writes 4 NS bytes at a time, so every array it touches that way has to
   // start on that boundary (include/voge_hip.h).  The forward from the records (voge_composite_fwd_iso) is fed the fragments'
   // own tensors, like the other one-pass entries, and is not looked at here.
@@ -1172,7 +1175,7 @@ static int composite_shade_fwd_impl(const int gen /* 0: (mu, a) records; 1: pack
   //  dereferences nothing of its own)
   if (C > 0 && Nattr == 0) colors = rgb;
   if (Nattr * (C > 0 ? C : 1) >= (1l << 30)) return VOGE_ERR_BAD_ARG;      // 32-bit byte offsets of the colour gathers
-  const CompPlan P = comp_plan(K, npix, 0, true);
+  const CompPlan P = comp_plan(K, npix, 0, true, true);
   CompShade sh{colors, bg, {thr}, {Nattr}, {rgb}, img, wsum, C < 0 ? nullptr : idx};      // (C = -1: depth_bg, normalize, depth)
   sh.sil = C != 0 ? sil : nullptr;
   const hipError_t e = comp_zero_rider(sh, P, zero_p, zero_bytes, (hipStream_t)stream);

@@ -101,8 +101,9 @@ struct FragBwdLds {
 //      (a = g_D / S, b = -a D where S > 0) else the plain sum (a = g_D, b = 0); the silhouette's pass-through adds to b, and
 //      a w_k is added to the trace's g_len.  No kernel argument of its own.
 // NS: slots per lane (2; 4 for lists of more than 128 slots, so that a pixel's lanes still fit one wave).
-// OffT: uint32_t when every BYTE offset into the [pix][K] arrays fits 32 bits (the loads
-// then take scalar base + 32-bit lane offset and the address arithmetic leaves the vector unit), else size_t.
+// OffT: uint32_t when every BYTE offset the kernel forms in it fits 32 bits -- into the [pix][K] arrays (4 K bytes per pixel),
+// the rays (12), the shade form's rgb (4 C) and the per-pixel scalars (4): fb_launch's test -- (the loads then take scalar base +
+// 32-bit lane offset and the address arithmetic leaves the vector unit), else size_t.
 // ISO: every Gaussian is A = a I (rec = [P] (mu, a)); otherwise rec = [P][3] packed (mu, A) as in trace_bwd.hip.
 // NOAD: the forward kept no act / dsd (voge_fragments_fwd_iso* with act = dsd = NULL, voge_trace_lean_fwd); they are re-derived
 // from the records, the ray and len with the forward's own operations (pair_eval_iso_at / pair_eval): 8 bytes per slot less to read.
@@ -879,7 +880,12 @@ void fb_launch(const FbArgs &a, hipStream_t st) {
                        a.rays, colors, a.idx, a.cnt, a.weight, a.act, a.len, a.dsd, a.rgb, a.wsum, a.bg, a.thr, a.g, a.gs_pix, a.gs_c,
                        a.g_hitlen, a.occ, a.P, a.nrows, a.W, a.K, a.Nattr, a.acc);
   };
-  if ((double)a.nrows * a.W * a.K < (double)(1l << 30)) launch(uint32_t{}); else launch(size_t{});      // (every byte offset fits 32 bits)
+  // The 32-bit form where every byte offset formed in OffT fits: per pixel the slot arrays take 4 K bytes, the ray 12, the shade
+  // form's rgb 4 C (addressed through OffT only with a background), cnt / wsum / bg 4.  (4 K alone is not enough: with K <= 2 --
+  // and K = 3 with C = 4 -- a launch under 2^30 slots has pixels whose ray or rgb offset is past 2^32.)
+  long per_pix = a.K >= 3 ? 4l * a.K : 12l;
+  if (SRC == 0 && a.bg != nullptr && 4l * C > per_pix) per_pix = 4l * C;
+  if ((double)a.nrows * a.W * (double)per_pix < 4294967296.0) launch(uint32_t{}); else launch(size_t{});
 }
 // The instantiations are the ones listed here and no product of the parameters: depth has one form, DIAG one (ISO, NOAD) pair.
 template <int SRC, int C, int NS>
