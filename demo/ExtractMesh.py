@@ -20,8 +20,13 @@ point-to-mesh search in both roles: the mean distance from every point to the me
 covers) and from every face to its nearest point (accuracy: how far the mesh strays from the scene).  Both take route="grid",
 which has no pair cap: the million faces of a 256^3 volume are scored whole, neither kept small nor sampled.  LAST holds both.
 
+--simplify CELL runs Meshing.simplify_mesh after clean_mesh, with cells of CELL voxels and placement="quadric" (vertex clustering:
+no target face count -- a count is reached by trying cell sizes -- and no promise of a manifold result); the colours go with it
+through attr=.  It prints the faces before and after and the same two scores for both meshes; the simplified mesh is what is
+saved and returned.  LAST then holds simplified = (F before, F after, the scores before, the scores after).
+
 usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]
-                                  [--colour]"""
+                                  [--colour] [--simplify CELL]"""
 import argparse
 import os
 import sys
@@ -35,7 +40,7 @@ from VoGE.Losses import closest_faces                                           
 from VoGE.Converter.IO import save_off                                                 # noqa: E402
 from VoGE.Meshes import GaussianMeshesNaive                                            # noqa: E402
 from VoGE.Converter.Converters import normal_mesh_converter                            # noqa: E402
-from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh, vertex_normals    # noqa: E402
+from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh, simplify_mesh, vertex_normals    # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_depth, get_silhouette, interpolate_attr   # noqa: E402
 from voge_amd.Meshes import OrientedGaussianMeshesNaive                                # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
@@ -78,7 +83,7 @@ def round_trip(renderer, mesh_verts, faces, vert_attr, R, T, first, device):
     return float((back - first).abs().mean())
 
 
-def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None, colour=False):
+def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None, colour=False, simplify=None):
     g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_gaussians.npz"))
     verts, sigmas = (torch.from_numpy(g[k]) for k in ("verts", "isigma"))
     colours = torch.from_numpy(g["colors"]).to(device) if colour else None
@@ -121,6 +126,20 @@ def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:
         V, F, chi, boundary = mesh_report(mesh_verts, faces)
         report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
         print(f"cleaned (keep_largest {keep_largest}, min_faces {min_faces}): {before} -> {connected_components(faces, V)[2]} components: {report}")
+    if simplify is not None:
+        fine = score_mesh(mesh_verts, faces, verts.to(device=device, dtype=torch.float32))
+        faces_before = len(faces)
+        cell = [simplify * h for h in vol.voxel_size]
+        if colour:
+            mesh_verts, faces, vert_attr = simplify_mesh(mesh_verts, faces, cell, placement="quadric", attr=vert_attr)
+        else:
+            mesh_verts, faces = simplify_mesh(mesh_verts, faces, cell, placement="quadric")
+        coarse = score_mesh(mesh_verts, faces, verts.to(device=device, dtype=torch.float32))
+        V, F, chi, boundary = mesh_report(mesh_verts, faces)
+        report = f"V {V}, F {F}, Euler characteristic {chi}, boundary edges {boundary}"
+        print(f"simplified (cells of {simplify:g} voxels, quadric placement): faces {faces_before} -> {F}: {report}; points -> mesh "
+              f"{fine[0]:.5f} -> {coarse[0]:.5f}, faces -> points {fine[1]:.5f} -> {coarse[1]:.5f}")
+        LAST.update(simplified=(faces_before, F, fine, coarse))
     completeness, accuracy = score_mesh(mesh_verts, faces, verts.to(device=device, dtype=torch.float32))
     report += f", points -> mesh {completeness:.5f}, faces -> points {accuracy:.5f}"
     print(f"scored against the scene's {len(verts)} points (closest_faces, route=\"grid\", {len(faces)} faces): mean distance points -> mesh "
@@ -146,5 +165,6 @@ if __name__ == "__main__":
     ap.add_argument("--keep-largest", type=int, default=None)
     ap.add_argument("--min-faces", type=int, default=None)
     ap.add_argument("--colour", action="store_true")
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL")
     a = ap.parse_args()
-    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, colour=a.colour)
+    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, colour=a.colour, simplify=a.simplify)

@@ -1227,6 +1227,42 @@ size_t voge_vertex_normals_workspace_bytes(long V);
 int voge_vertex_normals(const float *verts, long V, const int32_t *faces, long F, float *normals, void *workspace,
                         size_t workspace_bytes, int stages, voge_stream_t stream);
 
+/*
+ * Mesh simplification (EXTENSION): vertex clustering on a uniform grid with mean or quadric placement.  Replaces
+ * voge_amd/Aggregation.py mesh_simplify, the definition, whose docstring states the rule in five steps; csrc/mesh_simplify.hip's
+ * header has the launches, the table's argument and the derived bounds.  verts [V,3] fp32, faces [F,3] int32, cells of
+ * (hx, hy, hz).  Integer atomics only: the same bits on every run and under any permutation of the faces.
+ *   voge_mesh_simplify_scan   steps 1 to 4 on a workspace of voge_mesh_simplify_workspace_bytes(V, F), which the other two entries
+ *                             read.  `stages` is a bit mask, 255 for a call: 1 the fills and the bounding box, 2 the cells into
+ *                             the table, 4 the labels, 8 the rotated triples, 16 the refill and the triples into the table, 32 the
+ *                             face and label flags, 64 and 128 the two scan levels.  totals [3] = (V', F', error word), what the
+ *                             caller reads back to allocate the outputs -- the one synchronisation.  Error word: bit 0 a probe
+ *                             reached its cap (never in a correct run), bit 1 a face index outside [0, V), bit 2 a vertex that is
+ *                             not finite, bit 3 more than 2^21 - 1 cells on an axis.
+ *   voge_mesh_simplify_emit   step 5 and the outputs: verts_out [V',3], faces_out [F',3], vert_index [V] (the output row of every
+ *                             input vertex, -1: dropped), face_index [F'] (the input faces that stay); acc: scratch of
+ *                             voge_mesh_simplify_acc_bytes(V', quadric), 8-byte aligned, read again by voge_mesh_simplify_attr.
+ *                             `stages`, 15 for a call: 1 the zero fill of acc, 2 indices and position sums, 4 the quadrics
+ *                             (quadric != 0 only), 8 the finish.  V' and F' as read back, both >= 1 (an empty result needs no call).
+ *   voge_mesh_simplify_attr   attr_out [V',C] channels c0 .. c0 + nc - 1 (nc <= 8) of attr [V,C]: the clusters' means, after emit,
+ *                             on a scratch of voge_mesh_simplify_attr_workspace_bytes(V'), 16-byte aligned.  `stages`, 15 for a
+ *                             call: 1 its zero fill, 2 the largest |value|, 4 the scatter, 8 the finish.
+ * V or F below 1 or above 2^28 - 1, a cell size that is not positive and finite, a null pointer, a misaligned workspace, V' or F'
+ * outside 1 .. V or F, stages outside their mask: VOGE_ERR_BAD_ARG; a workspace too small: VOGE_ERR_WORKSPACE -- all before any
+ * HIP call.
+ */
+size_t voge_mesh_simplify_workspace_bytes(long V, long F);
+size_t voge_mesh_simplify_acc_bytes(long Vk, int quadric);
+size_t voge_mesh_simplify_attr_workspace_bytes(long Vk);
+int voge_mesh_simplify_scan(const float *verts, long V, const int32_t *faces, long F, float hx, float hy, float hz, void *workspace,
+                            size_t workspace_bytes, long long *totals, int stages, voge_stream_t stream);
+int voge_mesh_simplify_emit(const float *verts, long V, const int32_t *faces, long F, float hx, float hy, float hz, int quadric,
+                            void *workspace, size_t workspace_bytes, long Vk, long Fk, void *acc, size_t acc_bytes, float *verts_out,
+                            int32_t *faces_out, int32_t *vert_index, int32_t *face_index, int stages, voge_stream_t stream);
+int voge_mesh_simplify_attr(const float *attr, long V, long F, int C, int c0, int nc, const void *workspace, size_t workspace_bytes,
+                            long Vk, const void *acc, int quadric, void *attr_workspace, size_t attr_workspace_bytes, float *attr_out,
+                            int stages, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

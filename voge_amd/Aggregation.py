@@ -966,3 +966,159 @@ def mesh_vertex_normals(verts, faces):
     acc = torch.where(ok, acc, torch.ones_like(acc))
     n = torch.sqrt((acc[:, 0] * acc[:, 0] + acc[:, 1] * acc[:, 1]) + acc[:, 2] * acc[:, 2])[:, None]
     return torch.where(ok, acc / n, torch.zeros_like(acc)).to(verts.dtype)
+
+
+MESH_SIMPLIFY_MAX_CELLS = 2 ** 21 - 1      # cells on an axis: three cell indices share one 63-bit key
+MESH_SIMPLIFY_LAMBDA = 1e-3                # the quadric placement's pull towards the cluster mean
+
+
+def _det3(m00, m01, m02, m10, m11, m12, m20, m21, m22):
+    return (m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20)) + m02 * (m10 * m21 - m11 * m20)
+
+
+def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
+    """Vertex clustering on a uniform grid with mean or quadric placement (an extension here: the decimation step between
+    extracting a mesh and using it; Rossignac-Borrel cells, Lindstrom's placement) -> (verts' [V',3] fp32, faces' [F',3] int64,
+    attr' [V',C] fp32 or None, vert_index [V] int64, face_index [F'] int64).  Integers are int64, positions fp64 computed from the
+    fp32 vertices.  THE RULE, in five steps:
+
+      1 cells     lo = the per-axis minimum of verts in fp32; cell(v) = floor((v - lo) / h) per axis as three separate IEEE fp32
+                  operations (h = cell_size as fp32 numbers).  Every vertex takes part, whether a face names it or not.  More than
+                  2^21 - 1 cells on an axis, a vertex that is not finite and a face index outside [0, V) raise ValueError.
+      2 clusters  the vertices of one cell are one cluster; its label is its smallest vertex index (mesh_components' convention).
+      3 faces     a face's corners are replaced by their labels; the face is dropped when two labels are equal; the triple is
+                  rotated so that its smallest label comes first (the orientation stays) to name it; among the faces with the
+                  same rotated triple the one with the smallest face index stays, in its own corner order (two faces of opposite orientation are different triples and
+                  both stay).  Surviving faces keep their order.
+      4 outputs   the output vertices are the clusters a surviving face names, in ascending order of their labels.  vert_index[v]
+                  is the output row of the cluster of v, -1 where that cluster was dropped; face_index holds the input indices of
+                  the surviving faces.
+      5 values    a cluster of one vertex keeps that vertex's bits (and its attribute row's) under both placements.  Otherwise
+                  attr' is the mean of the cluster's attribute rows (NaN where one of them is not finite), and the position is
+                  "mean"     the mean of the cluster's vertices;
+                  "quadric"  in cell coordinates x = (p - c) / h per axis, c = lo + (cell + 1/2) h the cell's centre: every input
+                             face -- those that collapse too -- adds at each of its three corners, to that corner's cluster, the
+                             plane quadric of its unit normal n through that corner: n n^T to A, n d to b with d = -n . x_corner.
+                             n is e1 x e2 normalised with e1 = (b - a) / h, e2 = (c - a) / h per axis (cell coordinates as well:
+                             for a scalar cell_size the face's own unit normal); a face whose cross product is zero or not
+                             finite adds nothing.  With m contributions and mu the cluster's mean in the same coordinates,
+                             (A + lambda m I) x = -b + lambda m mu, lambda = 1e-3 (it bounds the condition number by
+                             (1 + lambda) / lambda and pulls the directions the planes leave free to the mean), by Cramer's rule;
+                             x is clamped to [-1/2, 1/2]^3 and the result is c + x h, rounded once to fp32.  m = 0: the mean.
+    A corner of a cell lies inside it, so every entry of a term is bounded by about 1: what lets the kernels add them in fixed point.
+    Vertex clustering does not promise a manifold result (two sheets closer than a cell merge) and has no target face count.  Not
+    differentiable.  Torch on any device: the definition voge_mesh_simplify_* are tested against and the route for everything
+    they do not take."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh_simplify: verts [V,3] and faces [F,3] expected, got {tuple(verts.shape)} / {tuple(faces.shape)}")
+    if placement not in ("mean", "quadric"):
+        raise ValueError(f"mesh_simplify: placement 'mean' or 'quadric' expected, got {placement!r}")
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    if attr is not None and (attr.dim() != 2 or attr.shape[0] != V):
+        raise ValueError(f"mesh_simplify: attr [{V},C] expected, got {tuple(attr.shape)}")
+    h32 = torch.as_tensor(cell_size, dtype=torch.float32, device="cpu").reshape(-1)
+    if h32.numel() == 1:
+        h32 = h32.expand(3)
+    if h32.numel() != 3 or not bool((torch.isfinite(h32) & (h32 > 0)).all()):
+        raise ValueError(f"mesh_simplify: cell_size must be one or three positive finite numbers, got {cell_size}")
+    h32 = h32.to(dev)
+    v32 = verts.detach().to(torch.float32)
+    f = faces.detach().long().to(dev)
+    if not bool(torch.isfinite(v32).all()):
+        raise ValueError("mesh_simplify: a vertex is not finite")
+    if F > 0 and (V == 0 or int(f.min()) < 0 or int(f.max()) >= V):
+        raise ValueError(f"mesh_simplify: a face names a vertex outside [0, {V})")
+    C = 0 if attr is None else attr.shape[1]
+    a32 = None if attr is None else attr.detach().to(device=dev, dtype=torch.float32)
+    idx = lambda n: torch.arange(n, dtype=torch.int64, device=dev)
+    none = (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, 3), dtype=torch.int64, device=dev),
+            None if attr is None else torch.zeros((0, C), dtype=torch.float32, device=dev),
+            torch.full((V,), -1, dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int64, device=dev))
+    if V == 0:
+        return none
+    # 1 cells
+    lo32 = v32.amin(0)
+    cellf = torch.floor((v32 - lo32) / h32)
+    if not bool((cellf <= MESH_SIMPLIFY_MAX_CELLS - 1).all()):
+        raise ValueError(f"mesh_simplify: more than {MESH_SIMPLIFY_MAX_CELLS} cells on an axis")
+    cell = cellf.long()
+    # 2 clusters
+    _, inv = torch.unique((cell[:, 2] << 42) | (cell[:, 1] << 21) | cell[:, 0], return_inverse=True)
+    first = torch.full((int(inv.max()) + 1,), V, dtype=torch.int64, device=dev).scatter_reduce(0, inv, idx(V), "amin")
+    label = first[inv]
+    if F == 0:
+        return none
+    # 3 faces
+    lab = label[f]
+    dropped = (lab[:, 0] == lab[:, 1]) | (lab[:, 1] == lab[:, 2]) | (lab[:, 2] == lab[:, 0])
+    turn = (lab.argmin(1)[:, None] + idx(3)[None]) % 3
+    tri = torch.gather(lab, 1, turn)
+    cand = torch.nonzero(~dropped)[:, 0]
+    keep = torch.zeros((F,), dtype=torch.bool, device=dev)
+    if cand.numel():
+        _, tinv = torch.unique(tri[cand], dim=0, return_inverse=True)
+        tfirst = torch.full((int(tinv.max()) + 1,), F, dtype=torch.int64, device=dev).scatter_reduce(0, tinv, cand, "amin")
+        keep[cand] = tfirst[tinv] == cand
+    face_index = torch.nonzero(keep)[:, 0]
+    if face_index.numel() == 0:
+        return none
+    # 4 outputs
+    used = torch.zeros((V,), dtype=torch.bool, device=dev)
+    used[tri[face_index].reshape(-1)] = True
+    out_label = torch.nonzero(used)[:, 0]
+    row_of = torch.where(used, torch.cumsum(used, 0) - 1, torch.full((V,), -1, dtype=torch.int64, device=dev))
+    vert_index = row_of[label]
+    new_faces = row_of[lab[face_index]]      # (in the face's own corner order: the rotation only names the triple)
+    # 5 values
+    Vk = out_label.numel()
+    member = vert_index >= 0
+    rows = vert_index[member]
+    count = torch.bincount(rows, minlength=Vk)
+    single = count == 1
+    p = v32.double()
+    mean = torch.zeros((Vk, 3), dtype=torch.float64, device=dev).index_add(0, rows, p[member]) / count[:, None]
+    if placement == "quadric":
+        h, lo = h32.double(), lo32.double()
+        centre = lo + (cell[out_label].double() + 0.5) * h
+        mu = torch.zeros((Vk, 3), dtype=torch.float64, device=dev).index_add(0, rows, (p[member] - centre[rows]) / h) / count[:, None]
+        pa, pb, pc = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+        e1, e2 = (pb - pa) / h, (pc - pa) / h
+        cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        norm = torch.sqrt((cx * cx + cy * cy) + cz * cz)
+        good = torch.isfinite(norm) & (norm > 0)
+        n = torch.stack([cx, cy, cz], -1)[good] / norm[good][:, None]
+        fg = f[good]
+        A = torch.zeros((Vk, 6), dtype=torch.float64, device=dev)
+        b = torch.zeros((Vk, 3), dtype=torch.float64, device=dev)
+        m = torch.zeros((Vk,), dtype=torch.float64, device=dev)
+        for k in range(3):
+            r = vert_index[fg[:, k]]
+            on = r >= 0
+            r, nk = r[on], n[on]
+            x = (p[fg[:, k]][on] - centre[r]) / h
+            d = -((nk[:, 0] * x[:, 0] + nk[:, 1] * x[:, 1]) + nk[:, 2] * x[:, 2])
+            A.index_add_(0, r, torch.stack([nk[:, 0] * nk[:, 0], nk[:, 0] * nk[:, 1], nk[:, 0] * nk[:, 2], nk[:, 1] * nk[:, 1],
+                                            nk[:, 1] * nk[:, 2], nk[:, 2] * nk[:, 2]], -1))
+            b.index_add_(0, r, nk * d[:, None])
+            m.index_add_(0, r, torch.ones_like(d))
+        lm = MESH_SIMPLIFY_LAMBDA * m
+        solve = m > 0
+        lm1 = torch.where(solve, lm, torch.ones_like(lm))      # (the rows without a contribution: any regular system)
+        a00, a01, a02, a11, a12, a22 = A[:, 0] + lm1, A[:, 1], A[:, 2], A[:, 3] + lm1, A[:, 4], A[:, 5] + lm1
+        r0, r1, r2 = (lm[:, None] * mu - b).unbind(-1)
+        det = _det3(a00, a01, a02, a01, a11, a12, a02, a12, a22)
+        x = torch.stack([_det3(r0, a01, a02, r1, a11, a12, r2, a12, a22) / det, _det3(a00, r0, a02, a01, r1, a12, a02, r2, a22) / det,
+                         _det3(a00, a01, r0, a01, a11, r1, a02, a12, r2) / det], -1)
+        x = torch.minimum(torch.maximum(x, torch.full_like(x, -0.5)), torch.full_like(x, 0.5))
+        pos = torch.where(solve[:, None], centre + x * h, mean)
+    else:
+        pos = mean
+    new_verts = torch.where(single[:, None], v32[out_label], pos.to(torch.float32))
+    new_attr = None
+    if attr is not None:
+        am = torch.zeros((Vk, C), dtype=torch.float64, device=dev).index_add(0, rows, a32.double()[member]) / count[:, None]
+        am = torch.where(torch.isfinite(am), am, torch.full_like(am, float("nan")))      # (a value that is not finite: NaN)
+        new_attr = torch.where(single[:, None], a32[out_label], am.to(torch.float32))
+    return new_verts, new_faces, new_attr, vert_index, face_index

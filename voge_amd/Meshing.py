@@ -46,14 +46,33 @@ edge gets attr_a + t (attr_b - attr_a) with the edge's own t.  On a HIP device: 
 the C running averages in registers (16 + 8 C bytes a grid point however many views), and voge_mtet_attr, one launch after the
 emit on its tables; tsdf, weight, verts and faces keep the bits of the calls without an attribute.  The kernels are compiled for
 C <= 8: a volume of more channels on the device is fused by the definition (torch, on the device), a field of more channels is
-carried to the vertices eight channels a launch.  Not here: gradients through either step, bilinear pixel sampling, per-view
-confidence weights, colouring an existing mesh by projecting its vertices into images with a visibility test, textures and UV maps.
+carried to the vertices eight channels a launch.
+
+Simplification, the step between extraction and use (marching tetrahedra makes about eight faces a surface cell, and everything
+downstream pays per face or per vertex):
+
+    verts, faces = simplify_mesh(verts, faces, cell_size, placement="mean")
+    verts, faces, colours = simplify_mesh(verts, faces, cell_size, placement="quadric", attr=colours)
+    ..., vert_index, face_index = simplify_mesh(..., return_index=True)
+
+Vertex clustering on a uniform grid: the vertices of one cell of size cell_size become one vertex at their mean, or where the
+planes of the faces around them meet (placement="quadric": corners and creases survive); faces that collapse or repeat go.
+Aggregation.mesh_simplify IS the definition and states the rule in five steps; fp32 verts and int32 faces on one HIP device take
+the kernels of csrc/mesh_simplify.hip -- equal connectivity and index tables, positions and attributes within the bounds that
+file's header derives, the same bits on every run and in every order of the faces --, everything else the definition.  ONE
+synchronisation per call (V', F' and an error word), a one-off step like extraction, not capturable and NOT DIFFERENTIABLE.
+Vertex clustering does not promise a manifold result: two sheets closer than a cell merge.  It gives no target face count either:
+a count is reached by trying cell sizes.
+
+Not here: gradients through any of these steps, bilinear pixel sampling, per-view confidence weights, colouring an existing mesh by
+projecting its vertices into images with a visibility test, textures and UV maps, edge-collapse decimation, a target_faces=
+argument and boundary preservation for the simplification.
 """
 import torch
 
 from . import Aggregation, cameras as _cameras, ops
 
-__all__ = ["TSDFVolume", "extract_mesh", "connected_components", "clean_mesh", "vertex_normals"]
+__all__ = ["TSDFVolume", "extract_mesh", "connected_components", "clean_mesh", "vertex_normals", "simplify_mesh"]
 
 
 def _triple(v, name, integer=False):
@@ -304,3 +323,45 @@ def vertex_normals(verts, faces):
     if _on_device(verts, faces):
         return ops.vertex_normals(verts, faces)
     return Aggregation.mesh_vertex_normals(verts, faces.to(verts.device)).to(torch.float32)
+
+
+def simplify_mesh(verts, faces, cell_size, placement="mean", attr=None, return_index=False):
+    """(verts' [V',3] fp32, faces' [F',3] int32[, attr' [V',C] fp32][, vert_index [V] int32, face_index [F'] int32]) -- the mesh with
+    the vertices of every grid cell merged into one: Aggregation.mesh_simplify's rule, five steps.  cell_size, a scalar or
+    (x, y, z), positive and finite, is kept as the fp32 numbers the kernels see; cells start at the vertices' per-axis minimum, and
+    a vertex on a cell boundary belongs to the upper cell (floor((v - lo) / h) in fp32, the same decision on every route).  A
+    cluster's vertex sits at the mean of its vertices (placement="mean") or where the planes of all the faces at its vertices
+    meet, pulled towards the mean with weight 1e-3 and kept inside the cell (placement="quadric": a box keeps its corners); a
+    cluster of one vertex keeps its bits.  Faces with two corners in one cluster are dropped; of the faces that become the same
+    oriented triple the first stays; two faces of opposite orientation both stay; surviving faces keep their order, and only
+    clusters they name become vertices, in the order of their smallest vertex index.  attr [V,C] (colours[, normals, ...]) comes
+    back as the clusters' means.  vert_index[v] is the output row of input vertex v or -1, face_index the input faces that stay.
+    A cell smaller than every gap between vertices returns the input bit for bit; a cell larger than the mesh returns [0,3]
+    tensors (and [0,C]).  ValueError for a cell_size that is not positive and finite, a placement other than "mean" / "quadric", an
+    attr that is not [V,C], a vertex that is not finite, a face index outside [0, V) and more than 2^21 - 1 cells on an axis.
+    Vertex clustering does NOT promise a manifold result -- two sheets closer than a cell merge -- and has NO target face count:
+    a count is reached by trying cell sizes.  Edge-collapse decimation, target_faces=, boundary preservation and gradients are out
+    of scope.  fp32 verts and int32 faces on one HIP device: the launches of csrc/mesh_simplify.hip and ONE synchronisation (see the
+    module's header); integer atomics only, the same bits on every run and in every order of the faces.  Not differentiable."""
+    _check_mesh(verts, faces, "simplify_mesh")
+    if placement not in ("mean", "quadric"):
+        raise ValueError(f"simplify_mesh: placement 'mean' or 'quadric' expected, got {placement!r}")
+    try:
+        h = torch.tensor(_triple(cell_size, "cell_size"), dtype=torch.float32)
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(f"simplify_mesh: cell_size must be a scalar or (x, y, z), got {cell_size!r}") from e
+    if not bool((torch.isfinite(h) & (h > 0)).all()):
+        raise ValueError(f"simplify_mesh: cell_size must be positive and finite as fp32, got {cell_size}")
+    h = tuple(h.tolist())
+    if attr is not None and (not isinstance(attr, torch.Tensor) or attr.dim() != 2 or attr.shape[0] != verts.shape[0]
+                             or not attr.dtype.is_floating_point):
+        raise ValueError(f"simplify_mesh: attr [{verts.shape[0]},C] of floats expected, got {tuple(getattr(attr, 'shape', ()))}")
+    verts, faces = verts.detach(), faces.detach()
+    if attr is not None:
+        attr = attr.detach().to(verts.device)
+    if _on_device(verts, faces):
+        v, f, a, vi, fi = ops.mesh_simplify(verts, faces, h, placement, attr)
+    else:
+        v, f, a, vi, fi = Aggregation.mesh_simplify(verts, faces.to(verts.device), h, placement, attr)
+        f, vi, fi = f.to(torch.int32), vi.to(torch.int32), fi.to(torch.int32)
+    return (v, f) + (() if attr is None else (a,)) + ((vi, fi) if return_index else ())

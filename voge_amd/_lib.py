@@ -160,6 +160,15 @@ SIGNATURES = {
     "voge_mesh_clean_emit": (_c_int, [_c_void_p] * 2 + [_c_long] * 2 + [_c_void_p] * 5 + [_c_long] * 2 + [_c_void_p] * 5),
     "voge_vertex_normals_workspace_bytes": (_c_size_t, [_c_long]),
     "voge_vertex_normals": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 2 + [_c_size_t, _c_int, _c_void_p]),
+    "voge_mesh_simplify_workspace_bytes": (_c_size_t, [_c_long] * 2),
+    "voge_mesh_simplify_acc_bytes": (_c_size_t, [_c_long, _c_int]),
+    "voge_mesh_simplify_attr_workspace_bytes": (_c_size_t, [_c_long]),
+    "voge_mesh_simplify_scan": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_float] * 3 + [_c_void_p, _c_size_t, _c_void_p, _c_int,
+                                         _c_void_p]),
+    "voge_mesh_simplify_emit": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_float] * 3 + [_c_int, _c_void_p, _c_size_t, _c_long,
+                                         _c_long, _c_void_p, _c_size_t] + [_c_void_p] * 4 + [_c_int, _c_void_p]),
+    "voge_mesh_simplify_attr": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_int] * 3 + [_c_void_p, _c_size_t, _c_long, _c_void_p, _c_int,
+                                         _c_void_p, _c_size_t, _c_void_p, _c_int, _c_void_p]),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

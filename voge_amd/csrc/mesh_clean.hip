@@ -61,12 +61,10 @@
 #include <math.h>
 
 #include "voge_common.h"
+#include "mesh_scan.h"      // kMcBlock, kMcTop, kMcMax and the two scan levels, shared with mesh_simplify.hip
 
 namespace voge {
 
-constexpr int kMcBlock = 256;          // flags of a scan block (= threads of the local scan); ops.MESH_CLEAN_BLOCK
-constexpr int kMcTop = 1024;           // block totals one round of the top level takes (= its threads); ops.MESH_CLEAN_TOP
-constexpr long kMcMax = 268435455l;    // V, F <= 2^28 - 1
 constexpr int kMcErrCap = 1, kMcErrIndex = 2;
 constexpr int kMcPeel = 4;             // rounds in which the label launch counts a root once for all the lanes of a wave that have it
 
@@ -207,58 +205,22 @@ mc_mark_kernel(const int32_t *__restrict__ faces, const int F, const int V, cons
 __global__ void __launch_bounds__(kMcBlock)
 mc_local_scan_kernel(const int F, const int V, const int32_t *__restrict__ face_label, const uint8_t *__restrict__ keep_root,
                      const uint8_t *__restrict__ vflag, const int nbv, uint16_t *__restrict__ loc, uint32_t *__restrict__ btot) {
-  __shared__ uint32_t wtot[kMcBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const bool is_v = (int)blockIdx.x < nbv;
   const size_t i = (size_t)(is_v ? blockIdx.x : blockIdx.x - nbv) * kMcBlock + tid;
   const bool in = i < (size_t)(is_v ? V : F);
   uint32_t x = 0u;
   if (in) x = is_v ? (vflag[i] != 0) : mc_face_kept(face_label, keep_root, i, V);
-  uint32_t incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0u;
-  for (int k = 0; k < wave; ++k) base += wtot[k];
-  if (in) loc[(is_v ? (size_t)0 : (size_t)V) + i] = (uint16_t)(base + incl - x);
-  if (tid == kMcBlock - 1) btot[blockIdx.x] = base + incl;
+  mesh_scan_local(x, in, loc + (is_v ? (size_t)0 : (size_t)V) + i, btot + blockIdx.x);
 }
 
 // ONE workgroup: the exclusive scans of btot[0, nbv) and btot[nbv, nbv + nbf) in place; totals = (V', F', error word)
 __global__ void __launch_bounds__(kMcTop)
 mc_top_scan_kernel(uint32_t *__restrict__ btot, const long nbv, const long nbf, const int32_t *__restrict__ err, long long *__restrict__ totals) {
-  __shared__ uint32_t wtot[kMcTop / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int seg = 0; seg < 2; ++seg) {      // (the bounds are the same in every thread: the barriers below are uniform)
-    uint32_t *tab = btot + (seg ? nbv : 0);
-    const long nb = seg ? nbf : nbv;
-    uint32_t carry = 0u;      // (at most 2^28 - 1 flags in all)
-    for (long r0 = 0; r0 < nb; r0 += kMcTop) {
-      const long i = r0 + tid;
-      const uint32_t x = i < nb ? tab[i] : 0u;
-      uint32_t incl = x;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, o, 64);
-        if (lane >= o) incl += y;
-      }
-      if (lane == 63) wtot[wave] = incl;
-      __syncthreads();
-      uint32_t base = 0u, all = 0u;
-      for (int k = 0; k < kMcTop / 64; ++k) {
-        if (k < wave) base += wtot[k];
-        all += wtot[k];
-      }
-      if (i < nb) tab[i] = carry + base + incl - x;
-      carry += all;
-      __syncthreads();      // (wtot is rewritten by the next round)
-    }
-    if (tid == 0) totals[seg] = (long long)carry;
-  }
+  const int tid = threadIdx.x;
+  const uint32_t nv = mesh_scan_top(btot, nbv), nf = mesh_scan_top(btot + nbv, nbf);
+  if (tid == 0) totals[0] = (long long)nv;
+  if (tid == 0) totals[1] = (long long)nf;
   if (tid == 0) totals[2] = (long long)err[0];
 }
 

@@ -2598,6 +2598,101 @@ def vertex_normals(verts, faces):
     return out
 
 
+MESH_SIMPLIFY_BLOCK = MESH_CLEAN_BLOCK      # the scans are mesh_clean.hip's (csrc/mesh_scan.h)
+MESH_SIMPLIFY_TOP = MESH_CLEAN_TOP
+MESH_SIMPLIFY_CHANNELS = 8                  # kMsChannels of mesh_simplify.hip: the attribute channels of one launch set
+MESH_SIMPLIFY_MAX_CELLS = 2 ** 21 - 1       # cells on an axis (Aggregation.MESH_SIMPLIFY_MAX_CELLS)
+MESH_SIMPLIFY_LAMBDA = 1e-3                 # kMsLambda
+
+
+def mesh_simplify_capacity(V, F):
+    """Entries of the table voge_mesh_simplify_scan probes: the power of two >= 2 max(V, F) (the tests step it)"""
+    return 1 << max(2 * max(int(V), int(F)) - 1, 0).bit_length()
+
+
+def mesh_simplify_scales(V, F):
+    """(sp, sq): the fixed-point exponents of the position and the quadric sums (mesh_simplify.hip's header, SCALES)"""
+    return 60 - max(int(V) - 1, 0).bit_length(), 60 - max(3 * int(F) - 1, 0).bit_length()
+
+
+def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
+    """(verts' [V',3] fp32, faces' [F',3] int32, attr' [V',C] fp32 or None, vert_index [V] int32, face_index [F'] int32) of verts
+    [V,3] fp32, faces [F,3] int32 (and attr [V,C] fp32) on a HIP device (extension; voge_mesh_simplify_scan / _emit / _attr): the
+    values of Aggregation.mesh_simplify -- equal labels, faces and index tables; positions and attributes within the bounds
+    mesh_simplify.hip's header derives.  cell_size: three fp32 numbers.  The scan's launches on the stream's cached workspace, then
+    V', F' and the error word are read back on the host -- ONE synchronisation, what sizes the outputs -- and the launches that
+    write them.  ValueError for an index outside [0, V), a vertex that is not finite and more than 2^21 - 1 cells on an axis.
+    Fixed-point sums with integer atomics: the same bits on every run and for every order of the faces.  Not differentiable, not
+    capturable."""
+    v = _dev(verts.detach(), torch.float32, "verts")
+    f = _mesh_faces(faces, "mesh_simplify")
+    V, F, dev = v.shape[0], f.shape[0], v.device
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"mesh_simplify: verts [V,3] expected, got {tuple(v.shape)}")
+    if V > MESH_MAX:
+        raise ValueError(f"mesh_simplify: {V} vertices, at most {MESH_MAX}")
+    if placement not in ("mean", "quadric"):
+        raise ValueError(f"mesh_simplify: placement 'mean' or 'quadric' expected, got {placement!r}")
+    quadric = int(placement == "quadric")
+    h = [float(x) for x in cell_size]
+    a = None
+    if attr is not None:
+        a = _dev(attr.detach(), torch.float32, "attr")
+        if a.dim() != 2 or a.shape[0] != V or a.device != dev:
+            raise ValueError(f"mesh_simplify: attr [{V},C] on {dev} expected, got {tuple(a.shape)} on {a.device}")
+    if f.device != dev:
+        raise _lib.VogeHipError(f"mesh_simplify: verts on {dev}, faces on {f.device}")
+    C = 0 if a is None else a.shape[1]
+    if V == 0 and F > 0:
+        raise ValueError("mesh_simplify: a face names a vertex outside [0, 0)")
+    empty = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    none = lambda: (empty((0, 3), torch.float32), empty((0, 3), torch.int32), None if a is None else empty((0, C), torch.float32),
+                    torch.full((V,), -1, dtype=torch.int32, device=dev), empty((0,), torch.int32))
+    if V == 0:
+        return none()
+    if F == 0:      # (no face, no output; the vertices are still examined -- one comparison read back)
+        if not bool(torch.isfinite(v).all()):
+            raise ValueError("mesh_simplify: a vertex is not finite")
+        return none()
+    totals = empty((3,), torch.int64)
+    lib = _lib.load()
+    with _on(dev):
+        st = _stream()
+        nbytes = lib.voge_mesh_simplify_workspace_bytes(V, F)
+        ws = _workspace(dev, nbytes)
+        rc = lib.voge_mesh_simplify_scan(_p(v), V, _p(f), F, h[0], h[1], h[2], _p(ws), nbytes, _p(totals), 255, st)
+        _lib.check(rc, "voge_mesh_simplify_scan")
+        Vk, Fk, bad = (int(x) for x in totals.tolist())      # the synchronisation
+        if bad & 4:
+            raise ValueError("mesh_simplify: a vertex is not finite")
+        if bad & 2:
+            raise ValueError(f"mesh_simplify: a face names a vertex outside [0, {V})")
+        if bad & 8:
+            raise ValueError(f"mesh_simplify: more than {MESH_SIMPLIFY_MAX_CELLS} cells on an axis")
+        if bad:
+            raise _lib.VogeHipError(f"voge_mesh_simplify_scan: a probe of the table reached its cap (error word {bad})")
+        if Vk == 0 or Fk == 0:
+            return none()
+        out_v, out_f = empty((Vk, 3), torch.float32), empty((Fk, 3), torch.int32)
+        vert_index, face_index = empty((V,), torch.int32), empty((Fk,), torch.int32)
+        acc_bytes = lib.voge_mesh_simplify_acc_bytes(Vk, quadric)
+        acc = empty((acc_bytes // 8,), torch.int64)
+        rc = lib.voge_mesh_simplify_emit(_p(v), V, _p(f), F, h[0], h[1], h[2], quadric, _p(ws), nbytes, Vk, Fk, _p(acc), acc_bytes, _p(out_v),
+                                         _p(out_f), _p(vert_index), _p(face_index), 15, st)
+        _lib.check(rc, "voge_mesh_simplify_emit")
+        out_a = None
+        if a is not None:
+            out_a = empty((Vk, C), torch.float32)
+            if C:
+                abytes = lib.voge_mesh_simplify_attr_workspace_bytes(Vk)
+                aws = empty((abytes // 8,), torch.int64)
+            for c0 in range(0, C, MESH_SIMPLIFY_CHANNELS):      # (more channels than one launch set takes: one per slice of them)
+                rc = lib.voge_mesh_simplify_attr(_p(a), V, F, C, c0, min(MESH_SIMPLIFY_CHANNELS, C - c0), _p(ws), nbytes, Vk, _p(acc), quadric,
+                                                 _p(aws), abytes, _p(out_a), 15, st)
+                _lib.check(rc, "voge_mesh_simplify_attr")
+    return out_v, out_f, out_a, vert_index, face_index
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
