@@ -48,7 +48,10 @@ def kernels(text):
     found = {}
     for m in re.finditer(r"^(_ZN4voge\w+):\s", text, flags=re.M):
         name = m.group(1)
-        body = text[m.start():text.index(".Lfunc_end", m.start())]
+        end = text.find(".Lfunc_end", m.start())
+        if end < 0:      # (a constant table behind the last function: data, no code)
+            continue
+        body = text[m.start():end]
         regs = None
         d = text.find(".amdhsa_kernel " + name + "\n")
         if d >= 0:      # (a device function that was not inlined has no descriptor)

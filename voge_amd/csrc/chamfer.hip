@@ -9,9 +9,9 @@
 //          four waves take a quarter of a tile each and the four keys of a query meet in LDS (a minimum: no order to depend on);
 //   grid   the search of knn.hip between two clouds, over a grid chosen ON THE DEVICE -- nothing of the call depends on a value
 //          the host would have to read, so it can be captured into a graph:
-//     (a) chamfer_box_kernel / chamfer_grid_kernel: the bounding box of the UNION of the clouds, and one thread that runs the rule
-//         of ops.knn_grid: about 2 n cubic cells (n = max(Nx, Ny)), cell >= max extent / 1023, G_a = floor(extent_a / cell) + 1 <=
-//         1024 on every axis, G = Gx Gy Gz <= max(8 n, 2^15); the loop that enlarges the cell has 64 trips at most, and a box that
+//     (a) grid_box_kernel / chamfer_grid_kernel: the bounding box of the UNION of the clouds, and one thread that runs the rule
+//         of ops.knn_grid (grid_choose of knn_grid.h): about 2 n cubic cells (n = max(Nx, Ny)), cell >= max extent / 1023,
+//         G_a = floor(extent_a / cell) + 1 <= 1024 on every axis, G = Gx Gy Gz <= max(8 n, 2^15); the loop that enlarges the cell has 64 trips at most, and a box that
 //         is not finite or a loop that did not end gives the one-cell grid (every point a candidate of ring 0: a brute force).
 //         The grid goes into the workspace's head, every later kernel reads it from there; the workspace and the launches are
 //         sized for the cap on G, which depends on (Nx, Ny) alone, and the scan reads the real G from memory;
@@ -56,15 +56,7 @@ namespace voge {
 constexpr long kChamferMaxN = 268435455l;
 constexpr double kChamferBruteMaxPairs = 8388608.0;      // Nx Ny at or below this: the brute route (measured: profiles/r17_chamfer.txt)
 constexpr int kChSearchBlock = 128;
-constexpr int kChBoxItems = 8;          // points a thread of the box pass: 2048 a workgroup
 constexpr int kChTile = 1024;           // points of a brute-force tile
-constexpr int kChGridTrips = 64;
-
-// the most cells a grid for clouds of at most n points may have (ops.knn_grid's cap; G and G + 1 stay ints)
-__host__ __device__ inline long chamfer_cell_cap(const long n) {
-  const long cap = 8 * n > 32768l ? 8 * n : 32768l;
-  return cap < 2147483646l ? cap : 2147483646l;
-}
 
 struct ChamferHead {      // the workspace's first 64 bytes
   KnnGrid g;
@@ -75,107 +67,15 @@ static_assert(sizeof(ChamferHead) == 64, "ChamferHead is 64 bytes");
 
 // ---- the grid, chosen on the device -------------------------------------------------------------------------------------------
 
-// fminf / fmaxf drop a NaN: a cloud with some NaN coordinates still gets the box of its numbers
-__global__ void __launch_bounds__(256)
-chamfer_box_kernel(const float *__restrict__ x, const int Nx, const float *__restrict__ y, const int Ny, float *__restrict__ partial) {
-  const size_t n = (size_t)Nx + (size_t)Ny;
-  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < kChBoxItems; ++k) {
-    const size_t i = ((size_t)blockIdx.x * kChBoxItems + k) * 256 + threadIdx.x;
-    if (i < n) {
-      const float *p = i < (size_t)Nx ? x + 3 * i : y + 3 * (i - (size_t)Nx);
-      const float a = p[0], b = p[1], c = p[2];
-      lo0 = fminf(lo0, a); lo1 = fminf(lo1, b); lo2 = fminf(lo2, c);
-      hi0 = fmaxf(hi0, a); hi1 = fmaxf(hi1, b); hi2 = fmaxf(hi2, c);
-    }
-  }
-  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
-  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
-  __shared__ float red[4][6];
-  if ((threadIdx.x & 63) == 0) {
-    float *r = red[threadIdx.x >> 6];
-    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int c = threadIdx.x;
-    const float a = red[0][c], b = red[1][c], d = red[2][c], e = red[3][c];
-    partial[(size_t)blockIdx.x * 6 + c] = c < 3 ? fminf(fminf(a, b), fminf(d, e)) : fmaxf(fmaxf(a, b), fmaxf(d, e));
-  }
-}
-
-// ONE workgroup: the box of the partial boxes, then thread 0 chooses the grid (the rule of ops.knn_grid; n = max(Nx, Ny),
-// cell_size > 0 asks for a cell of that size and goes through the same enlargement)
+// ONE workgroup: the box of the partial boxes, then thread 0 chooses the grid (grid_choose with n = max(Nx, Ny) and no floor)
 __global__ void __launch_bounds__(256)
 chamfer_grid_kernel(const float *__restrict__ partial, const int nb, const long n, const float cell_size, ChamferHead *__restrict__ head) {
-  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
-  for (int i = threadIdx.x; i < nb; i += 256) {
-    const float *p = partial + (size_t)i * 6;
-    lo0 = fminf(lo0, p[0]); lo1 = fminf(lo1, p[1]); lo2 = fminf(lo2, p[2]);
-    hi0 = fmaxf(hi0, p[3]); hi1 = fmaxf(hi1, p[4]); hi2 = fmaxf(hi2, p[5]);
-  }
-  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
-  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
-  __shared__ float red[4][6];
-  if ((threadIdx.x & 63) == 0) {
-    float *r = red[threadIdx.x >> 6];
-    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
   float lo[3], hi[3];
-  for (int c = 0; c < 3; ++c) {
-    lo[c] = fminf(fminf(red[0][c], red[1][c]), fminf(red[2][c], red[3][c]));
-    hi[c] = fmaxf(fmaxf(red[0][c + 3], red[1][c + 3]), fmaxf(red[2][c + 3], red[3][c + 3]));
-  }
-  double ext[3], mx = 0.0;
-  bool fin = true;
-  for (int c = 0; c < 3; ++c) {
-    const float e = hi[c] - lo[c];
-    fin = fin && fabsf(lo[c]) < INFINITY && fabsf(hi[c]) < INFINITY && fabsf(e) < INFINITY;
-    ext[c] = e > 0.0f ? (double)e : 0.0;
-    mx = fmax(mx, ext[c]);
-  }
+  grid_box_reduce(partial, nb, lo, hi);
+  if (threadIdx.x != 0) return;
   ChamferHead h;
-  h.g = KnnGrid{fin ? lo[0] : 0.0f, fin ? lo[1] : 0.0f, fin ? lo[2] : 0.0f, 1.0f, 1.0f, 1, 1, 1};      // the one-cell fallback
-  h.G = 1;
+  grid_choose(lo, hi, n, cell_size, 0.0, h.g, h.G);
   for (int k = 0; k < 7; ++k) h.pad[k] = 0;
-  if (fin) {
-    const double cap = (double)chamfer_cell_cap(n);
-    double cell;
-    if (cell_size > 0.0f && cell_size < INFINITY) {
-      cell = (double)cell_size;
-    } else {
-      int np = 0;
-      double vol = 1.0;
-      for (int c = 0; c < 3; ++c)
-        if (ext[c] > 0.0) { vol *= ext[c]; ++np; }
-      cell = np ? pow(vol / (2.0 * (double)(n > 1 ? n : 1)), 1.0 / (double)np) : 1.0;
-    }
-    cell = fmax(cell, fmax(mx / 1023.0, 1e-30));
-    for (int trip = 0; trip < kChGridTrips; ++trip) {
-      const float cf = (float)cell;
-      const float inv = 1.0f / cf;
-      if (!(cf > 0.0f) || !(cf < INFINITY) || !(inv > 0.0f) || !(inv < INFINITY)) break;
-      double cells = 1.0;
-      bool fits = true;
-      int g[3];
-      for (int c = 0; c < 3; ++c) {
-        const double q = floor(ext[c] / (double)cf) + 1.0;
-        fits = fits && q <= (double)kKnnMaxAxis;
-        g[c] = (int)fmin(q, (double)kKnnMaxAxis);
-        cells *= q;
-      }
-      if (fits && cells <= cap) {
-        h.g.cell = cf; h.g.inv = inv;
-        h.g.gx = g[0]; h.g.gy = g[1]; h.g.gz = g[2];
-        h.G = g[0] * g[1] * g[2];
-        break;
-      }
-      cell = (double)cf * fmax(1.05, cbrt(cells / cap));      // (every round grows the cell)
-    }
-  }
   *head = h;
 }
 
@@ -189,29 +89,14 @@ struct ChamferCloud {
 };
 
 __global__ void __launch_bounds__(256)
-chamfer_zero_kernel(const ChamferHead *__restrict__ head, int *__restrict__ c0, int *__restrict__ c1) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)head->G) return;
-  c0[i] = 0;
-  c1[i] = 0;
-}
-
-__global__ void __launch_bounds__(256)
 chamfer_count_kernel(const ChamferCloud a, const ChamferCloud b, const unsigned nba, const ChamferHead *__restrict__ head) {
   const bool first = blockIdx.x < nba;
   const size_t i = (size_t)(blockIdx.x - (first ? 0u : nba)) * 256 + threadIdx.x;
   const int N = first ? a.N : b.N;
   if (i >= (size_t)N) return;
-  const KnnGrid g = head->g;
-  const float *p = (first ? a.pts : b.pts) + 3 * i;
-  const int cx = knn_axis_cell(p[0], g.lox, g.inv, g.gx), cy = knn_axis_cell(p[1], g.loy, g.inv, g.gy),
-            cz = knn_axis_cell(p[2], g.loz, g.inv, g.gz);
-  const int c = (cz * g.gy + cy) * g.gx + cx;
-  (first ? a.cellid : b.cellid)[i] = c;
-  atomicAdd((first ? a.counts : b.counts) + c, 1);
+  grid_count_point(head->g, first ? a.pts : b.pts, i, first ? a.cellid : b.cellid, first ? a.counts : b.counts);
 }
 
-// counts[c] falls back to zero, one slot a point: slot = the value after the decrement, in [0, count)
 __global__ void __launch_bounds__(256)
 chamfer_fill_kernel(const ChamferCloud a, const ChamferCloud b, const unsigned nba, const ChamferHead *__restrict__ head) {
   const bool first = blockIdx.x < nba;
@@ -220,11 +105,7 @@ chamfer_fill_kernel(const ChamferCloud a, const ChamferCloud b, const unsigned n
   if (i >= (size_t)N) return;
   const int c = (first ? a.cellid : b.cellid)[i];
   if (c < 0 || c >= head->G) return;      // (the count pass wrote a cell of this grid: a guard, not a route)
-  const int slot = atomicSub((first ? a.counts : b.counts) + c, 1) - 1;
-  const int pos = (first ? a.start : b.start)[c] + slot;
-  if (slot < 0 || pos < 0 || pos >= N) return;      // (cannot happen after the count pass over the same cellid: a guard, not a route)
-  const float *p = (first ? a.pts : b.pts) + 3 * i;
-  (first ? a.sorted : b.sorted)[pos] = make_float4(p[0], p[1], p[2], __int_as_float((int)i));
+  grid_fill_point(first ? a.pts : b.pts, i, c, first ? a.counts : b.counts, first ? a.start : b.start, N, first ? a.sorted : b.sorted);
 }
 
 // ---- the two searches ---------------------------------------------------------------------------------------------------------
@@ -343,10 +224,6 @@ chamfer_brute_kernel(const float *__restrict__ qs, const int Nq, const float *__
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void chamfer_add(long long *acc, const float diff, const double scale) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)llrint((double)diff * scale));
-}
-
 // workgroups [0, nbx): point i of x adds (y_nn(i) - x_i) 2^s to acc_y[nn(i)]; the rest: point j of y adds (x_nn(j) - y_j) 2^s to
 // acc_x[nn(j)] (nn_y == nullptr, the single-directional form: no such workgroups)
 __global__ void __launch_bounds__(256)
@@ -362,9 +239,9 @@ chamfer_scatter_kernel(const float *__restrict__ x, const int Nx, const float *_
   const double scale = ldexp(1.0, meta[0]);
   const float *p = (first ? x : y) + 3 * i, *o = (first ? y : x) + 3 * (size_t)j;
   long long *acc = (first ? acc_y : acc_x) + 3 * (size_t)j;
-  chamfer_add(acc, o[0] - p[0], scale);
-  chamfer_add(acc + 1, o[1] - p[1], scale);
-  chamfer_add(acc + 2, o[2] - p[2], scale);
+  atomic_add_i64(acc, llrint((double)(o[0] - p[0]) * scale));
+  atomic_add_i64(acc + 1, llrint((double)(o[1] - p[1]) * scale));
+  atomic_add_i64(acc + 2, llrint((double)(o[2] - p[2]) * scale));
 }
 
 // one point a thread, x then y: g = G (w_gather (own - nearest) + w_scatter acc 2^-s), every element written
@@ -411,9 +288,9 @@ static ChamferLayout chamfer_layout(const long Nx, const long Ny) {
   ChamferLayout l;
   const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   const long N[2] = {Nx, Ny}, n = Nx > Ny ? Nx : Ny;
-  l.cap = chamfer_cell_cap(n);
+  l.cap = grid_cell_cap(n);
   l.nb_scan = (int)((l.cap + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
-  l.nb_box = (int)((Nx + Ny + 256 * kChBoxItems - 1) / (256 * kChBoxItems));
+  l.nb_box = (int)((Nx + Ny + 256 * kGridBoxItems - 1) / (256 * kGridBoxItems));
   size_t at = 0;
   l.head = at; at += sizeof(ChamferHead);
   l.boxp = at; at += up16((size_t)l.nb_box * 6 * sizeof(float));
@@ -462,16 +339,11 @@ static void chamfer_searches(const float *x, const long Nx, const float *y, cons
   }
   const long n = Nx > Ny ? Nx : Ny;
   const unsigned nbx = (unsigned)((Nx + 255) / 256), nby = (unsigned)((Ny + 255) / 256);
-  hipLaunchKernelGGL(chamfer_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, boxp);
+  hipLaunchKernelGGL(grid_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, boxp);
   hipLaunchKernelGGL(chamfer_grid_kernel, dim3(1), dim3(256), 0, st, boxp, l.nb_box, n, cell_size, head);
-  hipLaunchKernelGGL(chamfer_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, head, c[0].counts, c[1].counts);
+  hipLaunchKernelGGL(grid_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, &head->G, c[0].counts, c[1].counts);
   hipLaunchKernelGGL(chamfer_count_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
-  for (int k = 0; k < 2; ++k) {
-    hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, c[k].counts, 0, &head->G, bsum[k]);
-    hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum[k], l.nb_scan);
-    hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, c[k].counts, 0, &head->G, bsum[k],
-                       c[k].N, c[k].start);
-  }
+  for (int k = 0; k < 2; ++k) grid_scan_launch(c[k].counts, 0, &head->G, bsum[k], l.nb_scan, c[k].N, c[k].start, st);
   hipLaunchKernelGGL(chamfer_fill_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
   const ChamferDir d0{c[0].sorted, (int)Nx, c[1].sorted, c[1].start, (int)Ny, idx_x, d2_x};
   const ChamferDir d1{c[1].sorted, (int)Ny, c[0].sorted, c[0].start, (int)Nx, idx_y, d2_y};

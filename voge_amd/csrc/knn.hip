@@ -29,7 +29,7 @@
 // the largest, R = [t1, n x t1, n] as a quaternion (w, x, y, z) with w >= 0.  Entries of idx outside [0, N) are skipped.
 #include <math.h>
 
-#include "knn_grid.h"      // the grid, knn_axis_cell and the scan, shared with chamfer.hip
+#include "knn_grid.h"      // the grid, its binning steps and the scan, shared with chamfer.hip and point_mesh_grid.h
 
 namespace voge {
 
@@ -40,26 +40,15 @@ __global__ void __launch_bounds__(256)
 knn_count_kernel(const float *__restrict__ pts, const int N, const KnnGrid g, int *__restrict__ cellid, int *__restrict__ counts) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)N) return;
-  const float *p = pts + 3 * i;
-  const int cx = knn_axis_cell(p[0], g.lox, g.inv, g.gx), cy = knn_axis_cell(p[1], g.loy, g.inv, g.gy),
-            cz = knn_axis_cell(p[2], g.loz, g.inv, g.gz);
-  const int c = (cz * g.gy + cy) * g.gx + cx;
-  cellid[i] = c;
-  atomicAdd(counts + c, 1);
+  grid_count_point(g, pts, i, cellid, counts);
 }
 
-// counts[c] falls back to zero, one slot a point: slot = the value after the decrement, in [0, count)
 __global__ void __launch_bounds__(256)
 knn_fill_kernel(const float *__restrict__ pts, const int N, const int *__restrict__ cellid, int *__restrict__ counts,
                 const int *__restrict__ start, float4 *__restrict__ sorted) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)N) return;
-  const int c = cellid[i];
-  const int slot = atomicSub(counts + c, 1) - 1;
-  const int pos = start[c] + slot;
-  if (slot < 0 || pos < 0 || pos >= N) return;      // (cannot happen after the count pass over the same cellid: a guard, not a route)
-  const float *p = pts + 3 * i;
-  sorted[pos] = make_float4(p[0], p[1], p[2], __int_as_float((int)i));
+  grid_fill_point(pts, i, cellid[i], counts, start, N, sorted);
 }
 
 template <bool SELF>
@@ -311,9 +300,7 @@ extern "C" int voge_knn_points(const float *points, long N, int k, int include_s
   const hipError_t fe = voge_fill_async(counts, 0, (size_t)G * 4, st);
   if (fe != hipSuccess) return (int)fe;
   hipLaunchKernelGGL(knn_count_kernel, dim3(nblk), dim3(256), 0, st, points, (int)N, g, cellid, counts);
-  hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, nullptr, bsum);
-  hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, l.nb);
-  hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb), dim3(kKnnScanBlock), 0, st, counts, (int)G, nullptr, bsum, (int)N, start);
+  grid_scan_launch(counts, (int)G, nullptr, bsum, l.nb, (int)N, start, st);
   hipLaunchKernelGGL(knn_fill_kernel, dim3(nblk), dim3(256), 0, st, points, (int)N, cellid, counts, start, sorted);
   const unsigned sblk = (unsigned)((N + kKnnSearchBlock - 1) / kKnnSearchBlock);
   const size_t lds = (size_t)k * kKnnSearchBlock * sizeof(uint64_t);

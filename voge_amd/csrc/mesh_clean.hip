@@ -211,7 +211,10 @@ mc_local_scan_kernel(const int F, const int V, const int32_t *__restrict__ face_
   const bool in = i < (size_t)(is_v ? V : F);
   uint32_t x = 0u;
   if (in) x = is_v ? (vflag[i] != 0) : mc_face_kept(face_label, keep_root, i, V);
-  mesh_scan_local(x, in, loc + (is_v ? (size_t)0 : (size_t)V) + i, btot + blockIdx.x);
+  uint32_t upto;
+  const uint32_t excl = mesh_scan_local(x, upto);
+  if (in) loc[(is_v ? (size_t)0 : (size_t)V) + i] = (uint16_t)excl;
+  if (tid == kMcBlock - 1) btot[blockIdx.x] = upto;      // (the last thread's inclusive prefix: the block's total)
 }
 
 // ONE workgroup: the exclusive scans of btot[0, nbv) and btot[nbv, nbv + nbf) in place; totals = (V', F', error word)
@@ -307,10 +310,6 @@ __device__ __forceinline__ int vn_scale_exponent(const VnHead *__restrict__ head
   return s < -1000 ? -1000 : (s > 1000 ? 1000 : s);
 }
 
-__device__ __forceinline__ void vn_add(long long *acc, const long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)v);
-}
-
 __global__ void __launch_bounds__(256)
 vn_scatter_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F,
                   const VnHead *__restrict__ head, const int list_bits, long long *__restrict__ acc) {
@@ -321,7 +320,7 @@ vn_scatter_kernel(const float *__restrict__ verts, const int V, const int32_t *_
   if (!c.ok) return;
   if (!vn_finite(c)) {
 #pragma unroll
-    for (int r = 0; r < 3; ++r) vn_add(acc + 4 * (size_t)iv[r] + 3, 1ll);
+    for (int r = 0; r < 3; ++r) atomic_add_i64(acc + 4 * (size_t)iv[r] + 3, 1ll);
     return;
   }
   const double scale = ldexp(1.0, vn_scale_exponent(head, list_bits));
@@ -330,9 +329,9 @@ vn_scatter_kernel(const float *__restrict__ verts, const int V, const int32_t *_
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     long long *a = acc + 4 * (size_t)iv[r];
-    vn_add(a, tx);
-    vn_add(a + 1, ty);
-    vn_add(a + 2, tz);
+    atomic_add_i64(a, tx);
+    atomic_add_i64(a + 1, ty);
+    atomic_add_i64(a + 2, tz);
   }
 }
 

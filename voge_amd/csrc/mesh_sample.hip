@@ -249,10 +249,6 @@ __device__ __forceinline__ int ms_scale_exponent(const MsHead *__restrict__ head
   return s < -1000 ? -1000 : (s > 1000 ? 1000 : s);
 }
 
-__device__ __forceinline__ void ms_add(long long *acc, const double v) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)llrint(v));
-}
-
 __global__ void __launch_bounds__(256)
 ms_scatter_kernel(const int32_t *__restrict__ faces, const int V, const int F, const int32_t *__restrict__ face_idx,
                   const float *__restrict__ bary, const int S, const float *__restrict__ g_points, const float *__restrict__ g_normals,
@@ -271,17 +267,17 @@ ms_scatter_kernel(const int32_t *__restrict__ faces, const int V, const int F, c
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
         long long *acc = acc_v + 3 * (size_t)iv[r];
-        ms_add(acc, w[r] * gx);
-        ms_add(acc + 1, w[r] * gy);
-        ms_add(acc + 2, w[r] * gz);
+        atomic_add_i64(acc, llrint(w[r] * gx));
+        atomic_add_i64(acc + 1, llrint(w[r] * gy));
+        atomic_add_i64(acc + 2, llrint(w[r] * gz));
       }
     }
   }
   if (g_normals) {
     long long *acc = acc_f + 3 * (size_t)f;
-    ms_add(acc, (double)g_normals[3 * s] * scale);
-    ms_add(acc + 1, (double)g_normals[3 * s + 1] * scale);
-    ms_add(acc + 2, (double)g_normals[3 * s + 2] * scale);
+    atomic_add_i64(acc, llrint((double)g_normals[3 * s] * scale));
+    atomic_add_i64(acc + 1, llrint((double)g_normals[3 * s + 1] * scale));
+    atomic_add_i64(acc + 2, llrint((double)g_normals[3 * s + 2] * scale));
   }
 }
 

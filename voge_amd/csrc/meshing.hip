@@ -49,12 +49,12 @@
 //     write is guarded by V.
 #include <math.h>
 
-#include "voge_common.h"
+#include "mesh_scan.h"      // the two scan levels, shared with mesh_clean.hip and mesh_simplify.hip
 
 namespace voge {
 
-constexpr int kMtBlock = 256;      // grid points of a scan block (= threads of the count launch); ops.MTET_BLOCK
-constexpr int kMtTop = 1024;       // block totals one round of the top level takes (= its threads); ops.MTET_TOP
+constexpr int kMtBlock = kMcBlock;      // grid points of a scan block (= threads of the count launch); ops.MTET_BLOCK
+constexpr int kMtTop = kMcTop;          // block totals one round of the top level takes (= its threads); ops.MTET_TOP
 constexpr long kMtMaxKeys = 2147483647l;      // nx ny nz 7 <= 2^31 - 1
 
 // the six tetrahedra of a cell as corner masks (c0, c1, c2, c3), positively oriented: one per permutation of the axes
@@ -151,9 +151,8 @@ __global__ void __launch_bounds__(kMtBlock)
 mtet_count_kernel(const float *__restrict__ values, const float *__restrict__ weight, const int nx, const int ny, const int nz,
                   const float level, uint8_t *__restrict__ edge_mask, uint8_t *__restrict__ face_count, uint16_t *__restrict__ vloc,
                   uint16_t *__restrict__ floc, uint32_t *__restrict__ block_v, uint32_t *__restrict__ block_f) {
-  __shared__ uint32_t wtot[kMtBlock / 64];
   const uint32_t n = (uint32_t)nx * (uint32_t)ny * (uint32_t)nz;      // (below 2^31 / 7: the host's mt_dims -- 32-bit index arithmetic)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const uint32_t q = blockIdx.x * (uint32_t)kMtBlock + (uint32_t)tid;
   uint32_t mask = 0u, fc = 0u;
   if (q < n) {
@@ -176,61 +175,26 @@ mtet_count_kernel(const float *__restrict__ values, const float *__restrict__ we
   }
   // both counts in one number (vertices below bit 16: at most 256 x 7; faces above: at most 256 x 12), scanned over the workgroup
   const uint32_t x = (uint32_t)__popc(mask) | (fc << 16);
-  uint32_t incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0u;
-  for (int k = 0; k < wave; ++k) base += wtot[k];
-  const uint32_t excl = base + incl - x;
+  uint32_t upto;
+  const uint32_t excl = mesh_scan_local(x, upto);
   if (q < n) {
     edge_mask[q] = (uint8_t)mask;
     face_count[q] = (uint8_t)fc;
     vloc[q] = (uint16_t)(excl & 0xffffu);
     floc[q] = (uint16_t)(excl >> 16);
   }
-  if (tid == kMtBlock - 1) {
-    block_v[blockIdx.x] = (base + incl) & 0xffffu;
-    block_f[blockIdx.x] = (base + incl) >> 16;
+  if (tid == kMtBlock - 1) {      // (the last thread's inclusive prefix: the block's totals)
+    block_v[blockIdx.x] = upto & 0xffffu;
+    block_f[blockIdx.x] = upto >> 16;
   }
 }
 
-// ONE workgroup: the exclusive scan of block_v / block_f in place, kMtTop entries a round, the totals carried in `carry`
-// (vertices in the low 32 bits: below 2^31 in all; faces in the high 32: below 2^32 in all -- no carry between the halves)
+// ONE workgroup: the exclusive scan of block_v / block_f in place, kMtTop entries a round (mesh_scan.h's top level on the pair:
+// vertices in the low 32 bits: below 2^31 in all; faces in the high 32: below 2^32 in all -- no carry between the halves)
 __global__ void __launch_bounds__(kMtTop)
 mtet_scan_kernel(uint32_t *__restrict__ block_v, uint32_t *__restrict__ block_f, const long nb, long long *__restrict__ totals) {
-  __shared__ unsigned long long wtot[kMtTop / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned long long carry = 0ull;
-  for (long r0 = 0; r0 < nb; r0 += kMtTop) {      // (nb is the same in every thread: the barriers below are uniform)
-    const long i = r0 + tid;
-    const unsigned long long x = i < nb ? ((unsigned long long)block_v[i] | ((unsigned long long)block_f[i] << 32)) : 0ull;
-    unsigned long long incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t ylo = (uint32_t)__shfl_up((int)(uint32_t)incl, o, 64), yhi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), o, 64);
-      if (lane >= o) incl += (unsigned long long)ylo | ((unsigned long long)yhi << 32);
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    unsigned long long base = 0ull, all = 0ull;
-    for (int k = 0; k < kMtTop / 64; ++k) {
-      if (k < wave) base += wtot[k];
-      all += wtot[k];
-    }
-    const unsigned long long excl = carry + base + incl - x;
-    if (i < nb) {
-      block_v[i] = (uint32_t)excl;
-      block_f[i] = (uint32_t)(excl >> 32);
-    }
-    carry += all;
-    __syncthreads();      // (wtot is rewritten by the next round)
-  }
-  if (tid == 0) {
+  const unsigned long long carry = mesh_scan_top<unsigned long long>(block_v, block_f, nb);
+  if (threadIdx.x == 0) {
     totals[0] = (long long)(carry & 0xffffffffull);
     totals[1] = (long long)(carry >> 32);
   }

@@ -242,10 +242,6 @@ pm_face_kernel(const float *__restrict__ points, const int P, const float *__res
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ void pm_add(long long *acc, const float term, const double scale) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)llrint((double)term * scale));
-}
-
 // item t < P: point t with its face; item P + f: face f with its point (point_idx == nullptr, the single-directional form: no such
 // items).  Adds - u fl(w_k r) 2^s to the three vertices of the face and, for a face item, u r 2^s to the point
 __global__ void __launch_bounds__(256)
@@ -271,15 +267,15 @@ pm_scatter_kernel(const float *__restrict__ points, const int P, const float *__
     const float wk = b[k];
     if (wk == 0.0f) continue;      // (an edge or a corner: the vertex across gets nothing)
     long long *acc = acc_v + 3 * (size_t)iv[k];
-    pm_add(acc, -(wk * r[0]), scale);
-    pm_add(acc + 1, -(wk * r[1]), scale);
-    pm_add(acc + 2, -(wk * r[2]), scale);
+    atomic_add_i64(acc, llrint((double)(-(wk * r[0])) * scale));
+    atomic_add_i64(acc + 1, llrint((double)(-(wk * r[1])) * scale));
+    atomic_add_i64(acc + 2, llrint((double)(-(wk * r[2])) * scale));
   }
   if (!first) {
     long long *acc = acc_p + 3 * i;
-    pm_add(acc, r[0], scale);
-    pm_add(acc + 1, r[1], scale);
-    pm_add(acc + 2, r[2], scale);
+    atomic_add_i64(acc, llrint((double)r[0] * scale));
+    atomic_add_i64(acc + 1, llrint((double)r[1] * scale));
+    atomic_add_i64(acc + 2, llrint((double)r[2] * scale));
   }
 }
 

@@ -3,7 +3,7 @@
 // record of pm_record --, found without meeting every pair, so the pair cap of the brute route does not bind it.  What a search
 // has to prove is that it never skips an item that could hold the smallest key.
 //
-// (a) The grid, chosen on the device.  pm_grid_box_kernel: the bounding box of the UNION of verts and points (chamfer.hip's pass);
+// (a) The grid, chosen on the device.  grid_box_kernel (knn_grid.h): the bounding box of the UNION of verts and points;
 //     pm_grid_extent_kernel: the sum over the faces of 2 h_f (below: the largest extent of a face's bounding box), fp64 partial
 //     sums in an order fixed by the shapes; pm_grid_choose_kernel, one workgroup: the rule of ops.knn_grid with n = max(F, P) --
 //     about 2 n cubic cells, cell >= max extent / 1023, G_a <= 1024, G <= max(8 n, 2^15), at most 64 enlargements, the one-cell grid
@@ -58,8 +58,7 @@ constexpr float kPmGridBig = 1.0f;          // a triangle is small while h_f <= 
 constexpr double kPmGridFloor = 1.0;        // cell >= kPmGridFloor x the mean largest bounding-box extent of a face
 constexpr int kPmGridBlock = 128;           // queries a workgroup of the two searches
 constexpr int kPmGridLargeTile = 256;       // records of a tile of the large list: 16 KB of LDS
-constexpr int kPmGridItems = 8;             // items a thread of the box and extent passes: 2048 a workgroup
-constexpr int kPmGridTrips = 64;
+constexpr int kPmGridItems = 8;             // faces a thread of the extent pass: 2048 a workgroup
 // Route None takes the grid from this many pairs P F on (ops.POINT_MESH_GRID_MIN_PAIRS chooses; profiles/r28_point_mesh_grid.txt).
 // Measured: with the points near the surface the grid route wins from 10^7 pairs on (2 000 x 5 120: 247 against 258 us,
 // 200 000 x 81 920: 0.43 against 48.3 ms; 2^24 by the rule), with the points spread through the box it loses at EVERY size below the pair cap (its
@@ -67,12 +66,6 @@ constexpr int kPmGridTrips = 64;
 // 0.74 against 0.74 s one way, 0.75 against 1.46 s both).  The shapes cannot tell the two apart, so None stays on the brute force
 // up to the cap: the crossover is the cap.
 constexpr double kPmGridMinPairs = 274877906944.0;      // 2^38 = kPmMaxPairs
-
-// ops.knn_grid's cap on the cells of a grid for at most n items (chamfer.hip's chamfer_cell_cap; G and G + 1 stay ints)
-__host__ __device__ inline long pm_grid_cell_cap(const long n) {
-  const long cap = 8 * n > 32768l ? 8 * n : 32768l;
-  return cap < 2147483646l ? cap : 2147483646l;
-}
 
 struct PmGridHead {      // the workspace's first 64 bytes
   KnnGrid g;
@@ -122,36 +115,6 @@ __device__ __forceinline__ PmTriBox pm_grid_tribox(const float *__restrict__ ver
 
 // ---- the grid, chosen on the device -------------------------------------------------------------------------------------------
 
-// chamfer.hip's box pass over verts then points (fminf / fmaxf drop a NaN)
-__global__ void __launch_bounds__(256)
-pm_grid_box_kernel(const float *__restrict__ x, const int Nx, const float *__restrict__ y, const int Ny, float *__restrict__ partial) {
-  const size_t n = (size_t)Nx + (size_t)Ny;
-  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < kPmGridItems; ++k) {
-    const size_t i = ((size_t)blockIdx.x * kPmGridItems + k) * 256 + threadIdx.x;
-    if (i < n) {
-      const float *p = i < (size_t)Nx ? x + 3 * i : y + 3 * (i - (size_t)Nx);
-      const float a = p[0], b = p[1], c = p[2];
-      lo0 = fminf(lo0, a); lo1 = fminf(lo1, b); lo2 = fminf(lo2, c);
-      hi0 = fmaxf(hi0, a); hi1 = fmaxf(hi1, b); hi2 = fmaxf(hi2, c);
-    }
-  }
-  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
-  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
-  __shared__ float red[4][6];
-  if ((threadIdx.x & 63) == 0) {
-    float *r = red[threadIdx.x >> 6];
-    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int c = threadIdx.x;
-    const float a = red[0][c], b = red[1][c], d = red[2][c], e = red[3][c];
-    partial[(size_t)blockIdx.x * 6 + c] = c < 3 ? fminf(fminf(a, b), fminf(d, e)) : fmaxf(fmaxf(a, b), fmaxf(d, e));
-  }
-}
-
 // one fp64 sum of 2 h_f per 2048 faces (a face that is not finite adds nothing), added in an order fixed by the shapes
 __global__ void __launch_bounds__(256)
 pm_grid_extent_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F,
@@ -175,27 +138,16 @@ pm_grid_extent_kernel(const float *__restrict__ verts, const int V, const int32_
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// ONE workgroup: the box of the partial boxes, the mean extent, then thread 0 chooses the grid (chamfer_grid_kernel's rule plus
-// the floor), H, and zeroes the large list's counter
+// ONE workgroup: the box of the partial boxes, the mean extent, then thread 0 chooses the grid (grid_choose with the floor on the
+// default cell), H, and zeroes the large list's counter
 __global__ void __launch_bounds__(256)
 pm_grid_choose_kernel(const float *__restrict__ boxp, const int nb_box, const double *__restrict__ extp, const int nb_ext, const long F,
                       const long n, const float cell_size, PmGridHead *__restrict__ head) {
-  float lo0 = INFINITY, lo1 = INFINITY, lo2 = INFINITY, hi0 = -INFINITY, hi1 = -INFINITY, hi2 = -INFINITY;
-  for (int i = threadIdx.x; i < nb_box; i += 256) {
-    const float *p = boxp + (size_t)i * 6;
-    lo0 = fminf(lo0, p[0]); lo1 = fminf(lo1, p[1]); lo2 = fminf(lo2, p[2]);
-    hi0 = fmaxf(hi0, p[3]); hi1 = fmaxf(hi1, p[4]); hi2 = fmaxf(hi2, p[5]);
-  }
-  lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
-  hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
+  float lo[3], hi[3];
+  grid_box_reduce(boxp, nb_box, lo, hi);
   double es = 0.0;
   for (int i = threadIdx.x; i < nb_ext; i += 256) es += extp[i];
-  __shared__ float red[4][6];
   __shared__ double rede[256];
-  if ((threadIdx.x & 63) == 0) {
-    float *r = red[threadIdx.x >> 6];
-    r[0] = lo0; r[1] = lo1; r[2] = lo2; r[3] = hi0; r[4] = hi1; r[5] = hi2;
-  }
   rede[threadIdx.x] = es;
   __syncthreads();
   for (int h = 128; h > 0; h >>= 1) {
@@ -203,62 +155,12 @@ pm_grid_choose_kernel(const float *__restrict__ boxp, const int nb_box, const do
     __syncthreads();
   }
   if (threadIdx.x != 0) return;
-  float lo[3], hi[3];
-  for (int c = 0; c < 3; ++c) {
-    lo[c] = fminf(fminf(red[0][c], red[1][c]), fminf(red[2][c], red[3][c]));
-    hi[c] = fmaxf(fmaxf(red[0][c + 3], red[1][c + 3]), fmaxf(red[2][c + 3], red[3][c + 3]));
-  }
-  double ext[3], mx = 0.0;
-  bool fin = true;
-  for (int c = 0; c < 3; ++c) {
-    const float e = hi[c] - lo[c];
-    fin = fin && fabsf(lo[c]) < INFINITY && fabsf(hi[c]) < INFINITY && fabsf(e) < INFINITY;
-    ext[c] = e > 0.0f ? (double)e : 0.0;
-    mx = fmax(mx, ext[c]);
-  }
+  const double mean = rede[0] / (double)F;
   PmGridHead h;
-  h.g = KnnGrid{fin ? lo[0] : 0.0f, fin ? lo[1] : 0.0f, fin ? lo[2] : 0.0f, 1.0f, 1.0f, 1, 1, 1};      // the one-cell fallback
-  h.G = 1;
+  grid_choose(lo, hi, n, cell_size, mean > 0.0 && mean < (double)INFINITY ? kPmGridFloor * mean : 0.0, h.g, h.G);
   h.nlarge = 0;
-  for (int k = 0; k < 5; ++k) h.pad[k] = 0;
-  if (fin) {
-    const double cap = (double)pm_grid_cell_cap(n);
-    double cell;
-    if (cell_size > 0.0f && cell_size < INFINITY) {
-      cell = (double)cell_size;
-    } else {
-      int np = 0;
-      double vol = 1.0;
-      for (int c = 0; c < 3; ++c)
-        if (ext[c] > 0.0) { vol *= ext[c]; ++np; }
-      cell = np ? pow(vol / (2.0 * (double)(n > 1 ? n : 1)), 1.0 / (double)np) : 1.0;
-      const double mean = rede[0] / (double)F;
-      if (mean > 0.0 && mean < (double)INFINITY) cell = fmax(cell, kPmGridFloor * mean);
-    }
-    cell = fmax(cell, fmax(mx / 1023.0, 1e-30));
-    for (int trip = 0; trip < kPmGridTrips; ++trip) {
-      const float cf = (float)cell;
-      const float inv = 1.0f / cf;
-      if (!(cf > 0.0f) || !(cf < INFINITY) || !(inv > 0.0f) || !(inv < INFINITY)) break;
-      double cells = 1.0;
-      bool fits = true;
-      int g[3];
-      for (int c = 0; c < 3; ++c) {
-        const double q = floor(ext[c] / (double)cf) + 1.0;
-        fits = fits && q <= (double)kKnnMaxAxis;
-        g[c] = (int)fmin(q, (double)kKnnMaxAxis);
-        cells *= q;
-      }
-      if (fits && cells <= cap) {
-        h.g.cell = cf; h.g.inv = inv;
-        h.g.gx = g[0]; h.g.gy = g[1]; h.g.gz = g[2];
-        h.G = g[0] * g[1] * g[2];
-        break;
-      }
-      cell = (double)cf * fmax(1.05, cbrt(cells / cap));      // (every round grows the cell)
-    }
-  }
   h.H = kPmGridBig * h.g.cell;
+  for (int k = 0; k < 5; ++k) h.pad[k] = 0;
   *head = h;
 }
 
@@ -278,14 +180,6 @@ struct PmGridTables {
   int *pcell, *pcounts, *pstart;
 };
 
-__global__ void __launch_bounds__(256)
-pm_grid_zero_kernel(const PmGridHead *__restrict__ head, int *__restrict__ c0, int *__restrict__ c1) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)head->G) return;
-  c0[i] = 0;
-  c1[i] = 0;
-}
-
 // workgroups [0, nbf): a face a thread -- its cell's count, or a slot of the large list (fcell = -1 - slot); the rest: a point a thread
 __global__ void __launch_bounds__(256)
 pm_grid_count_kernel(const PmGridTables t, const unsigned nbf, PmGridHead *__restrict__ head) {
@@ -296,8 +190,7 @@ pm_grid_count_kernel(const PmGridTables t, const unsigned nbf, PmGridHead *__res
   if (first) {
     const PmTriBox b = pm_grid_tribox(t.verts, t.V, t.faces, i);
     if (b.fin && b.h <= head->H) {
-      const int c = (knn_axis_cell(b.cz, g.loz, g.inv, g.gz) * g.gy + knn_axis_cell(b.cy, g.loy, g.inv, g.gy)) * g.gx +
-                    knn_axis_cell(b.cx, g.lox, g.inv, g.gx);
+      const int c = grid_cell_of(g, b.cx, b.cy, b.cz);
       t.fcell[i] = c;
       atomicAdd(t.fcounts + c, 1);
     } else {
@@ -305,14 +198,10 @@ pm_grid_count_kernel(const PmGridTables t, const unsigned nbf, PmGridHead *__res
     }
     return;
   }
-  const float *p = t.points + 3 * i;
-  const int c = (knn_axis_cell(p[2], g.loz, g.inv, g.gz) * g.gy + knn_axis_cell(p[1], g.loy, g.inv, g.gy)) * g.gx +
-                knn_axis_cell(p[0], g.lox, g.inv, g.gx);
-  t.pcell[i] = c;
-  atomicAdd(t.pcounts + c, 1);
+  grid_count_point(g, t.points, i, t.pcell, t.pcounts);
 }
 
-// counts[c] falls back to zero, one slot an item (chamfer_fill_kernel); a large triangle takes slot F - 1 - k of the table
+// a point takes its row as chamfer.hip's do; a small triangle claims its row the same way, a large one takes slot F - 1 - k of the table
 __global__ void __launch_bounds__(256)
 pm_grid_fill_kernel(const PmGridTables t, const unsigned nbf, const PmGridHead *__restrict__ head) {
   const bool first = blockIdx.x < nbf;
@@ -320,23 +209,16 @@ pm_grid_fill_kernel(const PmGridTables t, const unsigned nbf, const PmGridHead *
   const int N = first ? t.F : t.P;
   if (i >= (size_t)N) return;
   const int c = (first ? t.fcell : t.pcell)[i];
-  int pos;
-  if (first && c < 0) {
-    pos = N + c;      // N - 1 - k, k = -1 - c
-  } else {
-    if (c < 0 || c >= head->G) return;      // (the count pass wrote a cell of this grid: a guard, not a route)
-    const int slot = atomicSub((first ? t.fcounts : t.pcounts) + c, 1) - 1;
-    pos = (first ? t.fstart : t.pstart)[c] + slot;
-    if (slot < 0) return;
+  const bool large = first && c < 0;
+  if (!large && (c < 0 || c >= head->G)) return;      // (the count pass wrote a cell of this grid: a guard, not a route)
+  if (!first) {
+    grid_fill_point(t.points, i, c, t.pcounts, t.pstart, N, t.psorted);
+    return;
   }
+  const int pos = large ? N + c : grid_claim_row(t.fcounts, t.fstart, c, N);      // N - 1 - k, k = -1 - c
   if (pos < 0 || pos >= N) return;      // (cannot happen after the count pass over the same table: a guard, not a route)
-  if (first) {
-    t.rec[pos] = pm_record(t.verts, t.V, t.faces, i);
-    t.fidx[pos] = (int32_t)i;
-  } else {
-    const float *p = t.points + 3 * i;
-    t.psorted[pos] = make_float4(p[0], p[1], p[2], __int_as_float((int)i));
-  }
+  t.rec[pos] = pm_record(t.verts, t.V, t.faces, i);
+  t.fidx[pos] = (int32_t)i;
 }
 
 // ---- the two searches ---------------------------------------------------------------------------------------------------------
@@ -470,9 +352,9 @@ static PmGridLayout pm_grid_layout(const long V, const long F, const long P) {
   PmGridLayout l;
   const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   const long n = F > P ? F : P;
-  l.cap = pm_grid_cell_cap(n);
+  l.cap = grid_cell_cap(n);
   l.nb_scan = (int)((l.cap + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
-  l.nb_box = (int)((V + P + 256 * kPmGridItems - 1) / (256 * kPmGridItems));
+  l.nb_box = (int)((V + P + 256 * kGridBoxItems - 1) / (256 * kGridBoxItems));
   l.nb_ext = (int)((F + 256 * kPmGridItems - 1) / (256 * kPmGridItems));
   l.nb_loss[0] = (unsigned)((P + 256 * kChLossItems - 1) / (256 * kChLossItems));
   l.nb_loss[1] = (unsigned)((F + 256 * kChLossItems - 1) / (256 * kChLossItems));
@@ -513,19 +395,14 @@ static void pm_grid_searches(const float *points, const long P, const float *ver
                        ints(l.fcounts), ints(l.fstart), reinterpret_cast<float4 *>(ws + l.psorted), ints(l.pcell), ints(l.pcounts),
                        ints(l.pstart)};
   const unsigned nbf = (unsigned)((F + 255) / 256), nbp = (unsigned)((P + 255) / 256);
-  hipLaunchKernelGGL(pm_grid_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, verts, (int)V, points, (int)P, boxp);
+  hipLaunchKernelGGL(grid_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, verts, (int)V, points, (int)P, boxp);
   hipLaunchKernelGGL(pm_grid_extent_kernel, dim3((unsigned)l.nb_ext), dim3(256), 0, st, verts, (int)V, faces, (int)F, extp);
   hipLaunchKernelGGL(pm_grid_choose_kernel, dim3(1), dim3(256), 0, st, boxp, l.nb_box, extp, l.nb_ext, F, F > P ? F : P, cell_size, head);
-  hipLaunchKernelGGL(pm_grid_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, head, t.fcounts, t.pcounts);
+  hipLaunchKernelGGL(grid_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, &head->G, t.fcounts, t.pcounts);
   hipLaunchKernelGGL(pm_grid_count_kernel, dim3(nbf + nbp), dim3(256), 0, st, t, nbf, head);
   int *counts[2] = {t.fcounts, t.pcounts}, *start[2] = {t.fstart, t.pstart}, *bsum[2] = {ints(l.fbsum), ints(l.pbsum)};
   const int N[2] = {(int)F, (int)P};
-  for (int k = 0; k < 2; ++k) {
-    hipLaunchKernelGGL(knn_scan_partial_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, counts[k], 0, &head->G, bsum[k]);
-    hipLaunchKernelGGL(knn_scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum[k], l.nb_scan);
-    hipLaunchKernelGGL(knn_scan_final_kernel, dim3((unsigned)l.nb_scan), dim3(kKnnScanBlock), 0, st, counts[k], 0, &head->G, bsum[k], N[k],
-                       start[k]);
-  }
+  for (int k = 0; k < 2; ++k) grid_scan_launch(counts[k], 0, &head->G, bsum[k], l.nb_scan, N[k], start[k], st);
   hipLaunchKernelGGL(pm_grid_fill_kernel, dim3(nbf + nbp), dim3(256), 0, st, t, nbf, head);
   hipLaunchKernelGGL(pm_grid_point_kernel, dim3((unsigned)((P + kPmGridBlock - 1) / kPmGridBlock)), dim3(kPmGridBlock), 0, st, t, head,
                      face_idx, d2p, bary_p);

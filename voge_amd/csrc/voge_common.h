@@ -434,6 +434,11 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   v += VOGE_DPP(v, 0x140);
   return (VOGE_LANE(v, 0) + VOGE_LANE(v, 16)) + (VOGE_LANE(v, 32) + VOGE_LANE(v, 48));
 }
+// the fixed-point scatters' one atomic: a signed 64-bit integer add (two's complement, so the unsigned add is the signed one);
+// integer addition is exact, the sum depends on no order
+__device__ __forceinline__ void atomic_add_i64(long long *acc, const long long v) {
+  atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)v);
+}
 
 // A bounding cone of a set of unit directions: axis a, cos/sin of the half angle with the
 // rounding pushed to the conservative side.  ok == false -> cone too wide / degenerate,

@@ -2600,9 +2600,9 @@ def vertex_normals(verts, faces):
 
 MESH_SIMPLIFY_BLOCK = MESH_CLEAN_BLOCK      # the scans are mesh_clean.hip's (csrc/mesh_scan.h)
 MESH_SIMPLIFY_TOP = MESH_CLEAN_TOP
-MESH_SIMPLIFY_CHANNELS = 8                  # kMsChannels of mesh_simplify.hip: the attribute channels of one launch set
+MESH_SIMPLIFY_CHANNELS = 8                  # kSimpChannels of mesh_simplify.hip: the attribute channels of one launch set
 MESH_SIMPLIFY_MAX_CELLS = 2 ** 21 - 1       # cells on an axis (Aggregation.MESH_SIMPLIFY_MAX_CELLS)
-MESH_SIMPLIFY_LAMBDA = 1e-3                 # kMsLambda
+MESH_SIMPLIFY_LAMBDA = 1e-3                 # kSimpLambda
 
 
 def mesh_simplify_capacity(V, F):
