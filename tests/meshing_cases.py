@@ -218,13 +218,16 @@ def radial_error(verts):
     return float((verts.double().norm(dim=-1) - SPHERE_R).abs().max())
 
 
-def tsdf_bound(centre, trunc, B, depth_max):
-    """TSDF_BOUND of the header for the end-to-end grid"""
-    X = abs(GRID_LO) + (GRID_N - 1) * GRID_H
-    C = float(centre.abs().max())
+def tsdf_bound_of(X, C, trunc, B, depth_max):
+    """TSDF_BOUND of the header for any grid: X bounds the numbers a coordinate lo + i h passes through, C = max |centre component|"""
     e1 = EPS * (3 * X + 1.5 * C)
     dist = math.sqrt(3) * (X + C)
     return (math.sqrt(3) * e1 + EPS * (4 * dist + depth_max)) / trunc + EPS + 3 * B * EPS
+
+
+def tsdf_bound(centre, trunc, B, depth_max):
+    """TSDF_BOUND of the header for the end-to-end grid"""
+    return tsdf_bound_of(abs(GRID_LO) + (GRID_N - 1) * GRID_H, float(centre.abs().max()), trunc, B, depth_max)
 
 
 def definition_fp64(depth, R, T, focal, pp, trunc, mark=None, max_weight=None, n=GRID_N):

@@ -33,14 +33,25 @@ def remade_at(ptr, make, tries=32):
 
 def recycled_faces(check, width, device="cpu", rounds=8):
     """`rounds` times: a good table is checked and freed, and a bad one of its shape and dtype, made right after, must raise
-    ValueError.  -> in how many rounds the bad table really had the good one's address (both at version 0)."""
+    ValueError.  -> in how many rounds the bad table really had the good one's address (both at version 0).
+    On the host the two tables wrap one numpy buffer in turn (at_the_same_address below), so the address is the same in every
+    round whatever the heap looks like: whether malloc hands a freed 2 400-byte block back depends on where the pieces trimmed
+    off its aligned allocation went, and came out anywhere between 0 and 8 rounds of 8 from one run of the suite to the next.  A device's
+    caching allocator does hand the block back, and there the tables are made and freed as a caller's are."""
     reused = 0
+    buf = np.zeros((len(GOOD), width), np.int64)
     for _ in range(rounds):
-        f = torch.tensor([row[3 - width:] for row in GOOD], device=device)
+        if device == "cpu":
+            f = at_the_same_address(buf, np.asarray(GOOD)[:, 3 - width:])
+        else:
+            f = torch.tensor([row[3 - width:] for row in GOOD], device=device)
         check(f)
         ptr = f.data_ptr()
         del f
-        g = remade_at(ptr, lambda: torch.tensor([row[3 - width:] for row in BAD], device=device))
+        if device == "cpu":
+            g = at_the_same_address(buf, np.asarray(BAD)[:, 3 - width:])
+        else:
+            g = remade_at(ptr, lambda: torch.tensor([row[3 - width:] for row in BAD], device=device))
         assert g._version == 0
         reused += int(g.data_ptr() == ptr)
         with pytest.raises(ValueError, match="indices must lie"):

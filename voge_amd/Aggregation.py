@@ -633,8 +633,22 @@ def point_mesh_term(verts, faces, points, single_directional=False, point_reduct
 
 
 def camera_centres(R, T):
-    """C [B,3] = -T @ R^-1 in the tensors' dtype (row vectors, X_view = X_world @ R + T): the point every pixel ray of a view leaves."""
+    """C [B,3] = -T @ R^-1 in the tensors' dtype (row vectors, X_view = X_world @ R + T): the point every pixel ray of a view leaves.
+    On a device R^-1 is the closed form adj(R) / det(R) from elementwise operations: torch.linalg.inv reads its status word back on
+    the host, a synchronisation that TSDFVolume.integrate promises not to make and that a stream capture refuses.  In fp64 the two
+    agree to a few 2^-53, the same fp32 centre once rounded; a singular R raises on the host and gives a centre that is not finite
+    on a device."""
+    if R.is_cuda:
+        return _camera_centres_closed_form(R, T)
     return -torch.einsum("bj,bjk->bk", T, torch.linalg.inv(R))
+
+
+def _camera_centres_closed_form(R, T):
+    """camera_centres from elementwise operations alone: column k of det(R) R^-1 is the cross product of the other two rows of R"""
+    r0, r1, r2 = R[:, 0], R[:, 1], R[:, 2]
+    adj = torch.stack((torch.linalg.cross(r1, r2), torch.linalg.cross(r2, r0), torch.linalg.cross(r0, r1)), -1)      # [B,j,k] = det(R) R^-1
+    det = (r0 * adj[:, :, 0]).sum(-1, keepdim=True)
+    return -(T[:, :, None] * adj).sum(1) / det
 
 
 def tsdf_integrate(tsdf, weight, depth, R, T, focal, pp, lo, voxel_size, trunc, max_weight=None, centre=None, mark=None, *, attr=None,

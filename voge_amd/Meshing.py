@@ -150,7 +150,9 @@ class TSDFVolume:
         """Fuse depth [B,H,W] (get_depth's: the distance along the unit pixel ray; not finite or <= 0: no surface) seen by
         `cameras` (R, T, focal_length, principal_point, as cameras.pixel_rays reads them; B views or one for all) into the
         volume, in place, the views in their order: Aggregation.tsdf_integrate's rule.  rows= bands and distributed.Stripes
-        are not taken.  One launch on a HIP device, nothing read back; not differentiable.  Returns the volume.
+        are not taken.  One launch on a HIP device, nothing read back (the call can be captured into a graph; R is therefore not checked
+        there: a singular R, which raises on the host, gives a centre that is not finite and poisons what its view updates); not
+        differentiable.  Returns the volume.
         attr [B,H,W,C] -- the layout of the renderer's images and of interpolate_attr's outputs -- is required if and only if the
         volume has channels = C > 0: the attribute of the depth's own nearest pixel enters vol.attr as a running average under the
         weight of the distance, wherever the view updates the grid point (step 6 of the rule).  Its VALUES ARE NOT EXAMINED: a NaN
