@@ -96,7 +96,9 @@ def clashes(csrc=CSRC, dirs=INCLUDE_DIRS):
 
 def test_the_scan_sees_the_library():
     files = {os.path.basename(p) for u in units() for p in closure(u, INCLUDE_DIRS)}
-    assert {"knn.hip", "chamfer.hip", "point_mesh.hip", "point_mesh_grid.h", "knn_grid.h", "mesh_scan.h", "voge_common.h"} <= files
+    assert {"knn.hip", "chamfer.hip", "point_mesh.hip", "point_mesh_grid.h", "knn_grid.h", "mesh_scan.h", "voge_common.h", "fixed_point.h"} <= files
+    types, kernels = definitions(os.path.join(CSRC, "fixed_point.h"))
+    assert "FixedHead" in types and not kernels      # (a kernel in a header is emitted by every unit that includes it)
     types, kernels = definitions(os.path.join(CSRC, "knn_grid.h"))
     assert "KnnGrid" in types and "knn_scan_final_kernel" in kernels
     types, kernels = definitions(os.path.join(CSRC, "knn.hip"))

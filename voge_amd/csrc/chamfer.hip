@@ -282,31 +282,29 @@ struct ChamferLayout {
   size_t head, boxp, sorted[2], cellid[2], counts[2], start[2], bsum[2], d2[2], psum, pmax, total;
   long cap;
   int nb_scan, nb_box;
-  unsigned nb_loss[2];
 };
 static ChamferLayout chamfer_layout(const long Nx, const long Ny) {
   ChamferLayout l;
-  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   const long N[2] = {Nx, Ny}, n = Nx > Ny ? Nx : Ny;
   l.cap = grid_cell_cap(n);
   l.nb_scan = (int)((l.cap + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
   l.nb_box = (int)((Nx + Ny + 256 * kGridBoxItems - 1) / (256 * kGridBoxItems));
-  size_t at = 0;
-  l.head = at; at += sizeof(ChamferHead);
-  l.boxp = at; at += up16((size_t)l.nb_box * 6 * sizeof(float));
-  for (int c = 0; c < 2; ++c) {
-    l.nb_loss[c] = (unsigned)((N[c] + 256 * kChLossItems - 1) / (256 * kChLossItems));
-    l.sorted[c] = at; at += (size_t)N[c] * 16;
-    l.cellid[c] = at; at += up16((size_t)N[c] * 4);
-    l.counts[c] = at; at += up16((size_t)l.cap * 4);
-    l.start[c] = at; at += up16((size_t)(l.cap + 1) * 4);
-    l.bsum[c] = at; at += up16((size_t)l.nb_scan * 4);
-    l.d2[c] = at; at += up16((size_t)N[c] * 4);
+  const size_t nb_loss = chamfer_loss_blocks(Nx) + chamfer_loss_blocks(Ny);
+  Carve c;
+  l.head = c.take_exact(sizeof(ChamferHead));
+  l.boxp = c.take((size_t)l.nb_box * 6 * sizeof(float));
+  for (int k = 0; k < 2; ++k) {
+    l.sorted[k] = c.take_exact((size_t)N[k] * 16);
+    l.cellid[k] = c.take((size_t)N[k] * 4);
+    l.counts[k] = c.take((size_t)l.cap * 4);
+    l.start[k] = c.take((size_t)(l.cap + 1) * 4);
+    l.bsum[k] = c.take((size_t)l.nb_scan * 4);
+    l.d2[k] = c.take((size_t)N[k] * 4);
   }
-  l.psum = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(double));
-  l.pmax = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(float));
+  l.psum = c.take(nb_loss * sizeof(double));
+  l.pmax = c.take(nb_loss * sizeof(float));
   const size_t bwd = (size_t)(Nx + Ny) * 3 * sizeof(long long);      // the backward's accumulators, a call of its own
-  l.total = at > bwd ? at : bwd;
+  l.total = c.at > bwd ? c.at : bwd;
   return l;
 }
 
@@ -338,10 +336,10 @@ static void chamfer_searches(const float *x, const long Nx, const float *y, cons
     bsum[k] = reinterpret_cast<int *>(ws + l.bsum[k]);
   }
   const long n = Nx > Ny ? Nx : Ny;
-  const unsigned nbx = (unsigned)((Nx + 255) / 256), nby = (unsigned)((Ny + 255) / 256);
+  const unsigned nbx = blocks256(Nx), nby = blocks256(Ny);
   hipLaunchKernelGGL(grid_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, boxp);
   hipLaunchKernelGGL(chamfer_grid_kernel, dim3(1), dim3(256), 0, st, boxp, l.nb_box, n, cell_size, head);
-  hipLaunchKernelGGL(grid_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, &head->G, c[0].counts, c[1].counts);
+  hipLaunchKernelGGL(grid_zero_kernel, dim3(blocks256(l.cap)), dim3(256), 0, st, &head->G, c[0].counts, c[1].counts);
   hipLaunchKernelGGL(chamfer_count_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
   for (int k = 0; k < 2; ++k) grid_scan_launch(c[k].counts, 0, &head->G, bsum[k], l.nb_scan, c[k].N, c[k].start, st);
   hipLaunchKernelGGL(chamfer_fill_kernel, dim3(nbx + nby), dim3(256), 0, st, c[0], c[1], nbx, head);
@@ -351,8 +349,6 @@ static void chamfer_searches(const float *x, const long Nx, const float *y, cons
   const unsigned sb1 = both ? (unsigned)((Ny + kChSearchBlock - 1) / kChSearchBlock) : 0u;
   hipLaunchKernelGGL(chamfer_search_kernel, dim3(sb0 + sb1), dim3(kChSearchBlock), 0, st, d0, d1, sb0, head);
 }
-
-static bool chamfer_ws_bad(const void *ws) { return !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0; }
 
 }  // namespace voge
 
@@ -368,7 +364,7 @@ extern "C" int voge_nearest_points(const float *queries, long Nq, const float *p
   if (Nq < 0 || Nq > kChamferMaxN || Np < 1 || Np > kChamferMaxN || route < kRouteAuto || route > kRouteGrid) return VOGE_ERR_BAD_ARG;
   if (!(cell_size >= 0.0f) || !(cell_size < INFINITY)) return VOGE_ERR_BAD_ARG;      // (0: the default cell)
   if (Nq == 0) return 0;
-  if (!queries || !points || !idx || !d2 || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  if (!queries || !points || !idx || !d2 || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const ChamferLayout l = chamfer_layout(Nq, Np);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
   chamfer_searches(queries, Nq, points, Np, chamfer_brute(route, Nq, Np), cell_size, false, idx, d2, nullptr, nullptr,
@@ -380,23 +376,16 @@ extern "C" int voge_chamfer_fwd(const float *x, long Nx, const float *y, long Ny
                                 int32_t *nn_y, int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream) {
   if (!chamfer_sizes_ok(Nx, Ny) || route < kRouteAuto || route > kRouteGrid || (flags & ~3)) return VOGE_ERR_BAD_ARG;
   const bool both = !(flags & kChamferSingle);
-  if (!x || !y || !loss || !nn_x || (both && !nn_y) || !meta || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  if (!x || !y || !loss || !nn_x || (both && !nn_y) || !meta || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const ChamferLayout l = chamfer_layout(Nx, Ny);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
   char *ws = static_cast<char *>(workspace);
   hipStream_t st = (hipStream_t)stream;
   float *d2x = reinterpret_cast<float *>(ws + l.d2[0]), *d2y = reinterpret_cast<float *>(ws + l.d2[1]);
   chamfer_searches(x, Nx, y, Ny, chamfer_brute(route, Nx, Ny), 0.0f, both, nn_x, d2x, nn_y, d2y, ws, l, st);
-  double *psum = reinterpret_cast<double *>(ws + l.psum);
-  float *pmax = reinterpret_cast<float *>(ws + l.pmax);
-  const unsigned nba = l.nb_loss[0], nbb = both ? l.nb_loss[1] : 0u;
-  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2x, (int)Nx, d2y, (int)Ny, nba, psum, pmax);
-  const long n = Nx > Ny ? Nx : Ny;
-  int bits = 0;
-  while ((1l << bits) < n) ++bits;      // n <= 2^bits: every scatter list of the backward
-  const bool sum = flags & kChamferSum;
-  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)Nx,
-                     sum ? 1.0 : (double)Ny, bits, loss, meta);
+  // max(Nx, Ny): every scatter list of the backward -- the points of one cloud that name one point of the other
+  chamfer_loss_launch(d2x, Nx, d2y, Ny, both, flags & kChamferSum, Nx > Ny ? Nx : Ny, reinterpret_cast<double *>(ws + l.psum),
+                      reinterpret_cast<float *>(ws + l.pmax), loss, meta, st);
   return launch_status();
 }
 
@@ -405,19 +394,19 @@ extern "C" int voge_chamfer_bwd(const float *x, long Nx, const float *y, long Ny
                                 size_t workspace_bytes, voge_stream_t stream) {
   if (!chamfer_sizes_ok(Nx, Ny) || (flags & ~3)) return VOGE_ERR_BAD_ARG;
   const bool both = !(flags & kChamferSingle);
-  if (!x || !y || !nn_x || (both && !nn_y) || !meta || !g_loss || !g_x || !g_y || chamfer_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  if (!x || !y || !nn_x || (both && !nn_y) || !meta || !g_loss || !g_x || !g_y || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const size_t acc_bytes = (size_t)(Nx + Ny) * 3 * sizeof(long long);
   if (workspace_bytes < acc_bytes) return VOGE_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   long long *acc_x = static_cast<long long *>(workspace), *acc_y = acc_x + 3 * (size_t)Nx;
   const hipError_t fe = voge_fill_async(workspace, 0, acc_bytes, st);
   if (fe != hipSuccess) return (int)fe;
-  const unsigned nbx = (unsigned)((Nx + 255) / 256), nby = both ? (unsigned)((Ny + 255) / 256) : 0u;
+  const unsigned nbx = blocks256(Nx), nby = both ? blocks256(Ny) : 0u;
   hipLaunchKernelGGL(chamfer_scatter_kernel, dim3(nbx + nby), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, nn_x, both ? nn_y : nullptr, meta,
                      acc_x, acc_y, nbx);
   const bool sum = flags & kChamferSum;
   const double w_x = sum ? 2.0 : 2.0 / (double)Nx, w_y = both ? (sum ? 2.0 : 2.0 / (double)Ny) : 0.0;
-  hipLaunchKernelGGL(chamfer_finish_kernel, dim3((unsigned)((Nx + Ny + 255) / 256)), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, nn_x,
+  hipLaunchKernelGGL(chamfer_finish_kernel, dim3(blocks256(Nx + Ny)), dim3(256), 0, st, x, (int)Nx, y, (int)Ny, nn_x,
                      both ? nn_y : nullptr, meta, acc_x, acc_y, g_loss, w_x, w_y, g_x, g_y);
   return launch_status();
 }

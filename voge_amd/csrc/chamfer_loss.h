@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "voge_common.h"
+#include "fixed_point.h"
 
 namespace voge {
 
@@ -47,6 +48,7 @@ chamfer_loss_partial_kernel(const float *__restrict__ d2a, const int Na, const f
 
 // ONE workgroup: loss = sum_a / div_a + sum_b / div_b in fp64, rounded once; meta[0] = the backward's scale exponent s:
 // with D = sqrt(max d2 (1 + 2^-20) + 2^-148) < 2^e and every scatter list at most 2^list_bits long, s = 62 - list_bits - e
+// (fixed_point.h's rule on a double D, without the head and without the clamp)
 static __global__ void __launch_bounds__(256)
 chamfer_loss_final_kernel(const double *__restrict__ psum, const float *__restrict__ pmax, const unsigned nba, const unsigned nbb,
                           const double div_a, const double div_b, const int list_bits, float *__restrict__ loss,
@@ -71,12 +73,22 @@ chamfer_loss_final_kernel(const double *__restrict__ psum, const float *__restri
   loss[0] = (float)(red[0][0] / div_a + (nbb ? red[1][0] / div_b : 0.0));
   int s = 0;
   const double D = sqrt((double)redm[0] * (1.0 + 0x1p-20) + 0x1p-148);
-  if (D < (double)INFINITY) {      // (false for a NaN too: s = 0, the values are out of contract)
-    int e;
-    frexp(D, &e);      // D = f 2^e, f in [0.5, 1): D < 2^e
-    s = 62 - list_bits - e;
-  }
+  if (D < (double)INFINITY) s = fixed_exponent(D, list_bits);      // (false for a NaN too: s = 0, the values are out of contract)
   meta[0] = s; meta[1] = 0; meta[2] = 0; meta[3] = 0;
+}
+
+// workgroups of chamfer_loss_partial_kernel for a list of n distances: one psum and one pmax entry each
+static inline unsigned chamfer_loss_blocks(const long n) { return (unsigned)((n + 256 * kChLossItems - 1) / (256 * kChLossItems)); }
+
+// The loss tail of a forward, two launches: the partial sums of d2a [Na] and -- both -- d2b [Nb], then the one workgroup that writes
+// loss = sum_a / Na + sum_b / Nb (sum: the plain sums) and meta.  list_bound: no scatter list of the backward is longer (the caller
+// says why).  psum and pmax hold chamfer_loss_blocks(Na) + chamfer_loss_blocks(Nb) entries.
+static inline void chamfer_loss_launch(const float *d2a, const long Na, const float *d2b, const long Nb, const bool both, const bool sum,
+                                       const long list_bound, double *psum, float *pmax, float *loss, int32_t *meta, hipStream_t st) {
+  const unsigned nba = chamfer_loss_blocks(Na), nbb = both ? chamfer_loss_blocks(Nb) : 0u;
+  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2a, (int)Na, d2b, (int)Nb, nba, psum, pmax);
+  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)Na,
+                     sum ? 1.0 : (double)Nb, ceil_log2(list_bound), loss, meta);
 }
 
 }  // namespace voge

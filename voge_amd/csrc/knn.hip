@@ -256,14 +256,14 @@ struct KnnLayout {
 };
 static KnnLayout knn_layout(const long N, const long G) {
   KnnLayout l;
-  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   l.nb = (int)((G + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
-  l.sorted = 0;
-  l.cellid = l.sorted + (size_t)N * 16;
-  l.counts = l.cellid + up16((size_t)N * 4);
-  l.start = l.counts + up16((size_t)G * 4);
-  l.bsum = l.start + up16((size_t)(G + 1) * 4);
-  l.total = l.bsum + up16((size_t)l.nb * 4);
+  Carve c;
+  l.sorted = c.take_exact((size_t)N * 16);
+  l.cellid = c.take((size_t)N * 4);
+  l.counts = c.take((size_t)G * 4);
+  l.start = c.take((size_t)(G + 1) * 4);
+  l.bsum = c.take((size_t)l.nb * 4);
+  l.total = c.at;
   return l;
 }
 
@@ -286,7 +286,7 @@ extern "C" int voge_knn_points(const float *points, long N, int k, int include_s
   const float inv = 1.0f / cell;
   if (!(inv > 0.0f) || !(inv < INFINITY) || !knn_grid_ok(N, gx, gy, gz)) return VOGE_ERR_BAD_ARG;
   if (N == 0) return 0;
-  if (!points || !idx || !d2 || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return VOGE_ERR_BAD_ARG;
+  if (!points || !idx || !d2 || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const long G = knn_cells(gx, gy, gz);
   const KnnLayout l = knn_layout(N, G);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
@@ -296,7 +296,7 @@ extern "C" int voge_knn_points(const float *points, long N, int k, int include_s
       *start = reinterpret_cast<int *>(ws + l.start), *bsum = reinterpret_cast<int *>(ws + l.bsum);
   const KnnGrid g{lo_x, lo_y, lo_z, cell, inv, gx, gy, gz};
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nblk = (unsigned)((N + 255) / 256);
+  const unsigned nblk = blocks256(N);
   const hipError_t fe = voge_fill_async(counts, 0, (size_t)G * 4, st);
   if (fe != hipSuccess) return (int)fe;
   hipLaunchKernelGGL(knn_count_kernel, dim3(nblk), dim3(256), 0, st, points, (int)N, g, cellid, counts);
@@ -317,7 +317,7 @@ extern "C" int voge_knn_frames(const float *points, const int32_t *idx, long N, 
   if (k > kKnnMaxK) return VOGE_ERR_K_TOO_LARGE;
   if (N == 0) return 0;
   if (!points || !idx || !quats || !eig) return VOGE_ERR_BAD_ARG;
-  hipLaunchKernelGGL(knn_frames_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, points, idx, (int)N, k,
+  hipLaunchKernelGGL(knn_frames_kernel, dim3(blocks256(N)), dim3(256), 0, (hipStream_t)stream, points, idx, (int)N, k,
                      toward, toward_per_point != 0, quats, eig);
   return launch_status();
 }

@@ -49,7 +49,7 @@
 // voge_vertex_normals, four launches, nothing read back (capturable): PyTorch3D's verts_normals_packed, the normalised sum over the
 // faces at a vertex of cr = (b - a) x (c - a), which weights them by area.  cr is mesh_sample.hip's ms_face: differences first,
 // every component (p q) - (r s), one IEEE fp32 operation each (-ffp-contract=off): the bits of Aggregation._face_cross.  The sum is
-// made in FIXED POINT as mesh_sample.hip's backward and chamfer.hip make theirs: the zero fill of acc [V][4] and the head;
+// made in FIXED POINT (fixed_point.h: the head, the exponent rule and its bound): the zero fill of acc [V][4] and the head;
 // vn_absmax_kernel (D = the largest finite |cr| component, by an integer atomic max on the float's bits: a maximum has no order);
 // vn_scatter_kernel (s = 62 - L - e with 2^L >= 3 F -- a vertex is named by at most 3 F corners -- and 2^e > D, chosen by every
 // thread from D, clamped to +-1000; round(cr 2^s) added to the face's three vertices with 64-bit INTEGER atomics: |term| <= 2^(62 - L),
@@ -61,6 +61,7 @@
 #include <math.h>
 
 #include "voge_common.h"
+#include "fixed_point.h"
 #include "mesh_scan.h"      // kMcBlock, kMcTop, kMcMax and the two scan levels, shared with mesh_simplify.hip
 
 namespace voge {
@@ -258,11 +259,6 @@ mc_emit_kernel(const float *__restrict__ verts, const int32_t *__restrict__ face
 
 // ---- vertex normals -----------------------------------------------------------------------------------------------------------
 
-struct VnHead {      // the workspace's first 16 bytes, zero-filled with the accumulators
-  uint32_t dmax_bits;
-  uint32_t pad[3];
-};
-
 struct VnCross {
   float x, y, z;
   bool ok;      // the face's indices are inside the table
@@ -273,7 +269,7 @@ __device__ __forceinline__ VnCross vn_cross(const float *__restrict__ verts, con
                                             int (&iv)[3]) {
   VnCross c = {0.0f, 0.0f, 0.0f, false};
   iv[0] = faces[3 * f]; iv[1] = faces[3 * f + 1]; iv[2] = faces[3 * f + 2];
-  if ((unsigned)iv[0] >= (unsigned)V || (unsigned)iv[1] >= (unsigned)V || (unsigned)iv[2] >= (unsigned)V) return c;
+  if (!face_in_range(iv[0], iv[1], iv[2], V)) return c;
   const float *a = verts + 3 * (size_t)iv[0], *b = verts + 3 * (size_t)iv[1], *cc = verts + 3 * (size_t)iv[2];
   const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
   const float e2x = cc[0] - a[0], e2y = cc[1] - a[1], e2z = cc[2] - a[2];
@@ -287,7 +283,7 @@ __device__ __forceinline__ VnCross vn_cross(const float *__restrict__ verts, con
 __device__ __forceinline__ bool vn_finite(const VnCross &c) { return fabsf(c.x) < INFINITY && fabsf(c.y) < INFINITY && fabsf(c.z) < INFINITY; }
 
 __global__ void __launch_bounds__(256)
-vn_absmax_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F, VnHead *__restrict__ head) {
+vn_absmax_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F, FixedHead *__restrict__ head) {
   uint32_t m = 0u;
   for (size_t f = (size_t)blockIdx.x * 256 + threadIdx.x; f < (size_t)F; f += (size_t)gridDim.x * 256) {
     int iv[3];
@@ -295,24 +291,12 @@ vn_absmax_kernel(const float *__restrict__ verts, const int V, const int32_t *__
     if (c.ok && vn_finite(c))
       m = max(m, max(__float_as_uint(c.x) & 0x7fffffffu, max(__float_as_uint(c.y) & 0x7fffffffu, __float_as_uint(c.z) & 0x7fffffffu)));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(&head->dmax_bits, m);
-}
-
-// s = 62 - L - e, 2^e > D (header); D is finite by construction
-__device__ __forceinline__ int vn_scale_exponent(const VnHead *__restrict__ head, const int list_bits) {
-  const float D = __uint_as_float(head->dmax_bits);
-  if (!(D < INFINITY)) return 0;
-  int e;
-  frexp((double)D, &e);      // D = f 2^e, f in [0.5, 1), e = 0 for D = 0
-  const int s = 62 - list_bits - e;
-  return s < -1000 ? -1000 : (s > 1000 ? 1000 : s);
+  fixed_commit_max(head, m);      // (D is finite by construction)
 }
 
 __global__ void __launch_bounds__(256)
 vn_scatter_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F,
-                  const VnHead *__restrict__ head, const int list_bits, long long *__restrict__ acc) {
+                  const FixedHead *__restrict__ head, const int list_bits, long long *__restrict__ acc) {
   const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= (size_t)F) return;
   int iv[3];
@@ -323,7 +307,7 @@ vn_scatter_kernel(const float *__restrict__ verts, const int V, const int32_t *_
     for (int r = 0; r < 3; ++r) atomic_add_i64(acc + 4 * (size_t)iv[r] + 3, 1ll);
     return;
   }
-  const double scale = ldexp(1.0, vn_scale_exponent(head, list_bits));
+  const double scale = ldexp(1.0, fixed_scale_exponent(head, list_bits));
   const long long tx = llrint((double)c.x * scale), ty = llrint((double)c.y * scale), tz = llrint((double)c.z * scale);
   if ((tx | ty | tz) == 0) return;
 #pragma unroll
@@ -353,13 +337,7 @@ vn_finish_kernel(const int V, const long long *__restrict__ acc, float *__restri
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
 static bool mc_sizes_ok(const long V, const long F) { return V >= 0 && F >= 0 && V <= kMcMax && F <= kMcMax; }
-static unsigned mc_grid(const long n) { return (unsigned)((n + 255) / 256); }
-static int vn_list_bits(const long F) {
-  int bits = 0;
-  while ((1l << bits) < 3 * F) ++bits;      // 3 F <= 2^bits: the corners that can name one vertex
-  return bits;
-}
-static size_t vn_bytes(const long V) { return sizeof(VnHead) + (size_t)V * 4 * sizeof(long long); }
+static size_t vn_bytes(const long V) { return sizeof(FixedHead) + (size_t)V * 4 * sizeof(long long); }
 
 }  // namespace voge
 
@@ -370,10 +348,10 @@ extern "C" int voge_mesh_components(const int32_t *faces, long F, long V, int32_
   if (!mc_sizes_ok(V, F) || !meta || (stages & ~7) || !stages) return VOGE_ERR_BAD_ARG;
   if ((F > 0 && (!faces || !face_label)) || (V > 0 && (!parent || !vert_label || !count))) return VOGE_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (stages & 1) hipLaunchKernelGGL(mc_init_kernel, dim3(mc_grid(V > 4 ? V : 4)), dim3(256), 0, st, parent, count, (int)V, meta);
-  if ((stages & 2) && F > 0) hipLaunchKernelGGL(mc_link_kernel, dim3(mc_grid(F)), dim3(256), 0, st, faces, (int)F, (int)V, parent, meta);
+  if (stages & 1) hipLaunchKernelGGL(mc_init_kernel, dim3(blocks256(V > 4 ? V : 4)), dim3(256), 0, st, parent, count, (int)V, meta);
+  if ((stages & 2) && F > 0) hipLaunchKernelGGL(mc_link_kernel, dim3(blocks256(F)), dim3(256), 0, st, faces, (int)F, (int)V, parent, meta);
   if ((stages & 4) && (V > 0 || F > 0))
-    hipLaunchKernelGGL(mc_label_kernel, dim3(mc_grid(V > F ? V : F)), dim3(256), 0, st, faces, (int)F, (int)V, parent, vert_label, face_label,
+    hipLaunchKernelGGL(mc_label_kernel, dim3(blocks256(V > F ? V : F)), dim3(256), 0, st, faces, (int)F, (int)V, parent, vert_label, face_label,
                        count, meta);
   return launch_status();
 }
@@ -390,7 +368,7 @@ extern "C" int voge_mesh_clean_scan(const int32_t *faces, long F, long V, const 
     if (fe == hipSuccess) fe = voge_fill_async(err, 0, 4, st);
     if (fe != hipSuccess) return (int)fe;
   }
-  if (stages & 2) hipLaunchKernelGGL(mc_mark_kernel, dim3(mc_grid(F)), dim3(256), 0, st, faces, (int)F, (int)V, face_label, keep_root, vflag, err);
+  if (stages & 2) hipLaunchKernelGGL(mc_mark_kernel, dim3(blocks256(F)), dim3(256), 0, st, faces, (int)F, (int)V, face_label, keep_root, vflag, err);
   if (stages & 4)
     hipLaunchKernelGGL(mc_local_scan_kernel, dim3((unsigned)(nbv + nbf)), dim3(kMcBlock), 0, st, (int)F, (int)V, face_label, keep_root, vflag,
                        (int)nbv, loc, blocks);
@@ -408,7 +386,7 @@ extern "C" int voge_mesh_clean_emit(const float *verts, const int32_t *faces, lo
     return VOGE_ERR_BAD_ARG;
   if (Vk == 0 && Fk == 0) return 0;
   const long nbv = (V + kMcBlock - 1) / kMcBlock;
-  hipLaunchKernelGGL(mc_emit_kernel, dim3(mc_grid(V > F ? V : F)), dim3(256), 0, (hipStream_t)stream, verts, faces, (int)F, (int)V, face_label,
+  hipLaunchKernelGGL(mc_emit_kernel, dim3(blocks256(V > F ? V : F)), dim3(256), 0, (hipStream_t)stream, verts, faces, (int)F, (int)V, face_label,
                      keep_root, vflag, loc, blocks, (int)nbv, Vk, Fk, verts_out, faces_out, vert_index, face_index);
   return launch_status();
 }
@@ -421,21 +399,20 @@ extern "C" size_t voge_vertex_normals_workspace_bytes(long V) {
 extern "C" int voge_vertex_normals(const float *verts, long V, const int32_t *faces, long F, float *normals, void *workspace,
                                    size_t workspace_bytes, int stages, voge_stream_t stream) {
   if (!mc_sizes_ok(V, F) || V < 1 || (stages & ~15) || !stages) return VOGE_ERR_BAD_ARG;
-  if (!verts || !normals || (F > 0 && !faces) || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return VOGE_ERR_BAD_ARG;
+  if (!verts || !normals || (F > 0 && !faces) || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   if (workspace_bytes < vn_bytes(V)) return VOGE_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  VnHead *head = reinterpret_cast<VnHead *>(workspace);
-  long long *acc = reinterpret_cast<long long *>(static_cast<char *>(workspace) + sizeof(VnHead));
-  const int bits = vn_list_bits(F);
+  FixedHead *head = reinterpret_cast<FixedHead *>(workspace);
+  long long *acc = reinterpret_cast<long long *>(static_cast<char *>(workspace) + sizeof(FixedHead));
+  const int bits = ceil_log2(3 * F);      // 3 F <= 2^bits: the corners that can name one vertex
   if (stages & 1) {
     const hipError_t fe = voge_fill_async(workspace, 0, vn_bytes(V), st);
     if (fe != hipSuccess) return (int)fe;
   }
   if (F > 0) {
-    const size_t want = ((size_t)F + 255) / 256;
-    if (stages & 2) hipLaunchKernelGGL(vn_absmax_kernel, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, verts, (int)V, faces, (int)F, head);
-    if (stages & 4) hipLaunchKernelGGL(vn_scatter_kernel, dim3(mc_grid(F)), dim3(256), 0, st, verts, (int)V, faces, (int)F, head, bits, acc);
+    if (stages & 2) hipLaunchKernelGGL(vn_absmax_kernel, dim3(blocks256_capped((size_t)F)), dim3(256), 0, st, verts, (int)V, faces, (int)F, head);
+    if (stages & 4) hipLaunchKernelGGL(vn_scatter_kernel, dim3(blocks256(F)), dim3(256), 0, st, verts, (int)V, faces, (int)F, head, bits, acc);
   }
-  if (stages & 8) hipLaunchKernelGGL(vn_finish_kernel, dim3(mc_grid(V)), dim3(256), 0, st, (int)V, acc, normals);
+  if (stages & 8) hipLaunchKernelGGL(vn_finish_kernel, dim3(blocks256(V)), dim3(256), 0, st, (int)V, acc, normals);
   return launch_status();
 }

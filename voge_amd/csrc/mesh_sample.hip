@@ -26,7 +26,7 @@
 //
 // voge_mesh_sample_bwd, four launches, no float atomics.  p = (1 - w1 - w2) a + w1 b + w2 c, so a sample adds w_r g_s to the three
 // vertices of its face, and its normal's gradient to its face.  Lists can be as long as S (one face), so the sums are made in
-// FIXED POINT as chamfer.hip's are: the zero fill of the accumulators, ms_absmax_kernel (D = max |g| over g_points and g_normals
+// FIXED POINT (fixed_point.h: the head, the exponent rule and its bound) as chamfer.hip's are: the zero fill of the accumulators, ms_absmax_kernel (D = max |g| over g_points and g_normals
 // by an integer atomic max on the bits of |g|: a maximum has no order), ms_scatter_kernel (s = 62 - L - e with 2^L >= S and
 // 2^e > D chosen by every thread from D, clamped to +-1000; round(w_r g 2^s) added with 64-bit INTEGER atomics into acc_v [V][3],
 // round(g_n 2^s) into acc_f [F][3]; |w_r| <= 1, so |sum| < 2^62 + S cannot overflow), and ms_finish_kernel, one thread a vertex:
@@ -40,6 +40,7 @@
 #include <math.h>
 
 #include "voge_common.h"
+#include "fixed_point.h"
 
 namespace voge {
 
@@ -67,10 +68,6 @@ __device__ __forceinline__ MsFace ms_face(const float *__restrict__ verts, const
   return f;
 }
 
-__device__ __forceinline__ bool ms_in_range(const int ia, const int ib, const int ic, const int V) {
-  return (unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V;
-}
-
 // ---- forward ------------------------------------------------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(kMsBlock)
@@ -83,7 +80,7 @@ ms_area_scan_kernel(const float *__restrict__ verts, const int V, const int32_t 
   float A2 = 0.0f;
   if (f < (size_t)F) {
     const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-    if (ms_in_range(ia, ib, ic, V)) A2 = ms_face(verts, ia, ib, ic).A2;      // (a face off the table: area 0, never chosen)
+    if (face_in_range(ia, ib, ic, V)) A2 = ms_face(verts, ia, ib, ic).A2;      // (a face off the table: area 0, never chosen)
     if (a2_out) a2_out[f] = A2;
   }
   val[tid] = (double)A2;
@@ -197,7 +194,7 @@ ms_sample_kernel(const float *__restrict__ verts, const int V, const int32_t *__
   float px = 0.0f, py = 0.0f, pz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, w0 = 0.0f, w1 = 0.0f, w2 = 0.0f;
   if (f >= 0 && f < F) {
     const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
-    if (ms_in_range(ia, ib, ic, V)) {
+    if (face_in_range(ia, ib, ic, V)) {
       const MsFace g = ms_face(verts, ia, ib, ic);
       const float r = sqrtf(u1);
       w0 = 1.0f - r;
@@ -221,46 +218,29 @@ ms_sample_kernel(const float *__restrict__ verts, const int V, const int32_t *__
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 
-struct MsHead {      // the backward workspace's first 16 bytes, zero-filled with the accumulators
-  uint32_t dmax_bits;
-  uint32_t pad[3];
-};
-
 // the largest |g| (as bits: |g| >= 0 orders as its bits do, and a NaN lies above the infinity) over g_points and g_normals
 __global__ void __launch_bounds__(256)
-ms_absmax_kernel(const float *__restrict__ g_points, const float *__restrict__ g_normals, const size_t n, MsHead *__restrict__ head) {
+ms_absmax_kernel(const float *__restrict__ g_points, const float *__restrict__ g_normals, const size_t n, FixedHead *__restrict__ head) {
   uint32_t m = 0u;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     if (g_points) m = max(m, __float_as_uint(g_points[i]) & 0x7fffffffu);
     if (g_normals) m = max(m, __float_as_uint(g_normals[i]) & 0x7fffffffu);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(&head->dmax_bits, m);
-}
-
-// s = 62 - L - e, 2^e > D (header); D that is not finite: 0
-__device__ __forceinline__ int ms_scale_exponent(const MsHead *__restrict__ head, const int list_bits) {
-  const float D = __uint_as_float(head->dmax_bits);
-  if (!(D < INFINITY)) return 0;
-  int e;
-  frexp((double)D, &e);      // D = f 2^e, f in [0.5, 1), e = 0 for D = 0
-  const int s = 62 - list_bits - e;
-  return s < -1000 ? -1000 : (s > 1000 ? 1000 : s);
+  fixed_commit_max(head, m);
 }
 
 __global__ void __launch_bounds__(256)
 ms_scatter_kernel(const int32_t *__restrict__ faces, const int V, const int F, const int32_t *__restrict__ face_idx,
                   const float *__restrict__ bary, const int S, const float *__restrict__ g_points, const float *__restrict__ g_normals,
-                  const MsHead *__restrict__ head, const int list_bits, long long *__restrict__ acc_v, long long *__restrict__ acc_f) {
+                  const FixedHead *__restrict__ head, const int list_bits, long long *__restrict__ acc_v, long long *__restrict__ acc_f) {
   const size_t s = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (s >= (size_t)S) return;
   const int f = face_idx[s];
   if (f < 0 || f >= F) return;
-  const double scale = ldexp(1.0, ms_scale_exponent(head, list_bits));
+  const double scale = ldexp(1.0, fixed_scale_exponent(head, list_bits));
   if (g_points) {
     const int iv[3] = {faces[3 * (size_t)f], faces[3 * (size_t)f + 1], faces[3 * (size_t)f + 2]};
-    if (ms_in_range(iv[0], iv[1], iv[2], V)) {
+    if (face_in_range(iv[0], iv[1], iv[2], V)) {
       const double w1 = (double)bary[3 * s + 1], w2 = (double)bary[3 * s + 2];
       const double w[3] = {(1.0 - w1) - w2, w1, w2};
       const double gx = (double)g_points[3 * s] * scale, gy = (double)g_points[3 * s + 1] * scale, gz = (double)g_points[3 * s + 2] * scale;
@@ -283,12 +263,12 @@ ms_scatter_kernel(const int32_t *__restrict__ faces, const int V, const int F, c
 
 __global__ void __launch_bounds__(256)
 ms_finish_kernel(const float *__restrict__ verts, const int V, const int32_t *__restrict__ faces, const int F,
-                 const int32_t *__restrict__ corner_off, const int32_t *__restrict__ corner, const MsHead *__restrict__ head,
+                 const int32_t *__restrict__ corner_off, const int32_t *__restrict__ corner, const FixedHead *__restrict__ head,
                  const int list_bits, const long long *__restrict__ acc_v, const long long *__restrict__ acc_f,
                  float *__restrict__ g_verts) {
   const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= (size_t)V) return;
-  const double unscale = ldexp(1.0, -ms_scale_exponent(head, list_bits));
+  const double unscale = ldexp(1.0, -fixed_scale_exponent(head, list_bits));
   double gx = (double)acc_v[3 * v] * unscale, gy = (double)acc_v[3 * v + 1] * unscale, gz = (double)acc_v[3 * v + 2] * unscale;
   if (acc_f) {
     const long c0 = corner_off[v], c1 = corner_off[v + 1];
@@ -300,7 +280,7 @@ ms_finish_kernel(const float *__restrict__ verts, const int V, const int32_t *__
       const long long *af = acc_f + 3 * (size_t)f;
       if ((af[0] | af[1] | af[2]) == 0) continue;      // (no sample on the face asked for its normal, or the requests cancel: + 0)
       const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
-      if (!ms_in_range(ia, ib, ic, V)) continue;
+      if (!face_in_range(ia, ib, ic, V)) continue;
       const float *a = verts + 3 * (size_t)ia, *b = verts + 3 * (size_t)ib, *cc = verts + 3 * (size_t)ic;
       const double e1x = (double)b[0] - (double)a[0], e1y = (double)b[1] - (double)a[1], e1z = (double)b[2] - (double)a[2];
       const double e2x = (double)cc[0] - (double)a[0], e2y = (double)cc[1] - (double)a[1], e2z = (double)cc[2] - (double)a[2];
@@ -331,29 +311,21 @@ struct MsLayout {
 static MsLayout ms_layout(const long V, const long F, const long S) {
   (void)S;
   MsLayout l;
-  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   l.nb = (int)((F + kMsBlock - 1) / kMsBlock);
-  size_t at = 0;
-  l.cdf = at; at += up16((size_t)F * sizeof(double));
-  l.btotal = at; at += up16((size_t)l.nb * sizeof(double));
-  l.bincl = at; at += up16((size_t)l.nb * sizeof(double));
-  l.fwd = at;
-  at = 0;
-  l.head = at; at += sizeof(MsHead);
-  l.acc_v = at; at += (size_t)V * 3 * sizeof(long long);
-  l.acc_f = at; at += (size_t)F * 3 * sizeof(long long);
-  l.bwd = up16(at);
+  Carve fwd, bwd;      // (two calls on one workspace: each starts at its front)
+  l.cdf = fwd.take((size_t)F * sizeof(double));
+  l.btotal = fwd.take((size_t)l.nb * sizeof(double));
+  l.bincl = fwd.take((size_t)l.nb * sizeof(double));
+  l.fwd = fwd.at;
+  l.head = bwd.take_exact(sizeof(FixedHead));
+  l.acc_v = bwd.take_exact((size_t)V * 3 * sizeof(long long));
+  l.acc_f = bwd.take_exact((size_t)F * 3 * sizeof(long long));
+  l.bwd = up16(bwd.at);
   return l;
 }
 
 static bool ms_sizes_ok(const long V, const long F, const long S) {
   return V >= 1 && F >= 1 && S >= 0 && V <= kMsMax && F <= kMsMax && S <= kMsMax;
-}
-static bool ms_ws_bad(const void *ws) { return !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0; }
-static int ms_list_bits(const long S) {
-  int bits = 0;
-  while ((1l << bits) < S) ++bits;      // S <= 2^bits: every list of the scatter
-  return bits;
 }
 
 }  // namespace voge
@@ -371,7 +343,7 @@ extern "C" int voge_mesh_sample_fwd(const float *verts, long V, const int32_t *f
                                     size_t workspace_bytes, voge_stream_t stream) {
   if (!ms_sizes_ok(V, F, S)) return VOGE_ERR_BAD_ARG;
   if (S == 0 && !a2_out) return 0;
-  if (!verts || !faces || ms_ws_bad(workspace) || (S > 0 && (!u || !points || !face_idx || !bary))) return VOGE_ERR_BAD_ARG;
+  if (!verts || !faces || bad_workspace(workspace) || (S > 0 && (!u || !points || !face_idx || !bary))) return VOGE_ERR_BAD_ARG;
   const MsLayout l = ms_layout(V, F, S);
   if (workspace_bytes < l.fwd) return VOGE_ERR_WORKSPACE;
   char *ws = static_cast<char *>(workspace);
@@ -381,7 +353,7 @@ extern "C" int voge_mesh_sample_fwd(const float *verts, long V, const int32_t *f
   hipLaunchKernelGGL(ms_area_scan_kernel, dim3((unsigned)l.nb), dim3(kMsBlock), 0, st, verts, (int)V, faces, (int)F, cdf, btotal, a2_out);
   if (S > 0) {
     hipLaunchKernelGGL(ms_block_scan_kernel, dim3(1), dim3(1024), 0, st, btotal, l.nb, bincl);
-    hipLaunchKernelGGL(ms_sample_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, verts, (int)V, faces, (int)F, u, (int)S, cdf,
+    hipLaunchKernelGGL(ms_sample_kernel, dim3(blocks256(S)), dim3(256), 0, st, verts, (int)V, faces, (int)F, u, (int)S, cdf,
                        bincl, l.nb, points, normals, face_idx, bary);
   }
   return launch_status();
@@ -392,27 +364,26 @@ extern "C" int voge_mesh_sample_bwd(const float *verts, long V, const int32_t *f
                                     const float *g_normals, float *g_verts, void *workspace, size_t workspace_bytes,
                                     voge_stream_t stream) {
   if (!ms_sizes_ok(V, F, S)) return VOGE_ERR_BAD_ARG;
-  if (!verts || !faces || !g_verts || ms_ws_bad(workspace) || (S > 0 && (!face_idx || !bary))) return VOGE_ERR_BAD_ARG;
+  if (!verts || !faces || !g_verts || bad_workspace(workspace) || (S > 0 && (!face_idx || !bary))) return VOGE_ERR_BAD_ARG;
   if (g_normals && (!corner_off || !corner)) return VOGE_ERR_BAD_ARG;
   const MsLayout l = ms_layout(V, F, S);
   const size_t bytes = g_normals ? l.bwd : l.acc_f;      // (without normals the faces' accumulators are not used)
   if (workspace_bytes < bytes) return VOGE_ERR_WORKSPACE;
   char *ws = static_cast<char *>(workspace);
   hipStream_t st = (hipStream_t)stream;
-  MsHead *head = reinterpret_cast<MsHead *>(ws + l.head);
+  FixedHead *head = reinterpret_cast<FixedHead *>(ws + l.head);
   long long *acc_v = reinterpret_cast<long long *>(ws + l.acc_v);
   long long *acc_f = g_normals ? reinterpret_cast<long long *>(ws + l.acc_f) : nullptr;
   const hipError_t fe = voge_fill_async(workspace, 0, g_normals ? l.acc_f + (size_t)F * 3 * sizeof(long long) : l.acc_f, st);
   if (fe != hipSuccess) return (int)fe;
-  const int bits = ms_list_bits(S);
+  const int bits = ceil_log2(S);      // S <= 2^bits: every list of the scatter
   if (S > 0 && (g_points || g_normals)) {
     const size_t n = (size_t)S * 3;
-    const size_t want = (n + 255) / 256;
-    hipLaunchKernelGGL(ms_absmax_kernel, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, g_points, g_normals, n, head);
-    hipLaunchKernelGGL(ms_scatter_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, faces, (int)V, (int)F, face_idx, bary, (int)S,
+    hipLaunchKernelGGL(ms_absmax_kernel, dim3(blocks256_capped(n)), dim3(256), 0, st, g_points, g_normals, n, head);
+    hipLaunchKernelGGL(ms_scatter_kernel, dim3(blocks256(S)), dim3(256), 0, st, faces, (int)V, (int)F, face_idx, bary, (int)S,
                        g_points, g_normals, head, bits, acc_v, acc_f);
   }
-  hipLaunchKernelGGL(ms_finish_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, verts, (int)V, faces, (int)F, corner_off, corner,
+  hipLaunchKernelGGL(ms_finish_kernel, dim3(blocks256(V)), dim3(256), 0, st, verts, (int)V, faces, (int)F, corner_off, corner,
                      head, bits, acc_v, acc_f, g_verts);
   return launch_status();
 }

@@ -49,7 +49,7 @@
 //   simp_attr_finish_kernel (count == 1: the row's own bits; a flagged channel: NaN; else sum / count, one rounding).
 // SCALES.  A cell index is decided in fp32 and may be off the fp64 quotient by 2^-23 of it, at most 3/8 below 2^21: |x| < 1 per axis,
 // |x| < 2 as a vector, |d| < 2, |n_i n_j| <= 1.  With 2^Lv >= V and 2^Lf >= 3 F (the items that can meet in one row):
-// sp = 60 - Lv, sq = 60 - Lf: |term| < 2^(s + 2), |sum| < 2^62.  sa = 62 - Lv - e with 2^e > D, clamped to +-1000, as vn_scatter_kernel's.
+// sp = 60 - Lv, sq = 60 - Lf: |term| < 2^(s + 2), |sum| < 2^62.  sa = 62 - Lv - e with 2^e > D, clamped to +-1000: fixed_point.h's rule, as vn_scatter_kernel's.
 // Integer addition is exact: the same bits on every run and under any permutation of the faces.
 //
 // BOUNDS against the definition (eps = 2^-24, u = 2^-53, M = max |coordinate|, q = 2^-s; a cluster of n vertices, m contributions):
@@ -67,6 +67,7 @@
 #include <math.h>
 
 #include "voge_common.h"
+#include "fixed_point.h"
 #include "mesh_scan.h"
 
 namespace voge {
@@ -419,43 +420,26 @@ simp_finish_kernel(const SimpGrid g, const int V, const SimpRows rows, const int
 
 // ---- attributes ---------------------------------------------------------------------------------------------------------------
 
-struct SimpAttrHead {      // the attribute workspace's first 16 bytes, zero-filled with the accumulators
-  uint32_t dmax_bits;
-  uint32_t pad[3];
-};
-
 __global__ void __launch_bounds__(256)
-simp_attr_absmax_kernel(const float *__restrict__ attr, const int V, const int C, const int c0, const int nc, SimpAttrHead *__restrict__ head) {
+simp_attr_absmax_kernel(const float *__restrict__ attr, const int V, const int C, const int c0, const int nc, FixedHead *__restrict__ head) {
   uint32_t m = 0u;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < (size_t)V; v += (size_t)gridDim.x * 256)
     for (int k = 0; k < nc; ++k) {
       const float x = attr[v * C + c0 + k];
       if (fabsf(x) < INFINITY) m = max(m, __float_as_uint(x) & 0x7fffffffu);
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(&head->dmax_bits, m);
-}
-
-// sa = 62 - Lv - e, 2^e > D (header); D is finite by construction
-__device__ __forceinline__ int simp_attr_exponent(const SimpAttrHead *__restrict__ head, const int list_bits) {
-  const float D = __uint_as_float(head->dmax_bits);
-  if (!(D < INFINITY)) return 0;
-  int e;
-  frexp((double)D, &e);      // D = f 2^e, f in [0.5, 1), e = 0 for D = 0
-  const int s = 62 - list_bits - e;
-  return s < -1000 ? -1000 : (s > 1000 ? 1000 : s);
+  fixed_commit_max(head, m);      // (D is finite by construction)
 }
 
 __global__ void __launch_bounds__(256)
 simp_attr_scatter_kernel(const float *__restrict__ attr, const int V, const int C, const int c0, const int nc, const int32_t *__restrict__ vlabel,
-                       const SimpRows rows, const SimpAttrHead *__restrict__ head, const int list_bits, long long *__restrict__ acc) {
+                       const SimpRows rows, const FixedHead *__restrict__ head, const int list_bits, long long *__restrict__ acc) {
   const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= (size_t)V) return;
   const int l = vlabel[v];
   const long row = (unsigned)l < (unsigned)V ? rows.of(l) : -1;
   if (row < 0) return;
-  const double scale = ldexp(1.0, simp_attr_exponent(head, list_bits));
+  const double scale = ldexp(1.0, fixed_scale_exponent(head, list_bits));
   long long *a = acc + (size_t)row * kSimpRowAttr;
   unsigned long long bad = 0ull;
   for (int k = 0; k < nc; ++k) {
@@ -472,7 +456,7 @@ simp_attr_scatter_kernel(const float *__restrict__ attr, const int V, const int 
 
 __global__ void __launch_bounds__(256)
 simp_attr_finish_kernel(const float *__restrict__ attr, const int V, const int C, const int c0, const int nc, const SimpRows rows,
-                      const SimpAttrHead *__restrict__ head, const int list_bits, const long long *__restrict__ acc,
+                      const FixedHead *__restrict__ head, const int list_bits, const long long *__restrict__ acc,
                       const long long *__restrict__ count, const int count_words, float *__restrict__ attr_out) {
   const size_t l = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (l >= (size_t)V) return;
@@ -480,7 +464,7 @@ simp_attr_finish_kernel(const float *__restrict__ attr, const int V, const int C
   if (row < 0) return;
   const long long n = count[(size_t)row * count_words];
   const long long *a = acc + (size_t)row * kSimpRowAttr;
-  const double unit = ldexp(1.0, -simp_attr_exponent(head, list_bits));
+  const double unit = ldexp(1.0, -fixed_scale_exponent(head, list_bits));
   for (int k = 0; k < nc; ++k) {
     float y;
     if (n <= 1) y = attr[l * C + c0 + k];      // (the label is the cluster's only vertex)
@@ -493,14 +477,7 @@ simp_attr_finish_kernel(const float *__restrict__ attr, const int V, const int C
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
 static bool simp_sizes_ok(const long V, const long F) { return V >= 1 && F >= 1 && V <= kMcMax && F <= kMcMax; }
-static unsigned simp_grid(const long n) { return (unsigned)((n + 255) / 256); }
-static size_t simp_up16(const size_t n) { return (n + 15) & ~(size_t)15; }
-static int simp_bits(const long n) {
-  int bits = 0;
-  while ((1l << bits) < n) ++bits;      // n <= 2^bits
-  return bits;
-}
-static size_t simp_capacity(const long V, const long F) { return (size_t)1 << simp_bits(2 * (V > F ? V : F)); }
+static size_t simp_capacity(const long V, const long F) { return (size_t)1 << ceil_log2(2 * (V > F ? V : F)); }
 
 struct SimpLayout {      // the scan's workspace: [err 16 | vflag] is zero-filled as one range, [lo 16 | table] with 0xFF as one
   size_t err, vflag, lo, table, vlabel, tri, fkeep, loc, blocks, bytes;
@@ -512,23 +489,23 @@ static SimpLayout simp_layout(const long V, const long F) {
   w.nbv = (V + kMcBlock - 1) / kMcBlock;
   w.nbf = (F + kMcBlock - 1) / kMcBlock;
   w.cap = simp_capacity(V, F);
-  size_t o = 0;
-  w.err = o; o += 16;
-  w.vflag = o; o += simp_up16((size_t)V);
-  w.lo = o; o += 16;
-  w.table = o; o += w.cap * 4;
-  w.vlabel = o; o += simp_up16((size_t)V * 4);
-  w.tri = o; o += simp_up16((size_t)F * 12);
-  w.fkeep = o; o += simp_up16((size_t)F);
-  w.loc = o; o += simp_up16((size_t)(V + F) * 2);
-  w.blocks = o; o += simp_up16((size_t)(w.nbv + w.nbf) * 4);
-  w.bytes = o;
+  Carve c;
+  w.err = c.take(16);
+  w.vflag = c.take((size_t)V);
+  w.lo = c.take(16);
+  w.table = c.take_exact(w.cap * 4);      // (a power of two >= 2 entries: 8 bytes for V = F = 1, a multiple of 16 otherwise)
+  w.vlabel = c.take((size_t)V * 4);
+  w.tri = c.take((size_t)F * 12);
+  w.fkeep = c.take((size_t)F);
+  w.loc = c.take((size_t)(V + F) * 2);
+  w.blocks = c.take((size_t)(w.nbv + w.nbf) * 4);
+  w.bytes = c.at;
   return w;
 }
 static bool simp_cell_size_ok(const float hx, const float hy, const float hz) {
   return hx > 0.0f && hy > 0.0f && hz > 0.0f && hx < INFINITY && hy < INFINITY && hz < INFINITY;
 }
-static size_t simp_attr_bytes(const long Vk) { return sizeof(SimpAttrHead) + (size_t)Vk * kSimpRowAttr * sizeof(long long); }
+static size_t simp_attr_bytes(const long Vk) { return sizeof(FixedHead) + (size_t)Vk * kSimpRowAttr * sizeof(long long); }
 
 template <class T>
 static T *simp_at(void *workspace, const size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + offset); }
@@ -559,7 +536,7 @@ extern "C" size_t voge_mesh_simplify_attr_workspace_bytes(long Vk) {
 extern "C" int voge_mesh_simplify_scan(const float *verts, long V, const int32_t *faces, long F, float hx, float hy, float hz,
                                        void *workspace, size_t workspace_bytes, long long *totals, int stages, voge_stream_t stream) {
   if (!simp_sizes_ok(V, F) || !simp_cell_size_ok(hx, hy, hz) || (stages & ~255) || !stages) return VOGE_ERR_BAD_ARG;
-  if (!verts || !faces || !totals || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return VOGE_ERR_BAD_ARG;
+  if (!verts || !faces || !totals || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const SimpLayout w = simp_layout(V, F);
   if (workspace_bytes < w.bytes) return VOGE_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -572,18 +549,17 @@ extern "C" int voge_mesh_simplify_scan(const float *verts, long V, const int32_t
     hipError_t fe = voge_fill_async(err, 0, w.lo - w.err, st);
     if (fe == hipSuccess) fe = voge_fill_async(simp_at<void>(workspace, w.lo), 0xff, 16 + w.cap * 4, st);
     if (fe != hipSuccess) return (int)fe;
-    const size_t want = ((size_t)V + 255) / 256;
-    hipLaunchKernelGGL(simp_bbox_kernel, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, verts, (int)V, simp_at<uint32_t>(workspace, w.lo), err);
+    hipLaunchKernelGGL(simp_bbox_kernel, dim3(blocks256_capped((size_t)V)), dim3(256), 0, st, verts, (int)V, simp_at<uint32_t>(workspace, w.lo), err);
   }
-  if (stages & 2) hipLaunchKernelGGL(simp_cell_insert_kernel, dim3(simp_grid(V)), dim3(256), 0, st, g, (int)V, table, mask, err);
-  if (stages & 4) hipLaunchKernelGGL(simp_cell_label_kernel, dim3(simp_grid(V)), dim3(256), 0, st, g, (int)V, table, mask, vlabel, err);
-  if (stages & 8) hipLaunchKernelGGL(simp_triple_kernel, dim3(simp_grid(F)), dim3(256), 0, st, faces, (int)F, (int)V, vlabel, tri, err);
+  if (stages & 2) hipLaunchKernelGGL(simp_cell_insert_kernel, dim3(blocks256(V)), dim3(256), 0, st, g, (int)V, table, mask, err);
+  if (stages & 4) hipLaunchKernelGGL(simp_cell_label_kernel, dim3(blocks256(V)), dim3(256), 0, st, g, (int)V, table, mask, vlabel, err);
+  if (stages & 8) hipLaunchKernelGGL(simp_triple_kernel, dim3(blocks256(F)), dim3(256), 0, st, faces, (int)F, (int)V, vlabel, tri, err);
   if (stages & 16) {
     const hipError_t fe = voge_fill_async(table, 0xff, w.cap * 4, st);
     if (fe != hipSuccess) return (int)fe;
-    hipLaunchKernelGGL(simp_face_insert_kernel, dim3(simp_grid(F)), dim3(256), 0, st, tri, (int)F, table, mask, err);
+    hipLaunchKernelGGL(simp_face_insert_kernel, dim3(blocks256(F)), dim3(256), 0, st, tri, (int)F, table, mask, err);
   }
-  if (stages & 32) hipLaunchKernelGGL(simp_face_mark_kernel, dim3(simp_grid(F)), dim3(256), 0, st, tri, (int)F, (int)V, table, mask, fkeep, vflag, err);
+  if (stages & 32) hipLaunchKernelGGL(simp_face_mark_kernel, dim3(blocks256(F)), dim3(256), 0, st, tri, (int)F, (int)V, table, mask, fkeep, vflag, err);
   if (stages & 64)
     hipLaunchKernelGGL(simp_local_scan_kernel, dim3((unsigned)(w.nbv + w.nbf)), dim3(kMcBlock), 0, st, (int)F, (int)V, fkeep, vflag, (int)w.nbv,
                        simp_at<uint16_t>(workspace, w.loc), simp_at<uint32_t>(workspace, w.blocks));
@@ -598,8 +574,8 @@ extern "C" int voge_mesh_simplify_emit(const float *verts, long V, const int32_t
                                        voge_stream_t stream) {
   if (!simp_sizes_ok(V, F) || !simp_cell_size_ok(hx, hy, hz) || Vk < 1 || Fk < 1 || Vk > V || Fk > F || (stages & ~15) || !stages)
     return VOGE_ERR_BAD_ARG;
-  if (!verts || !faces || !workspace || !acc || !verts_out || !faces_out || !vert_index || !face_index ||
-      (reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(acc) & 7) != 0)
+  if (!verts || !faces || bad_workspace(workspace) || !acc || !verts_out || !faces_out || !vert_index || !face_index ||
+      (reinterpret_cast<uintptr_t>(acc) & 7) != 0)
     return VOGE_ERR_BAD_ARG;
   const SimpLayout w = simp_layout(V, F);
   const int words = quadric ? kSimpRowQuadric : kSimpRowMean;
@@ -609,16 +585,16 @@ extern "C" int voge_mesh_simplify_emit(const float *verts, long V, const int32_t
   const SimpRows rows = simp_rows(workspace, w, Vk);
   const int32_t *vlabel = simp_at<int32_t>(workspace, w.vlabel);
   long long *sums = static_cast<long long *>(acc);
-  const int sp = 60 - simp_bits(V), sq = 60 - simp_bits(3 * F);
+  const int sp = 60 - ceil_log2(V), sq = 60 - ceil_log2(3 * F);      // the vertices, the corners that can meet in one row (SCALES)
   if (stages & 1) {
     const hipError_t fe = voge_fill_async(acc, 0, (size_t)Vk * words * sizeof(long long), st);
     if (fe != hipSuccess) return (int)fe;
   }
   if (stages & 2)
-    hipLaunchKernelGGL(simp_emit_kernel, dim3(simp_grid(V > F ? V : F)), dim3(256), 0, st, g, (int)V, faces, (int)F, vlabel,
+    hipLaunchKernelGGL(simp_emit_kernel, dim3(blocks256(V > F ? V : F)), dim3(256), 0, st, g, (int)V, faces, (int)F, vlabel,
                        simp_at<uint8_t>(workspace, w.fkeep), rows, (int)w.nbv, Fk, sp, words, sums, faces_out, vert_index, face_index);
-  if ((stages & 4) && quadric) hipLaunchKernelGGL(simp_quadric_kernel, dim3(simp_grid(F)), dim3(256), 0, st, g, (int)V, faces, (int)F, vlabel, rows, sq, sums);
-  if (stages & 8) hipLaunchKernelGGL(simp_finish_kernel, dim3(simp_grid(V)), dim3(256), 0, st, g, (int)V, rows, sp, sq, words, sums, verts_out);
+  if ((stages & 4) && quadric) hipLaunchKernelGGL(simp_quadric_kernel, dim3(blocks256(F)), dim3(256), 0, st, g, (int)V, faces, (int)F, vlabel, rows, sq, sums);
+  if (stages & 8) hipLaunchKernelGGL(simp_finish_kernel, dim3(blocks256(V)), dim3(256), 0, st, g, (int)V, rows, sp, sq, words, sums, verts_out);
   return launch_status();
 }
 
@@ -627,27 +603,23 @@ extern "C" int voge_mesh_simplify_attr(const float *attr, long V, long F, int C,
                                        float *attr_out, int stages, voge_stream_t stream) {
   if (!simp_sizes_ok(V, F) || Vk < 1 || Vk > V || C < 1 || c0 < 0 || nc < 1 || nc > kSimpChannels || c0 + nc > C || (stages & ~15) || !stages)
     return VOGE_ERR_BAD_ARG;
-  if (!attr || !workspace || !acc || !attr_workspace || !attr_out || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(attr_workspace) & 15) != 0)
-    return VOGE_ERR_BAD_ARG;
+  if (!attr || bad_workspace(workspace) || !acc || bad_workspace(attr_workspace) || !attr_out) return VOGE_ERR_BAD_ARG;
   const SimpLayout w = simp_layout(V, F);
   if (workspace_bytes < w.bytes || attr_workspace_bytes < simp_attr_bytes(Vk)) return VOGE_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const SimpRows rows = simp_rows(const_cast<void *>(workspace), w, Vk);
   const int32_t *vlabel = simp_at<int32_t>(const_cast<void *>(workspace), w.vlabel);
-  SimpAttrHead *head = static_cast<SimpAttrHead *>(attr_workspace);
-  long long *sums = simp_at<long long>(attr_workspace, sizeof(SimpAttrHead));
-  const int bits = simp_bits(V);
+  FixedHead *head = static_cast<FixedHead *>(attr_workspace);
+  long long *sums = simp_at<long long>(attr_workspace, sizeof(FixedHead));
+  const int bits = ceil_log2(V);      // V <= 2^bits: the vertices that can meet in one row
   if (stages & 1) {
     const hipError_t fe = voge_fill_async(attr_workspace, 0, simp_attr_bytes(Vk), st);
     if (fe != hipSuccess) return (int)fe;
   }
-  const size_t want = ((size_t)V + 255) / 256;
-  if (stages & 2)
-    hipLaunchKernelGGL(simp_attr_absmax_kernel, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, st, attr, (int)V, C, c0, nc, head);
-  if (stages & 4) hipLaunchKernelGGL(simp_attr_scatter_kernel, dim3(simp_grid(V)), dim3(256), 0, st, attr, (int)V, C, c0, nc, vlabel, rows, head, bits, sums);
+  if (stages & 2) hipLaunchKernelGGL(simp_attr_absmax_kernel, dim3(blocks256_capped((size_t)V)), dim3(256), 0, st, attr, (int)V, C, c0, nc, head);
+  if (stages & 4) hipLaunchKernelGGL(simp_attr_scatter_kernel, dim3(blocks256(V)), dim3(256), 0, st, attr, (int)V, C, c0, nc, vlabel, rows, head, bits, sums);
   if (stages & 8)
-    hipLaunchKernelGGL(simp_attr_finish_kernel, dim3(simp_grid(V)), dim3(256), 0, st, attr, (int)V, C, c0, nc, rows, head, bits, sums,
+    hipLaunchKernelGGL(simp_attr_finish_kernel, dim3(blocks256(V)), dim3(256), 0, st, attr, (int)V, C, c0, nc, rows, head, bits, sums,
                        static_cast<const long long *>(acc), quadric ? kSimpRowQuadric : kSimpRowMean, attr_out);
   return launch_status();
 }

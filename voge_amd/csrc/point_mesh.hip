@@ -319,20 +319,17 @@ enum { kPmSum = 1, kPmSingle = 2, kPmGridPairs = 4 };      // (bit 2, the backwa
 
 struct PmLayout {
   size_t d2p, d2f, psum, pmax, total;
-  unsigned nb_loss[2];
 };
 static PmLayout pm_layout(const long V, const long F, const long P) {
   PmLayout l;
-  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
-  size_t at = 0;
-  l.nb_loss[0] = (unsigned)((P + 256 * kChLossItems - 1) / (256 * kChLossItems));
-  l.nb_loss[1] = (unsigned)((F + 256 * kChLossItems - 1) / (256 * kChLossItems));
-  l.d2p = at; at += up16((size_t)P * 4);
-  l.d2f = at; at += up16((size_t)F * 4);
-  l.psum = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(double));
-  l.pmax = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(float));
+  const size_t nb_loss = chamfer_loss_blocks(P) + chamfer_loss_blocks(F);
+  Carve c;
+  l.d2p = c.take((size_t)P * 4);
+  l.d2f = c.take((size_t)F * 4);
+  l.psum = c.take(nb_loss * sizeof(double));
+  l.pmax = c.take(nb_loss * sizeof(float));
   const size_t bwd = (size_t)(V + P) * 3 * sizeof(long long);      // the backward's accumulators, a call of its own
-  l.total = at > bwd ? at : bwd;
+  l.total = c.at > bwd ? c.at : bwd;
   return l;
 }
 
@@ -374,7 +371,6 @@ static void pm_search(const bool by_face, const float *points, const long P, con
 
 static bool pm_size_ok(const long n) { return n >= 1 && n <= kPmMaxN; }
 static bool pm_pairs_ok(const long F, const long P) { return (double)F * (double)P <= kPmMaxPairs; }
-static bool pm_ws_bad(const void *ws) { return !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0; }
 
 }  // namespace voge
 
@@ -410,7 +406,7 @@ extern "C" int voge_point_mesh_fwd(const float *verts, long V, const int32_t *fa
   if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P) || (flags & ~3)) return VOGE_ERR_BAD_ARG;
   if (!pm_pairs_ok(F, P)) return VOGE_ERR_K_TOO_LARGE;
   const bool both = !(flags & kPmSingle);
-  if (!verts || !faces || !points || !loss || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || pm_ws_bad(workspace))
+  if (!verts || !faces || !points || !loss || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || bad_workspace(workspace))
     return VOGE_ERR_BAD_ARG;
   const PmLayout l = pm_layout(V, F, P);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
@@ -419,15 +415,9 @@ extern "C" int voge_point_mesh_fwd(const float *verts, long V, const int32_t *fa
   float *d2p = reinterpret_cast<float *>(ws + l.d2p), *d2f = reinterpret_cast<float *>(ws + l.d2f);
   pm_search(false, points, P, verts, V, faces, F, face_idx, d2p, bary_p, st);
   if (both) pm_search(true, points, P, verts, V, faces, F, point_idx, d2f, bary_f, st);
-  double *psum = reinterpret_cast<double *>(ws + l.psum);
-  float *pmax = reinterpret_cast<float *>(ws + l.pmax);
-  const unsigned nba = l.nb_loss[0], nbb = both ? l.nb_loss[1] : 0u;
-  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2p, (int)P, d2f, (int)F, nba, psum, pmax);
-  int bits = 0;
-  while ((1l << bits) < P + F) ++bits;      // P + F <= 2^bits: every scatter list of the backward
-  const bool sum = flags & kPmSum;
-  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)P,
-                     sum ? 1.0 : (double)F, bits, loss, meta);
+  // P + F, the items of the backward's scatter (a point or a face each): no scatter list is longer
+  chamfer_loss_launch(d2p, P, d2f, F, both, flags & kPmSum, P + F, reinterpret_cast<double *>(ws + l.psum),
+                      reinterpret_cast<float *>(ws + l.pmax), loss, meta, st);
   return launch_status();
 }
 
@@ -443,7 +433,7 @@ extern "C" int voge_closest_faces_grid(const float *points, long P, const float 
                                        size_t workspace_bytes, voge_stream_t stream) {
   if (P < 0 || P > kPmMaxN || !pm_size_ok(V) || !pm_size_ok(F) || !pm_cell_size_ok(cell_size)) return VOGE_ERR_BAD_ARG;
   if (P == 0) return 0;
-  if (!points || !verts || !faces || !face_idx || !d2 || !bary || pm_ws_bad(workspace)) return VOGE_ERR_BAD_ARG;
+  if (!points || !verts || !faces || !face_idx || !d2 || !bary || bad_workspace(workspace)) return VOGE_ERR_BAD_ARG;
   const PmGridLayout l = pm_grid_layout(V, F, P);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
   pm_grid_searches(points, P, verts, V, faces, F, cell_size, false, face_idx, d2, bary, nullptr, nullptr, nullptr,
@@ -456,7 +446,7 @@ extern "C" int voge_point_mesh_fwd_grid(const float *verts, long V, const int32_
                                         float *bary_f, int32_t *meta, void *workspace, size_t workspace_bytes, voge_stream_t stream) {
   if (!pm_size_ok(V) || !pm_size_ok(F) || !pm_size_ok(P) || (flags & ~3) || !pm_cell_size_ok(cell_size)) return VOGE_ERR_BAD_ARG;
   const bool both = !(flags & kPmSingle);
-  if (!verts || !faces || !points || !loss || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || pm_ws_bad(workspace))
+  if (!verts || !faces || !points || !loss || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || bad_workspace(workspace))
     return VOGE_ERR_BAD_ARG;
   const PmGridLayout l = pm_grid_layout(V, F, P);
   if (workspace_bytes < l.total) return VOGE_ERR_WORKSPACE;
@@ -464,15 +454,9 @@ extern "C" int voge_point_mesh_fwd_grid(const float *verts, long V, const int32_
   hipStream_t st = (hipStream_t)stream;
   float *d2p = reinterpret_cast<float *>(ws + l.d2p), *d2f = reinterpret_cast<float *>(ws + l.d2f);
   pm_grid_searches(points, P, verts, V, faces, F, cell_size, both, face_idx, d2p, bary_p, point_idx, d2f, bary_f, ws, l, st);
-  double *psum = reinterpret_cast<double *>(ws + l.psum);
-  float *pmax = reinterpret_cast<float *>(ws + l.pmax);
-  const unsigned nba = l.nb_loss[0], nbb = both ? l.nb_loss[1] : 0u;
-  hipLaunchKernelGGL(chamfer_loss_partial_kernel, dim3(nba + nbb), dim3(256), 0, st, d2p, (int)P, d2f, (int)F, nba, psum, pmax);
-  int bits = 0;
-  while ((1l << bits) < P + F) ++bits;      // P + F <= 2^bits: every scatter list of the backward
-  const bool sum = flags & kPmSum;
-  hipLaunchKernelGGL(chamfer_loss_final_kernel, dim3(1), dim3(256), 0, st, psum, pmax, nba, nbb, sum ? 1.0 : (double)P,
-                     sum ? 1.0 : (double)F, bits, loss, meta);
+  // P + F: every scatter list of the backward, as in voge_point_mesh_fwd -- the two routes share it
+  chamfer_loss_launch(d2p, P, d2f, F, both, flags & kPmSum, P + F, reinterpret_cast<double *>(ws + l.psum),
+                      reinterpret_cast<float *>(ws + l.pmax), loss, meta, st);
   return launch_status();
 }
 
@@ -484,7 +468,7 @@ extern "C" int voge_point_mesh_bwd(const float *verts, long V, const int32_t *fa
   if (!(flags & kPmGridPairs) && !pm_pairs_ok(F, P)) return VOGE_ERR_K_TOO_LARGE;
   const bool both = !(flags & kPmSingle);
   if (!verts || !faces || !points || !face_idx || !bary_p || (both && (!point_idx || !bary_f)) || !meta || !g_loss || !g_verts ||
-      !g_points || pm_ws_bad(workspace))
+      !g_points || bad_workspace(workspace))
     return VOGE_ERR_BAD_ARG;
   const size_t acc_bytes = (size_t)(V + P) * 3 * sizeof(long long);
   if (workspace_bytes < acc_bytes) return VOGE_ERR_WORKSPACE;
@@ -495,9 +479,9 @@ extern "C" int voge_point_mesh_bwd(const float *verts, long V, const int32_t *fa
   const bool sum = flags & kPmSum;
   const double u_p = sum ? 1.0 : 1.0 / (double)P, u_f = sum ? 1.0 : 1.0 / (double)F;
   const long items = P + (both ? F : 0);
-  hipLaunchKernelGGL(pm_scatter_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, points, (int)P, verts, (int)V, faces,
+  hipLaunchKernelGGL(pm_scatter_kernel, dim3(blocks256(items)), dim3(256), 0, st, points, (int)P, verts, (int)V, faces,
                      (int)F, face_idx, bary_p, both ? point_idx : nullptr, bary_f, meta, u_p, u_f, acc_v, acc_p);
-  hipLaunchKernelGGL(pm_finish_kernel, dim3((unsigned)((V + P + 255) / 256)), dim3(256), 0, st, points, (int)P, verts, (int)V, faces,
+  hipLaunchKernelGGL(pm_finish_kernel, dim3(blocks256(V + P)), dim3(256), 0, st, points, (int)P, verts, (int)V, faces,
                      (int)F, face_idx, meta, acc_v, g_loss, u_p, g_verts, g_points);
   return launch_status();
 }

@@ -346,39 +346,36 @@ struct PmGridLayout {
   size_t head, boxp, extp, rec, fidx, fcell, fcounts, fstart, fbsum, psorted, pcell, pcounts, pstart, pbsum, d2p, d2f, psum, pmax, total;
   long cap;
   int nb_scan, nb_box, nb_ext;
-  unsigned nb_loss[2];
 };
 static PmGridLayout pm_grid_layout(const long V, const long F, const long P) {
   PmGridLayout l;
-  const auto up16 = [](const size_t v) { return (v + 15) & ~(size_t)15; };
   const long n = F > P ? F : P;
   l.cap = grid_cell_cap(n);
   l.nb_scan = (int)((l.cap + kKnnScanBlock * kKnnScanItems - 1) / (kKnnScanBlock * kKnnScanItems));
   l.nb_box = (int)((V + P + 256 * kGridBoxItems - 1) / (256 * kGridBoxItems));
   l.nb_ext = (int)((F + 256 * kPmGridItems - 1) / (256 * kPmGridItems));
-  l.nb_loss[0] = (unsigned)((P + 256 * kChLossItems - 1) / (256 * kChLossItems));
-  l.nb_loss[1] = (unsigned)((F + 256 * kChLossItems - 1) / (256 * kChLossItems));
-  size_t at = 0;
-  l.head = at; at += sizeof(PmGridHead);
-  l.boxp = at; at += up16((size_t)l.nb_box * 6 * sizeof(float));
-  l.extp = at; at += up16((size_t)l.nb_ext * sizeof(double));
-  l.rec = at; at += (size_t)F * sizeof(PmRec);
-  l.fidx = at; at += up16((size_t)F * 4);
-  l.fcell = at; at += up16((size_t)F * 4);
-  l.fcounts = at; at += up16((size_t)l.cap * 4);
-  l.fstart = at; at += up16((size_t)(l.cap + 1) * 4);
-  l.fbsum = at; at += up16((size_t)l.nb_scan * 4);
-  l.psorted = at; at += (size_t)P * 16;
-  l.pcell = at; at += up16((size_t)P * 4);
-  l.pcounts = at; at += up16((size_t)l.cap * 4);
-  l.pstart = at; at += up16((size_t)(l.cap + 1) * 4);
-  l.pbsum = at; at += up16((size_t)l.nb_scan * 4);
-  l.d2p = at; at += up16((size_t)P * 4);
-  l.d2f = at; at += up16((size_t)F * 4);
-  l.psum = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(double));
-  l.pmax = at; at += up16((size_t)(l.nb_loss[0] + l.nb_loss[1]) * sizeof(float));
+  const size_t nb_loss = chamfer_loss_blocks(P) + chamfer_loss_blocks(F);
+  Carve c;
+  l.head = c.take_exact(sizeof(PmGridHead));
+  l.boxp = c.take((size_t)l.nb_box * 6 * sizeof(float));
+  l.extp = c.take((size_t)l.nb_ext * sizeof(double));
+  l.rec = c.take_exact((size_t)F * sizeof(PmRec));
+  l.fidx = c.take((size_t)F * 4);
+  l.fcell = c.take((size_t)F * 4);
+  l.fcounts = c.take((size_t)l.cap * 4);
+  l.fstart = c.take((size_t)(l.cap + 1) * 4);
+  l.fbsum = c.take((size_t)l.nb_scan * 4);
+  l.psorted = c.take_exact((size_t)P * 16);
+  l.pcell = c.take((size_t)P * 4);
+  l.pcounts = c.take((size_t)l.cap * 4);
+  l.pstart = c.take((size_t)(l.cap + 1) * 4);
+  l.pbsum = c.take((size_t)l.nb_scan * 4);
+  l.d2p = c.take((size_t)P * 4);
+  l.d2f = c.take((size_t)F * 4);
+  l.psum = c.take(nb_loss * sizeof(double));
+  l.pmax = c.take(nb_loss * sizeof(float));
   const size_t bwd = (size_t)(V + P) * 3 * sizeof(long long);      // the backward's accumulators, a call of its own
-  l.total = at > bwd ? at : bwd;
+  l.total = c.at > bwd ? c.at : bwd;
   return l;
 }
 
@@ -394,11 +391,11 @@ static void pm_grid_searches(const float *points, const long P, const float *ver
   const PmGridTables t{verts, (int)V, faces, (int)F, points, (int)P, reinterpret_cast<PmRec *>(ws + l.rec), ints(l.fidx), ints(l.fcell),
                        ints(l.fcounts), ints(l.fstart), reinterpret_cast<float4 *>(ws + l.psorted), ints(l.pcell), ints(l.pcounts),
                        ints(l.pstart)};
-  const unsigned nbf = (unsigned)((F + 255) / 256), nbp = (unsigned)((P + 255) / 256);
+  const unsigned nbf = blocks256(F), nbp = blocks256(P);
   hipLaunchKernelGGL(grid_box_kernel, dim3((unsigned)l.nb_box), dim3(256), 0, st, verts, (int)V, points, (int)P, boxp);
   hipLaunchKernelGGL(pm_grid_extent_kernel, dim3((unsigned)l.nb_ext), dim3(256), 0, st, verts, (int)V, faces, (int)F, extp);
   hipLaunchKernelGGL(pm_grid_choose_kernel, dim3(1), dim3(256), 0, st, boxp, l.nb_box, extp, l.nb_ext, F, F > P ? F : P, cell_size, head);
-  hipLaunchKernelGGL(grid_zero_kernel, dim3((unsigned)((l.cap + 255) / 256)), dim3(256), 0, st, &head->G, t.fcounts, t.pcounts);
+  hipLaunchKernelGGL(grid_zero_kernel, dim3(blocks256(l.cap)), dim3(256), 0, st, &head->G, t.fcounts, t.pcounts);
   hipLaunchKernelGGL(pm_grid_count_kernel, dim3(nbf + nbp), dim3(256), 0, st, t, nbf, head);
   int *counts[2] = {t.fcounts, t.pcounts}, *start[2] = {t.fstart, t.pstart}, *bsum[2] = {ints(l.fbsum), ints(l.pbsum)};
   const int N[2] = {(int)F, (int)P};

@@ -440,6 +440,11 @@ __device__ __forceinline__ void atomic_add_i64(long long *acc, const long long v
   atomicAdd(reinterpret_cast<unsigned long long *>(acc), (unsigned long long)v);
 }
 
+// a face's three vertex indices are inside a table of V rows
+__device__ __forceinline__ bool face_in_range(const int ia, const int ib, const int ic, const int V) {
+  return (unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V;
+}
+
 // A bounding cone of a set of unit directions: axis a, cos/sin of the half angle with the
 // rounding pushed to the conservative side.  ok == false -> cone too wide / degenerate,
 // nothing may be culled against it.
@@ -1161,6 +1166,34 @@ __device__ __forceinline__ float seg_sum_key(float x, const int key, const int l
 }
 
 inline int launch_status() { return (int)hipGetLastError(); }
+
+// ---- the host vocabulary of sizes, launch grids and workspaces ------------------------------------------------------------------
+// the smallest bits with n <= 2^bits (0 for n <= 1): the list_bits of fixed_point.h for lists of at most n terms
+static inline int ceil_log2(const long n) {
+  int bits = 0;
+  while ((1l << bits) < n) ++bits;
+  return bits;
+}
+static inline size_t up16(const size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+// every workspace an entry takes is there and on a 16-byte boundary
+static inline bool bad_workspace(const void *ws) { return !ws || (reinterpret_cast<uintptr_t>(ws) & 15) != 0; }
+// workgroups of 256 threads, one item each, for n items; capped: the grid of a reduction whose threads stride over the items
+static inline unsigned blocks256(const long n) { return (unsigned)((n + 255) / 256); }
+static inline unsigned blocks256_capped(const size_t n) {
+  const size_t want = (n + 255) / 256;
+  return (unsigned)(want < 1024 ? want : 1024);
+}
+// Carves a workspace front to back: take(bytes) is the offset of the next field, which then holds `bytes` rounded up to 16, so every
+// field behind it starts on a 16-byte boundary; take_exact leaves the size as it is (the heads, and records that are 16 bytes each).
+struct Carve {
+  size_t at = 0;
+  size_t take(const size_t bytes) { return take_exact(up16(bytes)); }
+  size_t take_exact(const size_t bytes) {
+    const size_t offset = at;
+    at += bytes;
+    return offset;
+  }
+};
 
 // Fill `bytes` (a multiple of 4) at p with one 32-bit pattern -- by a kernel of this library, never hipMemsetAsync.
 // A memset captured into a HIP graph (torch.cuda.graph around a training iteration) did NOT reliably take effect on

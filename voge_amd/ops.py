@@ -1940,6 +1940,22 @@ class _MeshReg(torch.autograd.Function):
         return g_verts, None, None, None
 
 
+def _sized_workspace(dev, size_entry, *sizes):
+    """(ws, nbytes): the stream's cached workspace of the bytes the library's size entry asks for these sizes"""
+    nbytes = size_entry(*sizes)
+    return _workspace(dev, nbytes), nbytes
+
+
+def _cell_size(cell_size, what):
+    """The cell edge a grid entry takes: 0.0 for None (the entry's default cell), else a positive finite fp32 number"""
+    if cell_size is None:
+        return 0.0
+    cell = float(cell_size)
+    if not (cell > 0.0 and cell < 3.0e38):
+        raise ValueError(f"{what}: cell_size must be a positive finite fp32 number, got {cell_size}")
+    return cell
+
+
 def knn_grid(lo, hi, n, cell_size=None):
     """The uniform grid voge_knn_points searches: (cell, gx, gy, gz) for a cloud of n points whose bounding box is lo .. hi
     (three floats each).  Default: about 2 n cubic cells over the box, cell = (volume / 2n)^(1/3) -- over the axes that have an
@@ -1956,9 +1972,7 @@ def knn_grid(lo, hi, n, cell_size=None):
                 vol *= e
             cell = (vol / (2.0 * max(n, 1))) ** (1.0 / len(pos))
     else:
-        cell = float(cell_size)
-        if not (cell > 0.0 and cell < 3.0e38):
-            raise ValueError(f"knn_points: cell_size must be a positive finite fp32 number, got {cell_size}")
+        cell = _cell_size(cell_size, "knn_points")
     cap = max(8 * n, 1 << 15)
     cell = max(cell, max(ext) / 1023.0, 1e-30)
     while True:
@@ -1990,8 +2004,7 @@ def knn_points(points, k, include_self=False, cell_size=None):
         raise ValueError("knn_points: points hold non-finite coordinates")
     cell, gx, gy, gz = knn_grid(box[:3], box[3:], N, cell_size)
     with _on(pts.device):
-        nbytes = lib.voge_knn_workspace_bytes(N, gx, gy, gz)
-        ws = _workspace(pts.device, nbytes)
+        ws, nbytes = _sized_workspace(pts.device, lib.voge_knn_workspace_bytes, N, gx, gy, gz)
         rc = lib.voge_knn_points(_p(pts), N, k, int(bool(include_self)), box[0], box[1], box[2], cell, gx, gy, gz, _p(idx), _p(d2),
                                  _p(ws), nbytes, _stream())
     _lib.check(rc, "voge_knn_points")
@@ -2046,9 +2059,7 @@ def nearest_points(queries, points, cell_size=None, route=None, return_grid=Fals
     -- what the tests read to see which grid ran."""
     q, p = _cloud(queries, "queries"), _cloud(points, "points")
     r = _chamfer_route(route)
-    cell = 0.0 if cell_size is None else float(cell_size)
-    if cell_size is not None and not (cell > 0.0 and cell < 3.0e38):
-        raise ValueError(f"nearest_points: cell_size must be a positive finite fp32 number, got {cell_size}")
+    cell = _cell_size(cell_size, "nearest_points")
     Nq, Np = q.shape[0], p.shape[0]
     if Np == 0:
         raise ValueError("nearest_points: points is empty")
@@ -2058,8 +2069,7 @@ def nearest_points(queries, points, cell_size=None, route=None, return_grid=Fals
     grid = None
     if Nq > 0:
         with _on(q.device):
-            nbytes = lib.voge_chamfer_workspace_bytes(Nq, Np)
-            ws = _workspace(q.device, nbytes)
+            ws, nbytes = _sized_workspace(q.device, lib.voge_chamfer_workspace_bytes, Nq, Np)
             rc = lib.voge_nearest_points(_p(q), Nq, _p(p), Np, r, cell, _p(idx), _p(d2), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_nearest_points")
         if return_grid:
@@ -2091,8 +2101,7 @@ class _Chamfer(torch.autograd.Function):
         nn_y = None if flags & 2 else torch.empty((Ny,), dtype=torch.int32, device=dev)
         meta = torch.empty((4,), dtype=torch.int32, device=dev)
         with _on(dev):
-            nbytes = lib.voge_chamfer_workspace_bytes(Nx, Ny)
-            ws = _workspace(dev, nbytes)
+            ws, nbytes = _sized_workspace(dev, lib.voge_chamfer_workspace_bytes, Nx, Ny)
             rc = lib.voge_chamfer_fwd(_p(x), Nx, _p(y), Ny, route, flags, _p(loss), _p(nn_x), _p(nn_y), _p(meta), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_chamfer_fwd")
         ctx.save_for_backward(x, y, nn_x, nn_y, meta)
@@ -2112,8 +2121,7 @@ class _Chamfer(torch.autograd.Function):
         g = _dev(g_loss, torch.float32, "grad_loss")
         g_x, g_y = torch.empty_like(x), torch.empty_like(y)
         with _on(x.device):
-            nbytes = lib.voge_chamfer_workspace_bytes(Nx, Ny)
-            ws = _workspace(x.device, nbytes)
+            ws, nbytes = _sized_workspace(x.device, lib.voge_chamfer_workspace_bytes, Nx, Ny)
             rc = lib.voge_chamfer_bwd(_p(x), Nx, _p(y), Ny, _p(nn_x), _p(nn_y), _p(meta), _p(g), ctx.flags, _p(g_x), _p(g_y), _p(ws),
                                       nbytes, _stream())
         _lib.check(rc, "voge_chamfer_bwd")
@@ -2163,19 +2171,11 @@ def _point_mesh_route(route, F, P, what):
     return route
 
 
-def _point_mesh_cell(cell_size, what):
-    if cell_size is None:
-        return 0.0
-    cell = float(cell_size)
-    if not (cell > 0.0 and cell < 3.0e38):
-        raise ValueError(f"{what}: cell_size must be a positive finite fp32 number, got {cell_size}")
-    return cell
+_point_mesh_cell = _cell_size      # (the name the point-mesh tests call it by)
 
 
 def _point_mesh_args(verts, faces, points, what, route=None):
-    """-> (verts, faces, points, "brute" | "grid")"""
-    if route not in POINT_MESH_ROUTES:
-        raise ValueError(f"{what}: route must be None, 'brute' or 'grid', got {route!r}")
+    """-> (verts, faces, points, "brute" | "grid"); the route is checked with the sizes, by _point_mesh_route"""
     verts, points = _cloud(verts, "verts"), _cloud(points, "points")
     faces = _dev(faces, torch.int32, "faces")
     if faces.dim() != 2 or faces.shape[1] != 3:
@@ -2195,7 +2195,7 @@ def closest_faces(points, verts, faces, route=None, cell_size=None):
     on the device, the same bits, no pair cap (cell_size asks the grid for a cell of that edge: the tests' and the tuner's knob);
     None: by P F (_point_mesh_route).  Nothing is read back on the host on either route; no gradient."""
     verts, faces, points, route = _point_mesh_args(verts, faces, points, "closest_faces", route)
-    cell = _point_mesh_cell(cell_size, "closest_faces")
+    cell = _cell_size(cell_size, "closest_faces")
     P = points.shape[0]
     d2 = torch.empty((P,), dtype=torch.float32, device=points.device)
     face_idx = torch.empty((P,), dtype=torch.int32, device=points.device)
@@ -2205,8 +2205,7 @@ def closest_faces(points, verts, faces, route=None, cell_size=None):
         V, F = verts.shape[0], faces.shape[0]
         with _on(points.device):
             if route == "grid":
-                nbytes = lib.voge_point_mesh_grid_workspace_bytes(V, F, P)
-                ws = _workspace(points.device, nbytes)
+                ws, nbytes = _sized_workspace(points.device, lib.voge_point_mesh_grid_workspace_bytes, V, F, P)
                 rc = lib.voge_closest_faces_grid(_p(points), P, _p(verts), V, _p(faces), F, cell, _p(face_idx), _p(d2), _p(bary), _p(ws),
                                                  nbytes, _stream())
             else:
@@ -2229,7 +2228,7 @@ class _PointMesh(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, points, flags, route=None, cell_size=None):
         verts, faces, points, route = _point_mesh_args(verts, faces, points, "point_mesh_face_distance", route)
-        cell = _point_mesh_cell(cell_size, "point_mesh_face_distance")
+        cell = _cell_size(cell_size, "point_mesh_face_distance")
         V, F, P = verts.shape[0], faces.shape[0], points.shape[0]
         if P == 0:
             raise ValueError("point_mesh_face_distance: an empty cloud")
@@ -2244,13 +2243,11 @@ class _PointMesh(torch.autograd.Function):
         meta = torch.empty((4,), dtype=torch.int32, device=dev)
         with _on(dev):
             if route == "grid":
-                nbytes = lib.voge_point_mesh_grid_workspace_bytes(V, F, P)
-                ws = _workspace(dev, nbytes)
+                ws, nbytes = _sized_workspace(dev, lib.voge_point_mesh_grid_workspace_bytes, V, F, P)
                 rc = lib.voge_point_mesh_fwd_grid(_p(verts), V, _p(faces), F, _p(points), P, flags, cell, _p(loss), _p(face_idx), _p(bary_p),
                                                   _p(point_idx), _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
             else:
-                nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
-                ws = _workspace(dev, nbytes)
+                ws, nbytes = _sized_workspace(dev, lib.voge_point_mesh_workspace_bytes, V, F, P)
                 rc = lib.voge_point_mesh_fwd(_p(verts), V, _p(faces), F, _p(points), P, flags, _p(loss), _p(face_idx), _p(bary_p),
                                              _p(point_idx), _p(bary_f), _p(meta), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_point_mesh_fwd_grid" if route == "grid" else "voge_point_mesh_fwd")
@@ -2271,8 +2268,7 @@ class _PointMesh(torch.autograd.Function):
         g = _dev(g_loss, torch.float32, "grad_loss")
         g_verts, g_points = torch.empty_like(verts), torch.empty_like(points)
         with _on(verts.device):
-            nbytes = lib.voge_point_mesh_workspace_bytes(V, F, P)
-            ws = _workspace(verts.device, nbytes)
+            ws, nbytes = _sized_workspace(verts.device, lib.voge_point_mesh_workspace_bytes, V, F, P)
             rc = lib.voge_point_mesh_bwd(_p(verts), V, _p(faces), F, _p(points), P, _p(face_idx), _p(bary_p), _p(point_idx), _p(bary_f),
                                          _p(meta), _p(g), ctx.flags, _p(g_verts), _p(g_points), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_point_mesh_bwd")
@@ -2318,8 +2314,7 @@ class _MeshSample(torch.autograd.Function):
         bary = torch.empty((S, 3), dtype=torch.float32, device=dev)
         a2 = torch.empty((F,), dtype=torch.float32, device=dev) if return_areas else None
         with _on(dev):
-            nbytes = lib.voge_mesh_sample_workspace_bytes(V, F, S)
-            ws = _workspace(dev, nbytes)
+            ws, nbytes = _sized_workspace(dev, lib.voge_mesh_sample_workspace_bytes, V, F, S)
             rc = lib.voge_mesh_sample_fwd(_p(v), V, _p(sampler.faces), F, _p(u), S, _p(points), _p(normals), _p(face_idx), _p(bary),
                                           _p(a2), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_mesh_sample_fwd")
@@ -2342,8 +2337,7 @@ class _MeshSample(torch.autograd.Function):
         gn = None if g_normals is None else _dev(g_normals, torch.float32, "grad_normals")
         g_verts = torch.empty_like(v)
         with _on(v.device):
-            nbytes = lib.voge_mesh_sample_workspace_bytes(V, F, S)
-            ws = _workspace(v.device, nbytes)
+            ws, nbytes = _sized_workspace(v.device, lib.voge_mesh_sample_workspace_bytes, V, F, S)
             rc = lib.voge_mesh_sample_bwd(_p(v), V, _p(sampler.faces), F, _p(sampler.corner_off), _p(sampler.corner), _p(face_idx),
                                           _p(bary), S, _p(gp), _p(gn), _p(g_verts), _p(ws), nbytes, _stream())
         _lib.check(rc, "voge_mesh_sample_bwd")
@@ -2499,6 +2493,15 @@ def _mesh_faces(faces, name):
     return f
 
 
+def _mesh_verts(verts, name):
+    v = _dev(verts.detach(), torch.float32, "verts")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"{name}: verts [V,3] expected, got {tuple(v.shape)}")
+    if v.shape[0] > MESH_MAX:
+        raise ValueError(f"{name}: {v.shape[0]} vertices, at most {MESH_MAX}")
+    return v
+
+
 def mesh_components(faces, num_verts, return_count=False):
     """(vert_label [V] int32, face_label [F] int32, num_components) of faces [F,3] int32 on a HIP device (extension;
     voge_mesh_components): the values of Aggregation.mesh_components.  Three launches on the current stream, then the error word
@@ -2535,16 +2538,13 @@ def mesh_clean(verts, faces, face_label, keep_root):
     (bool or bytes, at the labels) names, face_label [F] int32 from mesh_components.  Four launches, then V', F' and the error word
     are read back on the host -- ONE synchronisation, what sizes the outputs -- and one launch writes them.  Not differentiable,
     not capturable."""
-    v = _dev(verts.detach(), torch.float32, "verts")
+    v = _mesh_verts(verts, "mesh_clean")
     f = _mesh_faces(faces, "mesh_clean")
     fl = _dev(face_label, torch.int32, "face_label")
     kr = _dev(keep_root, torch.uint8, "keep_root")
     V, F, dev = v.shape[0], f.shape[0], v.device
-    if v.dim() != 2 or v.shape[1] != 3 or tuple(fl.shape) != (F,) or tuple(kr.shape) != (V,):
-        raise ValueError(f"mesh_clean: verts [V,3], face_label [F] and keep_root [V] expected, got {tuple(v.shape)} / {tuple(fl.shape)} / "
-                         f"{tuple(kr.shape)}")
-    if V > MESH_MAX:
-        raise ValueError(f"mesh_clean: {V} vertices, at most {MESH_MAX}")
+    if tuple(fl.shape) != (F,) or tuple(kr.shape) != (V,):
+        raise ValueError(f"mesh_clean: face_label [{F}] and keep_root [{V}] expected, got {tuple(fl.shape)} / {tuple(kr.shape)}")
     if f.device != dev or fl.device != dev or kr.device != dev:
         raise _lib.VogeHipError(f"mesh_clean: verts on {dev}, faces on {f.device}, face_label on {fl.device}, keep_root on {kr.device}")
     empty = lambda n, cols, dt: torch.empty((n, 3) if cols else (n,), dtype=dt, device=dev)
@@ -2577,13 +2577,9 @@ def vertex_normals(verts, faces):
     Aggregation.mesh_vertex_normals.  Four launches on the current stream from the stream's cached workspace, nothing read back:
     capturable.  Fixed-point sums with integer atomics: the same bits on every run and for every order of the faces.  Not
     differentiable."""
-    v = _dev(verts.detach(), torch.float32, "verts")
+    v = _mesh_verts(verts, "vertex_normals")
     f = _mesh_faces(faces, "vertex_normals")
     V, F, dev = v.shape[0], f.shape[0], v.device
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"vertex_normals: verts [V,3] expected, got {tuple(v.shape)}")
-    if V > MESH_MAX:
-        raise ValueError(f"vertex_normals: {V} vertices, at most {MESH_MAX}")
     if f.device != dev:
         raise _lib.VogeHipError(f"vertex_normals: verts on {dev}, faces on {f.device}")
     out = torch.empty((V, 3), dtype=torch.float32, device=dev)
@@ -2591,8 +2587,7 @@ def vertex_normals(verts, faces):
         return out
     lib = _lib.load()
     with _on(dev):
-        nbytes = lib.voge_vertex_normals_workspace_bytes(V)
-        ws = _workspace(dev, nbytes)
+        ws, nbytes = _sized_workspace(dev, lib.voge_vertex_normals_workspace_bytes, V)
         rc = lib.voge_vertex_normals(_p(v), V, _p(f) if F else None, F, _p(out), _p(ws), nbytes, 15, _stream())
     _lib.check(rc, "voge_vertex_normals")
     return out
@@ -2624,13 +2619,9 @@ def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
     write them.  ValueError for an index outside [0, V), a vertex that is not finite and more than 2^21 - 1 cells on an axis.
     Fixed-point sums with integer atomics: the same bits on every run and for every order of the faces.  Not differentiable, not
     capturable."""
-    v = _dev(verts.detach(), torch.float32, "verts")
+    v = _mesh_verts(verts, "mesh_simplify")
     f = _mesh_faces(faces, "mesh_simplify")
     V, F, dev = v.shape[0], f.shape[0], v.device
-    if v.dim() != 2 or v.shape[1] != 3:
-        raise ValueError(f"mesh_simplify: verts [V,3] expected, got {tuple(v.shape)}")
-    if V > MESH_MAX:
-        raise ValueError(f"mesh_simplify: {V} vertices, at most {MESH_MAX}")
     if placement not in ("mean", "quadric"):
         raise ValueError(f"mesh_simplify: placement 'mean' or 'quadric' expected, got {placement!r}")
     quadric = int(placement == "quadric")
@@ -2658,8 +2649,7 @@ def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
     lib = _lib.load()
     with _on(dev):
         st = _stream()
-        nbytes = lib.voge_mesh_simplify_workspace_bytes(V, F)
-        ws = _workspace(dev, nbytes)
+        ws, nbytes = _sized_workspace(dev, lib.voge_mesh_simplify_workspace_bytes, V, F)
         rc = lib.voge_mesh_simplify_scan(_p(v), V, _p(f), F, h[0], h[1], h[2], _p(ws), nbytes, _p(totals), 255, st)
         _lib.check(rc, "voge_mesh_simplify_scan")
         Vk, Fk, bad = (int(x) for x in totals.tolist())      # the synchronisation
