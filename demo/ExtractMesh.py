@@ -25,8 +25,13 @@ no target face count -- a count is reached by trying cell sizes -- and no promis
 through attr=.  It prints the faces before and after and the same two scores for both meshes; the simplified mesh is what is
 saved and returned.  LAST then holds simplified = (F before, F after, the scores before, the scores after).
 
+--depth-error closes the loop directly: the final mesh is rasterised under the fusion's own cameras (Meshing.rasterize_mesh, whose
+depth is get_depth's) and compared with the depth maps it was fused from, pixel for pixel: per view the mean and the largest
+|mesh depth - get_depth| over the pixels both cover, and the share of the pixels only one of the two covers.  LAST then holds
+depth_error = [(mean, largest, share), ...].
+
 usage: python demo/ExtractMesh.py [--resolution 128] [--views 24] [--image 256] [--out bunny_mesh.off] [--keep-largest K] [--min-faces M]
-                                  [--colour] [--simplify CELL]"""
+                                  [--colour] [--simplify CELL] [--depth-error]"""
 import argparse
 import os
 import sys
@@ -40,7 +45,7 @@ from VoGE.Losses import closest_faces                                           
 from VoGE.Converter.IO import save_off                                                 # noqa: E402
 from VoGE.Meshes import GaussianMeshesNaive                                            # noqa: E402
 from VoGE.Converter.Converters import normal_mesh_converter                            # noqa: E402
-from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh, simplify_mesh, vertex_normals    # noqa: E402
+from VoGE.Meshing import TSDFVolume, clean_mesh, connected_components, extract_mesh, rasterize_mesh, simplify_mesh, vertex_normals    # noqa: E402
 from VoGE.Renderer import GaussianRenderer, GaussianRenderSettings, get_depth, get_silhouette, interpolate_attr   # noqa: E402
 from voge_amd.Meshes import OrientedGaussianMeshesNaive                                # noqa: E402
 from voge_amd.cameras import PerspectiveCameras, look_at_view_transform               # noqa: E402
@@ -83,7 +88,21 @@ def round_trip(renderer, mesh_verts, faces, vert_attr, R, T, first, device):
     return float((back - first).abs().mean())
 
 
-def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None, colour=False, simplify=None):
+def depth_errors(mesh_verts, faces, cameras, depths):
+    """[(mean, largest |mesh depth - depth| over the pixels both cover, share of the pixels only one covers)] per view"""
+    frags = rasterize_mesh(mesh_verts, faces, cameras, tuple(depths.shape[1:]))
+    rows = []
+    for mesh, ours, ref in zip(frags.depth, frags.pix_to_face >= 0, depths):
+        theirs = ref > 0
+        both = ours & theirs
+        diff = (mesh - ref).abs()[both]
+        rows.append((float(diff.mean()) if len(diff) else float("nan"), float(diff.max()) if len(diff) else float("nan"),
+                     float((ours ^ theirs).float().mean())))
+    return rows
+
+
+def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:0", keep_largest=None, min_faces=None, colour=False, simplify=None,
+        depth_error=False):
     g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_gaussians.npz"))
     verts, sigmas = (torch.from_numpy(g[k]) for k in ("verts", "isigma"))
     colours = torch.from_numpy(g["colors"]).to(device) if colour else None
@@ -150,6 +169,12 @@ def run(resolution=128, views=24, image=256, out="bunny_mesh.off", device="cuda:
         report += f", round trip mean |dimage| {diff:.4f}"
         print(f"coloured mesh back as {len(mesh_verts)} oriented Gaussians, rendered from the first camera: round trip mean |dimage| {diff:.4f}")
         LAST.update(vert_attr=vert_attr, colour_range=(float(images.min()), float(images.max())), round_trip=diff)
+    if depth_error:
+        rows = depth_errors(mesh_verts, faces, cameras, torch.cat(depths))
+        for k, (mean, largest, share) in enumerate(rows):
+            print(f"view {k:2d}: |mesh depth - get_depth| mean {mean:.5f}, largest {largest:.5f} over the pixels both cover; "
+                  f"{share * 100:.2f} % of the pixels covered by one of the two only")
+        LAST.update(depth_error=rows)
     if out:
         save_off(out, mesh_verts, faces, vert_color=vert_attr if colour else None)
         print("->", out)
@@ -166,5 +191,7 @@ if __name__ == "__main__":
     ap.add_argument("--min-faces", type=int, default=None)
     ap.add_argument("--colour", action="store_true")
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL")
+    ap.add_argument("--depth-error", action="store_true", help="rasterise the final mesh under the fusion's cameras and compare the depth maps")
     a = ap.parse_args()
-    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, colour=a.colour, simplify=a.simplify)
+    run(a.resolution, a.views, a.image, a.out, keep_largest=a.keep_largest, min_faces=a.min_faces, colour=a.colour, simplify=a.simplify,
+        depth_error=a.depth_error)

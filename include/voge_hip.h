@@ -1263,6 +1263,37 @@ int voge_mesh_simplify_attr(const float *attr, long V, long F, int C, int c0, in
                             long Vk, const void *acc, int quadric, void *attr_workspace, size_t attr_workspace_bytes, float *attr_out,
                             int stages, voge_stream_t stream);
 
+/*
+ * Mesh depth maps (EXTENSION: PyTorch3D's rasterize_meshes, one face a pixel).  Replaces voge_amd/Aggregation.py mesh_rasterize,
+ * the definition, whose docstring states the rule in seven steps; csrc/mesh_raster.hip's header has the launches, the box's pad
+ * and the derived bounds.  verts [V,3] fp32, faces [F,3] int32, one mesh under B cameras R [B,3,3], T [B,3], focal [B,2], pp [B,2]
+ * (those of voge_tsdf_integrate), images of H x W in tiles of 16 x 16.  Outputs pix_to_face [B,H,W] int32 (-1: nothing hit), bary
+ * [B,H,W,3] and depth [B,H,W] fp32 (zeros there; depth is voge_depth_fwd's: along the unit pixel ray): the definition's fp32 bits,
+ * the same on both routes.  The workspace of voge_mesh_raster_workspace_bytes(B, V, F, H, W) holds the records and the bins
+ * route's tables (forward) or the fixed-point accumulators (backward); the backward reads nothing the forward left there.
+ *   voge_mesh_raster_fwd   `stages` is a bit mask of launches: 1 the records [B F], 2 the bins route's tables (zero fill, count,
+ *                          two scan levels; total [1] = the length of all the tiles' lists, what the caller reads back to
+ *                          allocate list -- the one synchronisation of that route), 4 the fill of list [list_len] int32 (the
+ *                          total as read back, at most 2^31 - 1), 8 the raster -- over the tiles' lists when stage 4 is in the
+ *                          same call, over all F records otherwise.  Route "brute": one call with stages 9, two launches, nothing
+ *                          read back.  Route "bins": stages 3, the read-back, stages 12 on the same workspace.
+ *   voge_mesh_raster_bwd   g_verts [V,3] of g_depth [B,H,W] at the faces pix_to_face names: zero fill, the largest |term|, the
+ *                          scatter with 64-bit integer atomics, the finish per vertex in fp64 (the rotation back through R^T,
+ *                          rounded once).  No float atomics, nothing read back, the same bits on every run.
+ * A face that names a vertex outside [0, V) hits nothing.  B below 1, V below 1 in voge_mesh_raster_bwd (there is no gradient to write: the
+ * caller returns an empty one), V or F above 2^28 - 1, B H W above 2^31 - 1, B F or B V above
+ * 2^36, a null pointer, a workspace that is null or off the 16-byte boundary, stages outside 1 .. 15: VOGE_ERR_BAD_ARG; a workspace
+ * too small: VOGE_ERR_WORKSPACE -- all before any HIP call.
+ */
+size_t voge_mesh_raster_workspace_bytes(long B, long V, long F, long H, long W);
+int voge_mesh_raster_fwd(const float *verts, long V, const int32_t *faces, long F, const float *R, const float *T, const float *focal,
+                         const float *pp, long B, long H, long W, int cull_backfaces, int stages, int32_t *list, long list_len,
+                         int32_t *pix_to_face, float *bary, float *depth, long long *total, void *workspace, size_t workspace_bytes,
+                         voge_stream_t stream);
+int voge_mesh_raster_bwd(const float *verts, long V, const int32_t *faces, long F, const float *R, const float *T, const float *focal,
+                         const float *pp, long B, long H, long W, const int32_t *pix_to_face, const float *g_depth, float *g_verts,
+                         void *workspace, size_t workspace_bytes, voge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1136,3 +1136,129 @@ def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
         am = torch.where(torch.isfinite(am), am, torch.full_like(am, float("nan")))      # (a value that is not finite: NaN)
         new_attr = torch.where(single[:, None], a32[out_label], am.to(torch.float32))
     return new_verts, new_faces, new_attr, vert_index, face_index
+
+
+MESH_RASTER_CHUNK_PAIRS = 1 << 21      # (pixel, face) pairs of one chunk of mesh_rasterize's walk over the faces
+
+
+def _view_space(verts, R, T):
+    """p [B,V,3] = verts @ R_b + T_b, each component ((x0 R0k + x1 R1k) + x2 R2k) + Tk: step 1 of tsdf_integrate"""
+    x0, x1, x2 = verts[None, :, 0, None], verts[None, :, 1, None], verts[None, :, 2, None]
+    return ((x0 * R[:, None, 0, :] + x1 * R[:, None, 1, :]) + x2 * R[:, None, 2, :]) + T[:, None, :]
+
+
+def _pixel_dirs(focal, pp, H, W):
+    """(d0 [B,W], d1 [B,H]): pixel (i, j) looks along ((px - (j + 0.5)) / fx, (py - (i + 0.5)) / fy, 1)"""
+    dt, dev = focal.dtype, focal.device
+    cj = torch.arange(W, device=dev).to(dt) + 0.5
+    ci = torch.arange(H, device=dev).to(dt) + 0.5
+    return (pp[:, 0:1] - cj[None, :]) / focal[:, 0:1], (pp[:, 1:2] - ci[None, :]) / focal[:, 1:2]
+
+
+def _edge_values(d0, d1, n):
+    """w = (d0 n_0 + d1 n_1) + n_2 of rays d0, d1 against records n [..., 3] (broadcast)"""
+    return (d0 * n[..., 0] + d1 * n[..., 1]) + n[..., 2]
+
+
+def mesh_rasterize(verts, faces, R, T, focal, pp, H, W, cull_backfaces=False, mark=None):
+    """The nearest face of a mesh under every pixel (an extension: PyTorch3D's rasterize_meshes with one face a pixel and an exact
+    ray-triangle test) -> (pix_to_face [B,H,W] int64, -1 where nothing is hit; bary [B,H,W,3] and depth [B,H,W] in the vertices'
+    dtype, zeros where nothing is hit).
+
+      verts [V,3], faces [F,3] integer                the mesh, one for all views;
+      R [B,3,3], T [B,3], focal [B,2], pp [B,2]       the cameras of cameras.pixel_rays and of tsdf_integrate.
+
+    depth is get_depth's: the distance along the UNIT pixel ray from the camera centre, not view z.  Every operation below is a
+    separate operation of the vertices' dtype, in this order:
+      1. view space: p = x @ R_b + T_b, each component ((x0 R0k + x1 R1k) + x2 R2k) + Tk (step 1 of tsdf_integrate);
+      2. pixel ray: pixel (i, j) looks along d = ((px - (j + 0.5)) / fx, (py - (i + 0.5)) / fy, 1) -- the centre of the pixel that
+         tsdf_integrate's floor(u), floor(v) names, so a grid point on the rasterised surface reads its own pixel;
+      3. face records: for the corners a, b, c in view space n_a = b x c, n_b = c x a, n_c = a x b, each component (p q) - (r s);
+      4. edge values: w_i = (d0 n_i0 + d1 n_i1) + n_i2, det = (w_a + w_b) + w_c.  a x b and b x a are exact negatives in IEEE
+         arithmetic, so two faces that share an edge get exactly opposite w on it: a ray on a shared edge is inside both faces,
+         and a closed mesh has no cracks;
+      5. hit test: hit <=> (w_a, w_b, w_c >= 0 and det > 0) or (w_a, w_b, w_c <= 0 and det < 0); with cull_backfaces only the
+         second arm, the front of a face whose normal (b - a) x (c - a) points at the camera for det R > 0.  bary_i = w_i / det,
+         z = (bary_a a_z + bary_b b_z) + bary_c c_z, and a hit needs z > 0.  A ray-triangle test in 3-D: a face that crosses the
+         camera plane needs no clipping; a face with a NaN corner hits nothing, every comparison being written positively;
+         infinite coordinates are out of contract;
+      6. winner: the lexicographically smallest (z, face index) -- an exact tie keeps the lower index;
+         depth = z * sqrt((d0 d0 + d1 d1) + 1), IEEE square root and division;
+      7. marks: mark = (c, rho) appends a bool [B,H,W] of the pixels whose decision a lower precision may take the other way: some
+         face with z > 0 has its smallest bary within c 2^-23 M |d| / |det| of zero, M the largest squared corner norm of the face
+         in view space; or the second-nearest hit lies within rho z of the nearest.
+    The faces are walked in chunks of MESH_RASTER_CHUNK_PAIRS / (B H W), so memory stays bounded; the choice is made without
+    autograd, bary and depth are then evaluated at the chosen face with it: differentiable to verts (and the cameras) through
+    depth and bary.  torch on any device / dtype: the definition csrc/mesh_raster.hip is tested against and the route for
+    everything it does not take."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or not verts.dtype.is_floating_point:
+        raise ValueError(f"mesh_rasterize: verts [V,3] of floats expected, got {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point:
+        raise ValueError(f"mesh_rasterize: faces [F,3] of integers expected, got {tuple(faces.shape)}")
+    B, H, W = R.shape[0], int(H), int(W)
+    if R.shape != (B, 3, 3) or T.shape != (B, 3) or focal.shape != (B, 2) or pp.shape != (B, 2):
+        raise ValueError(f"mesh_rasterize: R [B,3,3], T [B,3], focal [B,2], pp [B,2] expected, got {tuple(R.shape)} / {tuple(T.shape)} / "
+                         f"{tuple(focal.shape)} / {tuple(pp.shape)}")
+    if H < 1 or W < 1:
+        raise ValueError(f"mesh_rasterize: image_size (H, W) >= 1 expected, got ({H}, {W})")
+    dt, dev = verts.dtype, verts.device
+    V, F = verts.shape[0], faces.shape[0]
+    faces = faces.to(dev).long()
+    if F and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise ValueError(f"mesh_rasterize: a face names a vertex outside [0, {V})")
+    R, T, focal, pp = (torch.as_tensor(t, device=dev).to(dt) for t in (R, T, focal, pp))
+    p = _view_space(verts, R, T)                                                           # step 1 [B,V,3]
+    d0, d1 = _pixel_dirs(focal, pp, H, W)                                                  # step 2
+    dn = _ieee_sqrt((d0 * d0)[:, None, :] + (d1 * d1)[:, :, None] + 1)                      # |d| [B,H,W]
+    best_z = torch.full((B, H, W), float("inf"), dtype=dt, device=dev)
+    second_z = best_z.clone()
+    best_f = torch.full((B, H, W), -1, dtype=torch.long, device=dev)
+    marked = torch.zeros((B, H, W), dtype=torch.bool, device=dev)
+    chunk = max(1, MESH_RASTER_CHUNK_PAIRS // max(1, B * H * W))
+    with torch.no_grad():
+        pd = p.detach()
+        D0, D1 = d0[:, None, None, :].detach(), d1[:, None, :, None].detach()
+        for f0 in range(0, F if B else 0, chunk):
+            f = faces[f0:f0 + chunk]
+            a, b, c = pd[:, f[:, 0]], pd[:, f[:, 1]], pd[:, f[:, 2]]                       # [B,Fc,3]
+            w = [_edge_values(D0, D1, n[:, :, None, None, :]) for n in (_face_cross(b, c), _face_cross(c, a), _face_cross(a, b))]      # steps 3, 4
+            det = (w[0] + w[1]) + w[2]
+            back = (w[0] <= 0) & (w[1] <= 0) & (w[2] <= 0) & (det < 0)
+            hit = back if cull_backfaces else (back | ((w[0] >= 0) & (w[1] >= 0) & (w[2] >= 0) & (det > 0)))
+            bary = [x / det for x in w]
+            z = (bary[0] * a[:, :, None, None, 2] + bary[1] * b[:, :, None, None, 2]) + bary[2] * c[:, :, None, None, 2]
+            hit = hit & (z > 0)                                                            # step 5
+            zh = torch.where(hit, z, torch.full_like(z, float("inf")))
+            z1 = zh.min(1).values
+            ids = torch.arange(f0, f0 + f.shape[0], device=dev).view(1, -1, 1, 1)
+            first = torch.where(hit & (zh == z1[:, None]), ids, torch.full_like(ids, F)).min(1).values      # the lowest index at z1, F: no hit
+            z2 = torch.where(ids == first[:, None], torch.full_like(zh, float("inf")), zh).min(1).values
+            take = (first < F) & ((best_f < 0) | (z1 < best_z))                            # step 6 (the chunks ascend: a tie keeps the earlier)
+            second_z = torch.minimum(torch.maximum(best_z, z1), torch.minimum(second_z, z2))
+            best_z = torch.where(take, z1, best_z)
+            best_f = torch.where(take, first, best_f)
+            if mark is not None:
+                M = torch.stack(((a * a).sum(-1), (b * b).sum(-1), (c * c).sum(-1)), 0).max(0).values[:, :, None, None]
+                low = torch.minimum(torch.minimum(bary[0], bary[1]), bary[2]).abs()
+                marked |= ((z > 0) & (low <= (mark[0] * 2.0 ** -23) * M * dn[:, None] / det.abs())).any(1)
+        if mark is not None:
+            marked |= (best_f >= 0) & (second_z - best_z <= mark[1] * best_z)
+    # bary and depth at the chosen face, with the operations of steps 3 - 6 (and with autograd)
+    covered = best_f >= 0
+    tri = faces[best_f.clamp(min=0)] if F else torch.zeros((B, H, W, 3), dtype=torch.long, device=dev)
+    view = torch.arange(B, device=dev).view(B, 1, 1)
+    if V:
+        a, b, c = p[view, tri[..., 0]], p[view, tri[..., 1]], p[view, tri[..., 2]]         # [B,H,W,3]
+    else:
+        a = b = c = torch.zeros((B, H, W, 3), dtype=dt, device=dev)
+    D0, D1 = d0[:, None, :], d1[:, :, None]
+    w = [_edge_values(D0, D1, n) for n in (_face_cross(b, c), _face_cross(c, a), _face_cross(a, b))]
+    det = (w[0] + w[1]) + w[2]
+    det = torch.where(covered, det, torch.ones_like(det))
+    bary = [x / det for x in w]
+    z = (bary[0] * a[..., 2] + bary[1] * b[..., 2]) + bary[2] * c[..., 2]
+    zero = torch.zeros((), dtype=dt, device=dev)
+    depth = torch.where(covered, z * dn, zero)
+    bary = torch.where(covered[..., None], torch.stack(bary, -1), zero)
+    out = (best_f, bary, depth)
+    return out if mark is None else out + (marked,)

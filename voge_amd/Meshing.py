@@ -64,15 +64,33 @@ synchronisation per call (V', F' and an error word), a one-off step like extract
 Vertex clustering does not promise a manifold result: two sheets closer than a cell merge.  It gives no target face count either:
 a count is reached by trying cell sizes.
 
-Not here: gradients through any of these steps, bilinear pixel sampling, per-view confidence weights, colouring an existing mesh by
-projecting its vertices into images with a visibility test, textures and UV maps, edge-collapse decimation, a target_faces=
-argument and boundary preservation for the simplification.
+Depth maps of a mesh, the arrow back from a mesh to an image:
+
+    frags = rasterize_mesh(verts, faces, cameras, image_size, cull_backfaces=False, route=None)
+    frags.pix_to_face [B,H,W] int32 (-1: nothing hit), frags.bary [B,H,W,3], frags.depth [B,H,W]
+    image = interpolate_vertex_attr(frags, faces, vert_attr, background=0.0)      # [B,H,W,C]
+
+The nearest face under every pixel by an exact ray-triangle test: Aggregation.mesh_rasterize IS the definition, seven steps.  depth
+is get_depth's -- the distance along the unit pixel ray, under the cameras integrate reads -- so it goes unchanged into integrate,
+get_normals and a loss against get_depth; pix_to_face is the visibility test for colouring a mesh from images.  fp32 verts, int32 or
+int64 faces and cameras on one HIP device take the kernels of csrc/mesh_raster.hip: the definition's fp32 bits on both routes --
+"brute", two launches, nothing read back, capturable: the meshes of a fitting loop; "bins", per-tile lists and ONE synchronisation:
+large meshes; None chooses by ops.MESH_RASTER_BINS_MIN_WORK (brute won at every measured size).  depth IS DIFFERENTIABLE to verts there
+(integer atomics, the same bits on every run); pix_to_face and bary carry no gradient and the cameras take none.  Everything else
+-- host tensors, other dtypes -- takes the definition, differentiable through depth and bary by autograd.  No soft silhouettes, one
+face a pixel, no near plane, one mesh a call.
+
+Not here: gradients through any of the other steps, bilinear pixel sampling, per-view confidence weights, textures and UV maps,
+edge-collapse decimation, a target_faces= argument and boundary preservation for the simplification.
 """
+import collections
+
 import torch
 
 from . import Aggregation, cameras as _cameras, ops
 
-__all__ = ["TSDFVolume", "extract_mesh", "connected_components", "clean_mesh", "vertex_normals", "simplify_mesh"]
+__all__ = ["TSDFVolume", "extract_mesh", "connected_components", "clean_mesh", "vertex_normals", "simplify_mesh", "MeshFragments",
+           "rasterize_mesh", "interpolate_vertex_attr"]
 
 
 def _triple(v, name, integer=False):
@@ -367,3 +385,69 @@ def simplify_mesh(verts, faces, cell_size, placement="mean", attr=None, return_i
         v, f, a, vi, fi = Aggregation.mesh_simplify(verts, faces.to(verts.device), h, placement, attr)
         f, vi, fi = f.to(torch.int32), vi.to(torch.int32), fi.to(torch.int32)
     return (v, f) + (() if attr is None else (a,)) + ((vi, fi) if return_index else ())
+
+
+MeshFragments = collections.namedtuple("MeshFragments", ["pix_to_face", "bary", "depth"])
+
+
+def rasterize_mesh(verts, faces, cameras, image_size, cull_backfaces=False, route=None):
+    """MeshFragments(pix_to_face [B,H,W] int32, bary [B,H,W,3] fp32, depth [B,H,W] fp32) of the mesh verts [V,3], faces [F,3] seen
+    by `cameras` (R, T, focal_length, principal_point, as TSDFVolume.integrate reads them; B views or one) at image_size (H, W):
+    Aggregation.mesh_rasterize's rule, the nearest face under every pixel centre by an exact ray-triangle test, ties to the lower
+    index.  pix_to_face is -1, bary and depth are 0 where nothing is hit; depth is get_depth's, the distance along the unit pixel
+    ray.  cull_backfaces keeps only the fronts of faces whose normal (b - a) x (c - a) points at the camera.  route: None, "brute"
+    or "bins" (the module's header); host tensors and other dtypes take the definition whatever the route.  ValueError for verts or
+    faces of another shape, an image_size that is not two integers >= 1, an unknown route, cameras whose counts do not match, a
+    face index outside [0, V) (the definition; on the device such a face hits nothing) and, on the bins route, lists longer than
+    2^31 - 1.  depth is differentiable to verts; on the device nothing else is."""
+    _check_mesh(verts, faces, "rasterize_mesh")
+    try:
+        H, W = (int(x) for x in image_size)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"rasterize_mesh: image_size (H, W) expected, got {image_size!r}") from e
+    if H < 1 or W < 1:
+        raise ValueError(f"rasterize_mesh: image_size (H, W) >= 1 expected, got ({H}, {W})")
+    if route not in ops.MESH_RASTER_ROUTES:
+        raise ValueError(f"rasterize_mesh: route None, 'brute' or 'bins' expected, got {route!r}")
+    dev = verts.device
+    R = torch.as_tensor(cameras.R, device=dev).detach().to(torch.float32).reshape(-1, 3, 3)
+    T = torch.as_tensor(cameras.T, device=dev).detach().to(torch.float32).reshape(-1, 3)
+    B = max(R.shape[0], T.shape[0])
+    if R.shape[0] not in (1, B) or T.shape[0] not in (1, B):
+        raise ValueError(f"rasterize_mesh: {R.shape[0]} rotations and {T.shape[0]} translations")
+    if B == 0:
+        empty = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        return MeshFragments(empty(0, H, W, dt=torch.int32), empty(0, H, W, 3, dt=verts.dtype), empty(0, H, W, dt=verts.dtype))
+    try:
+        focal = _cameras._as_b2(torch.as_tensor(cameras.focal_length).detach(), B, dev)
+        pp = _cameras._as_b2(torch.as_tensor(cameras.principal_point).detach(), B, dev)
+    except RuntimeError as e:
+        raise ValueError(f"rasterize_mesh: {B} views do not match the cameras' focal_length / principal_point") from e
+    R, T = R.expand(B, 3, 3), T.expand(B, 3)
+    faces = faces.detach().to(dev)
+    if verts.is_cuda and verts.dtype == torch.float32 and faces.dtype in (torch.int32, torch.int64):
+        return MeshFragments(*ops.mesh_rasterize(verts, faces, R, T, focal, pp, H, W, bool(cull_backfaces), route))
+    dt = verts.dtype
+    pix, bary, depth = Aggregation.mesh_rasterize(verts, faces, R.to(dt), T.to(dt), focal.to(dt), pp.to(dt), H, W, bool(cull_backfaces))
+    return MeshFragments(pix.to(torch.int32), bary, depth)
+
+
+def interpolate_vertex_attr(fragments, faces, vert_attr, background=0.0):
+    """[B,H,W,C]: vert_attr [V,C] of the hit face's three vertices weighted by fragments.bary, `background` (a number or [C]) where
+    pix_to_face < 0 -- the image integrate(attr=) and a colour comparison take.  Plain torch, differentiable to vert_attr (and to
+    bary where it carries a gradient).  ValueError for faces that are not [F,3] integers or a vert_attr that is not [V,C] floats."""
+    _check_faces(faces, "interpolate_vertex_attr")
+    if not isinstance(vert_attr, torch.Tensor) or vert_attr.dim() != 2 or not vert_attr.dtype.is_floating_point:
+        raise ValueError(f"interpolate_vertex_attr: vert_attr [V,C] of floats expected, got {tuple(getattr(vert_attr, 'shape', ()))}")
+    pix, bary = fragments.pix_to_face, fragments.bary
+    covered = pix >= 0
+    if faces.shape[0] == 0:
+        tri = torch.zeros(tuple(pix.shape) + (3,), dtype=torch.long, device=pix.device)
+    else:
+        tri = faces.to(pix.device).long()[pix.long().clamp(min=0)]                      # [B,H,W,3]
+    if vert_attr.shape[0] == 0:
+        image = torch.zeros(tuple(pix.shape) + (vert_attr.shape[1],), dtype=vert_attr.dtype, device=vert_attr.device)
+    else:
+        image = (vert_attr[tri] * bary.to(vert_attr.dtype)[..., None]).sum(-2)      # [B,H,W,3,C] -> [B,H,W,C]
+    bg = torch.as_tensor(background, dtype=vert_attr.dtype, device=vert_attr.device)
+    return torch.where(covered[..., None], image, bg.expand_as(image))

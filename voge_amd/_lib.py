@@ -169,6 +169,11 @@ SIGNATURES = {
                                          _c_long, _c_void_p, _c_size_t] + [_c_void_p] * 4 + [_c_int, _c_void_p]),
     "voge_mesh_simplify_attr": (_c_int, [_c_void_p, _c_long, _c_long] + [_c_int] * 3 + [_c_void_p, _c_size_t, _c_long, _c_void_p, _c_int,
                                          _c_void_p, _c_size_t, _c_void_p, _c_int, _c_void_p]),
+    "voge_mesh_raster_workspace_bytes": (_c_size_t, [_c_long] * 5),
+    "voge_mesh_raster_fwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 4 + [_c_long] * 3 + [_c_int] * 2
+                             + [_c_void_p, _c_long] + [_c_void_p] * 5 + [_c_size_t, _c_void_p]),
+    "voge_mesh_raster_bwd": (_c_int, [_c_void_p, _c_long, _c_void_p, _c_long] + [_c_void_p] * 4 + [_c_long] * 3 + [_c_void_p] * 4
+                             + [_c_size_t, _c_void_p]),
     "voge_depth_normals_fwd": (_c_int, [_c_void_p] * 4 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_depth_normals_bwd": (_c_int, [_c_void_p] * 5 + [_c_int] * 4 + [_c_float, _c_int] + [_c_void_p] * 2),
     "voge_blend_bwd": (_c_int, [_c_void_p] * 3 + [_c_float, _c_void_p, _c_long, _c_int, _c_int] + [_c_void_p] * 3),

@@ -2683,6 +2683,106 @@ def mesh_simplify(verts, faces, cell_size, placement="mean", attr=None):
     return out_v, out_f, out_a, vert_index, face_index
 
 
+MESH_RASTER_TILE = 16      # kMrTile of mesh_raster.hip: a tile's edge in pixels, one workgroup of 256 lanes
+# route=None: "brute" while B tiles F <= this many (tile, face) pairs, "bins" above.  Measured (tools/mesh_raster_time.py,
+# profiles/r31_mesh_raster.txt): "brute" is the faster route at EVERY work measured up to 3.36e8 (one 512^2 view of 327 680 faces:
+# 1.50 against 1.72 ms; five 128^2 views: 2.2 - 2.4 x faster at every size), the two approaching each other on the 512^2 image.  The
+# constant sits just above the largest work at which "brute" was seen to win; the crossover itself lies beyond what was measured.
+MESH_RASTER_BINS_MIN_WORK = 1 << 29
+MESH_RASTER_ROUTES = (None, "brute", "bins")
+
+
+def mesh_raster_route(B, H, W, F, route=None):
+    """The route mesh_rasterize takes: `route` itself when given, else by MESH_RASTER_BINS_MIN_WORK"""
+    if route not in MESH_RASTER_ROUTES:
+        raise ValueError(f"mesh_rasterize: route None, 'brute' or 'bins' expected, got {route!r}")
+    if route is not None:
+        return route
+    tiles = ((H + MESH_RASTER_TILE - 1) // MESH_RASTER_TILE) * ((W + MESH_RASTER_TILE - 1) // MESH_RASTER_TILE)
+    return "brute" if B * tiles * F <= MESH_RASTER_BINS_MIN_WORK else "bins"
+
+
+class _MeshRaster(torch.autograd.Function):
+    """Mesh depth maps (extension; voge_mesh_raster_fwd / _bwd): forward(verts [V,3], faces [F,3] int32 | int64, R [B,3,3], T [B,3],
+    focal [B,2], pp [B,2], H, W, cull_backfaces, route) -> (pix_to_face [B,H,W] int32, bary [B,H,W,3], depth [B,H,W]), the fp32 bits
+    of Aggregation.mesh_rasterize, the same on both routes.  route "brute": two launches on the current stream from the stream's
+    cached workspace, nothing read back (capturable).  route "bins": five launches, ONE number read back on the host (the length of
+    the tiles' lists: one synchronisation), two more launches; ValueError when that length does not fit 31 bits.  int64 faces cost
+    one cast.  Only depth is differentiable, and only to verts: four launches (zero fill, largest |term|, integer-atomic scatter,
+    finish), every element of g_verts written, the same bits on every run, nothing read back.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, R, T, focal, pp, H, W, cull_backfaces, route):
+        v = _mesh_verts(verts, "mesh_rasterize")
+        f = _mesh_faces(faces, "mesh_rasterize")
+        dev = v.device
+        R, T = _dev(R.detach(), torch.float32, "R"), _dev(T.detach(), torch.float32, "T")
+        focal, pp = _dev(focal.detach(), torch.float32, "focal"), _dev(pp.detach(), torch.float32, "pp")
+        B, V, F, H, W = R.shape[0], v.shape[0], f.shape[0], int(H), int(W)
+        if tuple(R.shape) != (B, 3, 3) or tuple(T.shape) != (B, 3) or tuple(focal.shape) != (B, 2) or tuple(pp.shape) != (B, 2):
+            raise ValueError(f"mesh_rasterize: R [B,3,3], T [B,3], focal [B,2], pp [B,2] expected, got {tuple(R.shape)} / {tuple(T.shape)} / "
+                             f"{tuple(focal.shape)} / {tuple(pp.shape)}")
+        if any(t.device != dev for t in (f, R, T, focal, pp)):
+            raise _lib.VogeHipError(f"mesh_rasterize: verts on {dev}, faces on {f.device}, the cameras on {R.device}")
+        if H < 1 or W < 1 or B * H * W >= 2 ** 31:
+            raise ValueError(f"mesh_rasterize: B H W = {B} x {H} x {W} must lie in [1, 2^31) with H, W >= 1")
+        if V == 0 and F > 0:
+            raise ValueError("mesh_rasterize: a face names a vertex outside [0, 0)")
+        route = mesh_raster_route(B, H, W, F, route)
+        pix_to_face = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+        bary = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+        depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        if B > 0:
+            lib = _lib.load()
+            cull = int(bool(cull_backfaces))
+            with _on(dev):
+                st = _stream()
+                ws, nbytes = _sized_workspace(dev, lib.voge_mesh_raster_workspace_bytes, B, V, F, H, W)
+                args = (_p(v) if V else None, V, _p(f) if F else None, F, _p(R), _p(T), _p(focal), _p(pp), B, H, W, cull)
+                outs = (_p(pix_to_face), _p(bary), _p(depth))
+                if route == "brute":
+                    rc = lib.voge_mesh_raster_fwd(*args, 9, None, 0, *outs, None, _p(ws), nbytes, st)
+                else:
+                    total = torch.empty((1,), dtype=torch.int64, device=dev)
+                    rc = lib.voge_mesh_raster_fwd(*args, 3, None, 0, *outs, _p(total), _p(ws), nbytes, st)
+                    _lib.check(rc, "voge_mesh_raster_fwd")
+                    n = int(total.item())      # the synchronisation
+                    if n >= 2 ** 31:
+                        raise ValueError(f"mesh_rasterize: the tiles' lists hold {n} entries, more than 2^31 - 1")
+                    lists = torch.empty((n,), dtype=torch.int32, device=dev)
+                    rc = lib.voge_mesh_raster_fwd(*args, 12, _p(lists) if n else None, n, *outs, None, _p(ws), nbytes, st)
+            _lib.check(rc, "voge_mesh_raster_fwd")
+        ctx.save_for_backward(v, f, R, T, focal, pp, pix_to_face)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(pix_to_face, bary)
+        return pix_to_face, bary, depth
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gp, _gb, g_depth):
+        if g_depth is None or not ctx.needs_input_grad[0]:
+            return (None,) * 10
+        v, f, R, T, focal, pp, pix_to_face = ctx.saved_tensors
+        B, H, W = pix_to_face.shape
+        V, F = v.shape[0], f.shape[0]
+        if V == 0 or B == 0:
+            return (torch.zeros_like(v),) + (None,) * 9
+        lib = _lib.load()
+        g = _dev(g_depth, torch.float32, "grad_depth")
+        g_verts = torch.empty_like(v)
+        with _on(v.device):
+            ws, nbytes = _sized_workspace(v.device, lib.voge_mesh_raster_workspace_bytes, B, V, F, H, W)
+            rc = lib.voge_mesh_raster_bwd(_p(v), V, _p(f) if F else None, F, _p(R), _p(T), _p(focal), _p(pp), B, H, W, _p(pix_to_face), _p(g),
+                                          _p(g_verts), _p(ws), nbytes, _stream())
+        _lib.check(rc, "voge_mesh_raster_bwd")
+        return (g_verts,) + (None,) * 9
+
+
+def mesh_rasterize(verts, faces, R, T, focal, pp, H, W, cull_backfaces=False, route=None):
+    """(pix_to_face int32, bary, depth) of ONE mesh under B cameras on a HIP device: _MeshRaster.apply"""
+    return _MeshRaster.apply(verts, faces, R, T, focal, pp, H, W, cull_backfaces, route)
+
+
 class _DepthNormals(torch.autograd.Function):
     """Normals of a depth map (extension; voge_depth_normals_fwd / _bwd): forward(depth [B,h,W], R [B,3,3], focal [B,2], pp [B,2],
     row0, edge (None | relative depth jump), view_space) -> [B,h,W,3], the values of Aggregation.depth_normals on the rays of
